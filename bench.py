@@ -10,6 +10,11 @@ A "step" is the body of the reference's train.py:43-74 on one synthetic batch al
 zero_grad, forward (train-mode BatchNorm), weighted cross-entropy + arg-max/accuracy, backward,
 decay*L1 + Adam update.  Rank 0 prints ONE JSON line.
 
+A plain run sets up, warms up, times --steps steps and prints the line (headline figure only).  --full adds the `roofline` object
+(extra profiling passes over the step's kernels) and, on one GPU, the `cpu_baseline`; --no-roofline / --no-cpu-baseline drop either
+from a --full run.  --dump-outputs DIR writes what the last timed step returned to its caller as DIR/<name>.npy (float32 / float64,
+a fixed seeded pixel sample of the logits; inputs and weights are seeded, so two builds can be compared array for array).
+
 `roofline` describes the kernel family with the largest share of the step: its algorithmic FLOPs and bytes (engine.op_work: SURVEY
 8(d)'s per-layer figures) over the HIP-event time of its launches (rcv_run_timed on the stream the kernels run on, taken right after
 the timed region on the same buffers).  The roof is chosen per kernel from its arithmetic intensity: fp32-MFMA peak when
@@ -65,6 +70,53 @@ def synthetic(B, H, W, seed):
     x = torch.randn(B, 3, H, W, generator=g)
     t = torch.randint(0, 5, (B, H, W), generator=g)
     return x, t
+
+
+DUMP_PIXELS = 1 << 19           # logits / arg-max of this many pixels, drawn once from a fixed seed (the full logits of the headline
+DUMP_LIMIT_BYTES = 64 << 20     # step are 197 MB)
+
+
+def pixel_sample(B, H, W, n=DUMP_PIXELS, seed=0):
+    """Flat pixel indices (into B*H*W) of the dumped sample: all pixels when there are at most n, else n sorted seeded draws."""
+    total = B * H * W
+    if total <= n:
+        return torch.arange(total)
+    return torch.randperm(total, generator=torch.Generator().manual_seed(seed))[:n].sort()[0]
+
+
+def dump_outputs(dirn, arrays):
+    """arrays: name -> tensor (any device).  Floating tensors keep float32 / float64; everything else is written as float64."""
+    os.makedirs(dirn, exist_ok=True)
+    import numpy as np
+    host = {}
+    for name, t in arrays.items():
+        t = t.detach().cpu()
+        host[name] = t.numpy() if t.dtype in (torch.float32, torch.float64) else t.to(torch.float64).numpy()
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("bench.py: --dump-outputs would write %d bytes (limit %d)" % (total, DUMP_LIMIT_BYTES))
+    for name, a in host.items():
+        np.save(os.path.join(dirn, name + ".npy"), np.ascontiguousarray(a))
+    return total
+
+
+def train_step_outputs(model, trainer, pred):
+    """What a caller of Trainer.step holds after the last step: the logits it returned and the criterion's arg-max mask (both at
+    the seeded pixel sample), the loss and #correct of that step, the updated parameters and BatchNorm buffers, the gradients."""
+    B, C, H, W = pred.shape
+    idx = pixel_sample(B, H, W).to(pred.device)
+    b, hw = idx // (H * W), idx % (H * W)
+    h, w = hw // W, hw % W
+    crit = trainer.criterion
+    out = {"logits_sample": pred[b, :, h, w], "argmax_sample": crit.last_argmax[b, h, w],
+           "loss": crit.last_stats[0:1], "correct_pixels": crit.last_stats[2:3]}
+    for k, p in model.named_parameters():
+        out["param." + k] = p
+        if p.grad is not None:
+            out["grad." + k] = p.grad
+    for k, v in model.named_buffers():
+        out["buffer." + k] = v
+    return out
 
 
 def pmc_traffic(label, workload):
@@ -280,10 +332,15 @@ def run_labelprop(args, dev, rank, world):
         t0 = time.perf_counter()
         marks[0].record()
         for k in range(args.steps):
-            net(x)
+            pred = net(x)
             marks[k + 1].record()
         torch.cuda.synchronize()
         elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        Bp, _, Hp, Wp = pred.shape
+        idx = pixel_sample(Bp, Hp, Wp).to(pred.device)
+        hw = idx % (Hp * Wp)
+        dump_outputs(args.dump_outputs, {"logits_sample": pred[idx // (Hp * Wp), :, hw // Wp, hw % Wp]})
     ms = 1e3 * elapsed / args.steps
     per_step = sorted(marks[k].elapsed_time(marks[k + 1]) for k in range(args.steps))
     out = {"metric": "inference images/sec, LabelProp 160x120 8-channel frame-pair inputs, B=%d" % B,
@@ -293,10 +350,10 @@ def run_labelprop(args, dev, rank, world):
            "config": {"workload": args.workload, "per_gpu_batch": B, "height": H, "width": W,
                       "step": "one eval-mode forward call (validLabelProp.py:132-135), NCHW in -> logits", "latency_ms": round(ms, 4),
                       "parallelism": "replicas%d" % world, "weights": "seeded random init (the shipped .pth does not travel)"}}
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         rows = net.__dict__["_engine"].profile_last(reps=5)
         out["roofline"] = roofline_block(rows, ms, args.workload, args.batch, args.breakdown)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline_labelprop(sd, B, H, W)
     return out
 
@@ -367,10 +424,18 @@ def main():
     ap.add_argument("--graph", type=int, default=0, help="1: replay the whole training step as ONE captured hipGraph (Trainer.capture); "
                     "0 (default): eager.  Measured on robo_unet_160x120_bs64: 2.41 ms/step replayed vs 2.14 eager -- the step is bound by "
                     "its chain of dependent kernels, not by the host, and the replayed graph schedules its two streams worse")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--breakdown", action="store_true", help="print the per-kernel table to stderr")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline figure does not need: the roofline "
+                    "(profiling passes over the step's kernels) and, on one GPU, the CPU-oracle baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="(--full) skip the roofline")
+    ap.add_argument("--breakdown", action="store_true", help="(--full) print the per-kernel table to stderr")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned to its caller as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.breakdown and not (args.full and not args.no_roofline):
+        ap.error("--breakdown prints the roofline's per-kernel table: it needs --full (and no --no-roofline)")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # plain `python bench.py --gpus N`: this process becomes the launcher.  It has made NO GPU call yet (device_count() does not
@@ -448,7 +513,7 @@ def main():
     t0 = time.perf_counter()
     marks[0].record()
     for k in range(args.steps):
-        step(x, t)
+        pred = step(x, t)
         marks[k + 1].record()
     if dist is not None:
         _barrier(dist, local_rank)
@@ -460,6 +525,8 @@ def main():
         tt = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, train_step_outputs(model, trainer, pred))
     metrics = trainer.pop_metrics()
     ms_per_step = 1e3 * elapsed / args.steps
 
@@ -488,13 +555,13 @@ def main():
         out["config"]["second_stream"] = plans[0].side_mode      # "all": filter gradients + their reductions, "reduce": reductions only, "off"
         if plans[0].side_ms:
             out["config"]["backward_ms_all_reduce_off"] = [round(v, 3) for v in plans[0].side_ms]
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and args.full and not args.no_roofline:
         rows = eng.profile_last(reps=3)
         # the optimizer launch belongs to the step as well (one RCV_OP_ADAM_L1 over the flat buffers: 28 B per parameter)
         n_par = eng.flat.numel
         rows.append({"label": "adam_l1", "kind": 16, "ms": 0.0, "flops": 0.0, "bytes": 28.0 * n_par, "shape": "%d parameters" % n_par, "bwd": True})
         out["roofline"] = roofline_block(rows, ms_per_step, args.workload, args.batch, args.breakdown)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(ctor, H, W, dice=args.dice)
     if rank == 0:
         print(json.dumps(out))

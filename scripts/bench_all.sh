@@ -7,7 +7,7 @@ O=gpurun_out/bench_all_$TAG.jsonl
 : > $O
 for w in robo_unet_640x480_bs32 robo_unet_160x120_bs64 unet_640x480_bs32 labelprop_160x120_b2 labelprop_160x120_b64 robo_unet_320x240_bs32 robo_unet_v2_640x480_bs32; do
   steps=20; if [[ $w == labelprop* ]]; then steps=200; fi
-  timeout -k 10 300 python bench.py --workload $w --steps $steps --warmup 5 ${NOCPU:+--no-cpu-baseline} 2> gpurun_out/bench_all_$TAG.err | tail -1 >> $O
+  timeout -k 10 300 python bench.py --full --workload $w --steps $steps --warmup 5 ${NOCPU:+--no-cpu-baseline} 2> ${O%.jsonl}.err | tail -1 >> $O
 done
 python - $O <<'PY'
 import sys, json

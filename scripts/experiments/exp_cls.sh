@@ -8,7 +8,7 @@ echo "tests exit=$?" >> $O; tail -1 gpurun_out/cls_tests.log >> $O
 for r in 1 2; do
 for L in librcv_A.so librcv.so; do
   echo "== $L" >> $O
-  RCV_LIBRARY=$GRAFT_REPO_ROOT/robocupvision_amd/$L timeout -k 10 300 python bench.py --steps 20 --warmup 5 --breakdown --no-cpu-baseline "$@" 2>&1 >/dev/null | grep -E "^cls_|^adam|^wgrad_first|^conv_first" >> $O
+  RCV_LIBRARY=$PWD/robocupvision_amd/$L timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 --breakdown --no-cpu-baseline "$@" 2>&1 >/dev/null | grep -E "^cls_|^adam|^wgrad_first|^conv_first" >> $O
   RCV_LIBRARY=$GRAFT_REPO_ROOT/robocupvision_amd/$L timeout -k 10 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline "$@" 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('ms_per_step', d['ms_per_step'])" >> $O
 done; done
 cat $O

@@ -5,6 +5,7 @@
 #   dominant kernel:   SQ counters of one 128->128 launch (scripts/pmc_op.sh)
 # everything lands in gpurun_out/prof_TAG*/ ; scripts/summarize_profile.py copies the summaries into profiles/
 TAG=${1:-r03}
+BENCH=$(cd "$(dirname "$0")/.." && pwd)/bench.py
 cd /tmp && export TMPDIR=/tmp
 # per-kernel numbers are taken with the backward pass on ONE stream: with the filter gradients overlapped on the side stream a
 # kernel's duration includes the time it shares the chip, which is not what bench.py's per-op HIP events report
@@ -13,7 +14,7 @@ prof() {   # name, bench args...
   local name=$1; shift
   local OUT=$GRAFT_REPO_ROOT/gpurun_out/prof_$name
   mkdir -p $OUT
-  local CMD="python3 $GRAFT_REPO_ROOT/bench.py --steps 5 --warmup 2 --no-cpu-baseline $*"
+  local CMD="python3 $BENCH --full --steps 5 --warmup 2 --no-cpu-baseline $*"
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- $CMD > $OUT/bench_stats.json 2> $OUT/stats.err
   echo "$name stats exit=$?"
   timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/fetch -- $CMD --no-roofline > /dev/null 2> $OUT/fetch.err

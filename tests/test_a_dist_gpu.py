@@ -107,7 +107,7 @@ def test_bench_launches_its_own_ranks(tmp_path):
     env = dict(os.environ)
     env.update({"RCV_DIST_BACKEND": "gloo", "HSA_ENABLE_IPC_MODE_LEGACY": "0"})
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "2",
-           "--workload", "robo_unet_160x120_bs64", "--batch", "4"]
+           "--workload", "robo_unet_160x120_bs64", "--batch", "4", "--full"]
     r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]

@@ -5,6 +5,10 @@ import os
 import subprocess
 import sys
 
+import numpy as np
+import pytest
+import torch
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BENCH = os.path.join(ROOT, "bench.py")
 STUB = os.path.join(ROOT, "tests", "stub_launcher.py")
@@ -78,3 +82,39 @@ def test_roofline_block_fields():
     # per-layer roofline: sum of max(FLOPs / 157.3 TF/s, bytes / 8 TB/s) over ALL rows
     want = sum(max(x["flops"] / 157.3e9, x["bytes"] / 8000e6) for x in rows)
     assert abs(r["t_roof_ms"] - want) < 1e-3 and abs(r["step_frac"] - want / 0.5) < 1e-3
+
+
+def _bench_module():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", BENCH)
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    return bench
+
+
+def test_dump_outputs_sample_and_files(tmp_path):
+    """--dump-outputs: the pixel sample is fixed (same indices every run, inside the batch); arrays land as float32 / float64 .npy
+    files; a dump over the size limit is refused before anything is written."""
+    bench = _bench_module()
+    B, H, W = 32, 480, 640
+    idx = bench.pixel_sample(B, H, W)
+    assert torch.equal(idx, bench.pixel_sample(B, H, W)) and idx.numel() == bench.DUMP_PIXELS
+    assert int(idx.min()) >= 0 and int(idx.max()) < B * H * W and bool((idx[1:] > idx[:-1]).all())
+    assert torch.equal(bench.pixel_sample(2, 4, 6), torch.arange(48))        # small outputs are kept whole
+    logits = torch.randn(7, 5)
+    n = bench.dump_outputs(str(tmp_path / "d"), {"logits_sample": logits, "argmax_sample": torch.arange(7, dtype=torch.uint8),
+                                                 "loss": torch.ones(1, dtype=torch.float64)})
+    got = {f: np.load(str(tmp_path / "d" / f)) for f in sorted(os.listdir(str(tmp_path / "d")))}
+    assert sorted(got) == ["argmax_sample.npy", "logits_sample.npy", "loss.npy"] and n == 7 * 5 * 4 + 7 * 8 + 8
+    assert got["logits_sample.npy"].dtype == np.float32 and np.array_equal(got["logits_sample.npy"], logits.numpy())
+    assert got["argmax_sample.npy"].dtype == np.float64 and got["loss.npy"].dtype == np.float64
+    with pytest.raises(SystemExit):
+        bench.dump_outputs(str(tmp_path / "big"), {"x": torch.zeros(bench.DUMP_LIMIT_BYTES // 4 + 1)})
+    assert not os.path.exists(str(tmp_path / "big" / "x.npy"))
+
+
+def test_breakdown_needs_full_and_steps_must_be_positive():
+    r = _run(["--breakdown"])
+    assert r.returncode != 0 and "--full" in r.stderr
+    r = _run(["--steps", "0"])
+    assert r.returncode != 0 and "--steps" in r.stderr

@@ -1,11 +1,10 @@
 """CPU: the robot-side export (robocupvision_amd/export.py) -- flat float64 weight dump (paramSave.py) against the reference's
 own dump of the same twice-stepped PB_FCN (hash in tests/golden/pbfcn.json; the state is rebuilt here with the CPU oracle), and the
-net.cfg layer list against the reference's weights/net.cfg when that file is present (it is data, not copied into this repo)."""
+net.cfg layer list against the reference's weights/net.cfg (a layer-settings file, stored as tests/golden/net.cfg)."""
 import hashlib
 import os
 
 import numpy as np
-import pytest
 import torch
 
 from oracle import cpu_reference as O
@@ -45,10 +44,7 @@ def test_net_cfg_layer_list():
     assert lines[0] == "[net]" and lines[-1] == "[softmax]"
     assert [l for l in lines if l.startswith("from=")] == ["from=6", "from=3", "from=1"]       # closing layers of conv2, conv1, conv0
     assert sum(l == "[convolutional]" for l in lines) == 12 and sum(l == "[transposedconv]" for l in lines) == 3
-    ref_path = "/root/reference/weights/net.cfg"
-    if not os.path.exists(ref_path):
-        pytest.skip("reference checkout not present on this machine")
-    with open(ref_path) as f:
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "net.cfg")) as f:
         ref = [l.strip() for l in f.read().strip().splitlines() if l.strip()]
     assert lines == ref
     big = net_cfg(M.PB_FCN(32, 5, 1, True, 0))
