@@ -89,8 +89,13 @@ enum {
   RCV_OP_NCHW_TO_NHWC= 26, /* out[n][p][c] = c < cin ? in[n][c][p] : 0, cout channels per pixel     */
   RCV_OP_SGD         = 27, /* torch.optim.SGD(momentum, weight_decay) over a flat buffer (trainer.py:176-178) */
   RCV_OP_NOP         = 28, /* nothing is launched (a slot of an op list whose work was folded into a later record)       */
-  RCV_OP_WGRAD_REDUCE_BATCH = 29 /* RCV_OP_WGRAD_REDUCE of several layers in ONE launch: p[RCV_P_IN] -> rcv_reduce_job[i[RCV_I_COUNT]]
+  RCV_OP_WGRAD_REDUCE_BATCH = 29, /* RCV_OP_WGRAD_REDUCE of several layers in ONE launch: p[RCV_P_IN] -> rcv_reduce_job[i[RCV_I_COUNT]]
                                    * (device memory); same fixed summation order per layer as the single form                  */
+  RCV_OP_POOL_CLS_FWD = 30, /* pooled patch-classification head (model.py:255-266,403-414): k x k max (i[AUX0] = 2 / 4, floor) or plane
+                             * mean (i[AUX0] = 0) of load(r), optional Dropout2d keep-scale p[X0] = float[N][C], 1x1 classifier
+                             * (1..8 classes) -> NCHW logits; the pooled features [N][HO][WO][C] go to p[X1] (csrc/pool_cls.hip) */
+  RCV_OP_POOL_CLS_BWD = 31  /* its backward: dW (p[X2]), db (p[X3]) and d loss / d load(r) NHWC (first arg-max of a max window; the
+                             * mean's share of every pixel), RCV_F_RESID, RCV_STATS_BWD_ENC / _DEC partial rows of the producer  */
 };
 
 /* how an operand is produced from memory while it is staged (rcv_op.i[RCV_I_INMODE] etc.) */

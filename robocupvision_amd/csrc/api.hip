@@ -104,6 +104,9 @@ static int dispatch(const rcv_handle* h, const rcv_op* op, hipStream_t s, OpQuer
     case RCV_OP_WGRAD_REDUCE:
     case RCV_OP_WGRAD_REDUCE_BATCH:
       return rcv_launch_wgrad(h, op, s, q);
+    case RCV_OP_POOL_CLS_FWD:
+    case RCV_OP_POOL_CLS_BWD:
+      return rcv_launch_pool_cls(h, op, s, q);
     case RCV_OP_NOP:
       if (q) { snprintf(q->label, sizeof(q->label), "nop"); q->n_part = 0; q->n_split = 0; q->part_bytes = 0; }
       return RCV_OK;

@@ -203,6 +203,7 @@ class Plan:
         self.side_ms = None                  # backward ms under each of Engine.SIDE_MODES, from that measurement
         self.bytes = 0
         self.pinned = 0                      # > 0: referenced by a captured hipGraph -- never evicted
+        self.dropout = None                  # (keep-scale buffer [N][C], p) of a training plan whose pooled head drops features
 
 
 PLAN_BYTES_BUDGET = 96 << 30      # cached plans beyond this many bytes of engine buffers are dropped, least recently used first
@@ -534,6 +535,56 @@ class _Lowering:
         self.plan.logits = out
         self.plan.logits_slots = [(len(self.fwd) - 1, L.RCV_P_OUT)]
 
+    def pool_cls_shape(self, node: _Node):
+        """(source value, k, pooled H, pooled W) of a pooled classification head; k = 0 is the plane mean."""
+        d = node.d
+        src = self.ref(d["src"])
+        pool = tuple(d["pool"])
+        if pool[0] == "max" and len(pool) == 2:
+            k = int(pool[1])
+            Hp, Wp = src.H // k, src.W // k
+        elif pool == ("avg",):
+            k, Hp, Wp = 0, 1, 1
+        else:
+            raise L.RcvError("pool_cls node %d: pool %r unknown (('max', k) or ('avg',))" % (node.idx, pool))
+        return src, k, Hp, Wp
+
+    def fwd_pool_cls(self, node: _Node):
+        # pooled patch-classification head (model.py:255-266 Classifier with poolSize, model.py:403-414 UltClassifier with pool): pool,
+        # Dropout2d, 1x1 classifier in ONE launch; NCHW logits [N][nC][Hp][Wp]
+        d = node.d
+        src, k, Hp, Wp = self.pool_cls_shape(node)
+        w, b = d["weight"], d.get("bias")
+        nC, Cin = w.shape[0], w.shape[1]
+        if node.idx != len(self.nodes) - 1:
+            raise L.RcvError("pool_cls node %d must be the graph's last node" % node.idx)
+        if tuple(w.shape[2:]) != (1, 1):
+            raise L.RcvError("the pooled classification head is built for 1x1 classifier kernels only (got %dx%d; no reference script "
+                             "uses another size in classify mode)" % tuple(w.shape[2:]))
+        if Cin != src.C:
+            raise L.RcvError("pool_cls: input has %d channels, weight expects %d" % (src.C, Cin))
+        if src.kind not in ("plain", "affine", "affine_relu"):
+            raise L.RcvError("pool_cls: input kind '%s' unsupported" % src.kind)
+        if Hp < 1 or Wp < 1:
+            raise ValueError("the %dx%d max-pool of the classification head leaves an empty plane on a %dx%d feature map (input too small)"
+                             % (k, k, src.H, src.W))
+        logits = self.eng._alloc(self.plan, self.N, nC, Hp, Wp)
+        node.t["pooled"] = self.eng._alloc(self.plan, self.N, Hp, Wp, src.C)
+        p = float(d.get("dropout") or 0.0)
+        drop = None
+        if self.training and p > 0:
+            drop = self.eng._zeros(self.plan, self.N, src.C)
+            self.plan.dropout = (drop, p)
+        node.t["drop"] = drop
+        op = L.make_op(L.OP_POOL_CLS_FWD, 0, n=self.N, h=src.H, w=src.W, cin=src.C, cout=nC, ho=Hp, wo=Wp, aux0=k, inmode=src.load_mode,
+                       p_in_c=_ptr(src.consts), p_w=w.data_ptr(), p_bias=_ptr(b), p_out=logits.data_ptr(), p_x0=_ptr(drop),
+                       p_x1=node.t["pooled"].data_ptr())
+        op.p[L.RCV_P_IN] = self.bind_in(self.fwd, src, L.RCV_P_IN) or None
+        self.fwd.append(op)
+        node.out = Value("plain", logits, nC, Hp, Wp, None, node)
+        self.plan.logits = logits
+        self.plan.logits_slots = [(len(self.fwd) - 1, L.RCV_P_OUT)]
+
     def grad_target(self, v: Value, writer_op: L.RcvOp, Ho: int, Wo: int):
         """Configure writer_op (a dgrad-like op) to produce d loss / d v with the epilogue v's producer needs."""
         v.grad = self.eng._alloc(self.plan, self.N, v.H, v.W, v.C)
@@ -612,6 +663,22 @@ class _Lowering:
             self.plan.input_slots[src.input_index].append((True, len(self.bwd), L.RCV_P_IN))
         self.plan.dlogits_slots.append((len(self.bwd), L.RCV_P_IN2))
         self.grad_target(src, op, src.H, src.W)
+        self.bwd.append(op)
+
+    def bwd_pool_cls(self, node: _Node):
+        d = node.d
+        src, k, Hp, Wp = self.pool_cls_shape(node)
+        w, b = d["weight"], d.get("bias")
+        if src.producer is None or not src.needs_grad:
+            raise L.RcvError("the pooled classification head must read a block's output in a training graph")
+        if src.producer.op == "up":
+            raise L.RcvError("the pooled classification head directly after a decoder block is not supported")
+        op = L.make_op(L.OP_POOL_CLS_BWD, 0, n=self.N, h=src.H, w=src.W, cin=src.C, cout=w.shape[0], ho=Hp, wo=Wp, aux0=k,
+                       inmode=src.load_mode, p_in_c=_ptr(src.consts), p_w=w.data_ptr(), p_x0=_ptr(node.t["drop"]),
+                       p_x1=node.t["pooled"].data_ptr(), p_x2=self.fl.grad_ptr(w), p_x3=(self.fl.grad_ptr(b) if b is not None else 0))
+        self.plan.dlogits_slots.append((len(self.bwd), L.RCV_P_IN))
+        self.grad_target(src, op, src.H, src.W)
+        op.p[L.RCV_P_EPI_AUX] = src.buf.data_ptr()          # the arg-max of a window is recomputed from the stored tensor
         self.bwd.append(op)
 
     def bwd_mat(self, node: _Node):
@@ -756,7 +823,7 @@ class _Lowering:
             for node in self.nodes:
                 if node.op == "add_slice":
                     raise L.RcvError("this graph is inference only (add_slice has no backward); call .eval()")
-                if node.op not in ("cls", "mat"):
+                if node.op not in ("cls", "mat", "pool_cls"):
                     node.out.needs_grad = True
 
             for node in reversed(self.nodes):
@@ -885,6 +952,7 @@ class Engine:
         # data parallel: called as cb(lo, hi) during backward whenever flat.grad[lo:hi] is final (reverse layer order)
         self.grad_ready_cb = None
         self.grad_buckets = 3
+        self._imposed_dropout: Optional[torch.Tensor] = None
 
     # ------------------------------------------------------------------ device / parameter state
     def _ensure_device(self, dev: torch.device):
@@ -982,6 +1050,7 @@ class Engine:
                 (plan.bwd if is_bwd else plan.fwd).arr[idx].p[slot] = t.data_ptr()
         stream = torch.cuda.current_stream(self.device).cuda_stream
         if training:
+            self._fill_dropout(plan)
             plan.fwd.run(self.handle, stream)
             self.params_dirty = True          # train-mode BatchNorm updates the running statistics
             nbt = [m.num_batches_tracked for m in self.bn_modules if m.num_batches_tracked is not None]
@@ -1007,6 +1076,34 @@ class Engine:
         self._last = (plan, [t for t in inputs])
         self._generation += 1
         return out
+
+    def _fill_dropout(self, plan: Plan):
+        """Dropout2d of the pooled head (model.py:408): a fresh keep-scale [N][C] per training forward, drawn as torch's feature dropout
+        draws it -- bernoulli_(1 - p) on torch's device generator (torch.manual_seed governs it), then / (1 - p)."""
+        if plan.dropout is None:
+            return
+        buf, p = plan.dropout
+        if self._imposed_dropout is not None:
+            if self._imposed_dropout.numel() != buf.numel():
+                raise L.RcvError("the imposed dropout keep-scale has %d elements; this plan's is [%d][%d] (impose one per batch shape, "
+                                 "or None to draw again)" % (self._imposed_dropout.numel(), buf.shape[0], buf.shape[1]))
+            buf.copy_(self._imposed_dropout.reshape(buf.shape))
+        elif p >= 1.0:
+            buf.zero_()
+        else:
+            buf.bernoulli_(1.0 - p)
+            buf.div_(1.0 - p)
+
+    def _last_dropout_scale(self) -> Optional[torch.Tensor]:
+        """(tests) The keep-scale [N][C] the last training forward used (0 or 1/(1-p)), or None when its plan drops nothing."""
+        if self._last is None or self._last[0].dropout is None:
+            return None
+        return self._last[0].dropout[0].clone()
+
+    def _impose_dropout(self, scale: Optional[torch.Tensor]):
+        """(tests) Use this keep-scale [N][C] instead of drawing one in every following training forward; None draws again.  A plan whose
+        batch shape it does not fit refuses it (RcvError) rather than reshaping it."""
+        self._imposed_dropout = None if scale is None else scale.detach().to(torch.float32).contiguous()
 
     @staticmethod
     def op_work(op) -> tuple:
@@ -1056,6 +1153,13 @@ class Engine:
             nbytes = 4.0 * px * cin * 3
         elif k == L.OP_BWD_STATS:
             nbytes = 4.0 * px * ((cin or cout) + cout * (1 + bstats))
+        elif k == L.OP_POOL_CLS_FWD:
+            flops = 2.0 * cin * cout * n * ho * wo
+            nbytes = 4.0 * (px * cin + n * ho * wo * (cin + cout))
+        elif k == L.OP_POOL_CLS_BWD:
+            flops = 2.0 * 2 * cin * cout * n * ho * wo
+            reads_r = 1 if (i[L.RCV_I_AUX0] or i[L.RCV_I_STATS]) else 0
+            nbytes = 4.0 * (px * cin * (1 + reads_r + resid) + n * ho * wo * (2 * cin + cout))
         elif k in (L.OP_NHWC_TO_NCHW, L.OP_NCHW_TO_NHWC):
             nbytes = 4.0 * px * (cin + cout)
         elif k in (L.OP_ADAM_L1, L.OP_SGD):

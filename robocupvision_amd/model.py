@@ -78,6 +78,12 @@ def _bn_modules(m: nn.Module):
     return [x for x in m.modules() if isinstance(x, nn.BatchNorm2d)]
 
 
+def _graph_mode(m: nn.Module) -> bool:
+    """What the engine's graph depends on beyond the module tree: PB_FCN / PB_FCN_2 read ``classify`` at every forward
+    (model.py:294, 450), so a change of it after construction must reach the next forward."""
+    return bool(getattr(m, "classify", False))
+
+
 class _EngineOwner:
     """Mixed into every module that can own an Engine.  The engine caches, per eval plan, everything that depends on the parameters
     only (packed filters, BatchNorm constants) and re-derives it when it can SEE a change: its own kernels wrote parameters
@@ -294,8 +300,8 @@ class LevelDown(nn.Module):
 
 
 class UltClassifier(nn.Module):
-    """1x1 (or, for the v2 net, 3x3) classifier (model.py:403-414); the pooled/dropout variant belongs to the
-    patch classification scripts and is out of scope."""
+    """1x1 (or, for the v2 net, 3x3) classifier (model.py:403-414).  The pooled variant (AdaptiveAvgPool2d(1), Dropout2d, 1x1
+    classifier: PB_FCN_2.classifier) is the patch-classification head of classTrainer.py, run as PB_FCN_2(classify=True)'s graph."""
 
     def __init__(self, inplanes, nClass, pool, dropout=0.5, size=1):
         super().__init__()
@@ -303,7 +309,7 @@ class UltClassifier(nn.Module):
             raise NotImplementedError("classifier kernel sizes 1 and 3 are built (got %d)" % size)
         self.pooled = bool(pool)
         self.layers = nn.Sequential()
-        if pool:        # patch-classification head (PB_FCN_2.classifier): holds its parameters (state_dict / init parity), never executed
+        if pool:        # patch-classification head (PB_FCN_2.classifier): the containers hold the parameters and the dropout rate
             self.layers.add_module("Pool", nn.AdaptiveAvgPool2d(1))
             self.layers.add_module("DO", nn.Dropout2d(dropout))
         self.layers.add_module("Class", nn.Conv2d(inplanes, nClass, size, padding=size // 2))
@@ -313,6 +319,13 @@ class UltClassifier(nn.Module):
             raise L.RcvError("the pooled classification head (classify=True) is outside the segmentation path")
         c = self.layers.Class
         return {"op": "cls", "src": src, "weight": c.weight, "bias": c.bias}
+
+    def _head_node(self, src):
+        """The pooled head as the graph's last node (model.py:444-453): plane mean, Dropout2d(DO.p), 1x1 classifier."""
+        if not self.pooled:
+            raise L.RcvError("this UltClassifier has no pooled head")
+        c = self.layers.Class
+        return {"op": "pool_cls", "src": src, "pool": ("avg",), "weight": c.weight, "bias": c.bias, "dropout": float(self.layers.DO.p)}
 
     def forward(self, x):
         raise L.RcvError("UltClassifier is executed as part of its network graph; standalone use is not built")
@@ -371,9 +384,11 @@ class ROBO_UNet(_EngineOwner, nn.Module):
 
     def _get_engine(self) -> Engine:
         eng = self.__dict__.get("_engine")
-        if eng is None:
+        mode = _graph_mode(self)
+        if eng is None or self.__dict__.get("_engine_mode") != mode:
             eng = Engine(self._graph(), list(self.parameters()), _bn_modules(self))
             self.__dict__["_engine"] = eng
+            self.__dict__["_engine_mode"] = mode
         return eng
 
     def forward(self, x):
@@ -667,8 +682,8 @@ class DownSampler(nn.Module):
 
 
 class Classifier(nn.Module):
-    """1x1 (kernelSize) classifier conv, optionally behind a max-pool (model.py:255-266).  Only the un-pooled segmentation
-    head runs here; the pooled patch-classification head only holds its parameters."""
+    """1x1 (kernelSize) classifier conv, optionally behind a max-pool (model.py:255-266).  The un-pooled one is PB_FCN's segmenter;
+    the pooled one (poolSize > 1) is the patch-classification head, run as PB_FCN(classify=1)'s graph."""
 
     def __init__(self, inplanes, num_classes, poolSize=0, kernelSize=1):
         super().__init__()
@@ -682,19 +697,26 @@ class Classifier(nn.Module):
             raise L.RcvError("the pooled classification head of PB_FCN (classify=1) is outside the segmentation path")
         return {"op": "cls", "src": src, "weight": self.classifier.weight, "bias": self.classifier.bias}
 
+    def _head_node(self, src):
+        """The pooled head as the graph's last node (model.py:262-265): MaxPool2d(poolSize) (floor), then the classifier."""
+        if self.pool is None:
+            raise L.RcvError("this Classifier has no pooled head")
+        k = self.pool.kernel_size
+        return {"op": "pool_cls", "src": src, "pool": ("max", k if isinstance(k, int) else k[0]), "weight": self.classifier.weight,
+                "bias": self.classifier.bias, "dropout": 0.0}
+
     def forward(self, x):
         raise L.RcvError("Classifier is executed as part of PB_FCN's graph; standalone use is not built")
 
 
 class PB_FCN(_EngineOwner, nn.Module):
     """The older PB-FCN segmentation net of trainer.py (model.py:269-309): dilated conv->BN->ReLU encoder, three (four with
-    noScale) transposed-conv decoder blocks with skip adds, 1x1 segmenter.  classify=1 (patch classification through the
-    pooled head) is not built."""
+    noScale) transposed-conv decoder blocks with skip adds, 1x1 segmenter.  classify=1 (classTrainer.py:83, the pretraining
+    stage) runs the encoder and the pooled head instead: MaxPool2d(4) of f3 (MaxPool2d(2) of f4 with noScale), 1x1 classifier;
+    the decoder and the segmenter then keep grad None, as under the reference's autograd."""
 
     def __init__(self, planes, num_classes, kernelSize, noScale, classify):
         super().__init__()
-        if classify:
-            raise NotImplementedError("PB_FCN(classify=1) (patch classification) is outside the segmentation hot path")
         self.noScale = noScale
         self.classify = classify
         self.img_shape = (240, 320) if self.noScale else (120, 160)
@@ -708,10 +730,13 @@ class PB_FCN(_EngineOwner, nn.Module):
         self.classifier = Classifier(planes * 2, num_classes, poolSize=(2 if noScale else 4), kernelSize=kernelSize)
         self.segmenter = Classifier(outPlanes, num_classes, kernelSize=kernelSize)
 
-    # graph of model.py:291-309 (classify == 0)
+    # graph of model.py:291-309
     def _graph(self):
         nodes: list = []
         f4, f3, f2, f1, f0 = self.FCN._nodes(nodes, ("in", 0))
+        if self.classify:           # model.py:294-298
+            nodes.append(self.classifier._head_node(f4 if self.noScale else f3))
+            return {"inputs": [{"layout": "nchw"}], "nodes": nodes}
 
         def up(layer, x, skip):
             nodes.append(layer._node(x, skip))
@@ -731,9 +756,11 @@ class PB_FCN(_EngineOwner, nn.Module):
 
     def _get_engine(self) -> Engine:
         eng = self.__dict__.get("_engine")
-        if eng is None:
+        mode = _graph_mode(self)
+        if eng is None or self.__dict__.get("_engine_mode") != mode:
             eng = Engine(self._graph(), list(self.parameters()), _bn_modules(self))
             self.__dict__["_engine"] = eng
+            self.__dict__["_engine_mode"] = mode
         return eng
 
     def forward(self, x):
@@ -748,12 +775,12 @@ class PB_FCN(_EngineOwner, nn.Module):
 
 class PB_FCN_2(ROBO_UNet):
     """trainer.py's v2 net (model.py:416-458, built at trainer.py:126-127): the ROBO-UNet graph with a one-conv Level0 plus a
-    pooled patch-classification head whose parameters stay outside the segmentation graph (grad None).  classify=True is not built."""
+    pooled patch-classification head whose parameters stay outside the segmentation graph (grad None).  classify=True
+    (classTrainer.py:83 --v2) runs downPart -> PB -> plane mean -> Dropout2d -> 1x1 classifier instead (model.py:444-453); the
+    decoder and the segmenter then keep grad None."""
 
     def __init__(self, classify, nClass=5, planes=8, depth=4, levels=2, bellySize=5, bellyPlanes=128):
         nn.Module.__init__(self)
-        if classify:
-            raise NotImplementedError("PB_FCN_2(classify=True) (patch classification) is outside the segmentation hot path")
         self.classify = classify
         self.numClass = nClass
         self.planes = planes
@@ -774,3 +801,15 @@ class PB_FCN_2(ROBO_UNet):
             self.upPart.add_module("Up%d" % i, upSampleTransposeConv(nCh, nCh // 2))
         self.classifier = UltClassifier(maxDepth, nClass, True)
         self.segmenter = UltClassifier(planes, nClass, False)
+
+    def _graph(self):
+        if not self.classify:
+            return ROBO_UNet._graph(self)
+        nodes: list = []
+        x = ("in", 0)
+        for level in self.downPart:
+            x = level._nodes(nodes, x)
+        for level in self.PB:
+            x = level._nodes(nodes, x)
+        nodes.append(self.classifier._head_node(x))
+        return {"inputs": [{"layout": "nchw"}], "nodes": nodes}

@@ -116,6 +116,9 @@ class Trainer:
         if prune_indices is not None:
             self.set_prune_indices(prune_indices)
         if distributed:
+            if getattr(model, "classify", False):
+                raise L.RcvError("data-parallel training of the patch-classification mode (classify) is not built; train it on one GPU "
+                                 "with a stock loss and optimizer (classTrainer.py)")
             import torch.distributed as dist
             if not dist.is_initialized():
                 raise L.RcvError("distributed=True needs torch.distributed.init_process_group('nccl') first")
