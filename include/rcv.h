@@ -94,8 +94,12 @@ enum {
   RCV_OP_POOL_CLS_FWD = 30, /* pooled patch-classification head (model.py:255-266,403-414): k x k max (i[AUX0] = 2 / 4, floor) or plane
                              * mean (i[AUX0] = 0) of load(r), optional Dropout2d keep-scale p[X0] = float[N][C], 1x1 classifier
                              * (1..8 classes) -> NCHW logits; the pooled features [N][HO][WO][C] go to p[X1] (csrc/pool_cls.hip) */
-  RCV_OP_POOL_CLS_BWD = 31  /* its backward: dW (p[X2]), db (p[X3]) and d loss / d load(r) NHWC (first arg-max of a max window; the
+  RCV_OP_POOL_CLS_BWD = 31, /* its backward: dW (p[X2]), db (p[X3]) and d loss / d load(r) NHWC (first arg-max of a max window; the
                              * mean's share of every pixel), RCV_F_RESID, RCV_STATS_BWD_ENC / _DEC partial rows of the producer  */
+  RCV_OP_OBJECT_MATCH = 32  /* object-detection counts of test.py:28-89 (rcv_object_match; csrc/objdet.hip): i[N], i[H], i[W], i[COUT] = C,
+                             * i[COUNT] = K, i[INMODE] / i[INMODE2] = element bytes of p[IN] pred / p[IN2] target (1 = uint8, 8 = int64);
+                             * p[X0] / p[X1] = HOST double[K] IoU / distance thresholds (read when enqueued), p[OUT] = counts, p[PART] =
+                             * workspace, i[NPART] = its size in 256-byte units (filled by rcv_op_workspace)                          */
 };
 
 /* how an operand is produced from memory while it is staged (rcv_op.i[RCV_I_INMODE] etc.) */
@@ -314,6 +318,16 @@ int rcv_dice_bwd(rcv_handle* h, const float* logits, const int64_t* target, cons
  * mask loops of valid() (train.py:136-153).  counts is int32 [N][C][C] indexed [n][pred][label]; the call ADDS.   */
 int rcv_confusion(rcv_handle* h, const uint8_t* argmax, const int64_t* target, int N, int C, int H, int W,
                   int32_t* counts, void* stream);
+
+/* Object-detection precision / recall counts of the reference's validation (getPrecRecall, test.py:28-89,258-262) for every image n and
+ * class c in 1..C-1 of pred / target [N][H][W] (uint8 or int64: pred_bytes / target_bytes = 1 or 8; a value outside [1, C) is in no
+ * class).  Components are 8-connected and numbered by their first 2x2 block in raster order; each of the K threshold pairs greedily
+ * matches the preds, in that order, to the first unused target that passes inter/union > iou_thr[k] (fp64) resp.
+ * dist_thr[k] > |centre difference| (centre = bounding-box centre, as cv2.boundingRect).  counts int32 [N][C-1][2+2K] (overwritten):
+ * { nPred, nTrue, nCorrIoU[0..K), nCorrDist[0..K) }.  2 <= C <= 8, 1 <= K <= 8, iou_thr[k] finite >= 0, dist_thr[k] finite; the
+ * threshold arrays are host memory, read before the call returns.  ws: rcv_op_workspace bytes of the RCV_OP_OBJECT_MATCH record.  */
+int rcv_object_match(rcv_handle* h, const void* pred, int pred_bytes, const void* target, int target_bytes, int N, int C, int H, int W,
+                     const double* iou_thr, const double* dist_thr, int K, int32_t* counts, void* ws, size_t ws_bytes, void* stream);
 
 /* torch.optim.SGD.step (trainer.py:176-178,221): g = grad*grad_scale + weight_decay*p; buf = step==1 ? g : momentum*buf + g;
  * p -= lr*buf.  lr_elem (may be NULL) gives a per-element learning rate (0 = parameter without a gradient: untouched). */

@@ -107,6 +107,8 @@ static int dispatch(const rcv_handle* h, const rcv_op* op, hipStream_t s, OpQuer
     case RCV_OP_POOL_CLS_FWD:
     case RCV_OP_POOL_CLS_BWD:
       return rcv_launch_pool_cls(h, op, s, q);
+    case RCV_OP_OBJECT_MATCH:
+      return rcv_launch_objdet(h, op, s, q);
     case RCV_OP_NOP:
       if (q) { snprintf(q->label, sizeof(q->label), "nop"); q->n_part = 0; q->n_split = 0; q->part_bytes = 0; }
       return RCV_OK;
@@ -349,6 +351,22 @@ int rcv_confusion(rcv_handle* h, const uint8_t* argmax, const int64_t* target, i
   op.kind = RCV_OP_CONFUSION;
   op.i[RCV_I_N] = N; op.i[RCV_I_H] = H; op.i[RCV_I_W] = W; op.i[RCV_I_COUT] = C;
   op.p[RCV_P_IN] = (void*)argmax; op.p[RCV_P_IN2] = (void*)target; op.p[RCV_P_OUT] = counts;
+  return rcv_run(h, &op, 1, stream);
+}
+
+int rcv_object_match(rcv_handle* h, const void* pred, int pred_bytes, const void* target, int target_bytes, int N, int C, int H, int W,
+                     const double* iou_thr, const double* dist_thr, int K, int32_t* counts, void* ws, size_t ws_bytes, void* stream) {
+  rcv_op op;
+  memset(&op, 0, sizeof(op));
+  op.kind = RCV_OP_OBJECT_MATCH;
+  op.i[RCV_I_N] = N; op.i[RCV_I_H] = H; op.i[RCV_I_W] = W; op.i[RCV_I_COUT] = C; op.i[RCV_I_COUNT] = K;
+  op.i[RCV_I_INMODE] = pred_bytes; op.i[RCV_I_INMODE2] = target_bytes;
+  op.p[RCV_P_IN] = (void*)pred; op.p[RCV_P_IN2] = (void*)target; op.p[RCV_P_OUT] = counts; op.p[RCV_P_PART] = ws;
+  op.p[RCV_P_X0] = (void*)iou_thr; op.p[RCV_P_X1] = (void*)dist_thr;
+  size_t need = 0;
+  const int rc = rcv_op_workspace(h, &op, &need);
+  if (rc) return rc;
+  RCV_CHECK_ARG(ws_bytes >= need, "rcv_object_match: workspace of %zu bytes given, %zu needed (rcv_op_workspace)", ws_bytes, need);
   return rcv_run(h, &op, 1, stream);
 }
 

@@ -1,7 +1,13 @@
 """Device-side evaluation metrics: the pixel accuracy / mean class accuracy / mean IoU that
 the reference's valid() builds with O(B*C^2) Python mask loops and `.item()` syncs (train.py:136-178).  One kernel
-(RCV_OP_CONFUSION) counts (pred, label) pairs per image; everything else is arithmetic on B*C*C integers."""
+(RCV_OP_CONFUSION) counts (pred, label) pairs per image; everything else is arithmetic on B*C*C integers.
+
+DetectionMetrics: the object-detection precision / recall of test.py (getPrecRecall, test.py:28-89, printed as its `IoU:` /
+`Dist:` rows).  One op (RCV_OP_OBJECT_MATCH, csrc/objdet.hip) labels the blobs and matches them on the device; the host turns the
+integer counts into the reference's float64 numbers in the reference's order."""
 from __future__ import annotations
+
+import ctypes
 
 import torch
 
@@ -42,3 +48,130 @@ class SegmentationMetrics:
                 "mean_class_acc": float(class_acc.sum()) / self.C,
                 "mean_iou": float((self.iou_sum / max(self.n_img, 1)).sum()) / self.C * 100.0,
                 "confusion_percent": (self.conf / (lab_cnt / 100.0)).cpu()}
+
+
+DEFAULT_IOU_THRESHOLDS = (0.75, 0.5, 0.25, 0.1, 0.05)     # test.py:258
+DEFAULT_DIST_THRESHOLDS = (1.25, 2.5, 5, 10, 20)          # test.py:259; test.py:261-262 doubles them for --noScale
+
+
+def _elem_bytes(t: torch.Tensor, what: str, allowed) -> int:
+    nbytes = {torch.uint8: 1, torch.int64: 8}.get(t.dtype)
+    if nbytes is None or t.dtype not in allowed:
+        raise L.RcvError("%s: dtype %s unsupported (%s)" % (what, t.dtype, " or ".join(str(a) for a in allowed)))
+    return nbytes
+
+
+class ObjectMatchRecord:
+    """One RCV_OP_OBJECT_MATCH record and the host double[K] threshold arrays it points to (kept alive with it)."""
+
+    def __init__(self, N: int, H: int, W: int, num_class: int, iou_thresholds, dist_thresholds, pred_bytes: int = 1,
+                 target_bytes: int = 8):
+        iou = [float(t) for t in iou_thresholds]
+        dist = [float(d) for d in dist_thresholds]
+        if len(iou) != len(dist):
+            raise L.RcvError("object_match: %d IoU thresholds but %d distance thresholds" % (len(iou), len(dist)))
+        self.K = len(iou)
+        self.iou = (ctypes.c_double * max(self.K, 1))(*iou)
+        self.dist = (ctypes.c_double * max(self.K, 1))(*dist)
+        self.op = L.make_op(L.OP_OBJECT_MATCH, 0, n=N, h=H, w=W, cout=num_class, count=self.K, inmode=pred_bytes,
+                            inmode2=target_bytes, p_x0=ctypes.addressof(self.iou), p_x1=ctypes.addressof(self.dist))
+
+    def workspace_bytes(self, h) -> int:
+        """rcv_op_workspace: refuses the record (RcvError with the library's message) exactly as an enqueue would."""
+        return L.op_workspace(h, self.op)
+
+
+def object_match_counts(pred: torch.Tensor, target: torch.Tensor, num_class: int, iou_thresholds=DEFAULT_IOU_THRESHOLDS,
+                        dist_thresholds=DEFAULT_DIST_THRESHOLDS, workspace: torch.Tensor | None = None) -> torch.Tensor:
+    """The raw counts of RCV_OP_OBJECT_MATCH: int32 [N][C-1][2+2K] = {nPred, nTrue, nCorrIoU[K], nCorrDist[K]} per image and class
+    1..C-1 (rcv.h rcv_object_match).  pred: uint8 (CrossEntropyLoss2d.last_argmax) or int64 (torch.max(pred,1)[1]) [N,H,W];
+    target: int64 or uint8 [N,H,W]; both on the HIP device.  Enqueued on the current stream; nothing synchronises."""
+    if pred.device.type != "cuda" or target.device.type != "cuda" or pred.device != target.device:
+        raise L.RcvError("object_match_counts needs pred and target on one HIP device (there is no CPU path)")
+    if pred.dim() != 3 or pred.shape != target.shape:
+        raise L.RcvError("object_match_counts: pred %s and target %s must both be [N,H,W]" % (tuple(pred.shape), tuple(target.shape)))
+    pb = _elem_bytes(pred, "object_match_counts pred", (torch.uint8, torch.int64))
+    tb = _elem_bytes(target, "object_match_counts target", (torch.int64, torch.uint8))
+    N, H, W = pred.shape
+    pred, target = pred.contiguous(), target.contiguous()
+    rec = ObjectMatchRecord(N, H, W, num_class, iou_thresholds, dist_thresholds, pb, tb)
+    dev = pred.device
+    h = L.handle(dev.index if dev.index is not None else torch.cuda.current_device())
+    nbytes = rec.workspace_bytes(h)
+    if workspace is None or workspace.numel() < nbytes or workspace.device != dev:
+        workspace = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    counts = torch.empty(N, num_class - 1, 2 + 2 * rec.K, dtype=torch.int32, device=dev)
+    op = rec.op
+    op.p[L.RCV_P_IN], op.p[L.RCV_P_IN2] = pred.data_ptr(), target.data_ptr()
+    op.p[L.RCV_P_OUT], op.p[L.RCV_P_PART] = counts.data_ptr(), workspace.data_ptr()
+    L.OpList([op]).run(h, torch.cuda.current_stream(dev).cuda_stream)
+    return counts
+
+
+def detection_scores(batches, num_class: int, K: int):
+    """test.py's numbers from the counts of each update() (a list of int arrays [B][C-1][2+2K]): per batch and threshold pair,
+    prec / recall summed over c (outer) and b (inner) in Python float64, batch value (prec/(C-1) + recall/(C-1))/2, summed over the
+    batches (test.py:28-89,258-262).  Returns the two lists of sums [K] (IoU, distance); divide by the image count (test.py:183)."""
+    sums = [[0.0] * K, [0.0] * K]
+    for cnt in batches:
+        rows = cnt.tolist()
+        B = len(rows)
+        for crit in range(2):
+            for k in range(K):
+                j = 2 + crit * K + k
+                prec = 0.0
+                rec = 0.0
+                for c in range(num_class - 1):
+                    for b in range(B):
+                        n_pred, n_true, n_corr = rows[b][c][0], rows[b][c][1], rows[b][c][j]
+                        prec += n_corr / n_pred if n_pred != 0 else 1
+                        rec += n_corr / n_true if n_true != 0 else 1
+                sums[crit][k] += (prec / (num_class - 1) + rec / (num_class - 1)) / 2
+    return sums
+
+
+class DetectionMetrics:
+    """The `IoU:` / `Dist:` rows of test.py's validation.  update() enqueues one op per batch (the counts stay on the device);
+    compute() synchronises once and returns {"iou": [K], "dist": [K], "images": n} with test.py's float64 values."""
+
+    def __init__(self, num_class: int, iou_thresholds=DEFAULT_IOU_THRESHOLDS, dist_thresholds=DEFAULT_DIST_THRESHOLDS, device="cuda"):
+        self.C = num_class
+        self.iou_thresholds = tuple(float(t) for t in iou_thresholds)
+        self.dist_thresholds = tuple(float(d) for d in dist_thresholds)
+        self.K = len(self.iou_thresholds)
+        self.device = torch.device(device)
+        # the arguments are refused here, with the library's message, rather than at the first update
+        ObjectMatchRecord(1, 1, 1, num_class, self.iou_thresholds, self.dist_thresholds).workspace_bytes(L.planner_handle())
+        self._ws = None
+        self.reset()
+
+    def reset(self):
+        self._counts = []
+        self.n_img = 0
+
+    def update(self, pred_class: torch.Tensor, targets: torch.Tensor):
+        """pred_class: uint8 or int64 [B,H,W] class map on the HIP device; targets: int64 or uint8 [B,H,W]."""
+        if pred_class.device.type != "cuda":
+            raise L.RcvError("DetectionMetrics.update needs the class map on the HIP device (there is no CPU path)")
+        if targets.device != pred_class.device:
+            targets = targets.to(pred_class.device, non_blocking=True)
+        B, H, W = pred_class.shape
+        rec = ObjectMatchRecord(B, H, W, self.C, self.iou_thresholds, self.dist_thresholds)
+        h = L.handle(pred_class.device.index if pred_class.device.index is not None else torch.cuda.current_device())
+        need = rec.workspace_bytes(h)
+        if self._ws is None or self._ws.numel() < need or self._ws.device != pred_class.device:
+            self._ws = torch.empty(need, dtype=torch.uint8, device=pred_class.device)
+        self._counts.append(object_match_counts(pred_class, targets, self.C, self.iou_thresholds, self.dist_thresholds, self._ws))
+        self.n_img += B
+
+    def compute(self) -> dict:
+        if not self._counts:
+            return {"iou": [0.0] * self.K, "dist": [0.0] * self.K, "images": 0}
+        sizes = [c.shape[0] for c in self._counts]
+        host = torch.cat(self._counts).cpu().numpy()        # the one synchronisation
+        batches, at = [], 0
+        for b in sizes:
+            batches.append(host[at:at + b])
+            at += b
+        iou, dist = detection_scores(batches, self.C, self.K)
+        return {"iou": [v / self.n_img for v in iou], "dist": [v / self.n_img for v in dist], "images": self.n_img}
