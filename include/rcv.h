@@ -96,10 +96,27 @@ enum {
                              * (1..8 classes) -> NCHW logits; the pooled features [N][HO][WO][C] go to p[X1] (csrc/pool_cls.hip) */
   RCV_OP_POOL_CLS_BWD = 31, /* its backward: dW (p[X2]), db (p[X3]) and d loss / d load(r) NHWC (first arg-max of a max window; the
                              * mean's share of every pixel), RCV_F_RESID, RCV_STATS_BWD_ENC / _DEC partial rows of the producer  */
-  RCV_OP_OBJECT_MATCH = 32  /* object-detection counts of test.py:28-89 (rcv_object_match; csrc/objdet.hip): i[N], i[H], i[W], i[COUT] = C,
+  RCV_OP_OBJECT_MATCH = 32, /* object-detection counts of test.py:28-89 (rcv_object_match; csrc/objdet.hip): i[N], i[H], i[W], i[COUT] = C,
                              * i[COUNT] = K, i[INMODE] / i[INMODE2] = element bytes of p[IN] pred / p[IN2] target (1 = uint8, 8 = int64);
                              * p[X0] / p[X1] = HOST double[K] IoU / distance thresholds (read when enqueued), p[OUT] = counts, p[PART] =
                              * workspace, i[NPART] = its size in 256-byte units (filled by rcv_op_workspace)                          */
+  RCV_OP_LP_TAIL_FWD = 33,  /* LabelProp's tail in training mode (model.py:563-567: x = upConv3(x); x[:,0:8] += top; classifier(x)), one launch
+                             * (csrc/lp_tail.hip): logits = W v + b, v[c] = relu(t[c]*c0[c] + c1[c]) + (c < i[AUX1] ? f(r[c]) : 0) -- the ReLU is
+                             * taken BEFORE the skip is added (the out-of-place form of that line).  Slots as RCV_OP_CLS_FWD with RCV_F_FUSED_UP
+                             * (required): i[CIN] = 16, i[COUT] = 1..8 classes, p[IN] = t (NHWC, 16 channels), p[IN_C] = its constants, p[X3] = skip
+                             * tensor r (NHWC, i[AUX1] channels: a multiple of 4, 4..16), p[X4] = its constants, i[AUX0] = its load mode (PLAIN /
+                             * AFFINE / AFFINE_RELU), p[W], p[BIAS], p[OUT] = NCHW logits.  RCV_F_FUSED_CE: also the weighted cross entropy, as
+                             * documented at that flag (same partial rows and finalisation as RCV_OP_CE_FWD)                               */
+  RCV_OP_LP_TAIL_BWD = 34,  /* its backward, one launch + the fixed-order row reduction.  Slots as RCV_OP_CLS_BWD with RCV_F_FUSED_UP (required),
+                             * i[STATS] = RCV_STATS_BWD_DEC (required), i[AUX0] / i[AUX1] / p[X3] / p[X4] as the forward, p[EPI_AUX] = t, p[EPI_C] =
+                             * its constants (row 2 = batch mean), p[IN2] = NCHW logits gradient -- or, with RCV_F_FUSED_CE, the int64 target and
+                             * the other operands of that flag; outputs: p[OUT] = g = W^T dlogits (NHWC, 16 channels: the gradient of the decoder
+                             * block's output, its statistics rows in p[PART]), p[IN_AUX] = g[..., 0:i[AUX1]] as a dense NHWC tensor (the skip
+                             * tensor's gradient: handed to the data-gradient launch of its other consumer as RCV_F_RESID), p[X1] = dW
+                             * [COUT][16], p[X2] = db                                                                                         */
+  RCV_OP_LP_BATCH = 35      /* batch assembly of labelPropTrain.py:162-193 (rcv_labelprop_batch; csrc/lp_tail.hip): i[N] = B frame pairs, i[CIN] =
+                             * channels per frame, i[H], i[W], i[COUT] = classes (5); p[IN] = images float[B][2][C][H][W], p[IN2] = labels
+                             * int64[B][2][H][W], p[OUT] = inputs float[2B][H][W][8] (NHWC), p[X0] = targets int64[2B][H][W]              */
 };
 
 /* how an operand is produced from memory while it is staged (rcv_op.i[RCV_I_INMODE] etc.) */
@@ -328,6 +345,14 @@ int rcv_confusion(rcv_handle* h, const uint8_t* argmax, const int64_t* target, i
  * threshold arrays are host memory, read before the call returns.  ws: rcv_op_workspace bytes of the RCV_OP_OBJECT_MATCH record.  */
 int rcv_object_match(rcv_handle* h, const void* pred, int pred_bytes, const void* target, int target_bytes, int N, int C, int H, int W,
                      const double* iou_thr, const double* dist_thr, int K, int32_t* counts, void* ws, size_t ws_bytes, void* stream);
+
+/* The batch assembly of labelPropTrain.py:162-193 in one launch: for every frame pair b, inputs[2b] = [Ya, Yb, Ya - Yb,
+ * labelToPred(label_b)], targets[2b] = label_a, and the swapped sample at 2b + 1; Y = channel 0 of a frame, labelToPred
+ * (transform.py:172-183) = -1 everywhere and +1 at the label's class.  images float[B][2][C][H][W], labels int64[B][2][H][W], inputs
+ * float[2B][H][W][8] (NHWC: what the network's first conv reads), targets int64[2B][H][W].  num_class must be 5.  A label outside
+ * [0, 5) gives -1 in all five class channels (it is never used as an index).  Exact: copies, +-1 and one fp32 subtraction.        */
+int rcv_labelprop_batch(rcv_handle* h, const float* images, const int64_t* labels, int B, int C, int H, int W, int num_class,
+                        float* inputs, int64_t* targets, void* stream);
 
 /* torch.optim.SGD.step (trainer.py:176-178,221): g = grad*grad_scale + weight_decay*p; buf = step==1 ? g : momentum*buf + g;
  * p -= lr*buf.  lr_elem (may be NULL) gives a per-element learning rate (0 = parameter without a gradient: untouched). */

@@ -4,3 +4,12 @@ hand-written HIP kernels for MI355X (gfx950), behind the reference's nn.Module s
     from robocupvision_amd.model import ROBO_UNet, CrossEntropyLoss2d      # drop-in for `from model import *`
 """
 __version__ = "0.1.0"
+
+
+def __getattr__(name):
+    # robocupvision_amd.labelprop_batch(images, labels): the batch assembly of labelPropTrain.py (model.py); imported on first use so
+    # that `import robocupvision_amd` stays free of torch
+    if name == "labelprop_batch":
+        from .model import labelprop_batch
+        return labelprop_batch
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))

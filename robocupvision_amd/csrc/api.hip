@@ -109,6 +109,11 @@ static int dispatch(const rcv_handle* h, const rcv_op* op, hipStream_t s, OpQuer
       return rcv_launch_pool_cls(h, op, s, q);
     case RCV_OP_OBJECT_MATCH:
       return rcv_launch_objdet(h, op, s, q);
+    case RCV_OP_LP_TAIL_FWD:
+    case RCV_OP_LP_TAIL_BWD:
+      return rcv_launch_lp_tail(h, op, s, q);
+    case RCV_OP_LP_BATCH:
+      return rcv_launch_lp_batch(h, op, s, q);
     case RCV_OP_NOP:
       if (q) { snprintf(q->label, sizeof(q->label), "nop"); q->n_part = 0; q->n_split = 0; q->part_bytes = 0; }
       return RCV_OK;
@@ -367,6 +372,16 @@ int rcv_object_match(rcv_handle* h, const void* pred, int pred_bytes, const void
   const int rc = rcv_op_workspace(h, &op, &need);
   if (rc) return rc;
   RCV_CHECK_ARG(ws_bytes >= need, "rcv_object_match: workspace of %zu bytes given, %zu needed (rcv_op_workspace)", ws_bytes, need);
+  return rcv_run(h, &op, 1, stream);
+}
+
+int rcv_labelprop_batch(rcv_handle* h, const float* images, const int64_t* labels, int B, int C, int H, int W, int num_class,
+                        float* inputs, int64_t* targets, void* stream) {
+  rcv_op op;
+  memset(&op, 0, sizeof(op));
+  op.kind = RCV_OP_LP_BATCH;
+  op.i[RCV_I_N] = B; op.i[RCV_I_H] = H; op.i[RCV_I_W] = W; op.i[RCV_I_CIN] = C; op.i[RCV_I_COUT] = num_class;
+  op.p[RCV_P_IN] = (void*)images; op.p[RCV_P_IN2] = (void*)labels; op.p[RCV_P_OUT] = inputs; op.p[RCV_P_X0] = targets;
   return rcv_run(h, &op, 1, stream);
 }
 

@@ -1599,3 +1599,16 @@ int rcv_launch_small(const rcv_handle* h, const rcv_op* op, hipStream_t s, OpQue
   RCV_HIP(hipGetLastError());
   return RCV_OK;
 }
+
+// The two fixed-order reductions above, for the translation unit that shares them (lp_tail.hip: the partial rows of LabelProp's tail
+// are finalised by the very kernels that finalise the 8-channel classifier's).
+int rcv_enqueue_ce_finalize(const float* part, int n_part, float* loss_out, hipStream_t s) {
+  hipLaunchKernelGGL(ce_finalize_kernel, dim3(1), dim3(256), 0, s, part, n_part, loss_out);
+  RCV_HIP(hipGetLastError());
+  return RCV_OK;
+}
+int rcv_enqueue_rows_reduce(const float* part, int n_rows, int width, float* out0, int n0, float* out1, hipStream_t s) {
+  hipLaunchKernelGGL(rows_reduce_kernel, dim3(width), dim3(256), 0, s, part, n_rows, width, out0, n0, out1);
+  RCV_HIP(hipGetLastError());
+  return RCV_OK;
+}

@@ -470,7 +470,9 @@ class _Lowering:
         logits = self.eng._alloc(self.plan, self.N, Cout, src.H, src.W)
         if tuple(w.shape[2:]) == (1, 1) and src.kind == "fused_up":
             tt, skip = src.fused
-            self.fwd.append(L.make_op(L.OP_CLS_FWD, L.F_FUSED_UP, n=self.N, h=src.H, w=src.W, cin=Cin, cout=Cout, aux0=skip.load_mode,
+            # (LabelProp's tail in a training plan is a record of its own kind, rcv.h RCV_OP_LP_TAIL_FWD; inference keeps the classifier's)
+            kind = L.OP_LP_TAIL_FWD if getattr(src, "fused_src", None) is not None else L.OP_CLS_FWD
+            self.fwd.append(L.make_op(kind, L.F_FUSED_UP, n=self.N, h=src.H, w=src.W, cin=Cin, cout=Cout, aux0=skip.load_mode,
                                  aux1=getattr(src, "fused_rch", 0),
                                  p_in=tt.data_ptr(), p_in_c=src.consts.data_ptr(), p_x3=skip.buf.data_ptr(), p_x4=_ptr(skip.consts),
                                  p_w=w.data_ptr(), p_bias=_ptr(b), p_out=logits.data_ptr()))
@@ -503,9 +505,25 @@ class _Lowering:
         src, add = self.ref(d["src"]), self.ref(d["add"])
         if (add.H, add.W) != (src.H, src.W) or add.C > src.C:
             raise L.RcvError("add_slice: operand shapes do not match")
-        if (FUSE_UP_INTO_CLS and not self.training and src.kind == "affine_relu" and src.C == 16 and add.C % 4 == 0 and add.buf is not None
+        tail = (src.kind == "affine_relu" and src.C == 16 and add.C % 4 == 0 and add.buf is not None
                 and add.input_index is None and src.input_index is None and add.kind in ("plain", "affine", "affine_relu")
-                and self.only_consumer_is_cls1x1(node.idx)):
+                and self.only_consumer_is_cls1x1(node.idx))
+        if self.training:
+            # Training lowers the fused-tail form only: the classifier node owns the whole backward of the tail (filter and bias gradient,
+            # the gradient of the decoder block with its BatchNorm-backward sums, the skip gradient of `add`); add_slice emits nothing.
+            if not (tail and src.producer is not None and src.producer.op == "up" and add.producer is not None):
+                raise L.RcvError("add_slice in a training graph is built for LabelProp's tail only (model.py:563-567): a 16-channel decoder "
+                                 "block (conv-transpose, BatchNorm, ReLU) plus a stored block output of 4, 8, 12 or 16 channels, read by "
+                                 "nothing but a 1x1 classifier of at most 8 classes; this graph adds %d channels of a '%s' value to a "
+                                 "'%s' value of %d channels -- run it in eval mode" % (add.C, add.kind, src.kind, src.C))
+            # (the value's producer is the DECODER block, as for ROBO-UNet's fused tail: grad_target routes the gradient buffer and the
+            # statistics rows there; bwd_cls hands the buffer to the block's own output value)
+            node.out = Value("fused_up", None, src.C, src.H, src.W, src.consts, src.producer)
+            node.out.fused = (src.buf, add)
+            node.out.fused_rch = add.C
+            node.out.fused_src = src
+            return
+        if FUSE_UP_INTO_CLS and tail:
             # LabelProp's tail (model.py:563-567): the 1x1 classifier forms relu(bn(t)) and adds the skip to its first add.C input
             # channels itself (RCV_F_FUSED_UP with i[RCV_I_AUX1] = add.C): no RCV_OP_MATERIALIZE / RCV_OP_ADD_SLICE passes
             node.out = Value("fused_up", None, src.C, src.H, src.W, src.consts, node)
@@ -659,11 +677,24 @@ class _Lowering:
             op.i[L.RCV_I_AUX0] = skip.load_mode
             op.p[L.RCV_P_X3] = skip.buf.data_ptr()
             op.p[L.RCV_P_X4] = _ptr(skip.consts) or None
+            rch = getattr(src, "fused_rch", 0)
+            if rch:
+                # LabelProp's tail: the skip reaches the first rch channels only.  The kernel writes those channels of the data gradient
+                # a second time, densely: `skip`'s skip gradient, added by the data-gradient launch of its other consumer (RCV_F_RESID)
+                op.kind = L.OP_LP_TAIL_BWD
+                op.i[L.RCV_I_AUX1] = rch
+                skip.skip_grad = self.eng._alloc(self.plan, self.N, src.H, src.W, rch)
+                op.p[L.RCV_P_IN_AUX] = skip.skip_grad.data_ptr()
         if src.input_index is not None:
             self.plan.input_slots[src.input_index].append((True, len(self.bwd), L.RCV_P_IN))
         self.plan.dlogits_slots.append((len(self.bwd), L.RCV_P_IN2))
         self.grad_target(src, op, src.H, src.W)
+        if getattr(src, "fused_src", None) is not None:
+            src.fused_src.grad = src.grad          # the decoder block's own output value: bwd_up reads its gradient there
         self.bwd.append(op)
+
+    def bwd_add_slice(self, node: _Node):
+        pass        # (training lowers the fused tail only, fwd_add_slice: the classifier's backward op has done this node's work)
 
     def bwd_pool_cls(self, node: _Node):
         d = node.d
@@ -821,8 +852,6 @@ class _Lowering:
         if self.training:
             # which values need a gradient: everything produced by a node, plus flagged inputs
             for node in self.nodes:
-                if node.op == "add_slice":
-                    raise L.RcvError("this graph is inference only (add_slice has no backward); call .eval()")
                 if node.op not in ("cls", "mat", "pool_cls"):
                     node.out.needs_grad = True
 
@@ -1129,14 +1158,15 @@ class Engine:
             nbytes = 1024.0 * i[L.RCV_I_AUX0]          # the folded reductions' bytes (set when the group was built)
         elif k in (L.OP_BN_FINALIZE, L.OP_BN_BWD):
             nbytes = 4.0 * i[L.RCV_I_NPART] * 2 * cout
-        elif k == L.OP_CLS_FWD:
+        elif k in (L.OP_CLS_FWD, L.OP_LP_TAIL_FWD):
             flops = 2.0 * cin * cout * px
             skip_c = (i[L.RCV_I_AUX1] or cin) if op.flags & L.F_FUSED_UP else 0
             nbytes = 4.0 * px * (cin + skip_c + cout) + (px * 9.0 if op.flags & L.F_FUSED_CE else 0.0)
-        elif k == L.OP_CLS_BWD:
+        elif k in (L.OP_CLS_BWD, L.OP_LP_TAIL_BWD):
             flops = 2.0 * 2 * cin * cout * px        # data gradient + filter gradient
-            src = cin * (2 if op.flags & L.F_FUSED_UP else 1)
-            nbytes = 4.0 * px * (src + cin + (0 if op.flags & L.F_FUSED_CE else cout)) + (px * 8.0 if op.flags & L.F_FUSED_CE else 0.0)
+            rch = i[L.RCV_I_AUX1] if op.flags & L.F_FUSED_UP else 0      # (LabelProp's tail: a narrower skip, and its gradient written too)
+            src = cin + ((rch or cin) if op.flags & L.F_FUSED_UP else 0)
+            nbytes = 4.0 * px * (src + cin + rch + (0 if op.flags & L.F_FUSED_CE else cout)) + (px * 8.0 if op.flags & L.F_FUSED_CE else 0.0)
         elif k in (L.OP_CE_FWD, L.OP_DICE_FWD):
             nbytes = px * (4.0 * cout + 8 + 1)
         elif k in (L.OP_CE_BWD, L.OP_DICE_BWD):
@@ -1298,8 +1328,8 @@ class Engine:
         plan.ce = False
         if plan.bwd is None or plan.bwd.n == 0:
             return None
-        kf = [k for k in range(plan.fwd.n) if plan.fwd.arr[k].kind == L.OP_CLS_FWD and plan.fwd.arr[k].flags & L.F_FUSED_UP]
-        kb = [k for k in range(plan.bwd.n) if plan.bwd.arr[k].kind == L.OP_CLS_BWD and plan.bwd.arr[k].flags & L.F_FUSED_UP]
+        kf = [k for k in range(plan.fwd.n) if plan.fwd.arr[k].kind in (L.OP_CLS_FWD, L.OP_LP_TAIL_FWD) and plan.fwd.arr[k].flags & L.F_FUSED_UP]
+        kb = [k for k in range(plan.bwd.n) if plan.bwd.arr[k].kind in (L.OP_CLS_BWD, L.OP_LP_TAIL_BWD) and plan.bwd.arr[k].flags & L.F_FUSED_UP]
         if len(kf) != 1 or len(kb) != 1 or kf[0] != plan.fwd.n - 1 or kb[0] != 0:
             return None
         fops = [L.RcvOp.from_buffer_copy(plan.fwd.arr[k]) for k in range(plan.fwd.n)]

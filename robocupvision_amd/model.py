@@ -23,7 +23,7 @@ from . import _lib as L
 from .engine import Engine
 
 __all__ = ["ROBO_UNet", "CrossEntropyLoss2d", "DiceLoss", "PB_FCN", "PB_FCN_2", "LabelProp", "Conv", "Pool", "LevelDown",
-           "upSampleTransposeConv", "UltClassifier", "ConvPoolSimple", "ConvPool", "DownSampler", "Classifier", "pruneModelNew",
+           "labelprop_batch", "upSampleTransposeConv", "UltClassifier", "ConvPoolSimple", "ConvPool", "DownSampler", "Classifier", "pruneModelNew",
            "count_zero_weights", "getParamSize"]
 
 
@@ -552,7 +552,7 @@ class DiceLoss(nn.Module):
 
 
 # ------------------------------------------------------------------------------------------
-# LabelProp (model.py:538-567), inference only
+# LabelProp (model.py:538-567) and the batch assembly of its training script (labelPropTrain.py:162-193)
 # ------------------------------------------------------------------------------------------
 class LabelProp(_EngineOwner, nn.Module):
     def __init__(self, numClass, numPlanes, dropout=0.0):
@@ -591,17 +591,71 @@ class LabelProp(_EngineOwner, nn.Module):
         add({"op": "cls", "src": x, "weight": self.classifier.weight, "bias": self.classifier.bias})
         return {"inputs": [{"layout": "nhwc", "requires_grad": False}], "nodes": nodes}
 
-    def forward(self, x):
-        """Inference only (BASELINE config 5): x float32 [B,8,H,W] -> logits [B,numClass,H,W]."""
-        if self.training:
-            raise L.RcvError("LabelProp is built for inference only; call .eval()")
-        if x.dim() != 4 or x.shape[1] != 8 or x.shape[2] % 8 or x.shape[3] % 8:
-            raise ValueError("LabelProp expects float32 [B,8,H,W] with H,W multiples of 8, got %s" % (tuple(x.shape),))
+    def _get_engine(self) -> Engine:
         eng = self.__dict__.get("_engine")
-        if eng is None:
+        mode = _graph_mode(self)
+        if eng is None or self.__dict__.get("_engine_mode") != mode:
             eng = Engine(self._graph(), list(self.parameters()), _bn_modules(self))
             self.__dict__["_engine"] = eng
-        return _run_engine(eng, False, [x.to(torch.float32).permute(0, 2, 3, 1).contiguous()])
+            self.__dict__["_engine_mode"] = mode
+        return eng
+
+    def _engine_inputs(self, x):
+        """The engine reads the 8-channel input NHWC.  For a tensor whose memory already is NHWC (``labelprop_batch``, or
+        ``x.contiguous(memory_format=torch.channels_last)``) the permutation is a view and nothing is copied.  A TRAINING forward takes
+        only such a tensor: the first conv's filter gradient reads the input again in backward, so a re-laid-out copy would be a hidden
+        full-resolution pass per step plus a tensor the engine would have to keep alive behind the caller's back -- the step's input
+        is ``labelprop_batch``'s output, which has the layout already.  Inference re-lays a plain NCHW tensor out itself, as it always did."""
+        if x.dim() != 4 or x.shape[1] != 8 or x.shape[2] % 8 or x.shape[3] % 8:
+            raise ValueError("LabelProp expects float32 [B,8,H,W] with H,W multiples of 8, got %s" % (tuple(x.shape),))
+        if x.requires_grad and self.training:
+            raise L.RcvError("LabelProp does not produce a gradient for its input (labelPropTrain.py assembles it from frames and "
+                             "labels); pass a tensor with requires_grad=False")
+        nhwc = x.detach().to(torch.float32).permute(0, 2, 3, 1)
+        if self.training and not nhwc.is_contiguous():
+            raise L.RcvError("LabelProp in training mode reads its input as NHWC memory and makes no hidden copy of it: pass what "
+                             "labelprop_batch(images, labels) returns, or x.contiguous(memory_format=torch.channels_last) "
+                             "(got strides %s for shape %s); eval mode takes any layout" % (tuple(x.stride()), tuple(x.shape)))
+        return [nhwc.contiguous()]
+
+    def forward(self, x):
+        """x float32 [B,8,H,W] -> logits [B,numClass,H,W] (model.py:556-567).  In training mode the tail is the out-of-place form of
+        ``x[:,0:8] = x[:,0:8] + top``: upConv3's ReLU mask is taken from its own output, before the skip is added; the input must then be
+        NHWC in memory (``labelprop_batch``'s output, or ``memory_format=torch.channels_last``), see ``_engine_inputs``."""
+        return _run_engine(self._get_engine(), self.training, self._engine_inputs(x))
+
+
+def labelprop_batch(images, labels, num_class=5):
+    """The batch assembly of labelPropTrain.py:162-193 in one launch (RCV_OP_LP_BATCH).
+
+    ``images`` float32 [B,2,C,H,W] (frame pairs; only channel 0 of each frame is read, as the script does) and ``labels`` int64
+    [B,2,H,W] -> ``(inputs, targets)``: ``inputs`` of logical shape [2B,8,H,W] whose MEMORY is NHWC (``LabelProp`` reads it without a
+    copy), ``targets`` int64 [2B,H,W].  ``inputs[2b] = [Ya, Yb, Ya - Yb, labelToPred(label_b)]``, ``targets[2b] = label_a``, and the
+    swapped sample at ``2b + 1``; labelToPred (transform.py:172-183) is -1 everywhere and +1 at the label's class.  A label outside
+    [0, 5) cannot be refused without a host synchronisation (torch's ``scatter_`` would raise): such a pixel gets -1 in all five class
+    channels and the label is never used as an index.  Exact: copies, +-1 and one fp32 subtraction."""
+    if num_class != 5:
+        raise ValueError("labelprop_batch: num_class must be 5 (LabelProp's first conv reads 3 + 5 channels), got %r" % (num_class,))
+    if not (torch.is_tensor(images) and torch.is_tensor(labels)):
+        raise TypeError("labelprop_batch: images and labels must be tensors")
+    if images.dtype != torch.float32 or labels.dtype != torch.int64:
+        raise TypeError("labelprop_batch: images must be float32 and labels int64 (got %s, %s)" % (images.dtype, labels.dtype))
+    if images.dim() != 5 or images.shape[1] != 2 or images.shape[2] < 1 or labels.dim() != 4:
+        raise ValueError("labelprop_batch: images must be [B,2,C,H,W] and labels [B,2,H,W] (got %s, %s)"
+                         % (tuple(images.shape), tuple(labels.shape)))
+    B, _, Cc, H, W = images.shape
+    if tuple(labels.shape) != (B, 2, H, W) or B < 1 or H < 1 or W < 1:
+        raise ValueError("labelprop_batch: labels %s do not match images %s" % (tuple(labels.shape), tuple(images.shape)))
+    if images.device.type != "cuda" or labels.device != images.device:
+        raise L.RcvError("labelprop_batch runs on the HIP device only (images on %s, labels on %s)" % (images.device, labels.device))
+    images, labels = images.contiguous(), labels.contiguous()
+    dev = images.device
+    h = L.handle(dev.index if dev.index is not None else torch.cuda.current_device())
+    inputs = torch.empty(2 * B, H, W, 8, dtype=torch.float32, device=dev)
+    targets = torch.empty(2 * B, H, W, dtype=torch.int64, device=dev)
+    L.check(L.load().rcv_labelprop_batch(h, images.data_ptr(), labels.data_ptr(), B, Cc, H, W, num_class, inputs.data_ptr(),
+                                         targets.data_ptr(), torch.cuda.current_stream(dev).cuda_stream), "rcv_labelprop_batch")
+    return inputs.permute(0, 3, 1, 2), targets
 
 
 # ------------------------------------------------------------------------------------------

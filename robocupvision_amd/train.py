@@ -21,7 +21,7 @@ from typing import Optional, Sequence
 import torch
 
 from . import _lib as L
-from .model import CrossEntropyLoss2d, DiceLoss
+from .model import CrossEntropyLoss2d, DiceLoss, LabelProp
 from .optim import AdamL1
 
 
@@ -91,6 +91,8 @@ class Trainer:
                  decay: float = 1e-6, transfer: int = 0, distributed: bool = False, overlap: bool = True,
                  use_dice: bool = False, optimizer=None, fuse_loss: bool = True, prune_indices=None):
         self.model = model
+        if distributed and isinstance(model, LabelProp):
+            raise L.RcvError("data-parallel training of LabelProp is not built; train it on one GPU (labelPropTrain.py runs on one)")
         dev = next(model.parameters()).device
         if dev.type != "cuda":
             raise L.RcvError("Trainer needs the model on the HIP device (model.cuda())")
@@ -156,14 +158,16 @@ class Trainer:
         if exchanging:
             self.exchange.begin()
         fused = None
-        if self.fuse_loss and type(crit) is CrossEntropyLoss2d and imgs.dtype == torch.float32 and imgs.is_contiguous():
+        # (LabelProp reads its input NHWC: the model hands the engine a view of the assembled batch, model.py _engine_inputs)
+        ins = model._engine_inputs(imgs) if hasattr(model, "_engine_inputs") else [imgs]
+        if self.fuse_loss and type(crit) is CrossEntropyLoss2d and ins[0].dtype == torch.float32 and ins[0].is_contiguous():
             # fast path: the loss is evaluated inside the classifier op and its gradient inside the classifier's backward op
             # (no logits-gradient tensor, no separate loss kernels, no autograd graph); bit-identical to the path below
             w = crit.weight
             if w is not None and w.device != imgs.device:
                 w = w.to(imgs.device)
                 crit.weight = w
-            fused = eng.forward_ce([imgs], targets.to(torch.int64).contiguous(), w)
+            fused = eng.forward_ce(ins, targets.to(torch.int64).contiguous(), w)
         if fused is not None:
             pred, out, argmax = fused
             crit.last_stats, crit.last_argmax = out, argmax
