@@ -2,7 +2,7 @@
 //
 // The roles conv_wino.hip serves (forward of Conv2d(k3, pad 1) and the data gradient of the same layer, with the load transforms and
 // epilogues of conv_mfma.hip), as a DIRECT convolution: every fp32 operand is split exactly into three bf16 values (x = h + m + l, see
-// wgrad_bf3.hip for the arithmetic and its error against fp64) and each multiply-add is six v_mfma_f32_16x16x32_bf16 products.  Nine taps
+// split_bf16.h for the arithmetic and its error against fp64) and each multiply-add is six v_mfma_f32_16x16x32_bf16 products.  Nine taps
 // x 6/16 of an fp32 MFMA = 3.4 fp32-MFMA equivalents per output element and input channel against 4.0 for Winograd F(2x2,3x3) on the
 // fp32 instruction -- without its input / output transforms, which kept the matrix pipe of conv_wino 40 % busy.
 //
@@ -21,76 +21,12 @@
 // MFMA loop of the micro-benchmark is 20 % faster in that form; the kernel was SLOWER: 128 -> 128 0.065 -> 0.069 ms forward,
 // 0.070 -> 0.080 data gradient, 64 -> 64 0.074 -> 0.083 / 0.085 -> 0.101, results identical to 1e-6.)
 #include <type_traits>
-#include "conv_common.h"
+#include "conv_bf3_stage.h"
 #include "conv_epilogue.h"
-
-typedef __bf16 c3_bf16x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 c3_bf16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int C3_PITCH = 192;             // bytes per staged pixel (stride-1 form): three planes of 32 bf16
 constexpr int C3_NU = 13;                 // staging passes (256 / (CH / 4) pixels each): tiles with halo up to 416 (CH = 32) / 832 (CH = 16) pixels
 constexpr int C3_COT = 64;
-
-__device__ __forceinline__ uint32_t c3_pack(float a, float b) {
-  const c3_bf16x2 v = {(__bf16)a, (__bf16)b};            // v_cvt_pk_bf16_f32 (round to nearest even)
-  return __builtin_bit_cast(uint32_t, v);
-}
-struct C3Tri { uint32_t h, m, l; };
-__device__ __forceinline__ C3Tri c3_split2(float x0, float x1) {
-  C3Tri t;
-  t.h = c3_pack(x0, x1);
-  const float r0 = x0 - __uint_as_float(t.h << 16), r1 = x1 - __uint_as_float(t.h & 0xffff0000u);       // exact
-  t.m = c3_pack(r0, r1);
-  const float s0 = r0 - __uint_as_float(t.m << 16), s1 = r1 - __uint_as_float(t.m & 0xffff0000u);       // exact
-  t.l = c3_pack(s0, s1);
-  return t;
-}
-
-template <bool TWO>
-struct C3Regs {
-  float4 x[C3_NU], ax[TWO ? C3_NU : 1];
-  bool ok[C3_NU];
-};
-
-// all loads of one CH-channel chunk of the tile (CH / 4 threads per pixel, 256 / (CH / 4) pixels per pass)
-template <bool TWO, int CH = 32>
-__device__ __forceinline__ void c3_load(C3Regs<TWO>& r, const ConvArgs& a, const TileInfo& ti, int c0, int tid, int npix) {
-  constexpr int Q = CH / 4, PP = 256 / Q;
-  const int q = tid % Q, lp = tid / Q;
-#pragma unroll
-  for (int u = 0; u < C3_NU; ++u) {
-    const int pix = u * PP + lp;
-    const int iy = fd_div(pix, a.fdIW), ix = pix - iy * a.IW;
-    const int gy = ti.oy0 + iy, gx = ti.ox0 + ix;
-    r.ok[u] = pix < npix && (unsigned)gy < (unsigned)a.H && (unsigned)gx < (unsigned)a.W;
-    const uint32_t o = r.ok[u] ? (uint32_t)(((ti.n * a.H + gy) * a.W + gx) * a.Cin + c0 + 4 * q) : 0u;
-    r.x[u] = ld4(a.in + o);
-    if (TWO) r.ax[u] = ld4(a.in_aux + o);
-  }
-}
-template <int MODE, bool TWO, int CH = 32>
-__device__ __forceinline__ void c3_store(const C3Regs<TWO>& r, const ConvArgs& a, char* img, int c0, int tid, int npix) {
-  constexpr int Q = CH / 4, PP = 256 / Q;
-  const int q = tid % Q, lp = tid / Q;
-  float4 k[5];
-  if (MODE != RCV_LOAD_PLAIN) {
-#pragma unroll
-    for (int j = 0; j < 5; ++j) k[j] = ld4(a.in_c + (size_t)j * a.Cin + c0 + 4 * q);
-  }
-#pragma unroll
-  for (int u = 0; u < C3_NU; ++u) {
-    const int pix = u * PP + lp;
-    float4 v = xform4<MODE>(r.x[u], r.ax[TWO ? u : 0], k);
-    if (!r.ok[u]) v = make_float4(0.f, 0.f, 0.f, 0.f);          // zero padding AFTER the transform
-    if (pix < npix) {
-      const C3Tri lo = c3_split2(v.x, v.y), hi = c3_split2(v.z, v.w);
-      char* d = img + pix * (6 * CH) + 8 * q;
-      *reinterpret_cast<uint2*>(d) = make_uint2(lo.h, hi.h);
-      *reinterpret_cast<uint2*>(d + 2 * CH) = make_uint2(lo.m, hi.m);
-      *reinterpret_cast<uint2*>(d + 4 * CH) = make_uint2(lo.l, hi.l);
-    }
-  }
-}
 
 template <int WN, bool TWO>
 __global__ __launch_bounds__(512) void conv_bf3_kernel(const ConvArgs a) {
@@ -106,20 +42,7 @@ __global__ __launch_bounds__(512) void conv_bf3_kernel(const ConvArgs a) {
   const bool do_stage = !(a.flags & RCV_F_DBG_NOSTAGE), do_mfma = !(a.flags & RCV_F_DBG_NOMFMA);      // (ablation timings: scripts/bench_op.py --flags)
 
   if (producer) {
-    auto stage = [&](int c, char* buf) {
-      C3Regs<TWO> r;
-      c3_load<TWO>(r, a, ti, 32 * c, tid, npix);
-      if (TWO) {
-        if (a.in_mode == RCV_LOAD_GRAD_ENC) c3_store<RCV_LOAD_GRAD_ENC, TWO>(r, a, buf, 32 * c, tid, npix);
-        else c3_store<RCV_LOAD_GRAD_DEC, TWO>(r, a, buf, 32 * c, tid, npix);
-      } else {
-        switch (a.in_mode) {
-          case RCV_LOAD_PLAIN: c3_store<RCV_LOAD_PLAIN, TWO>(r, a, buf, 32 * c, tid, npix); break;
-          case RCV_LOAD_AFFINE: c3_store<RCV_LOAD_AFFINE, TWO>(r, a, buf, 32 * c, tid, npix); break;
-          default: c3_store<RCV_LOAD_AFFINE_RELU, TWO>(r, a, buf, 32 * c, tid, npix); break;
-        }
-      }
-    };
+    auto stage = [&](int c, char* buf) { bf3_conv_stage<32, C3_NU, TWO>(a, ti, buf, a.Cin, 32 * c, tid, npix); };
     // barrier for barrier the consumer path: 1 + one per chunk (+ the epilogue's when it reduces statistics)
     if (do_stage) stage(0, smem_c3);
     __syncthreads();
@@ -158,14 +81,14 @@ __global__ __launch_bounds__(512) void conv_bf3_kernel(const ConvArgs a) {
   }
   const size_t wstep = (size_t)a.CoutP * 64;                      // bytes per k-step (tap, chunk) of one plane
   const size_t wplane = 9 * (size_t)nchunks * wstep;
-  c3_bf16x8 A[3][WM][3];                                          // [ring slot][m][plane]
-  auto load_a = [&](int tap, int c, c3_bf16x8 (&dst)[WM][3]) {
+  bf16x8 A[3][WM][3];                                          // [ring slot][m][plane]
+  auto load_a = [&](int tap, int c, bf16x8 (&dst)[WM][3]) {
     if (c >= nchunks) { c = nchunks - 1; }                        // (past the end: a repeated fragment, never used)
     const size_t o = (size_t)(tap * nchunks + c) * wstep;
 #pragma unroll
     for (int m = 0; m < WM; ++m)
 #pragma unroll
-      for (int pl = 0; pl < 3; ++pl) dst[m][pl] = *reinterpret_cast<const c3_bf16x8*>(wb[m] + pl * wplane + o);
+      for (int pl = 0; pl < 3; ++pl) dst[m][pl] = *reinterpret_cast<const bf16x8*>(wb[m] + pl * wplane + o);
   };
   load_a(0, 0, A[0]);
   load_a(1, 0, A[1]);
@@ -177,22 +100,21 @@ __global__ __launch_bounds__(512) void conv_bf3_kernel(const ConvArgs a) {
 #pragma unroll
     for (int tap = 0; tap < 9; ++tap) {
       const int tapoff = ((tap / 3) * a.IW + (tap % 3)) * C3_PITCH;
-      const c3_bf16x8 (&Ac)[WM][3] = A[tap % 3];
-      c3_bf16x8 B[2][3];
-      auto load_b = [&](int n, c3_bf16x8 (&dst)[3]) {
+      const bf16x8 (&Ac)[WM][3] = A[tap % 3];
+      bf16x8 B[2][3];
+      auto load_b = [&](int n, bf16x8 (&dst)[3]) {
         const char* pb = xb + pixoff[n] + tapoff;
 #pragma unroll
-        for (int pl = 0; pl < 3; ++pl) dst[pl] = *reinterpret_cast<const c3_bf16x8*>(pb + pl * 64);
+        for (int pl = 0; pl < 3; ++pl) dst[pl] = *reinterpret_cast<const bf16x8*>(pb + pl * 64);
       };
       load_b(0, B[0]);
 #pragma unroll
       for (int n = 0; n < WN; ++n) {
         if (n + 1 < WN) load_b(n + 1, B[(n + 1) & 1]);
-        constexpr int TA[6] = {2, 0, 1, 1, 0, 0}, TB[6] = {0, 2, 1, 0, 1, 0};     // smallest products first
 #pragma unroll
         for (int e = 0; e < 6; ++e)
 #pragma unroll
-          for (int m = 0; m < WM; ++m) acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(Ac[m][TA[e]], B[n & 1][TB[e]], acc[m][n], 0, 0, 0);
+          for (int m = 0; m < WM; ++m) acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(Ac[m][BF3_TA[e]], B[n & 1][BF3_TB[e]], acc[m][n], 0, 0, 0);
         // the three reads of the next pixel block go behind the first MFMAs of this one (left alone the compiler sinks them to the end
         // of the block, and the next block starts with their latency)
         if (n + 1 < WN) {
@@ -239,20 +161,7 @@ __global__ __launch_bounds__(512) void conv2_bf3_kernel(const ConvArgs a) {
   const int nchunks = a.nchunks;
 
   if (producer) {
-    auto stage = [&](int c, char* buf) {
-      C3Regs<TWO> r;
-      c3_load<TWO, CH>(r, a, ti, CH * c, tid, npix);
-      if (TWO) {
-        if (a.in_mode == RCV_LOAD_GRAD_ENC) c3_store<RCV_LOAD_GRAD_ENC, TWO, CH>(r, a, buf, CH * c, tid, npix);
-        else c3_store<RCV_LOAD_GRAD_DEC, TWO, CH>(r, a, buf, CH * c, tid, npix);
-      } else {
-        switch (a.in_mode) {
-          case RCV_LOAD_PLAIN: c3_store<RCV_LOAD_PLAIN, TWO, CH>(r, a, buf, CH * c, tid, npix); break;
-          case RCV_LOAD_AFFINE: c3_store<RCV_LOAD_AFFINE, TWO, CH>(r, a, buf, CH * c, tid, npix); break;
-          default: c3_store<RCV_LOAD_AFFINE_RELU, TWO, CH>(r, a, buf, CH * c, tid, npix); break;
-        }
-      }
-    };
+    auto stage = [&](int c, char* buf) { bf3_conv_stage<CH, C3_NU, TWO>(a, ti, buf, a.Cin, CH * c, tid, npix); };
     stage(0, smem_c3);
     __syncthreads();
     for (int c = 0; c < nchunks; ++c) {
@@ -296,14 +205,14 @@ __global__ __launch_bounds__(512) void conv2_bf3_kernel(const ConvArgs a) {
   }
   const size_t wstep = (size_t)a.CoutP * 64;
   const size_t wplane = (size_t)NKS * nchunks * wstep;
-  c3_bf16x8 A[NKS][WM][3];
-  auto load_a = [&](int c, int ks, c3_bf16x8 (&dst)[WM][3]) {
+  bf16x8 A[NKS][WM][3];
+  auto load_a = [&](int c, int ks, bf16x8 (&dst)[WM][3]) {
     if (c >= nchunks) c = nchunks - 1;
     const size_t o = (size_t)(c * NKS + ks) * wstep;
 #pragma unroll
     for (int m = 0; m < WM; ++m)
 #pragma unroll
-      for (int pl = 0; pl < 3; ++pl) dst[m][pl] = *reinterpret_cast<const c3_bf16x8*>(wb[m] + pl * wplane + o);
+      for (int pl = 0; pl < 3; ++pl) dst[m][pl] = *reinterpret_cast<const bf16x8*>(wb[m] + pl * wplane + o);
   };
 #pragma unroll
   for (int ks = 0; ks < NKS; ++ks) load_a(0, ks, A[ks]);
@@ -312,21 +221,20 @@ __global__ __launch_bounds__(512) void conv2_bf3_kernel(const ConvArgs a) {
     const char* xb = smem_c3 + (c & 1) * xbytes;
 #pragma unroll
     for (int ks = 0; ks < NKS; ++ks) {
-      c3_bf16x8 B[2][3];
-      auto load_b = [&](int n, c3_bf16x8 (&dst)[3]) {
+      bf16x8 B[2][3];
+      auto load_b = [&](int n, bf16x8 (&dst)[3]) {
         const char* pb = xb + pixoff[n] + koff[ks];
 #pragma unroll
-        for (int pl = 0; pl < 3; ++pl) dst[pl] = *reinterpret_cast<const c3_bf16x8*>(pb + pl * 2 * CH);
+        for (int pl = 0; pl < 3; ++pl) dst[pl] = *reinterpret_cast<const bf16x8*>(pb + pl * 2 * CH);
       };
       load_b(0, B[0]);
 #pragma unroll
       for (int n = 0; n < WN; ++n) {
         if (n + 1 < WN) load_b(n + 1, B[(n + 1) & 1]);
-        constexpr int TA[6] = {2, 0, 1, 1, 0, 0}, TB[6] = {0, 2, 1, 0, 1, 0};
 #pragma unroll
         for (int e = 0; e < 6; ++e)
 #pragma unroll
-          for (int m = 0; m < WM; ++m) acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A[ks][m][TA[e]], B[n & 1][TB[e]], acc[m][n], 0, 0, 0);
+          for (int m = 0; m < WM; ++m) acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A[ks][m][BF3_TA[e]], B[n & 1][BF3_TB[e]], acc[m][n], 0, 0, 0);
         if (n + 1 < WN) {
 #pragma unroll
           for (int e = 0; e < 3; ++e) {
@@ -432,29 +340,9 @@ int conv_bf3_plan(const rcv_handle* h, const rcv_op* op, ConvPlan* pl) {
   return RCV_OK;
 }
 
-template <int WN, bool TWO>
-static int c3_launch_inst(const ConvPlan& pl, const ConvArgs& a, hipStream_t s) {
-  auto kern = conv_bf3_kernel<WN, TWO>;
-  static size_t configured[RCV_MAX_DEVICES];
-  RCV_ENSURE_LDS(kern, pl.lds, pl.dev, configured);
-  hipLaunchKernelGGL(kern, dim3(pl.grid), dim3(512), pl.lds, s, a);
-  RCV_HIP(hipGetLastError());
-  return RCV_OK;
-}
-
-template <bool TWO>
-static int c3_launch_s2(const ConvPlan& pl, const ConvArgs& a, hipStream_t s) {
-  auto kern = conv2_bf3_kernel<5, TWO>;
-  static size_t configured[RCV_MAX_DEVICES];
-  RCV_ENSURE_LDS(kern, pl.lds, pl.dev, configured);
-  hipLaunchKernelGGL(kern, dim3(pl.grid), dim3(512), pl.lds, s, a);
-  RCV_HIP(hipGetLastError());
-  return RCV_OK;
-}
-
 int conv_bf3_launch(const ConvPlan& pl, const ConvArgs& a, hipStream_t s) {
   const bool two = a.in_mode == RCV_LOAD_GRAD_ENC || a.in_mode == RCV_LOAD_GRAD_DEC;
-  if (a.stride == 2) return two ? c3_launch_s2<true>(pl, a, s) : c3_launch_s2<false>(pl, a, s);
-  if (pl.WN == 10) return two ? c3_launch_inst<10, true>(pl, a, s) : c3_launch_inst<10, false>(pl, a, s);
-  return two ? c3_launch_inst<5, true>(pl, a, s) : c3_launch_inst<5, false>(pl, a, s);
+  if (a.stride == 2) return two ? conv_launch_with_lds<conv2_bf3_kernel<5, true>>(pl, a, s) : conv_launch_with_lds<conv2_bf3_kernel<5, false>>(pl, a, s);
+  if (pl.WN == 10) return two ? conv_launch_with_lds<conv_bf3_kernel<10, true>>(pl, a, s) : conv_launch_with_lds<conv_bf3_kernel<10, false>>(pl, a, s);
+  return two ? conv_launch_with_lds<conv_bf3_kernel<5, true>>(pl, a, s) : conv_launch_with_lds<conv_bf3_kernel<5, false>>(pl, a, s);
 }

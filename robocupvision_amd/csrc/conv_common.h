@@ -1,8 +1,6 @@
 // Shared declarations of the convolution kernels (conv_mfma.hip: general; convs_mfma.hip: narrow layers).
 #pragma once
-#include "rcv_internal.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+#include "load_xform.h"
 
 enum { KIND_GATHER = 0, KIND_TPHASE = 1, KIND_TMERGED = 2, KIND_TALL = 3 };   // TALL: all four output parities of a transposed conv in one workgroup
 
@@ -38,8 +36,6 @@ struct TileInfo {
   int n, y0, x0, co0, py, px, oy0, ox0, pt;
 };
 
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-
 template <int KIND>
 __device__ __forceinline__ TileInfo decode_tile(const ConvArgs& a, int t, int COT) {
   TileInfo ti;
@@ -61,33 +57,6 @@ __device__ __forceinline__ TileInfo decode_tile(const ConvArgs& a, int t, int CO
   return ti;
 }
 
-// Operand transform applied while the tile is written to LDS (see RCV_LOAD_* in rcv.h).
-template <int MODE>
-__device__ __forceinline__ float4 xform4(float4 x, float4 a, const float4 (&k)[5]) {
-  float4 v;
-  if (MODE == RCV_LOAD_PLAIN || MODE == RCV_LOAD_NCHW) {
-    v = x;
-  } else if (MODE == RCV_LOAD_AFFINE) {
-    v.x = fmaf(x.x, k[0].x, k[1].x); v.y = fmaf(x.y, k[0].y, k[1].y);
-    v.z = fmaf(x.z, k[0].z, k[1].z); v.w = fmaf(x.w, k[0].w, k[1].w);
-  } else if (MODE == RCV_LOAD_AFFINE_RELU) {
-    v.x = fmaxf(fmaf(x.x, k[0].x, k[1].x), 0.f); v.y = fmaxf(fmaf(x.y, k[0].y, k[1].y), 0.f);
-    v.z = fmaxf(fmaf(x.z, k[0].z, k[1].z), 0.f); v.w = fmaxf(fmaf(x.w, k[0].w, k[1].w), 0.f);
-  } else if (MODE == RCV_LOAD_GRAD_ENC) {
-    v.x = a.x > 0.f ? fmaf(k[0].x, x.x, fmaf(k[2].x, a.x, k[1].x)) : 0.f;
-    v.y = a.y > 0.f ? fmaf(k[0].y, x.y, fmaf(k[2].y, a.y, k[1].y)) : 0.f;
-    v.z = a.z > 0.f ? fmaf(k[0].z, x.z, fmaf(k[2].z, a.z, k[1].z)) : 0.f;
-    v.w = a.w > 0.f ? fmaf(k[0].w, x.w, fmaf(k[2].w, a.w, k[1].w)) : 0.f;
-  } else {  // RCV_LOAD_GRAD_DEC
-    v.x = fmaf(k[0].x, (fmaf(a.x, k[3].x, k[4].x) > 0.f ? x.x : 0.f), fmaf(k[2].x, a.x, k[1].x));
-    v.y = fmaf(k[0].y, (fmaf(a.y, k[3].y, k[4].y) > 0.f ? x.y : 0.f), fmaf(k[2].y, a.y, k[1].y));
-    v.z = fmaf(k[0].z, (fmaf(a.z, k[3].z, k[4].z) > 0.f ? x.z : 0.f), fmaf(k[2].z, a.z, k[1].z));
-    v.w = fmaf(k[0].w, (fmaf(a.w, k[3].w, k[4].w) > 0.f ? x.w : 0.f), fmaf(k[2].w, a.w, k[1].w));
-  }
-  return v;
-}
-
-
 struct ConvPlan {
   int kind, tile, CK, R, Wt, tiles_x, tiles_y, IH, IW;
   int CoutV, CoutP, n_co_tiles, n_phases, total_tiles, grid;
@@ -103,6 +72,12 @@ struct ConvPlan {
   int bf3;               // 1: conv_bf3.hip (wide stride-1 layers: fp32 products on the bf16 matrix pipe, filter in the split layout); 2: convn_bf3.hip (narrow layers)
   int small;             // 1: conv_small.hip (inference on planes of a few hundred pixels: one MFMA block per workgroup, K split over its waves)
 };
+
+// 512-thread launch of a kernel whose grid and dynamic LDS are the plan's (rcv_launch_with_lds)
+template <auto KERN>
+static int conv_launch_with_lds(const ConvPlan& pl, const ConvArgs& a, hipStream_t s) {
+  return rcv_launch_with_lds<KERN>(a, dim3(pl.grid), pl.lds, pl.dev, s);
+}
 
 // LDS pitch of a staged input pixel holding CK channels.  The B operand of v_mfma_f32_16x16x4_f32 is read with ds_read_b32 at
 // (pixel(l15) * IS * pitch + l4): 16 pixels x 2 channel lanes per 32-lane half must fall on 32 different banks.  Unit-stride pixel

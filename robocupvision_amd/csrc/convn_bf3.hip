@@ -3,7 +3,7 @@
 // On the fp32 matrix instruction even the 8..32-channel layers of the step are matrix-pipe bound: 16 -> 16 at 32 x 240 x 320 moves 315 MB
 // (52 us at 6 TB/s) but needs 72 us of v_mfma_f32_16x16x4_f32 at peak -- the fp32 kernel (convs_mfma.hip) measured 117 us with its matrix
 // pipe 71 % busy.  With every operand split exactly into three bf16 values and six v_mfma_f32_16x16x32_bf16 products per multiply-add
-// (wgrad_bf3.hip has the arithmetic and its error against fp64) the same contraction is 2.0-2.5 x cheaper and these layers become what
+// (split_bf16.h has the arithmetic and its error against fp64) the same contraction is 2.0-2.5 x cheaper and these layers become what
 // their shapes say they are: HBM streams.
 //
 // Roles (those of convs_mfma.hip):  KIND_GATHER   conv / data gradient, stride 1 | 2, dilation 1;
@@ -18,73 +18,10 @@
 // transform -> split -> LDS) while four consumer waves contract tile i and run the epilogue of conv_mfma.hip (bias / ReLU / residual,
 // 16-byte NHWC stores, BatchNorm sums kept in registers across tiles: one partial row per workgroup).
 #include <type_traits>
-#include "conv_common.h"
+#include "conv_bf3_stage.h"
 #include "conv_epilogue.h"
 
-typedef __bf16 n3_bf16x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 n3_bf16x8 __attribute__((ext_vector_type(8)));
-
 constexpr int N3_NU = 11;                 // staging passes: tiles with halo up to 11 * (256 / (CIN / 4)) pixels
-
-__device__ __forceinline__ uint32_t n3_pack(float a, float b) {
-  const n3_bf16x2 v = {(__bf16)a, (__bf16)b};            // v_cvt_pk_bf16_f32 (round to nearest even)
-  return __builtin_bit_cast(uint32_t, v);
-}
-struct N3Tri { uint32_t h, m, l; };
-__device__ __forceinline__ N3Tri n3_split2(float x0, float x1) {
-  N3Tri t;
-  t.h = n3_pack(x0, x1);
-  const float r0 = x0 - __uint_as_float(t.h << 16), r1 = x1 - __uint_as_float(t.h & 0xffff0000u);       // exact
-  t.m = n3_pack(r0, r1);
-  const float s0 = r0 - __uint_as_float(t.m << 16), s1 = r1 - __uint_as_float(t.m & 0xffff0000u);       // exact
-  t.l = n3_pack(s0, s1);
-  return t;
-}
-
-template <bool TWO>
-struct N3Regs {
-  float4 x[N3_NU], ax[TWO ? N3_NU : 1];
-  bool ok[N3_NU];
-};
-
-template <int CIN, bool TWO>
-__device__ __forceinline__ void n3_load(N3Regs<TWO>& r, const ConvArgs& a, const TileInfo& ti, int tid, int npix) {
-  constexpr int Q = CIN / 4, PP = 256 / Q;
-  const int q = tid % Q, lp = tid / Q;
-#pragma unroll
-  for (int u = 0; u < N3_NU; ++u) {
-    const int pix = u * PP + lp;
-    const int iy = fd_div(pix, a.fdIW), ix = pix - iy * a.IW;
-    const int gy = ti.oy0 + iy, gx = ti.ox0 + ix;
-    r.ok[u] = pix < npix && (unsigned)gy < (unsigned)a.H && (unsigned)gx < (unsigned)a.W;
-    const uint32_t o = r.ok[u] ? (uint32_t)(((ti.n * a.H + gy) * a.W + gx) * CIN + 4 * q) : 0u;
-    r.x[u] = ld4(a.in + o);
-    if (TWO) r.ax[u] = ld4(a.in_aux + o);
-  }
-}
-template <int MODE, int CIN, bool TWO>
-__device__ __forceinline__ void n3_store(const N3Regs<TWO>& r, const ConvArgs& a, char* img, int tid, int npix) {
-  constexpr int Q = CIN / 4, PP = 256 / Q, PITCH = 6 * CIN;
-  const int q = tid % Q, lp = tid / Q;
-  float4 k[5];
-  if (MODE != RCV_LOAD_PLAIN) {
-#pragma unroll
-    for (int j = 0; j < 5; ++j) k[j] = ld4(a.in_c + j * CIN + 4 * q);
-  }
-#pragma unroll
-  for (int u = 0; u < N3_NU; ++u) {
-    const int pix = u * PP + lp;
-    float4 v = xform4<MODE>(r.x[u], r.ax[TWO ? u : 0], k);
-    if (!r.ok[u]) v = make_float4(0.f, 0.f, 0.f, 0.f);          // zero padding AFTER the transform
-    if (pix < npix) {
-      const N3Tri lo = n3_split2(v.x, v.y), hi = n3_split2(v.z, v.w);
-      char* d = img + pix * PITCH + 8 * q;
-      *reinterpret_cast<uint2*>(d) = make_uint2(lo.h, hi.h);
-      *reinterpret_cast<uint2*>(d + 2 * CIN) = make_uint2(lo.m, hi.m);
-      *reinterpret_cast<uint2*>(d + 4 * CIN) = make_uint2(lo.l, hi.l);
-    }
-  }
-}
 
 // Epilogue of a tile that lies entirely inside the plane, with everything that does not depend on the tile computed ONCE per (persistent)
 // workgroup: the lane's output offsets relative to the tile's first output element, its bias and BatchNorm-backward constants.  The
@@ -190,21 +127,7 @@ __global__ __launch_bounds__(512) void convn_bf3_kernel(const ConvArgs a) {
     reinterpret_cast<float4*>(wl)[e] = reinterpret_cast<const float4*>(a.w)[e];
 
   if (producer) {
-    auto stage = [&](int tile, char* buf) {
-      const TileInfo ti = decode_tile<KIND>(a, tile, COT);
-      N3Regs<TWO> r;
-      n3_load<CIN, TWO>(r, a, ti, tid, npix);
-      if (TWO) {
-        if (a.in_mode == RCV_LOAD_GRAD_ENC) n3_store<RCV_LOAD_GRAD_ENC, CIN, TWO>(r, a, buf, tid, npix);
-        else n3_store<RCV_LOAD_GRAD_DEC, CIN, TWO>(r, a, buf, tid, npix);
-      } else {
-        switch (a.in_mode) {
-          case RCV_LOAD_PLAIN: n3_store<RCV_LOAD_PLAIN, CIN, TWO>(r, a, buf, tid, npix); break;
-          case RCV_LOAD_AFFINE: n3_store<RCV_LOAD_AFFINE, CIN, TWO>(r, a, buf, tid, npix); break;
-          default: n3_store<RCV_LOAD_AFFINE_RELU, CIN, TWO>(r, a, buf, tid, npix); break;
-        }
-      }
-    };
+    auto stage = [&](int tile, char* buf) { bf3_conv_stage<CIN, N3_NU, TWO>(a, decode_tile<KIND>(a, tile, COT), buf, CIN, 0, tid, npix); };
     // barrier for barrier the consumer path: 1 + one per tile (+ the statistics reduction's).
     // (Round 3, measured and not kept: a second register set, so that the loads of tile i + 2 are issued before the data of tile i + 1 is
     // consumed -- 8 -> 16 stride 2 forward 0.127 -> 0.125 ms, 16 -> 8 transposed 0.164 -> 0.154: the compiler waits vmcnt(0) at the loop's
@@ -266,17 +189,17 @@ __global__ __launch_bounds__(512) void convn_bf3_kernel(const ConvArgs a) {
     for (int m = 0; m < WM; ++m)
 #pragma unroll
       for (int n = 0; n < WN; ++n) acc[m][n] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    n3_bf16x8 A[2][WM][3], B[2][3];
-    auto load_a = [&](int ks, n3_bf16x8 (&dst)[WM][3]) {
+    bf16x8 A[2][WM][3], B[2][3];
+    auto load_a = [&](int ks, bf16x8 (&dst)[WM][3]) {
 #pragma unroll
       for (int m = 0; m < WM; ++m)
 #pragma unroll
-        for (int pl = 0; pl < 3; ++pl) dst[m][pl] = *reinterpret_cast<const n3_bf16x8*>(abase + pl * WPLANE + (ks * COT + m * 16) * 64);
+        for (int pl = 0; pl < 3; ++pl) dst[m][pl] = *reinterpret_cast<const bf16x8*>(abase + pl * WPLANE + (ks * COT + m * 16) * 64);
     };
-    auto load_b = [&](int ks, int n, n3_bf16x8 (&dst)[3]) {
+    auto load_b = [&](int ks, int n, bf16x8 (&dst)[3]) {
       const char* pb = xb + pixoff[n] + koff[ks];
 #pragma unroll
-      for (int pl = 0; pl < 3; ++pl) dst[pl] = *reinterpret_cast<const n3_bf16x8*>(pb + pl * 2 * CIN);
+      for (int pl = 0; pl < 3; ++pl) dst[pl] = *reinterpret_cast<const bf16x8*>(pb + pl * 2 * CIN);
     };
     load_a(0, A[0]);
     load_b(0, 0, B[0]);
@@ -289,11 +212,10 @@ __global__ __launch_bounds__(512) void convn_bf3_kernel(const ConvArgs a) {
         const int i = ks * WN + n;                           // step counter: B double buffer
         if (n + 1 < WN) load_b(ks, n + 1, B[(i + 1) & 1]);
         else if (ks + 1 < NKS) load_b(ks + 1, 0, B[(i + 1) & 1]);
-        constexpr int TA[6] = {2, 0, 1, 1, 0, 0}, TB[6] = {0, 2, 1, 0, 1, 0};     // smallest products first
 #pragma unroll
         for (int e = 0; e < 6; ++e)
 #pragma unroll
-          for (int m = 0; m < WM; ++m) acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A[ks & 1][m][TA[e]], B[i & 1][TB[e]], acc[m][n], 0, 0, 0);
+          for (int m = 0; m < WM; ++m) acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A[ks & 1][m][BF3_TA[e]], B[i & 1][BF3_TB[e]], acc[m][n], 0, 0, 0);
         __builtin_amdgcn_sched_barrier(0);
       }
     }
@@ -418,19 +340,10 @@ int convn_bf3_plan(const rcv_handle* h, const rcv_op* op, int kind, ConvPlan* pl
   return RCV_OK;
 }
 
-template <int CIN, int WM, int WN, int KIND, bool TWO>
-static int n3_launch_inst(const ConvPlan& pl, const ConvArgs& a, hipStream_t s) {
-  auto kern = convn_bf3_kernel<CIN, WM, WN, KIND, TWO>;
-  static size_t configured[RCV_MAX_DEVICES];
-  RCV_ENSURE_LDS(kern, pl.lds, pl.dev, configured);
-  hipLaunchKernelGGL(kern, dim3(pl.grid), dim3(512), pl.lds, s, a);
-  RCV_HIP(hipGetLastError());
-  return RCV_OK;
-}
 template <int CIN, int WM, int KIND>
 static int n3_launch_wn(const ConvPlan& pl, const ConvArgs& a, bool two, hipStream_t s) {
-  if (pl.WN == 5) return two ? n3_launch_inst<CIN, WM, 5, KIND, true>(pl, a, s) : n3_launch_inst<CIN, WM, 5, KIND, false>(pl, a, s);
-  return two ? n3_launch_inst<CIN, WM, 3, KIND, true>(pl, a, s) : n3_launch_inst<CIN, WM, 3, KIND, false>(pl, a, s);
+  if (pl.WN == 5) return two ? conv_launch_with_lds<convn_bf3_kernel<CIN, WM, 5, KIND, true>>(pl, a, s) : conv_launch_with_lds<convn_bf3_kernel<CIN, WM, 5, KIND, false>>(pl, a, s);
+  return two ? conv_launch_with_lds<convn_bf3_kernel<CIN, WM, 3, KIND, true>>(pl, a, s) : conv_launch_with_lds<convn_bf3_kernel<CIN, WM, 3, KIND, false>>(pl, a, s);
 }
 
 int convn_bf3_launch(const ConvPlan& pl, const ConvArgs& a, hipStream_t s) {

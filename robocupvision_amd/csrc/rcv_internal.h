@@ -121,6 +121,19 @@ static inline void rcv_plan_put(const rcv_handle* h, const rcv_op* op, const P& 
     }                                                                                                                  \
   } while (0)
 
+#if defined(__HIPCC__)
+// Launches a 512-thread (4 producer + 4 consumer waves) kernel with `lds` bytes of dynamic LDS, raising its limit first where needed.
+// KERN is a template argument: every kernel instantiation has its own table.
+template <auto KERN, typename Args>
+static int rcv_launch_with_lds(const Args& a, dim3 grid, size_t lds, int dev, hipStream_t s) {
+  static size_t configured[RCV_MAX_DEVICES];
+  RCV_ENSURE_LDS(KERN, lds, dev, configured);
+  hipLaunchKernelGGL(KERN, grid, dim3(512), lds, s, a);
+  RCV_HIP(hipGetLastError());
+  return RCV_OK;
+}
+#endif
+
 // ---- launchers implemented in the .hip files; each validates, picks a tiling and enqueues ----
 // `query` != nullptr: do not launch, only fill tiling dependent outputs (n_part / n_split / bytes).
 struct OpQuery {

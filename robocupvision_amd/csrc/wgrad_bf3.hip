@@ -2,13 +2,9 @@
 //
 //   dW[cb][ca][tap] = sum_p  P[p][cb] * G[p + tap - 1][ca]          (same operands, load modes and partial-filter layout as wgrad_mfma.hip)
 //
-// gfx950 issues v_mfma_f32_16x16x4_f32 at 1/16 of the bf16 MFMA rate: the fp32 form of this kernel (wgrad_mfma.hip, 64 x 64 producer /
-// consumer tile) is matrix-pipe bound at 93 TFLOP/s.  An fp32 value splits EXACTLY into three bf16 values, x = h + m + l (8 + 8 + 8
-// significand bits, round-to-nearest at each step, every remainder exact); a product a*b is then the sum of nine bf16 x bf16 products, each
-// exact in the fp32 accumulator.  This kernel issues the six largest (hh, hm, mh, hl, lh, mm): what it leaves out (ml, lm, ll) is below
-// 2^-24 |ab|, the size of ONE fp32 rounding of the product.  Measured against fp64 (scripts/micro/split_mfma.hip, K = 1152 and 9216,
-// Gaussian and post-ReLU / wide-dynamic-range operands): max and rms error <= those of the fp32 MFMA chain in every case; six bf16 MFMAs
-// (v_mfma_f32_16x16x32_bf16) per K = 32 against eight fp32 MFMAs of four times the cycles each -- 2.0-2.5 x the fp32 matrix-pipe rate.
+// The arithmetic -- every fp32 operand split exactly into three bf16 values, six v_mfma_f32_16x16x32_bf16 products per multiply-add, 2.0-2.5 x
+// the fp32 matrix-pipe rate at an error no larger than the fp32 MFMA chain's -- is in split_bf16.h; the fp32 form of this kernel
+// (wgrad_mfma.hip, 64 x 64 producer / consumer tile) is matrix-pipe bound at 93 TFLOP/s.
 //
 // GEMM mapping (per tap): D[cb][ca] += A[cb][k] * B[k][ca], k = pixel, 32 pixels per MFMA.  Lane (i, g) of the bf16 MFMA holds EIGHT
 // consecutive k of row / column i -- the contraction index is the pixel, the tensors are NHWC -- so both operands are read from
@@ -24,12 +20,7 @@
 // kernel) + 4 producer waves that stage tile i+1 (global -> load transform -> split -> three 8-byte LDS writes per channel quad) while
 // tile i is contracted; pointwise tile 64 pixels (8 x 8 or 4 x 16) = 2 k-steps = 432 MFMAs per consumer wave per barrier.
 #include "wgrad_common.h"
-
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
-typedef __attribute__((address_space(3))) char lds_char;
+#include "split_bf16.h"
 
 constexpr int B3_GPITCH = 160, B3_PPITCH = 128, B3_PPLANE = 64 * B3_PPITCH;
 template <int TW>
@@ -38,22 +29,6 @@ struct B3Geom {
   static constexpr int GPLANE = GPIX * B3_GPITCH;
   static constexpr int BUF = 3 * GPLANE + 3 * B3_PPLANE;
 };
-
-// x = h + m + l for two values at once; each output word holds the two bf16 of one plane (element 0 in the low half)
-struct B3Tri { uint32_t h, m, l; };
-__device__ __forceinline__ uint32_t b3_pack(float a, float b) {
-  const bf16x2 v = {(__bf16)a, (__bf16)b};            // v_cvt_pk_bf16_f32 (round to nearest even)
-  return __builtin_bit_cast(uint32_t, v);
-}
-__device__ __forceinline__ B3Tri b3_split2(float x0, float x1) {
-  B3Tri t;
-  t.h = b3_pack(x0, x1);
-  const float r0 = x0 - __uint_as_float(t.h << 16), r1 = x1 - __uint_as_float(t.h & 0xffff0000u);       // exact
-  t.m = b3_pack(r0, r1);
-  const float s0 = r0 - __uint_as_float(t.m << 16), s1 = r1 - __uint_as_float(t.m & 0xffff0000u);       // exact, <= 8 significant bits
-  t.l = b3_pack(s0, s1);
-  return t;
-}
 
 // One operand tile: global -> load transform -> three bf16 planes in LDS, in two steps so that the loads of BOTH operand tiles of a pixel
 // tile are in flight before the first is consumed (staged one batch of four after the other, a tile cost three serialized HBM/L2 round
@@ -76,8 +51,8 @@ __device__ __forceinline__ void b3_load(B3Regs<NPIX, TWP, TWO>& r, const float* 
     const int iy = pix / TWP, ix = pix - iy * TWP;                  // (compile-time divisor)
     r.ok[u] = pix < NPIX && (unsigned)(oy + iy) < (unsigned)PH && (unsigned)(ox + ix) < (unsigned)PW;
     const uint32_t o = r.ok[u] ? (uint32_t)(((row0 + oy + iy) * PW + ox + ix) * C + ch) : 0u;
-    r.x[u] = wld4(src + o);
-    if (TWO) { if (two) r.ax[u] = wld4(aux + o); }
+    r.x[u] = ld4(src + o);
+    if (TWO) { if (two) r.ax[u] = ld4(aux + o); }
   }
 }
 // SWZ: the P image's swizzle.
@@ -89,16 +64,16 @@ __device__ __forceinline__ void b3_store(const B3Regs<NPIX, TWP, TWO>& r, const 
   float4 k[5];
   if (MODE != RCV_LOAD_PLAIN) {
 #pragma unroll
-    for (int j = 0; j < 5; ++j) k[j] = wld4(consts + (size_t)j * C + ch);
+    for (int j = 0; j < 5; ++j) k[j] = ld4(consts + (size_t)j * C + ch);
   }
 #pragma unroll
   for (int u = 0; u < B3Regs<NPIX, TWP, TWO>::NU; ++u) {
     const int pix = u * 16 + lp;
-    float4 v = wxform4<MODE>(r.x[u], r.ax[TWO ? u : 0], k);
+    float4 v = xform4<MODE>(r.x[u], r.ax[TWO ? u : 0], k);
     if (!r.ok[u]) v = make_float4(0.f, 0.f, 0.f, 0.f);
     if (SUM) { sum.x += v.x; sum.y += v.y; sum.z += v.z; sum.w += v.w; }
     if (pix < NPIX) {
-      const B3Tri a = b3_split2(v.x, v.y), b = b3_split2(v.z, v.w);
+      const Bf3Tri a = bf3_split2(v.x, v.y), b = bf3_split2(v.z, v.w);
       int off = pix * pitch + 8 * q;
       if (SWZ) off = pix * pitch + ((((q >> 2) ^ ((pix >> 1) & 3))) << 5) + 8 * (q & 3);
       *reinterpret_cast<uint2*>(img + off) = make_uint2(a.h, b.h);
@@ -106,12 +81,6 @@ __device__ __forceinline__ void b3_store(const B3Regs<NPIX, TWP, TWO>& r, const 
       *reinterpret_cast<uint2*>(img + 2 * plane_bytes + off) = make_uint2(a.l, b.l);
     }
   }
-}
-
-__device__ __forceinline__ bf16x8 b3_read(const lds_char* p, int off0, int off1) {
-  const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(p + off0));
-  const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)(p + off1));
-  return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
 }
 
 // GTWO: the gathered operand may be a two-tensor gradient load (then the pointwise one is not); otherwise the pointwise one may be.
@@ -147,16 +116,7 @@ __global__ __launch_bounds__(512) void wgrad_bf3_kernel(const WgradArgs a) {
     b3_load(rp, a.p, a.p_aux, p_two, tid, cb0, a.CB, n * a.Hp, y0, x0, a.Hp, a.Wp);
     char* gi = buf;
     char* pi = buf + 3 * G::GPLANE;
-    if (GTWO) {
-      if (a.g_mode == RCV_LOAD_GRAD_ENC) b3_store<RCV_LOAD_GRAD_ENC, G::GPIX, G::IW, GTWO, false, false>(rg, a.g_c, gi, G::GPLANE, B3_GPITCH, tid, ca0, a.CA, nosum);
-      else b3_store<RCV_LOAD_GRAD_DEC, G::GPIX, G::IW, GTWO, false, false>(rg, a.g_c, gi, G::GPLANE, B3_GPITCH, tid, ca0, a.CA, nosum);
-    } else {
-      switch (a.g_mode) {
-        case RCV_LOAD_PLAIN: b3_store<RCV_LOAD_PLAIN, G::GPIX, G::IW, GTWO, false, false>(rg, a.g_c, gi, G::GPLANE, B3_GPITCH, tid, ca0, a.CA, nosum); break;
-        case RCV_LOAD_AFFINE: b3_store<RCV_LOAD_AFFINE, G::GPIX, G::IW, GTWO, false, false>(rg, a.g_c, gi, G::GPLANE, B3_GPITCH, tid, ca0, a.CA, nosum); break;
-        default: b3_store<RCV_LOAD_AFFINE_RELU, G::GPIX, G::IW, GTWO, false, false>(rg, a.g_c, gi, G::GPLANE, B3_GPITCH, tid, ca0, a.CA, nosum); break;
-      }
-    }
+    with_load_mode<GTWO>(a.g_mode, [&](auto mode) { b3_store<mode(), G::GPIX, G::IW, GTWO, false, false>(rg, a.g_c, gi, G::GPLANE, B3_GPITCH, tid, ca0, a.CA, nosum); });
     switch (a.p_mode) {
       case RCV_LOAD_PLAIN: b3_store<RCV_LOAD_PLAIN, 64, TW, !GTWO, true, true>(rp, a.p_c, pi, B3_PPLANE, B3_PPITCH, tid, cb0, a.CB, bsum); break;
       case RCV_LOAD_AFFINE: b3_store<RCV_LOAD_AFFINE, 64, TW, !GTWO, true, true>(rp, a.p_c, pi, B3_PPLANE, B3_PPITCH, tid, cb0, a.CB, bsum); break;
@@ -221,8 +181,8 @@ __global__ __launch_bounds__(512) void wgrad_bf3_kernel(const WgradArgs a) {
       bf16x8 A[2][3];
 #pragma unroll
       for (int pl = 0; pl < 3; ++pl) {
-        A[0][pl] = b3_read(pa0, pl * B3_PPLANE + (32 * j) * B3_PPITCH, pl * B3_PPLANE + (32 * j + 16) * B3_PPITCH);
-        A[1][pl] = b3_read(pa1, pl * B3_PPLANE + (32 * j) * B3_PPITCH, pl * B3_PPLANE + (32 * j + 16) * B3_PPITCH);
+        A[0][pl] = bf3_read_tr(pa0, pl * B3_PPLANE + (32 * j) * B3_PPITCH, pl * B3_PPLANE + (32 * j + 16) * B3_PPITCH);
+        A[1][pl] = bf3_read_tr(pa1, pl * B3_PPLANE + (32 * j) * B3_PPITCH, pl * B3_PPLANE + (32 * j + 16) * B3_PPITCH);
       }
       // operands of tap t + 1 are requested before the MFMAs of tap t (two register sets; the scheduling barrier keeps the compiler from
       // hoisting more reads than that: it spilled accumulators for them)
@@ -234,7 +194,7 @@ __global__ __launch_bounds__(512) void wgrad_bf3_kernel(const WgradArgs a) {
 #pragma unroll
         for (int pl = 0; pl < 3; ++pl)
 #pragma unroll
-          for (int nn = 0; nn < 2; ++nn) B[nn][pl] = b3_read(pg, pl * G::GPLANE + r0 * B3_GPITCH + nn * 32, pl * G::GPLANE + r1 * B3_GPITCH + nn * 32);
+          for (int nn = 0; nn < 2; ++nn) B[nn][pl] = bf3_read_tr(pg, pl * G::GPLANE + r0 * B3_GPITCH + nn * 32, pl * G::GPLANE + r1 * B3_GPITCH + nn * 32);
       };
       bf16x8 Bb[2][2][3];
       load_b(0, Bb[0]);
@@ -242,13 +202,12 @@ __global__ __launch_bounds__(512) void wgrad_bf3_kernel(const WgradArgs a) {
       for (int t = 0; t < 9; ++t) {
         if (t < 8) load_b(t + 1, Bb[(t + 1) & 1]);
         // six products per block, smallest first; the four blocks of a term back to back (independent accumulators)
-        constexpr int TA[6] = {2, 0, 1, 1, 0, 0}, TB[6] = {0, 2, 1, 0, 1, 0};
 #pragma unroll
         for (int e = 0; e < 6; ++e)
 #pragma unroll
           for (int m = 0; m < 2; ++m)
 #pragma unroll
-            for (int nn = 0; nn < 2; ++nn) acc[t][m][nn] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A[m][TA[e]], Bb[t & 1][nn][TB[e]], acc[t][m][nn], 0, 0, 0);
+            for (int nn = 0; nn < 2; ++nn) acc[t][m][nn] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A[m][BF3_TA[e]], Bb[t & 1][nn][BF3_TB[e]], acc[t][m][nn], 0, 0, 0);
         // one LDS read behind each MFMA (a burst of 24 reads in front of them leaves the matrix pipe idle while they issue; left alone
         // the compiler sinks the reads to the END of the tap and the next tap starts with their latency)
         if (t < 8) {
@@ -316,13 +275,7 @@ void wgrad_bf3_geometry(const rcv_handle* h, const rcv_op* op, int* tw, int* til
 
 template <int TW, bool GTWO>
 static int b3_launch_inst(const WgradArgs& a, dim3 grid, hipStream_t s, int dev) {
-  auto kern = wgrad_bf3_kernel<TW, GTWO>;
-  const size_t lds = 2 * (size_t)B3Geom<TW>::BUF;
-  static size_t configured[RCV_MAX_DEVICES];
-  RCV_ENSURE_LDS(kern, lds, dev, configured);
-  hipLaunchKernelGGL(kern, grid, dim3(512), lds, s, a);
-  RCV_HIP(hipGetLastError());
-  return RCV_OK;
+  return rcv_launch_with_lds<wgrad_bf3_kernel<TW, GTWO>>(a, grid, 2 * (size_t)B3Geom<TW>::BUF, dev, s);
 }
 
 int wgrad_bf3_launch(const rcv_handle* h, const WgradArgs& a, int tw, hipStream_t s) {

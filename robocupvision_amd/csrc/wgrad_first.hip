@@ -35,7 +35,7 @@ __global__ __launch_bounds__(384) void wgrad_first_kernel(const WgradArgs a, int
   const bool p_two = a.p_mode == RCV_LOAD_GRAD_ENC || a.p_mode == RCV_LOAD_GRAD_DEC;
   const size_t plane = (size_t)a.H * a.W;
 
-  if (tid < 10) kc[tid] = a.p_mode != RCV_LOAD_PLAIN ? wld4(a.p_c + (size_t)(tid % 5) * a.CB + 4 * (tid / 5)) : make_float4(0.f, 0.f, 0.f, 0.f);
+  if (tid < 10) kc[tid] = a.p_mode != RCV_LOAD_PLAIN ? ld4(a.p_c + (size_t)(tid % 5) * a.CB + 4 * (tid / 5)) : make_float4(0.f, 0.f, 0.f, 0.f);
   float acc[9][4];
 #pragma unroll
   for (int t = 0; t < 9; ++t)
@@ -85,8 +85,8 @@ __global__ __launch_bounds__(384) void wgrad_first_kernel(const WgradArgs a, int
       const int gy = y0 + iy, gx = x0 + ix;
       ok[u] = pix < TY * TX && gy < a.Hp && gx < a.Wp;
       const uint32_t off = ok[u] ? (uint32_t)(((n * a.Hp + gy) * a.Wp + gx) * a.CB + 4 * q) : 0u;      // (host: < 2^31 elements)
-      x[u] = wld4(a.p + off);
-      ax[u] = wld4(p_aux + off);
+      x[u] = ld4(a.p + off);
+      ax[u] = ld4(p_aux + off);
     }
     float vimg[NU];
     bool iok[NU];
@@ -105,7 +105,7 @@ __global__ __launch_bounds__(384) void wgrad_first_kernel(const WgradArgs a, int
       for (int u = 0; u < UNR; ++u) {
         const int pix = (tid >> 1) + u * (NT / 2);
         if (pix < TY * TX) {
-          float4 v = wxform_rt(a.p_mode, x[u], ax[u], k);
+          float4 v = xform_rt(a.p_mode, x[u], ax[u], k);
           if (!ok[u]) v = make_float4(0.f, 0.f, 0.f, 0.f);
           dzs[pix * 2 + q] = v;
         }

@@ -39,7 +39,7 @@ __device__ __forceinline__ void wstage_tile(const float* __restrict__ src, const
   float4 k[5];
   if (MODE != RCV_LOAD_PLAIN) {
 #pragma unroll
-    for (int j = 0; j < 5; ++j) k[j] = ch_ok ? wld4(consts + (size_t)j * C + ch) : make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int j = 0; j < 5; ++j) k[j] = ch_ok ? ld4(consts + (size_t)j * C + ch) : make_float4(0.f, 0.f, 0.f, 0.f);
   }
   // A thread's slots are `step` tile pixels apart: its tile coordinates, its tensor offset and its LDS address advance by constants
   // (with one carry into the next tile row), instead of a division, two multiply-adds and a multiply per element; a tile that lies
@@ -63,8 +63,8 @@ __device__ __forceinline__ void wstage_tile(const float* __restrict__ src, const
       if (interior) ok[u] = ch_ok && pix < npix;
       else ok[u] = ch_ok && pix < npix && ix < TWV && (unsigned)(oy + iy) < (unsigned)PH && (unsigned)(ox + ix) < (unsigned)PW;
       const uint32_t o = ok[u] ? off : 0u;
-      x[u] = wld4(src + o);
-      if (TWO) ax[u] = wld4(aux + o);
+      x[u] = ld4(src + o);
+      if (TWO) ax[u] = ld4(aux + o);
       else ax[u] = x[u];
       ix += dqx; off += d_off;
       const bool carry = ix >= TW;
@@ -75,7 +75,7 @@ __device__ __forceinline__ void wstage_tile(const float* __restrict__ src, const
 #pragma unroll
     for (int u = 0; u < UNR; ++u) {
       const int pix = pix0 + u * step;
-      float4 v = wxform4<MODE>(x[u], ax[u], k);
+      float4 v = xform4<MODE>(x[u], ax[u], k);
       if (!ok[u]) v = make_float4(0.f, 0.f, 0.f, 0.f);
       if (SUM) { sum.x += v.x; sum.y += v.y; sum.z += v.z; sum.w += v.w; }
       if (pix < npix) {
@@ -411,13 +411,13 @@ __device__ __forceinline__ void wgrad_reduce_block(const float* __restrict__ par
   if (src) {
     int sidx = grp;
     for (; sidx + 48 < nsplit; sidx += 64) {
-      const float4 v0 = wld4(src + (size_t)sidx * st), v1 = wld4(src + (size_t)(sidx + 16) * st);
-      const float4 v2 = wld4(src + (size_t)(sidx + 32) * st), v3 = wld4(src + (size_t)(sidx + 48) * st);
+      const float4 v0 = ld4(src + (size_t)sidx * st), v1 = ld4(src + (size_t)(sidx + 16) * st);
+      const float4 v2 = ld4(src + (size_t)(sidx + 32) * st), v3 = ld4(src + (size_t)(sidx + 48) * st);
       a0[0] += (double)v0.x + (double)v2.x; a0[1] += (double)v0.y + (double)v2.y; a0[2] += (double)v0.z + (double)v2.z; a0[3] += (double)v0.w + (double)v2.w;
       a1[0] += (double)v1.x + (double)v3.x; a1[1] += (double)v1.y + (double)v3.y; a1[2] += (double)v1.z + (double)v3.z; a1[3] += (double)v1.w + (double)v3.w;
     }
     for (; sidx < nsplit; sidx += 16) {
-      const float4 v = wld4(src + (size_t)sidx * st);
+      const float4 v = ld4(src + (size_t)sidx * st);
       a0[0] += (double)v.x; a0[1] += (double)v.y; a0[2] += (double)v.z; a0[3] += (double)v.w;
     }
   }

@@ -4,8 +4,8 @@
 //
 // The fp32 kernels of these layers (wgrad_mfma.hip, shared-role tiles) run at 0.38-0.5 of either roofline: their staging and MFMA phases
 // add up, and 16 -> 16 at 32 x 240 x 320 needs 72 us of v_mfma_f32_16x16x4_f32 at peak against 39 us of HBM traffic.  Here, as in
-// wgrad_bf3.hip (which has the arithmetic: every operand split exactly into three bf16 values, six bf16 MFMA products per multiply-add,
-// and the transposing LDS read that feeds the MFMA from [pixel][channel] images), with the tiles of a narrow layer:
+// wgrad_bf3.hip (the arithmetic is in split_bf16.h: every operand split exactly into three bf16 values, six bf16 MFMA products per
+// multiply-add, and the transposing LDS read that feeds the MFMA from [pixel][channel] images), with the tiles of a narrow layer:
 //   * one workgroup = ALL channels of the layer (CBT x CAT = 16 | 32 each, 8-channel operands zero padded to 16) and a K split: its four
 //     consumer waves take the 32-pixel k-steps of a tile round robin, each with the full 9 x MB x NB accumulator set; every wave writes
 //     its own partial filter (split index = 4 * workgroup + wave), the RCV_OP_WGRAD_REDUCE pass sums them in a fixed order;
@@ -16,12 +16,7 @@
 //     immediates), the pointwise image a 64-byte pitch with its two 32-byte channel blocks swapped on every second group of four
 //     pixels (its reads start at multiples of eight pixels: a per-lane constant).
 #include "wgrad_common.h"
-
-typedef __bf16 w3_bf16x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 w3_bf16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 w3_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __attribute__((address_space(3))) w3_bf16x4 w3_lds_bf16x4;
-typedef __attribute__((address_space(3))) char w3_lds_char;
+#include "split_bf16.h"
 
 constexpr int w3_gpitch(int ch) { return ch == 16 ? 32 : 96; }
 constexpr int w3_ppitch(int ch) { return ch == 16 ? 32 : 64; }
@@ -33,21 +28,6 @@ struct W3Geom {
   static constexpr int GPLANE = GPIX * GP, PPLANE = PPIX * PP;
   static constexpr int BUF = (3 * GPLANE + 3 * PPLANE + 15) / 16 * 16;
 };
-
-__device__ __forceinline__ uint32_t w3_pack(float a, float b) {
-  const w3_bf16x2 v = {(__bf16)a, (__bf16)b};            // v_cvt_pk_bf16_f32 (round to nearest even)
-  return __builtin_bit_cast(uint32_t, v);
-}
-struct W3Tri { uint32_t h, m, l; };
-__device__ __forceinline__ W3Tri w3_split2(float x0, float x1) {
-  W3Tri t;
-  t.h = w3_pack(x0, x1);
-  const float r0 = x0 - __uint_as_float(t.h << 16), r1 = x1 - __uint_as_float(t.h & 0xffff0000u);       // exact
-  t.m = w3_pack(r0, r1);
-  const float s0 = r0 - __uint_as_float(t.m << 16), s1 = r1 - __uint_as_float(t.m & 0xffff0000u);       // exact
-  t.l = w3_pack(s0, s1);
-  return t;
-}
 
 // One operand tile in two steps (all loads in flight, then transform + split + LDS writes).  CH = staged channels (16 | 32): CH / 4
 // threads share a pixel; a quad beyond the tensor's C channels, or a pixel outside the plane, is stored as zero.
@@ -69,8 +49,8 @@ __device__ __forceinline__ void w3_load(W3Regs<NPIX, TWP, CH, TWO>& r, const flo
     const int iy = pix / TWP, ix = pix - iy * TWP;                  // (compile-time divisor)
     r.ok[u] = ch_ok && pix < NPIX && (unsigned)(oy + iy) < (unsigned)PH && (unsigned)(ox + ix) < (unsigned)PW;
     const uint32_t o = r.ok[u] ? (uint32_t)(((row0 + oy + iy) * PW + ox + ix) * C + 4 * q) : 0u;
-    r.x[u] = wld4(src + o);
-    if (TWO) { if (two) r.ax[u] = wld4(aux + o); }
+    r.x[u] = ld4(src + o);
+    if (TWO) { if (two) r.ax[u] = ld4(aux + o); }
   }
 }
 // IS_P: the pointwise image (its pitch and, with 32 channels, its block swizzle)
@@ -83,16 +63,16 @@ __device__ __forceinline__ void w3_store(const W3Regs<NPIX, TWP, CH, TWO>& r, co
   float4 k[5];
   if (MODE != RCV_LOAD_PLAIN) {
 #pragma unroll
-    for (int j = 0; j < 5; ++j) k[j] = ch_ok ? wld4(consts + (size_t)j * C + 4 * q) : make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int j = 0; j < 5; ++j) k[j] = ch_ok ? ld4(consts + (size_t)j * C + 4 * q) : make_float4(0.f, 0.f, 0.f, 0.f);
   }
 #pragma unroll
   for (int u = 0; u < R::NU; ++u) {
     const int pix = u * R::PP + lp;
-    float4 v = wxform4<MODE>(r.x[u], r.ax[TWO ? u : 0], k);
+    float4 v = xform4<MODE>(r.x[u], r.ax[TWO ? u : 0], k);
     if (!r.ok[u]) v = make_float4(0.f, 0.f, 0.f, 0.f);
     if (SUM) { sum.x += v.x; sum.y += v.y; sum.z += v.z; sum.w += v.w; }
     if (pix < NPIX) {
-      const W3Tri a = w3_split2(v.x, v.y), b = w3_split2(v.z, v.w);
+      const Bf3Tri a = bf3_split2(v.x, v.y), b = bf3_split2(v.z, v.w);
       char* d = img + pix * PITCH + 8 * q;
       if (IS_P && CH == 32) d = img + pix * PITCH + ((((q >> 2) ^ ((pix >> 2) & 1))) << 5) + 8 * (q & 3);
       *reinterpret_cast<uint2*>(d) = make_uint2(a.h, b.h);
@@ -100,12 +80,6 @@ __device__ __forceinline__ void w3_store(const W3Regs<NPIX, TWP, CH, TWO>& r, co
       *reinterpret_cast<uint2*>(d + 2 * PLANE) = make_uint2(a.l, b.l);
     }
   }
-}
-
-__device__ __forceinline__ w3_bf16x8 w3_read(const w3_lds_char* p, int off0, int off1) {
-  const w3_bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((w3_lds_bf16x4*)(p + off0));
-  const w3_bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((w3_lds_bf16x4*)(p + off1));
-  return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
 }
 
 // GTWO: the gathered operand may be a two-tensor gradient load (then the pointwise one is not); otherwise the pointwise one may be.
@@ -137,16 +111,7 @@ __global__ __launch_bounds__(512) void wgradn_bf3_kernel(const WgradArgs a) {
       w3_load(rp, a.p, a.p_aux, p_two, tid, a.CB, n * a.Hp, y0, x0, a.Hp, a.Wp);
       char* gi = buf;
       char* pi = buf + 3 * G::GPLANE;
-      if (GTWO) {
-        if (a.g_mode == RCV_LOAD_GRAD_ENC) w3_store<RCV_LOAD_GRAD_ENC, G::GPIX, G::IW, CAT, GTWO, false>(rg, a.g_c, gi, tid, a.CA, nosum);
-        else w3_store<RCV_LOAD_GRAD_DEC, G::GPIX, G::IW, CAT, GTWO, false>(rg, a.g_c, gi, tid, a.CA, nosum);
-      } else {
-        switch (a.g_mode) {
-          case RCV_LOAD_PLAIN: w3_store<RCV_LOAD_PLAIN, G::GPIX, G::IW, CAT, GTWO, false>(rg, a.g_c, gi, tid, a.CA, nosum); break;
-          case RCV_LOAD_AFFINE: w3_store<RCV_LOAD_AFFINE, G::GPIX, G::IW, CAT, GTWO, false>(rg, a.g_c, gi, tid, a.CA, nosum); break;
-          default: w3_store<RCV_LOAD_AFFINE_RELU, G::GPIX, G::IW, CAT, GTWO, false>(rg, a.g_c, gi, tid, a.CA, nosum); break;
-        }
-      }
+      with_load_mode<GTWO>(a.g_mode, [&](auto mode) { w3_store<mode(), G::GPIX, G::IW, CAT, GTWO, false>(rg, a.g_c, gi, tid, a.CA, nosum); });
       switch (a.p_mode) {
         case RCV_LOAD_PLAIN: w3_store<RCV_LOAD_PLAIN, G::PPIX, G::TW, CBT, !GTWO, true>(rp, a.p_c, pi, tid, a.CB, bsum); break;
         case RCV_LOAD_AFFINE: w3_store<RCV_LOAD_AFFINE, G::PPIX, G::TW, CBT, !GTWO, true>(rp, a.p_c, pi, tid, a.CB, bsum); break;
@@ -211,37 +176,36 @@ __global__ __launch_bounds__(512) void wgradn_bf3_kernel(const WgradArgs a) {
 #pragma unroll
   for (int m = 0; m < MB; ++m) a_lane[m] = 3 * G::GPLANE + kp * G::PP + ((CBT == 32 ? (m ^ ((kp >> 2) & 1)) : m) << 5) + 8 * p;
   const int g_lane = (kp * S) * G::GP + 8 * p;
-  const w3_lds_char* lds0 = (const w3_lds_char*)smem_w3;
+  const lds_char* lds0 = (const lds_char*)smem_w3;
 
-  auto contract = [&](const w3_lds_char* buf) {
+  auto contract = [&](const lds_char* buf) {
     for (int j = wave; j < NKS; j += 4) {
-      const w3_lds_char* pa = buf + (32 * j) * G::PP;
-      const w3_lds_char* pg = buf + g_lane + ((2 * j) * S * G::IW) * G::GP;
-      w3_bf16x8 A[MB][3];
+      const lds_char* pa = buf + (32 * j) * G::PP;
+      const lds_char* pg = buf + g_lane + ((2 * j) * S * G::IW) * G::GP;
+      bf16x8 A[MB][3];
 #pragma unroll
       for (int pl = 0; pl < 3; ++pl)
 #pragma unroll
-        for (int m = 0; m < MB; ++m) A[m][pl] = w3_read(pa + a_lane[m], pl * G::PPLANE, pl * G::PPLANE + 16 * G::PP);
-      auto load_b = [&](int t, w3_bf16x8 (&B)[NB][3]) {
+        for (int m = 0; m < MB; ++m) A[m][pl] = bf3_read_tr(pa + a_lane[m], pl * G::PPLANE, pl * G::PPLANE + 16 * G::PP);
+      auto load_b = [&](int t, bf16x8 (&B)[NB][3]) {
         const int ky = t / 3, kx = t % 3;
         const int r0 = ky * G::IW + kx, r1 = (S + ky) * G::IW + kx;         // tile rows 2 j and 2 j + 1
 #pragma unroll
         for (int pl = 0; pl < 3; ++pl)
 #pragma unroll
-          for (int nn = 0; nn < NB; ++nn) B[nn][pl] = w3_read(pg, pl * G::GPLANE + r0 * G::GP + nn * 32, pl * G::GPLANE + r1 * G::GP + nn * 32);
+          for (int nn = 0; nn < NB; ++nn) B[nn][pl] = bf3_read_tr(pg, pl * G::GPLANE + r0 * G::GP + nn * 32, pl * G::GPLANE + r1 * G::GP + nn * 32);
       };
-      w3_bf16x8 Bb[2][NB][3];
+      bf16x8 Bb[2][NB][3];
       load_b(0, Bb[0]);
 #pragma unroll
       for (int t = 0; t < 9; ++t) {
         if (t < 8) load_b(t + 1, Bb[(t + 1) & 1]);
-        constexpr int TA[6] = {2, 0, 1, 1, 0, 0}, TB[6] = {0, 2, 1, 0, 1, 0};      // smallest products first
 #pragma unroll
         for (int e = 0; e < 6; ++e)
 #pragma unroll
           for (int m = 0; m < MB; ++m)
 #pragma unroll
-            for (int nn = 0; nn < NB; ++nn) acc[t][m][nn] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A[m][TA[e]], Bb[t & 1][nn][TB[e]], acc[t][m][nn], 0, 0, 0);
+            for (int nn = 0; nn < NB; ++nn) acc[t][m][nn] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A[m][BF3_TA[e]], Bb[t & 1][nn][BF3_TB[e]], acc[t][m][nn], 0, 0, 0);
         if (t < 8) {
 #pragma unroll
           for (int e = 0; e < 6 * NB; ++e) {
@@ -317,13 +281,7 @@ void wgradn_bf3_geometry(const rcv_handle* h, const rcv_op* op, int* th, int* ti
 
 template <int CBT, int CAT, int S, int TH, bool GTWO>
 static int w3_launch_inst(const WgradArgs& a, int ngroups, hipStream_t s, int dev) {
-  auto kern = wgradn_bf3_kernel<CBT, CAT, S, TH, GTWO>;
-  const size_t lds = 2 * (size_t)W3Geom<CBT, CAT, S, TH>::BUF;
-  static size_t configured[RCV_MAX_DEVICES];
-  RCV_ENSURE_LDS(kern, lds, dev, configured);
-  hipLaunchKernelGGL(kern, dim3(ngroups), dim3(512), lds, s, a);
-  RCV_HIP(hipGetLastError());
-  return RCV_OK;
+  return rcv_launch_with_lds<wgradn_bf3_kernel<CBT, CAT, S, TH, GTWO>>(a, dim3(ngroups), 2 * (size_t)W3Geom<CBT, CAT, S, TH>::BUF, dev, s);
 }
 template <int CBT, int CAT, int S>
 static int w3_launch_th(const WgradArgs& a, int th, bool g_two, int ngroups, hipStream_t s, int dev) {

@@ -11,7 +11,7 @@
 //   raw tile i+1:  global --DMA--> LDS (lane-linear, no registers, no vector ALU, up to 64 KB per wave in flight), issued before
 //                  the MFMA phase of tile i and complete when it ends;
 //   transform:     raw -> operand layout in LDS, all 512 threads: the load transform of the producer (BatchNorm apply / ReLU /
-//                  BatchNorm+ReLU backward, wgrad_common.h), zeros outside the plane, the bias partial sums;
+//                  BatchNorm+ReLU backward, load_xform.h), zeros outside the plane, the bias partial sums;
 //   contract:      the 8 waves split the 4-pixel k-steps of the tile, operands prefetched one k-step ahead.
 //
 // LDS: tp[R*Wt4][SP] tg[IH*IW][SG] (operands, padded strides) | raw P (+ its second tensor) | raw G (+ its second tensor).
@@ -44,7 +44,7 @@ __device__ __forceinline__ void wdma_transform(const float* __restrict__ raw, co
   float4 k[5];
   if (MODE != RCV_LOAD_PLAIN) {
 #pragma unroll
-    for (int j = 0; j < 5; ++j) k[j] = ch_ok ? wld4(consts + (size_t)j * C + ch) : make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int j = 0; j < 5; ++j) k[j] = ch_ok ? ld4(consts + (size_t)j * C + ch) : make_float4(0.f, 0.f, 0.f, 0.f);
   }
   const float4* r4 = reinterpret_cast<const float4*>(raw);
   const float4* a4 = reinterpret_cast<const float4*>(raw_aux);
@@ -63,7 +63,7 @@ __device__ __forceinline__ void wdma_transform(const float* __restrict__ raw, co
       const int iy = fd_div(pix, fdTW), ix = pix - iy * TW;
       const int gy = oy + iy, gx = ox + ix;
       const bool ok = ch_ok && ix < TWV && (unsigned)gy < (unsigned)PH && (unsigned)gx < (unsigned)PW;
-      float4 v = wxform4<MODE>(x[u], ax[u], k);
+      float4 v = xform4<MODE>(x[u], ax[u], k);
       if (!ok) v = make_float4(0.f, 0.f, 0.f, 0.f);
       if (e < nslots) {
         if (SUM) { sum.x += v.x; sum.y += v.y; sum.z += v.z; sum.w += v.w; }

@@ -1,4 +1,4 @@
-"""The split-bf16 arithmetic of conv_bf3 / convn_bf3 / wgrad_bf3 / wgradn_bf3 (csrc/wgrad_bf3.hip has the statement).
+"""The split-bf16 arithmetic of conv_bf3 / convn_bf3 / wgrad_bf3 / wgradn_bf3 (csrc/split_bf16.h has the statement).
 
 CPU: the decomposition itself, restated in numpy -- an fp32 value is EXACTLY the sum of three bf16 values obtained by three
 round-to-nearest-even steps, and the three products the kernels leave out of the nine are below 2^-23 of |a b|.
