@@ -114,9 +114,15 @@ enum {
                              * block's output, its statistics rows in p[PART]), p[IN_AUX] = g[..., 0:i[AUX1]] as a dense NHWC tensor (the skip
                              * tensor's gradient: handed to the data-gradient launch of its other consumer as RCV_F_RESID), p[X1] = dW
                              * [COUT][16], p[X2] = db                                                                                         */
-  RCV_OP_LP_BATCH = 35      /* batch assembly of labelPropTrain.py:162-193 (rcv_labelprop_batch; csrc/lp_tail.hip): i[N] = B frame pairs, i[CIN] =
+  RCV_OP_LP_BATCH = 35,     /* batch assembly of labelPropTrain.py:162-193 (rcv_labelprop_batch; csrc/lp_tail.hip): i[N] = B frame pairs, i[CIN] =
                              * channels per frame, i[H], i[W], i[COUT] = classes (5); p[IN] = images float[B][2][C][H][W], p[IN2] = labels
                              * int64[B][2][H][W], p[OUT] = inputs float[2B][H][W][8] (NHWC), p[X0] = targets int64[2B][H][W]              */
+  RCV_OP_BATCH_PREP = 36    /* the loader's per-image work of dataset.py:107-133 for a whole batch (rcv_batch_prep; csrc/batch_prep.hip): i[N] = B,
+                             * i[H] / i[W] = source Hs / Ws, i[HO] / i[WO] = output H / W, i[CIN] / i[COUT] = taps per output column / row of the
+                             * frame tables, i[INMODE2] = label element bytes (1 = uint8, 4 = int32), i[AUX0] = train (0 / 1), i[AUX1] = maskLabel
+                             * flags (1 = nb, 2 = nr, 4 = ng, 8 = nl); p[IN] = frames uint8[B][Hs][Ws][3], p[IN2] = labels [B][Hs][Ws], p[X1] / p[X2] =
+                             * frame tables of x / y, p[X3] / p[X4] = label index tables of x / y, p[X5] = normalisation table float[3][256],
+                             * p[IN_C] = parameter rows float[B][8] (train only), p[OUT] = imgs float[B][3][H][W], p[X0] = targets int64[B][H][W] */
 };
 
 /* how an operand is produced from memory while it is staged (rcv_op.i[RCV_I_INMODE] etc.) */
@@ -353,6 +359,25 @@ int rcv_object_match(rcv_handle* h, const void* pred, int pred_bytes, const void
  * [0, 5) gives -1 in all five class channels (it is never used as an index).  Exact: copies, +-1 and one fp32 subtraction.        */
 int rcv_labelprop_batch(rcv_handle* h, const float* images, const int64_t* labels, int B, int C, int H, int W, int num_class,
                         float* inputs, int64_t* targets, void* stream);
+
+/* The per-image work of the reference's loader (SSYUVDataset.__getitem__, dataset.py:107-133; ColorJitter, dataset.py:19-39) and the
+ * training loop's maskLabel (transform.py:26-49, train.py:43-46) for a whole batch in one launch: frames uint8[B][Hs][Ws][3] (decoded
+ * RGB) and labels [B][Hs][Ws] (label_bytes 1 = uint8, 4 = int32: Image.convert('I')) -> imgs float[B][3][H][W] (NCHW: what the network's
+ * first conv reads) and targets int64[B][H][W].  Resize = Pillow's 8-bit BILINEAR as two integer passes (horizontal, rounded to uint8,
+ * then vertical; out = clip((sum + 2^21) >> 22)) and Pillow's NEAREST index rule for the labels, all from host-made tables:
+ * frame_x int32[W][2 + kx] / frame_y int32[H][2 + ky] = {first tap, tap count, 22-bit coefficients} per output index (kx, ky = Pillow's
+ * taps per index, ceil(max(in / out, 1)) * 2 + 1 <= 17: an axis shrinks by at most 8; an axis of equal size has the rows {i, 1, 2^22}),
+ * label_x int32[W] / label_y int32[H] = source index per output index.  Then norm float[3][256] (to_tensor + Normalize per byte value)
+ * and, with train != 0, per image the row params[b] = {flip, b, c, m00, m01, m10, m11, uv_off}: x mirrored when flip != 0,
+ * y = (y + b) * c, and unless uv_off != 0 u' = m00 u + m01 v, v' = m10 u + m11 v; train == 0 (the validation loader) takes none of
+ * these and params may be NULL.  The label is gathered, mirrored, passed through maskLabel's sequential rule (mask_flags bits 1 = nb,
+ * 2 = nr, 4 = ng, 8 = nl) and widened.  Exact (integer passes, a table lookup, two fp32 operations) except u' / v', which are one fused
+ * multiply-add each: within 2^-23 (|m0 u| + |m1 v|) of the exact value, as the reference's einsum is.  No random numbers and no
+ * trigonometry on the device.                                                                                                    */
+int rcv_batch_prep(rcv_handle* h, const uint8_t* frames, const void* labels, int label_bytes, int B, int Hs, int Ws, int H, int W,
+                   const int32_t* frame_x, int kx, const int32_t* frame_y, int ky, const int32_t* label_x, const int32_t* label_y,
+                   const float* norm, const float* params /*NULL unless train*/, int train, int mask_flags, float* imgs, int64_t* targets,
+                   void* stream);
 
 /* torch.optim.SGD.step (trainer.py:176-178,221): g = grad*grad_scale + weight_decay*p; buf = step==1 ? g : momentum*buf + g;
  * p -= lr*buf.  lr_elem (may be NULL) gives a per-element learning rate (0 = parameter without a gradient: untouched). */

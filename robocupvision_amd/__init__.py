@@ -12,4 +12,11 @@ def __getattr__(name):
     if name == "labelprop_batch":
         from .model import labelprop_batch
         return labelprop_batch
+    # robocupvision_amd.data / prepare_batch / draw_jitter / SSYUVDataset: batches prepared on the device (data.py)
+    if name == "data":
+        import importlib
+        return importlib.import_module(".data", __name__)
+    if name in ("prepare_batch", "draw_jitter", "SSYUVDataset"):
+        from . import data
+        return getattr(data, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

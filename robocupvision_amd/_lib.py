@@ -23,6 +23,7 @@ RCV_P__N = 20
  OP_WGRAD_REDUCE_BATCH, OP_POOL_CLS_FWD, OP_POOL_CLS_BWD) = range(1, 32)
 OP_OBJECT_MATCH = 32       # object-detection counts (rcv.h RCV_OP_OBJECT_MATCH, csrc/objdet.hip)
 OP_LP_TAIL_FWD, OP_LP_TAIL_BWD, OP_LP_BATCH = 33, 34, 35      # LabelProp's training tail and batch assembly (rcv.h, csrc/lp_tail.hip)
+OP_BATCH_PREP = 36          # the loader's per-image work for a whole batch (rcv.h RCV_OP_BATCH_PREP, csrc/batch_prep.hip)
 
 LOAD_PLAIN, LOAD_AFFINE, LOAD_GRAD_ENC, LOAD_GRAD_DEC, LOAD_NCHW, LOAD_AFFINE_RELU = range(6)
 STATS_NONE, STATS_FWD, STATS_BWD_ENC, STATS_BWD_DEC = range(4)
@@ -55,7 +56,7 @@ EXPORTS = [
     "rcv_conv3x3", "rcv_convT3x3s2", "rcv_wgrad3x3", "rcv_bn_finalize", "rcv_bn_backward", "rcv_maxpool2x2_fwd",
     "rcv_softmax_ce_argmax_fwd", "rcv_softmax_ce_bwd", "rcv_adam_l1_step", "rcv_adam_l1_step_metrics", "rcv_confusion",
     "rcv_dice_fwd", "rcv_dice_bwd", "rcv_sgd_step", "rcv_create_planner", "rcv_adam_l1_step_pruned", "rcv_op_filter_layout",
-    "rcv_object_match", "rcv_labelprop_batch",
+    "rcv_object_match", "rcv_labelprop_batch", "rcv_batch_prep",
 ]
 
 
@@ -97,6 +98,8 @@ def load():
                                          C.c_void_p]
         lib.rcv_labelprop_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                             C.c_void_p, C.c_void_p]
+        lib.rcv_batch_prep.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p, C.c_int, C.c_void_p, C.c_int] + \
+            [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         for name in ("rcv_conv3x3", "rcv_convT3x3s2", "rcv_wgrad3x3"):
             getattr(lib, name).argtypes = [C.c_void_p, C.POINTER(RcvOp), C.c_void_p]
         _lib = lib

@@ -114,6 +114,8 @@ static int dispatch(const rcv_handle* h, const rcv_op* op, hipStream_t s, OpQuer
       return rcv_launch_lp_tail(h, op, s, q);
     case RCV_OP_LP_BATCH:
       return rcv_launch_lp_batch(h, op, s, q);
+    case RCV_OP_BATCH_PREP:
+      return rcv_launch_batch_prep(h, op, s, q);
     case RCV_OP_NOP:
       if (q) { snprintf(q->label, sizeof(q->label), "nop"); q->n_part = 0; q->n_split = 0; q->part_bytes = 0; }
       return RCV_OK;
@@ -382,6 +384,20 @@ int rcv_labelprop_batch(rcv_handle* h, const float* images, const int64_t* label
   op.kind = RCV_OP_LP_BATCH;
   op.i[RCV_I_N] = B; op.i[RCV_I_H] = H; op.i[RCV_I_W] = W; op.i[RCV_I_CIN] = C; op.i[RCV_I_COUT] = num_class;
   op.p[RCV_P_IN] = (void*)images; op.p[RCV_P_IN2] = (void*)labels; op.p[RCV_P_OUT] = inputs; op.p[RCV_P_X0] = targets;
+  return rcv_run(h, &op, 1, stream);
+}
+
+int rcv_batch_prep(rcv_handle* h, const uint8_t* frames, const void* labels, int label_bytes, int B, int Hs, int Ws, int H, int W,
+                   const int32_t* frame_x, int kx, const int32_t* frame_y, int ky, const int32_t* label_x, const int32_t* label_y,
+                   const float* norm, const float* params, int train, int mask_flags, float* imgs, int64_t* targets, void* stream) {
+  rcv_op op;
+  memset(&op, 0, sizeof(op));
+  op.kind = RCV_OP_BATCH_PREP;
+  op.i[RCV_I_N] = B; op.i[RCV_I_H] = Hs; op.i[RCV_I_W] = Ws; op.i[RCV_I_HO] = H; op.i[RCV_I_WO] = W; op.i[RCV_I_CIN] = kx; op.i[RCV_I_COUT] = ky;
+  op.i[RCV_I_INMODE2] = label_bytes; op.i[RCV_I_AUX0] = train; op.i[RCV_I_AUX1] = mask_flags;
+  op.p[RCV_P_IN] = (void*)frames; op.p[RCV_P_IN2] = (void*)labels; op.p[RCV_P_OUT] = imgs; op.p[RCV_P_X0] = targets;
+  op.p[RCV_P_X1] = (void*)frame_x; op.p[RCV_P_X2] = (void*)frame_y; op.p[RCV_P_X3] = (void*)label_x; op.p[RCV_P_X4] = (void*)label_y;
+  op.p[RCV_P_X5] = (void*)norm; op.p[RCV_P_IN_C] = (void*)params;
   return rcv_run(h, &op, 1, stream);
 }
 

@@ -1,0 +1,259 @@
+// RCV_OP_BATCH_PREP (rcv_batch_prep): the per-image work of the reference's loader, dataset.py:107-133 (SSYUVDataset.__getitem__), with
+// ColorJitter (dataset.py:19-39) and the training loop's maskLabel (transform.py:26-49, train.py:43-46), for a whole batch in one launch:
+//   uint8 RGB frames [B][Hs][Ws][3] + label planes [B][Hs][Ws] (uint8 / int32)  ->  fp32 NCHW [B][3][H][W] + int64 targets [B][H][W].
+// Arithmetic in the reference's order:
+//   1. Pillow's 8-bit BILINEAR resize as two integer passes (horizontal, rounded to uint8, then vertical): per output index a first tap,
+//      a tap count and 22-bit integer coefficients, all made on the host (robocupvision_amd/data.py); out = clip((sum + 2^21) >> 22).
+//      A pass whose two sizes are equal has the one-tap table {i, 1, 2^22}, which returns the byte unchanged (Pillow skips the pass).
+//   2. to_tensor + Normalize as a [3][256] fp32 table lookup;  3. mirrored x when flip;  4. y = (y + b) * c;
+//   5. u' = m00 u + m01 v, v' = m10 u + m11 v (one fused multiply-add each: within 2^-23 (|m0 u| + |m1 v|) of exact, as the reference's);
+//   6. label: gather through the NEAREST index tables, mirror, maskLabel as the reference's sequential rule, widen to int64.
+// Nothing random and no trigonometry here: the parameter row {flip, b, c, m00, m01, m10, m11, uv_off} per image comes from the host.
+//
+// Tiling: one workgroup = 8 output rows x 64 output columns of one image; lane = output x (one wave = one row of the tile).  The
+// horizontal pass of the source rows the tile's vertical taps span goes to LDS as bytes ([rows][64][3], <= 74 rows); the vertical pass,
+// the lookup and the jitter read it back, and the three plane stores and the target store are each contiguous over the lanes (reversed
+// when flipped).  STAGE: the source-row segments of the tile are first copied to LDS with 16-byte aligned loads, 8 rows at a time, and
+// the horizontal taps read LDS bytes; otherwise the taps read global bytes through the cache (DESIGN.md 4.5 has the measurement).
+// Every table entry is clamped where it is used: a wrong table gives wrong pixels, never an access outside the operands.
+#include "rcv_internal.h"
+
+#define BP_TR 8
+#define BP_TC 64
+#define BP_MAXK 17                       /* taps of a downscale by 8: ceil(8) * 2 + 1 */
+#define BP_ROWS_MAX 74                   /* ceil(7 * 8 + 2 * 8) + 2 source rows under 8 output rows */
+#define BP_RC 8                          /* source rows staged at a time */
+#define BP_SEG 1600                      /* bytes of one staged row segment: ((63 * 8 + 2 * 8 + 2) * 3 + 15) rounded up to 16 */
+#define BP_PREC 22
+#define BP_STAGE_MIN_TAPS 9                  /* taps per output column from which the source rows are staged in LDS */
+
+struct BpArgs {
+  const uint8_t* frames; const void* labels; float* imgs; int64_t* tgt;
+  const int32_t* xtab; const int32_t* ytab; const int32_t* lx; const int32_t* ly; const float* norm; const float* params;
+  int B, Hs, Ws, H, W, kx, ky, lab_bytes, train, mask, rows_cap, tiles_x, tiles_y;
+};
+
+__device__ __forceinline__ int bp_clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+__device__ __forceinline__ int bp_clip8(int acc) { return bp_clampi(acc >> BP_PREC, 0, 255); }
+
+// transform.py:26-49 on one value; m bits: 1 = nb, 2 = nr, 4 = ng, 8 = nl (the branches are uniform over the launch)
+__device__ __forceinline__ int bp_mask(int v, int m) {
+  int rN = 2, gN = 3, lN = 4;
+  if (m & 1) { if (v == 1) v = 0; if (v > 1) v -= 1; rN = 1; gN = 2; lN = 3; }
+  if (m & 2) { if (v == rN) v = 0; if (v > rN) v -= 1; gN = 1; lN = 2; }
+  if (m & 4) { if (v == gN) v = 0; if (v > gN) v -= 1; lN = 1; }
+  if (m & 8) { if (v == lN) v = 0; }
+  return v;
+}
+
+struct BpJitter { bool flip, uv; float b, c, m00, m01, m10, m11; };
+
+__device__ __forceinline__ BpJitter bp_jitter(const BpArgs& a, int b) {
+  BpJitter j;
+  j.flip = false; j.uv = false; j.b = 0.f; j.c = 1.f; j.m00 = 1.f; j.m01 = 0.f; j.m10 = 0.f; j.m11 = 1.f;
+  if (a.train) {
+    const float* p = a.params + (size_t)b * 8;
+    j.flip = p[0] != 0.f; j.b = p[1]; j.c = p[2]; j.m00 = p[3]; j.m01 = p[4]; j.m10 = p[5]; j.m11 = p[6]; j.uv = p[7] == 0.f;
+  }
+  return j;
+}
+
+// steps 2-6 for one output pixel (x, y: coordinates before the mirror) of image b from its three resized bytes
+template <typename LUT>
+__device__ __forceinline__ void bp_finish(const BpArgs& a, const BpJitter& j, LUT lut, int b, int y, int x, int c0, int c1, int c2) {
+  float v0 = lut[c0], v1 = lut[256 + c1], v2 = lut[512 + c2];
+  const int xo = j.flip ? a.W - 1 - x : x;
+  if (a.train) {
+    v0 = (v0 + j.b) * j.c;
+    if (j.uv) {
+      const float u = v1, v = v2;
+      v1 = fmaf(j.m00, u, j.m01 * v);
+      v2 = fmaf(j.m10, u, j.m11 * v);
+    }
+  }
+  const size_t plane = (size_t)a.H * a.W, o = (size_t)y * a.W + xo;
+  float* img = a.imgs + (size_t)b * 3 * plane + o;
+  img[0] = v0; img[plane] = v1; img[2 * plane] = v2;
+  const int sy = bp_clampi(a.ly[y], 0, a.Hs - 1), sx = bp_clampi(a.lx[x], 0, a.Ws - 1);
+  const size_t li = ((size_t)b * a.Hs + sy) * a.Ws + sx;
+  const int lv = a.lab_bytes == 1 ? (int)((const uint8_t*)a.labels)[li] : ((const int32_t*)a.labels)[li];
+  a.tgt[(size_t)b * plane + o] = (int64_t)bp_mask(lv, a.mask);
+}
+
+template <bool STAGE>
+__global__ __launch_bounds__(256) void batch_prep_kernel(BpArgs a) {
+  __shared__ float s_lut[768];
+  __shared__ int32_t s_xc[BP_TC * (2 + BP_MAXK)];
+  __shared__ int32_t s_yc[BP_TR * (2 + BP_MAXK)];
+  __shared__ uint8_t s_h[BP_ROWS_MAX * BP_TC * 3];
+  __shared__ __align__(16) uint8_t s_src[STAGE ? BP_RC * BP_SEG : 16];
+  const int tid = threadIdx.x;
+  const int bid = blockIdx.x;
+  const int tx = bid % a.tiles_x, ty = (bid / a.tiles_x) % a.tiles_y, b = bid / (a.tiles_x * a.tiles_y);
+  const int x0 = tx * BP_TC, y0 = ty * BP_TR;
+  const int tw = min(BP_TC, a.W - x0), th = min(BP_TR, a.H - y0);
+  const int sx = 2 + a.kx, sy = 2 + a.ky;
+  for (int i = tid; i < 768; i += 256) s_lut[i] = a.norm[i];
+  for (int i = tid; i < tw * sx; i += 256) s_xc[i] = a.xtab[(size_t)x0 * sx + i];
+  for (int i = tid; i < th * sy; i += 256) s_yc[i] = a.ytab[(size_t)y0 * sy + i];
+  __syncthreads();
+  const BpJitter j = bp_jitter(a, b);
+  // source rows under this tile's vertical taps
+  const int ys0 = bp_clampi(s_yc[0], 0, a.Hs - 1);
+  const int ys1 = bp_clampi(s_yc[(th - 1) * sy] + s_yc[(th - 1) * sy + 1], ys0 + 1, a.Hs);
+  const int nrows = min(ys1 - ys0, a.rows_cap);
+  const uint8_t* fb = a.frames + (size_t)b * a.Hs * a.Ws * 3;
+
+  // ---- horizontal pass: s_h[r][x][c] for the rows ys0 .. ys0 + nrows; this thread's column is fixed
+  const int x = tid & (BP_TC - 1);
+  const int32_t* xc = s_xc + (x < tw ? x : 0) * sx;
+  const int xf = bp_clampi(xc[0], 0, a.Ws - 1);
+  const int xn = min(bp_clampi(xc[1], 0, a.kx), a.Ws - xf);
+  if (!STAGE) {
+    if (x < tw) {
+      for (int r = tid >> 6; r < nrows; r += 4) {
+        const uint8_t* p = fb + ((size_t)(ys0 + r) * a.Ws + xf) * 3;
+        int a0 = 1 << (BP_PREC - 1), a1 = a0, a2 = a0;
+        for (int k = 0; k < xn; ++k) {
+          const int c = xc[2 + k];
+          a0 += (int)p[3 * k] * c; a1 += (int)p[3 * k + 1] * c; a2 += (int)p[3 * k + 2] * c;
+        }
+        uint8_t* q = s_h + (r * BP_TC + x) * 3;
+        q[0] = (uint8_t)bp_clip8(a0); q[1] = (uint8_t)bp_clip8(a1); q[2] = (uint8_t)bp_clip8(a2);
+      }
+    }
+  } else {
+    // source pixels under this tile's horizontal taps: [xs0, xs0 + segpix)
+    const int xs0 = bp_clampi(s_xc[0], 0, a.Ws - 1);
+    const int xs1 = bp_clampi(s_xc[(tw - 1) * sx] + s_xc[(tw - 1) * sx + 1], xs0 + 1, a.Ws);
+    const int segpix = min(xs1 - xs0, (BP_SEG - 16) / 3);
+    const int seg = segpix * 3;
+    const int nvmax = (seg + 15 + 15) / 16;
+    const int rel = bp_clampi(xf - xs0, 0, segpix - 1);
+    const int xns = min(xn, segpix - rel);
+    const uintptr_t lo = (uintptr_t)a.frames, hi = lo + (size_t)a.B * a.Hs * a.Ws * 3;
+    for (int r0 = 0; r0 < nrows; r0 += BP_RC) {
+      const int nr = min(BP_RC, nrows - r0);
+      for (int i = tid; i < nr * nvmax; i += 256) {
+        const int rr = i / nvmax, v = i - rr * nvmax;
+        const uintptr_t A = (uintptr_t)(fb + ((size_t)(ys0 + r0 + rr) * a.Ws + xs0) * 3);
+        const uintptr_t va = (A & ~(uintptr_t)15) + 16u * (uintptr_t)v;
+        if (va >= A + seg) continue;
+        uint4 w;
+        if (va >= lo && va + 16 <= hi) {
+          w = *(const uint4*)va;
+        } else {                          // the first / last 16 bytes of the whole frame buffer when it is not 16-byte aligned
+          uint32_t d[4] = {0u, 0u, 0u, 0u};
+          for (int t = 0; t < 16; ++t) {
+            const uintptr_t ad = va + t;
+            if (ad >= lo && ad < hi) d[t >> 2] |= (uint32_t)(*(const uint8_t*)ad) << (8 * (t & 3));
+          }
+          w = make_uint4(d[0], d[1], d[2], d[3]);
+        }
+        *(uint4*)(s_src + rr * BP_SEG + 16 * v) = w;
+      }
+      __syncthreads();
+      if (x < tw) {
+        for (int rr = tid >> 6; rr < nr; rr += 4) {
+          const uintptr_t A = (uintptr_t)(fb + ((size_t)(ys0 + r0 + rr) * a.Ws + xs0) * 3);
+          const uint8_t* p = s_src + rr * BP_SEG + (int)(A & 15) + rel * 3;
+          int a0 = 1 << (BP_PREC - 1), a1 = a0, a2 = a0;
+          for (int k = 0; k < xns; ++k) {
+            const int c = xc[2 + k];
+            a0 += (int)p[3 * k] * c; a1 += (int)p[3 * k + 1] * c; a2 += (int)p[3 * k + 2] * c;
+          }
+          uint8_t* q = s_h + ((r0 + rr) * BP_TC + x) * 3;
+          q[0] = (uint8_t)bp_clip8(a0); q[1] = (uint8_t)bp_clip8(a1); q[2] = (uint8_t)bp_clip8(a2);
+        }
+      }
+      __syncthreads();
+    }
+  }
+  __syncthreads();
+
+  // ---- vertical pass + steps 2-6
+  for (int idx = tid; idx < th * BP_TC; idx += 256) {
+    const int yl = idx >> 6;
+    if (x >= tw) continue;
+    const int32_t* yc = s_yc + yl * sy;
+    const int yf = yc[0] - ys0, yn = bp_clampi(yc[1], 0, a.ky);
+    int a0 = 1 << (BP_PREC - 1), a1 = a0, a2 = a0;
+    for (int k = 0; k < yn; ++k) {
+      const int c = yc[2 + k];
+      const uint8_t* q = s_h + (bp_clampi(yf + k, 0, nrows - 1) * BP_TC + x) * 3;
+      a0 += (int)q[0] * c; a1 += (int)q[1] * c; a2 += (int)q[2] * c;
+    }
+    bp_finish(a, j, s_lut, b, y0 + yl, x0 + x, bp_clip8(a0), bp_clip8(a1), bp_clip8(a2));
+  }
+}
+
+// H == Hs and W == Ws: no resize (dataset.py:118-121); one thread per pixel, 2048 pixels of one image per workgroup
+#define BP_IDENT_PIX 2048
+__global__ __launch_bounds__(256) void batch_prep_ident_kernel(BpArgs a, int blocks_per_image) {
+  const int b = blockIdx.x / blocks_per_image, blk = blockIdx.x % blocks_per_image;
+  const BpJitter j = bp_jitter(a, b);
+  const int npix = a.H * a.W;
+  const uint8_t* fb = a.frames + (size_t)b * npix * 3;
+  const int end = min(npix, (blk + 1) * BP_IDENT_PIX);
+  for (int p = blk * BP_IDENT_PIX + threadIdx.x; p < end; p += 256) {
+    const int y = p / a.W, x = p - y * a.W;
+    const uint8_t* q = fb + (size_t)p * 3;
+    bp_finish(a, j, a.norm, b, y, x, (int)q[0], (int)q[1], (int)q[2]);
+  }
+}
+
+// Pillow's precompute_coeffs: taps per output index of the BILINEAR filter
+static int bp_ksize(int in, int out) {
+  double scale = (double)in / out;
+  if (scale < 1.0) scale = 1.0;
+  int c = (int)scale;
+  if ((double)c < scale) ++c;
+  return c * 2 + 1;
+}
+
+// Every refusal that depends on the shape of the record, and the tables (a plan without them has nothing to read), sits in front of
+// the `query` return; the batch operands are checked at launch.
+int rcv_launch_batch_prep(const rcv_handle* h, const rcv_op* op, hipStream_t s, OpQuery* query) {
+  const int B = op->i[RCV_I_N], Hs = op->i[RCV_I_H], Ws = op->i[RCV_I_W], H = op->i[RCV_I_HO], W = op->i[RCV_I_WO];
+  const int kx = op->i[RCV_I_CIN], ky = op->i[RCV_I_COUT], lab_bytes = op->i[RCV_I_INMODE2], train = op->i[RCV_I_AUX0], mask = op->i[RCV_I_AUX1];
+  if (query) { query->n_part = 0; query->n_split = 0; query->part_bytes = 0; snprintf(query->label, sizeof(query->label), "batch_prep"); }
+  RCV_CHECK_ARG(B >= 1 && H >= 1 && W >= 1 && Hs >= 1 && Ws >= 1, "batch prep: B %d, source %d x %d, output %d x %d: every size must be >= 1", B, Hs, Ws,
+                H, W);
+  RCV_CHECK_ARG((long long)Hs <= 8LL * H && (long long)Ws <= 8LL * W,
+                "batch prep: %d x %d -> %d x %d shrinks an axis by more than 8 (the kernel is built for at most %d taps)", Hs, Ws, H, W, BP_MAXK);
+  RCV_CHECK_ARG(lab_bytes == 1 || lab_bytes == 4, "batch prep: label element size %d unsupported (1 = uint8, 4 = int32)", lab_bytes);
+  RCV_CHECK_ARG(kx == bp_ksize(Ws, W) && ky == bp_ksize(Hs, H), "batch prep: %d / %d taps per column / row given, %d -> %d and %d -> %d take %d / %d", kx,
+                ky, Ws, W, Hs, H, bp_ksize(Ws, W), bp_ksize(Hs, H));
+  RCV_CHECK_ARG((train == 0 || train == 1) && mask >= 0 && mask <= 15, "batch prep: train %d / maskLabel flags %d out of range", train, mask);
+  const int tiles_x = ceil_div(W, BP_TC), tiles_y = ceil_div(H, BP_TR);
+  RCV_CHECK_ARG((double)B * Hs * Ws < 2147483647.0 && (double)B * H * W < 2147483647.0 && (double)B * tiles_x * tiles_y < 2147483647.0,
+                "batch prep: %d images of %d x %d -> %d x %d: more than 2^31 pixels", B, Hs, Ws, H, W);
+  RCV_CHECK_ARG(op->p[RCV_P_X1] && op->p[RCV_P_X2] && op->p[RCV_P_X3] && op->p[RCV_P_X4] && op->p[RCV_P_X5],
+                "batch prep: null table (frame taps of x / y, label index of x / y, normalisation)");
+  if (query) return RCV_OK;
+  RCV_CHECK_ARG(op->p[RCV_P_IN] && op->p[RCV_P_IN2] && op->p[RCV_P_OUT] && op->p[RCV_P_X0], "batch prep: null operand");
+  RCV_CHECK_ARG(!train || op->p[RCV_P_IN_C], "batch prep: training mode needs the parameter rows float[B][8]");
+  BpArgs a;
+  a.frames = (const uint8_t*)op->p[RCV_P_IN]; a.labels = op->p[RCV_P_IN2]; a.imgs = (float*)op->p[RCV_P_OUT]; a.tgt = (int64_t*)op->p[RCV_P_X0];
+  a.xtab = (const int32_t*)op->p[RCV_P_X1]; a.ytab = (const int32_t*)op->p[RCV_P_X2]; a.lx = (const int32_t*)op->p[RCV_P_X3];
+  a.ly = (const int32_t*)op->p[RCV_P_X4]; a.norm = (const float*)op->p[RCV_P_X5]; a.params = (const float*)op->p[RCV_P_IN_C];
+  a.B = B; a.Hs = Hs; a.Ws = Ws; a.H = H; a.W = W; a.kx = kx; a.ky = ky; a.lab_bytes = lab_bytes; a.train = train; a.mask = mask;
+  a.tiles_x = tiles_x; a.tiles_y = tiles_y;
+  if (H == Hs && W == Ws) {
+    const int bpi = ceil_div(H * W, BP_IDENT_PIX);
+    RCV_CHECK_ARG((double)B * bpi < 2147483647.0, "batch prep: grid too large");
+    hipLaunchKernelGGL(batch_prep_ident_kernel, dim3(B * bpi), dim3(256), 0, s, a, bpi);
+    RCV_HIP(hipGetLastError());
+    return RCV_OK;
+  }
+  const double scale_y = (double)Hs / H, support_y = scale_y < 1.0 ? 1.0 : scale_y;
+  const double span = (BP_TR - 1) * scale_y + 2.0 * support_y;
+  a.rows_cap = (int)span + ((double)(int)span < span ? 1 : 0) + 2;
+  if (a.rows_cap > BP_ROWS_MAX) a.rows_cap = BP_ROWS_MAX;
+  // staging pays where the row shrinks by more than about 3 (measured); RCV_BP_STAGE=0 / 1 overrides it in diagnostic builds
+  bool stage = kx >= BP_STAGE_MIN_TAPS;
+  if (const char* e = RCV_ENV("RCV_BP_STAGE")) stage = e[0] != '0';
+  hipLaunchKernelGGL(stage ? batch_prep_kernel<true> : batch_prep_kernel<false>, dim3(B * tiles_x * tiles_y), dim3(256), 0, s, a);
+  RCV_HIP(hipGetLastError());
+  return RCV_OK;
+}
