@@ -139,8 +139,8 @@ enum {
 enum {
   RCV_STATS_NONE   = 0,
   RCV_STATS_FWD    = 1,    /* sum v, sum v*v                     (BatchNorm batch statistics)    */
-  RCV_STATS_BWD_ENC= 2,    /* sum g, sum g*e      e = epi_aux    (BN backward, conv->ReLU->BN)   */
-  RCV_STATS_BWD_DEC= 3     /* sum g*m, sum g*m*e  m = (e*c0+c1>0) (BN backward, convT->BN->ReLU) */
+  RCV_STATS_BWD_ENC= 2,    /* sum g, sum g*(e-mean)     e = epi_aux, mean = epi_c row 2 (BN backward, conv->ReLU->BN)   */
+  RCV_STATS_BWD_DEC= 3     /* sum g*m, sum g*m*(e-mean) m = (e*c0+c1>0)                 (BN backward, convT->BN->ReLU) */
 };
 
 /* flag bits (rcv_op.flags) */
@@ -199,7 +199,7 @@ enum {
   RCV_P_OUT,
   RCV_P_RESID,
   RCV_P_EPI_AUX,     /* tensor e of the BWD statistics                                            */
-  RCV_P_EPI_C,       /* float[2][C]: (c0,c1) of RCV_STATS_BWD_DEC                                 */
+  RCV_P_EPI_C,       /* float[3][C]: (c0, c1) = the mask of RCV_STATS_BWD_DEC, row 2 = the batch mean both backward kinds centre e about */
   RCV_P_PART,        /* partial rows                                                              */
   RCV_P_IN2,         /* WGRAD: pointwise operand                                                  */
   RCV_P_IN2_AUX,

@@ -355,7 +355,7 @@ __global__ void cls_fwd_kernel(const float* __restrict__ x, const float* __restr
       const int tg = (int)target[p];
       float vt = 0.f;
 #pragma unroll
-      for (int c = 0; c < CLS_MAX_OUT; ++c) if (c == tg) vt = lg[c];
+      for (int c = 0; c < CLS_MAX_OUT; ++c) if (c == tg && c < COUT) vt = lg[c];     // (a label in [COUT, 8) has no logit: lg[c] is unset there)
       const float wt = (unsigned)tg < (unsigned)COUT ? (cw ? cw[tg] : 1.f) : 0.f;   // label outside [0, C) (e.g. -100): ignored, like NLLLoss's ignore_index
       const float nll = (mx - vt) + logf(se);
       a_nll += (double)(wt * nll);
@@ -598,7 +598,7 @@ __global__ void ce_fwd_kernel(const float* __restrict__ logits, const int64_t* _
     const int tg = (int)target[p];
     float vt = 0.f;
 #pragma unroll
-    for (int c = 0; c < CE_MAX_C; ++c) if (c == tg) vt = v[c];
+    for (int c = 0; c < CE_MAX_C; ++c) if (c == tg && c < C) vt = v[c];     // (a label in [C, 8) has no logit: v[c] is unset there)
     const float w = (unsigned)tg < (unsigned)C ? (cw ? cw[tg] : 1.f) : 0.f;   // label outside [0, C) (e.g. -100): ignored, like NLLLoss's ignore_index
     const float nll = (mx - vt) + logf(se);
     a_nll += (double)(w * nll);
@@ -1430,7 +1430,10 @@ int rcv_launch_small(const rcv_handle* h, const rcv_op* op, hipStream_t s, OpQue
       RCV_CHECK_ARG(Cout % 4 == 0 && Cout <= 512 && 256 % (Cout / 4) == 0 && H % 2 == 0 && W % 2 == 0, "maxpool backward: C=%d H=%d W=%d unsupported", Cout, H, W);
       const int g = reduce_grid(h, (size_t)N * (H / 2) * (W / 2) * (Cout / 4), 256);
       const int stats = op->i[RCV_I_STATS];
+      const int C4 = Cout / 4;
+      const bool rows = (C4 & (C4 - 1)) == 0 && C4 < 64 && ((long long)W * C4) % 64 == 0 && !RCV_ENV("RCV_NO_POOL_ROWS");      // see pool_bwd_rows_kernel
       if (query) {
+        if (rows) snprintf(query->label, sizeof(query->label), "pool_bwd_rows");
         query->n_part = stats != RCV_STATS_NONE ? g : 0;
         query->part_bytes = (size_t)query->n_part * 2 * Cout * sizeof(float);
         return RCV_OK;
@@ -1439,8 +1442,6 @@ int rcv_launch_small(const rcv_handle* h, const rcv_op* op, hipStream_t s, OpQue
       RCV_CHECK_ARG(stats == RCV_STATS_NONE || (op->p[RCV_P_PART] && op->i[RCV_I_NPART] == g), "maxpool backward: workspace rows mismatch");
       const float* resid = (op->flags & RCV_F_RESID) ? (const float*)op->p[RCV_P_RESID] : nullptr;
       const size_t lds = 2 * 256 * sizeof(float4);
-      const int C4 = Cout / 4;
-      const bool rows = (C4 & (C4 - 1)) == 0 && C4 < 64 && ((long long)W * C4) % 64 == 0 && !RCV_ENV("RCV_NO_POOL_ROWS");      // see pool_bwd_rows_kernel
       if (rows) {
         if (op->i[RCV_I_INMODE] != RCV_LOAD_PLAIN) RCV_CHECK_ARG(op->p[RCV_P_IN_C], "maxpool backward: constants missing");
         auto kern = op->i[RCV_I_INMODE] == RCV_LOAD_PLAIN ? pool_bwd_rows_kernel<RCV_LOAD_PLAIN> : pool_bwd_rows_kernel<RCV_LOAD_AFFINE>;

@@ -6,6 +6,7 @@ bias gradients 5e-7.  Measured (scripts/experiments/conv_check.py, wgrad_check.p
 import os
 import sys
 
+import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
@@ -332,3 +333,122 @@ def test_tiny_plane_conv_vs_fp64(N, H, W, Cin, Cout, s, d, mode_name, flags):
     torch.cuda.synchronize()
     err = float((out.double().cpu() - ref).abs().max() / ref.abs().max())
     assert err <= 3e-6, (label, err)
+
+
+# ------------------------------------------------------------------------------------------ epilogue statistics
+def _conv_layouts(Cin, Cout, s):
+    """The filter layouts test_conv_kernels_vs_fp64 enumerates for a shape."""
+    return [0] + ([2] if (s == 1 and Cin % 16 == 0 and Cin >= 32 and Cout >= 64) else []) + \
+        ([3] if (s == 1 and Cin % 32 == 0 and Cin >= 64 and Cout >= 64) or (Cin in (8, 16, 32) and Cout <= 32) else []) + \
+        ([5] if (s == 2 and Cin % 16 == 0 and Cin >= 32 and Cout >= 64) else [])
+
+
+def _stats_case_on_device(c, layout, merged, labels, variants=None, randn=False):
+    """Packs the filter of a small_ops_cases conv case in `layout` and runs the record once per statistics variant: the stored
+    tensor and the float64 sum of ALL partial rows (NaN-prefilled: an unwritten row shows) must equal the float64 answer exactly --
+    or, for random operands (randn), meet the accuracy bar of the tests above resp. close(rtol=1e-4, floor=1.0)."""
+    import numpy as np
+    import small_ops_cases as K
+    from robocupvision_amd import _lib as L
+    h = L.handle(0)
+    N, H, W, Cin, Cout, Ho, Wo = (c[k] for k in ("N", "H", "W", "Cin", "Cout", "Ho", "Wo"))
+    tr = c["transposed"]
+    dv = {k: torch.from_numpy(np.ascontiguousarray(c[k])).to(DEV) for k in ("x", "c", "w", "bias", "res", "e", "ec")}
+    if c["nchw"] or (layout == 0 and not tr and c["d"] != 1) or len(c["shape"]) > 6:
+        rp, cp = (Cin + 3) // 4 * 4, (Cout + 15) // 16 * 16
+        nfl = 9 * rp * cp
+    else:
+        rp, cp, nfl = _pack_dims(Cin, Cout, layout, merged=bool(merged))
+    wp = torch.zeros(nfl, device=DEV)
+    job = L.RcvPackJob()
+    job.src, job.dst, job.D0, job.D1 = dv["w"].data_ptr(), wp.data_ptr(), (Cin if tr else Cout), (Cout if tr else Cin)
+    job.rows_from_d1, job.flip, job.rows_pad, job.cols_pad, job.merged = (0 if tr else 1), 0, rp, cp, layout
+    table = torch.frombuffer(bytearray(bytes((L.RcvPackJob * 1)(job))), dtype=torch.uint8).to(DEV)
+    pack = L.make_op(L.OP_PACK, 0, count=1, aux0=16 * rp * cp, p_in=table.data_ptr())
+    for kind, flags in (variants or K.STATS_VARIANTS):
+        out = torch.full((N, Ho, Wo, Cout), float("nan"), device=DEV)
+        op = L.make_op(L.OP_TCONV if tr else L.OP_CONV, flags, n=N, h=H, w=W, cin=Cin, cout=Cout, ho=Ho, wo=Wo, stride=c["s"], dil=c["d"],
+                       inmode=L.LOAD_NCHW if c["nchw"] else L.LOAD_AFFINE, aux0=layout, stats=kind, p_in=dv["x"].data_ptr(),
+                       p_in_c=dv["c"].data_ptr(), p_w=wp.data_ptr(), p_bias=dv["bias"].data_ptr(), p_resid=dv["res"].data_ptr(),
+                       p_epi_aux=dv["e"].data_ptr(), p_epi_c=dv["ec"].data_ptr(), p_out=out.data_ptr())
+        nbytes = L.op_workspace(h, op)
+        n_part = op.i[L.RCV_I_NPART]
+        assert n_part > 0 and nbytes == n_part * 2 * Cout * 4
+        part = torch.full((n_part, 2, Cout), float("nan"), device=DEV)
+        op.p[L.RCV_P_PART] = part.data_ptr()
+        lst = L.OpList([pack, op])
+        label = lst.labels(h)[1]
+        if tr:
+            assert ("_bf3" in label) == (layout == 4), label
+        elif not c["nchw"] and len(c["shape"]) == 6:
+            assert label.startswith("conv_wino") == (layout == 2) and ("_bf3" in label) == (layout in (3, 5)), label
+        labels.add(label.split("<")[0])
+        lst.run(h, torch.cuda.current_stream().cuda_stream)
+        torch.cuda.synchronize()
+        v, ref, _ = K.conv_stats_reference(c, kind, flags)
+        what = "%s %s layout %d statistics %d flags %d" % (label, c["shape"], layout, kind, flags)
+        got = out.double().cpu()
+        rows = part.double().cpu().sum(0)
+        if randn:
+            from test_gpu_blocks import close
+            err = float((got - torch.from_numpy(v)).abs().max() / np.abs(v).max())
+            print(".%s: max error %.3e" % (what, err))
+            assert err <= (2e-6 if layout == 2 else 3e-6), (what, err)
+            close(rows, torch.from_numpy(ref), what + " rows", rtol=1e-4, floor=1.0)
+            continue
+        bad = (got != torch.from_numpy(v)).nonzero()
+        assert bad.numel() == 0, "%s: %d stored elements differ, first at %s" % (what, bad.shape[0], bad[0].tolist())
+        bad = (rows != torch.from_numpy(ref)).nonzero()
+        assert bad.numel() == 0, "%s: %d column sums differ, first (row, channel) %s: got %r, expected %r" % (
+            what, bad.shape[0], bad[0].tolist(), float(rows[tuple(bad[0])]), float(ref[tuple(bad[0].tolist())]))
+
+
+@pytest.mark.parametrize("family", ["conv", "tconv", "image", "tiny"])
+def test_epilogue_statistics_exact(family):
+    """The per-workgroup partial rows of RCV_STATS_FWD (with F_BIAS|F_RELU, without flags, with F_BIAS|F_RESID), RCV_STATS_BWD_ENC and
+    RCV_STATS_BWD_DEC (both with F_RESID; p[EPI_C] = (c0, c1, mean), pixels with e*c0 + c1 == 0 masked) of every conv / transposed
+    conv kernel family, under every filter layout the accuracy tests above enumerate, on integer-grid operands (tests/small_ops_cases.py:
+    activations and sparse filters in {-2..2}, +-2^k scales -- exact through split-bf16 and Winograd), ragged and tiny planes plus one
+    per family with several tiles per workgroup.  Labels covered (every tiling the shape lists above reach but those of the two
+    640 x 480 planes): conv_dma<1,5,4,1,4>, conv_mfma<1,5,2,2,8>, conv_wino<64,80>, conv_bf3<64,160>, conv2_bf3<64,160>,
+    convs_mfma<2,3,32> / <1,5,16> / <1,3,16> / <1,3,8> / <1,5,8> / <2,2,16>, convn_bf3<32,2,3> / <16,1,5> / <8,1,5> / <16,2,3> (conv);
+    tconva_dma<1,5,4,1,4> / <1,5,2,2,4>, tconvms_mfma<4,3,32> / <4,3,16> / <2,5,16>, tconvn_bf3<32,4,3> / <16,2,5> (tconv); conv_first<1> /
+    <2> (RCV_STATS_FWD without a residual), convs_mfma<1,5,4> / <2,5,4> (NCHW image); the tiny dilated planes leave conv_small, which
+    takes no statistics, for conv_dma<1,5,4,1,4>, conv_mfma<1,5,1,2,8> / <1,5,1,2,4>."""
+    import small_ops_cases as K
+    from robocupvision_amd.engine import MERGED_TCONV_MAX_COUT
+    labels = set()
+    shapes = dict(conv=K.CONV_STATS_SHAPES, tconv=K.TCONV_STATS_SHAPES, image=K.IMAGE_STATS_SHAPES, tiny=K.TINY_STATS_SHAPES)[family]
+    for shape in shapes:
+        c = K.build_conv_stats(shape, transposed=family == "tconv", nchw=family == "image")
+        if family == "conv":
+            for layout in _conv_layouts(c["Cin"], c["Cout"], c["s"]):
+                _stats_case_on_device(c, layout, False, labels)
+        elif family == "tconv":
+            merged = 1 if c["Cout"] <= MERGED_TCONV_MAX_COUT else 0
+            for layout in [merged] + ([4] if merged and (c["Cin"], (4 * c["Cout"] + 15) // 16 * 16) in ((16, 32), (32, 64)) else []):
+                _stats_case_on_device(c, layout, merged, labels)
+        else:
+            _stats_case_on_device(c, 0, False, labels)
+    print(".epilogue statistics %s: labels %s" % (family, sorted(labels)))
+    expected = dict(conv={"conv_dma", "conv_mfma", "conv_wino", "conv_bf3", "conv2_bf3", "convs_mfma", "convn_bf3"},
+                    tconv={"tconva_dma", "tconvms_mfma", "tconvn_bf3"}, image={"conv_first", "convs_mfma"}, tiny={"conv_dma", "conv_mfma"})[family]
+    assert labels == expected, (family, sorted(labels))
+
+
+@pytest.mark.parametrize("ci", range(11))
+def test_epilogue_statistics_randn(ci):
+    """Random operands (dense filters), one case per kernel family, every statistics kind: the stored tensor at the bar of the accuracy
+    tests above, the float64 sum of the partial rows within close(rtol=1e-4, floor=1.0) of the float64 restatement -- so that the exact
+    cases do not hide a rounding-order regression of the partial sums."""
+    import small_ops_cases as K
+    import small_ops_restatement as R
+    assert len(K.CONV_RANDN_CASES) == 11
+    family, shape, layout, prefix = K.CONV_RANDN_CASES[ci]
+    c = K.build_conv_stats(shape, transposed=family == "tconv", nchw=family == "image", randn=True)
+    variants = [(R.STATS_FWD, 3), (R.STATS_BWD_ENC, 4), (R.STATS_BWD_DEC, 4)]
+    if prefix == "conv_first":          # the first-layer kernel takes no residual and no backward statistics
+        variants = [(R.STATS_FWD, 3), (R.STATS_FWD, 0)]
+    labels = set()
+    _stats_case_on_device(c, layout, family == "tconv" and layout in (1, 4), labels, variants=variants, randn=True)
+    assert labels == {prefix}, labels
