@@ -117,12 +117,30 @@ enum {
   RCV_OP_LP_BATCH = 35,     /* batch assembly of labelPropTrain.py:162-193 (rcv_labelprop_batch; csrc/lp_tail.hip): i[N] = B frame pairs, i[CIN] =
                              * channels per frame, i[H], i[W], i[COUT] = classes (5); p[IN] = images float[B][2][C][H][W], p[IN2] = labels
                              * int64[B][2][H][W], p[OUT] = inputs float[2B][H][W][8] (NHWC), p[X0] = targets int64[2B][H][W]              */
-  RCV_OP_BATCH_PREP = 36    /* the loader's per-image work of dataset.py:107-133 for a whole batch (rcv_batch_prep; csrc/batch_prep.hip): i[N] = B,
+  RCV_OP_BATCH_PREP = 36,   /* the loader's per-image work of dataset.py:107-133 for a whole batch (rcv_batch_prep; csrc/batch_prep.hip): i[N] = B,
                              * i[H] / i[W] = source Hs / Ws, i[HO] / i[WO] = output H / W, i[CIN] / i[COUT] = taps per output column / row of the
                              * frame tables, i[INMODE2] = label element bytes (1 = uint8, 4 = int32), i[AUX0] = train (0 / 1), i[AUX1] = maskLabel
                              * flags (1 = nb, 2 = nr, 4 = ng, 8 = nl); p[IN] = frames uint8[B][Hs][Ws][3], p[IN2] = labels [B][Hs][Ws], p[X1] / p[X2] =
                              * frame tables of x / y, p[X3] / p[X4] = label index tables of x / y, p[X5] = normalisation table float[3][256],
                              * p[IN_C] = parameter rows float[B][8] (train only), p[OUT] = imgs float[B][3][H][W], p[X0] = targets int64[B][H][W] */
+  RCV_OP_CLS_LABEL = 37,    /* the inference form of the classifier tails (detect.py:131-133: `_, predClass = torch.max(pred, 1)`, then Colorize):
+                             * no logits are stored and no target is read; p[OUT] = class map uint8[N][H][W] (the FIRST maximum of the logits in
+                             * class order, the rule of RCV_F_FUSED_CE's arg-max: a NaN never wins, an all-NaN pixel is class 0), p[X0] = colour
+                             * image uint8[N][H][W][3] = palette[class] or NULL, p[X1] = palette uint8[8][3] in device memory (required iff
+                             * p[X0]).  i[N], i[H], i[W], i[CIN], i[COUT] = 1..8 classes; i[INMODE] = the source form:
+                             *   0 features: the 1x1 classifier is applied, slots exactly as RCV_OP_CLS_FWD (p[IN], p[W] = [COUT][CIN], p[BIAS] or
+                             *     NULL, CIN 8 / 16; with RCV_F_FUSED_UP p[IN_C], p[X3], p[X4], i[AUX0] = the skip's load mode, i[AUX1] = its channel
+                             *     count, 0 = CIN); the logits are formed in the order of RCV_OP_CLS_FWD, so the map is bit for bit the arg-max of
+                             *     the logits that record writes;
+                             *   1 logits: p[IN] is NHWC with i[CIN] floats per pixel (a multiple of 4, >= COUT), the first COUT of them logits;
+                             *     p[BIAS] (or NULL) is added, p[W] is not read (the tail of the 3x3 classifier, in place of RCV_OP_NHWC_TO_NCHW);
+                             *   2 class map: p[IN] is a class map of i[INMODE2] bytes per element (1 = uint8, 8 = int64); only the colour image is
+                             *     produced (a class outside [0, 8) is black, as Colorize leaves unmatched pixels 0); p[OUT] is not written.
+                             * i[COUNT] = store shape: 0 = the library's choice, 1 = one byte / three bytes per pixel and lane, 4 = the labels
+                             * and colours of four neighbouring pixels gathered into one / three dword stores (csrc/cls_label.hip)            */
+  RCV_OP_FRAME_PREP = 38    /* RCV_OP_BATCH_PREP with train = 0 for frames that have no labels (detect.py:125-130; rcv_frame_prep): the same slots
+                             * and the same resize / normalise code; no label is read, no label table and no target: p[IN2], p[X0], p[X3], p[X4]
+                             * and i[INMODE2], i[AUX0], i[AUX1] are not looked at.  p[OUT] is bit for bit what the other record writes             */
 };
 
 /* how an operand is produced from memory while it is staged (rcv_op.i[RCV_I_INMODE] etc.) */
@@ -378,6 +396,21 @@ int rcv_batch_prep(rcv_handle* h, const uint8_t* frames, const void* labels, int
                    const int32_t* frame_x, int kx, const int32_t* frame_y, int ky, const int32_t* label_x, const int32_t* label_y,
                    const float* norm, const float* params /*NULL unless train*/, int train, int mask_flags, float* imgs, int64_t* targets,
                    void* stream);
+
+/* RCV_OP_FRAME_PREP: the validation form of rcv_batch_prep for frames alone (the loop of detect.py:125-130 has no labels): imgs are
+ * bit for bit what rcv_batch_prep(train = 0) writes for the same frames and tables.                                                */
+int rcv_frame_prep(rcv_handle* h, const uint8_t* frames, int B, int Hs, int Ws, int H, int W, const int32_t* frame_x, int kx,
+                   const int32_t* frame_y, int ky, const float* norm, float* imgs, void* stream);
+
+/* RCV_OP_CLS_LABEL, source form 0 without the fused decoder input: labels uint8[N][H][W] = first arg-max over c of
+ * (bias[c] + sum_k x[p][k] w[c][k]) (detect.py:131-132), colour uint8[N][H][W][3] = palette[label] (detect.py:133 Colorize) or NULL;
+ * x NHWC with CIN = 8 or 16 channels, 1 <= COUT <= 8, palette uint8[8][3] in device memory (NULL iff colour is NULL).               */
+int rcv_cls_label(rcv_handle* h, const float* x, const float* w, const float* bias /*may be NULL*/, int N, int H, int W, int CIN, int COUT,
+                  uint8_t* labels, uint8_t* colour /*may be NULL*/, const uint8_t* palette, void* stream);
+/* RCV_OP_CLS_LABEL, source form 2 (transform.py:158-170 Colorize for a whole batch): colour uint8[N][H][W][3] = palette[classmap], black
+ * where the class is outside [0, 8); elem_bytes 1 = uint8, 8 = int64.                                                              */
+int rcv_colorize(rcv_handle* h, const void* classmap, int elem_bytes, int N, int H, int W, uint8_t* colour, const uint8_t* palette,
+                 void* stream);
 
 /* torch.optim.SGD.step (trainer.py:176-178,221): g = grad*grad_scale + weight_decay*p; buf = step==1 ? g : momentum*buf + g;
  * p -= lr*buf.  lr_elem (may be NULL) gives a per-element learning rate (0 = parameter without a gradient: untouched). */

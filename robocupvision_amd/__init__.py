@@ -16,7 +16,14 @@ def __getattr__(name):
     if name == "data":
         import importlib
         return importlib.import_module(".data", __name__)
-    if name in ("prepare_batch", "draw_jitter", "SSYUVDataset"):
+    if name in ("prepare_batch", "prepare_frames", "draw_jitter", "SSYUVDataset"):
         from . import data
         return getattr(data, name)
+    # class maps and colour masks on the device (detect.py): palette.py, infer.py
+    if name in ("colorize", "Colorize", "labelcolormap"):
+        from . import palette
+        return getattr(palette, name)
+    if name == "Segmenter":
+        from .infer import Segmenter
+        return Segmenter
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

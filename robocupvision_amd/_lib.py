@@ -24,6 +24,9 @@ RCV_P__N = 20
 OP_OBJECT_MATCH = 32       # object-detection counts (rcv.h RCV_OP_OBJECT_MATCH, csrc/objdet.hip)
 OP_LP_TAIL_FWD, OP_LP_TAIL_BWD, OP_LP_BATCH = 33, 34, 35      # LabelProp's training tail and batch assembly (rcv.h, csrc/lp_tail.hip)
 OP_BATCH_PREP = 36          # the loader's per-image work for a whole batch (rcv.h RCV_OP_BATCH_PREP, csrc/batch_prep.hip)
+OP_CLS_LABEL = 37           # classifier tail -> uint8 class map (+ colour image), no logits (rcv.h RCV_OP_CLS_LABEL, csrc/cls_label.hip)
+OP_FRAME_PREP = 38          # OP_BATCH_PREP's validation form for frames without labels (rcv.h RCV_OP_FRAME_PREP)
+CLS_LABEL_FEATURES, CLS_LABEL_LOGITS, CLS_LABEL_CLASSMAP = range(3)      # i[INMODE] of OP_CLS_LABEL: the source form
 
 LOAD_PLAIN, LOAD_AFFINE, LOAD_GRAD_ENC, LOAD_GRAD_DEC, LOAD_NCHW, LOAD_AFFINE_RELU = range(6)
 STATS_NONE, STATS_FWD, STATS_BWD_ENC, STATS_BWD_DEC = range(4)
@@ -56,7 +59,7 @@ EXPORTS = [
     "rcv_conv3x3", "rcv_convT3x3s2", "rcv_wgrad3x3", "rcv_bn_finalize", "rcv_bn_backward", "rcv_maxpool2x2_fwd",
     "rcv_softmax_ce_argmax_fwd", "rcv_softmax_ce_bwd", "rcv_adam_l1_step", "rcv_adam_l1_step_metrics", "rcv_confusion",
     "rcv_dice_fwd", "rcv_dice_bwd", "rcv_sgd_step", "rcv_create_planner", "rcv_adam_l1_step_pruned", "rcv_op_filter_layout",
-    "rcv_object_match", "rcv_labelprop_batch", "rcv_batch_prep",
+    "rcv_object_match", "rcv_labelprop_batch", "rcv_batch_prep", "rcv_frame_prep", "rcv_cls_label", "rcv_colorize",
 ]
 
 
@@ -100,6 +103,9 @@ def load():
                                             C.c_void_p, C.c_void_p]
         lib.rcv_batch_prep.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p, C.c_int, C.c_void_p, C.c_int] + \
             [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.rcv_frame_prep.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 3
+        lib.rcv_cls_label.argtypes = [C.c_void_p] * 4 + [C.c_int] * 5 + [C.c_void_p] * 4
+        lib.rcv_colorize.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 3
         for name in ("rcv_conv3x3", "rcv_convT3x3s2", "rcv_wgrad3x3"):
             getattr(lib, name).argtypes = [C.c_void_p, C.POINTER(RcvOp), C.c_void_p]
         _lib = lib

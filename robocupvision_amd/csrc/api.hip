@@ -115,7 +115,10 @@ static int dispatch(const rcv_handle* h, const rcv_op* op, hipStream_t s, OpQuer
     case RCV_OP_LP_BATCH:
       return rcv_launch_lp_batch(h, op, s, q);
     case RCV_OP_BATCH_PREP:
+    case RCV_OP_FRAME_PREP:
       return rcv_launch_batch_prep(h, op, s, q);
+    case RCV_OP_CLS_LABEL:
+      return rcv_launch_cls_label(h, op, s, q);
     case RCV_OP_NOP:
       if (q) { snprintf(q->label, sizeof(q->label), "nop"); q->n_part = 0; q->n_split = 0; q->part_bytes = 0; }
       return RCV_OK;
@@ -398,6 +401,39 @@ int rcv_batch_prep(rcv_handle* h, const uint8_t* frames, const void* labels, int
   op.p[RCV_P_IN] = (void*)frames; op.p[RCV_P_IN2] = (void*)labels; op.p[RCV_P_OUT] = imgs; op.p[RCV_P_X0] = targets;
   op.p[RCV_P_X1] = (void*)frame_x; op.p[RCV_P_X2] = (void*)frame_y; op.p[RCV_P_X3] = (void*)label_x; op.p[RCV_P_X4] = (void*)label_y;
   op.p[RCV_P_X5] = (void*)norm; op.p[RCV_P_IN_C] = (void*)params;
+  return rcv_run(h, &op, 1, stream);
+}
+
+int rcv_frame_prep(rcv_handle* h, const uint8_t* frames, int B, int Hs, int Ws, int H, int W, const int32_t* frame_x, int kx,
+                   const int32_t* frame_y, int ky, const float* norm, float* imgs, void* stream) {
+  rcv_op op;
+  memset(&op, 0, sizeof(op));
+  op.kind = RCV_OP_FRAME_PREP;
+  op.i[RCV_I_N] = B; op.i[RCV_I_H] = Hs; op.i[RCV_I_W] = Ws; op.i[RCV_I_HO] = H; op.i[RCV_I_WO] = W; op.i[RCV_I_CIN] = kx; op.i[RCV_I_COUT] = ky;
+  op.p[RCV_P_IN] = (void*)frames; op.p[RCV_P_OUT] = imgs; op.p[RCV_P_X1] = (void*)frame_x; op.p[RCV_P_X2] = (void*)frame_y;
+  op.p[RCV_P_X5] = (void*)norm;
+  return rcv_run(h, &op, 1, stream);
+}
+
+int rcv_cls_label(rcv_handle* h, const float* x, const float* w, const float* bias, int N, int H, int W, int CIN, int COUT, uint8_t* labels,
+                  uint8_t* colour, const uint8_t* palette, void* stream) {
+  rcv_op op;
+  memset(&op, 0, sizeof(op));
+  op.kind = RCV_OP_CLS_LABEL;
+  op.i[RCV_I_N] = N; op.i[RCV_I_H] = H; op.i[RCV_I_W] = W; op.i[RCV_I_CIN] = CIN; op.i[RCV_I_COUT] = COUT; op.i[RCV_I_INMODE] = 0;
+  op.p[RCV_P_IN] = (void*)x; op.p[RCV_P_W] = (void*)w; op.p[RCV_P_BIAS] = (void*)bias; op.p[RCV_P_OUT] = labels; op.p[RCV_P_X0] = colour;
+  op.p[RCV_P_X1] = (void*)palette;
+  return rcv_run(h, &op, 1, stream);
+}
+
+int rcv_colorize(rcv_handle* h, const void* classmap, int elem_bytes, int N, int H, int W, uint8_t* colour, const uint8_t* palette,
+                 void* stream) {
+  rcv_op op;
+  memset(&op, 0, sizeof(op));
+  op.kind = RCV_OP_CLS_LABEL;
+  op.i[RCV_I_N] = N; op.i[RCV_I_H] = H; op.i[RCV_I_W] = W; op.i[RCV_I_CIN] = 1; op.i[RCV_I_COUT] = 8; op.i[RCV_I_INMODE] = 2;
+  op.i[RCV_I_INMODE2] = elem_bytes;
+  op.p[RCV_P_IN] = (void*)classmap; op.p[RCV_P_X0] = colour; op.p[RCV_P_X1] = (void*)palette;
   return rcv_run(h, &op, 1, stream);
 }
 

@@ -1,4 +1,4 @@
-// RCV_OP_BATCH_PREP (rcv_batch_prep): the per-image work of the reference's loader, dataset.py:107-133 (SSYUVDataset.__getitem__), with
+// RCV_OP_BATCH_PREP (rcv_batch_prep; RCV_OP_FRAME_PREP / rcv_frame_prep is its validation form without labels): the per-image work of the reference's loader, dataset.py:107-133 (SSYUVDataset.__getitem__), with
 // ColorJitter (dataset.py:19-39) and the training loop's maskLabel (transform.py:26-49, train.py:43-46), for a whole batch in one launch:
 //   uint8 RGB frames [B][Hs][Ws][3] + label planes [B][Hs][Ws] (uint8 / int32)  ->  fp32 NCHW [B][3][H][W] + int64 targets [B][H][W].
 // Arithmetic in the reference's order:
@@ -74,6 +74,7 @@ __device__ __forceinline__ void bp_finish(const BpArgs& a, const BpJitter& j, LU
   const size_t plane = (size_t)a.H * a.W, o = (size_t)y * a.W + xo;
   float* img = a.imgs + (size_t)b * 3 * plane + o;
   img[0] = v0; img[plane] = v1; img[2 * plane] = v2;
+  if (!a.tgt) return;                      // RCV_OP_FRAME_PREP: frames without labels (uniform over the launch)
   const int sy = bp_clampi(a.ly[y], 0, a.Hs - 1), sx = bp_clampi(a.lx[x], 0, a.Ws - 1);
   const size_t li = ((size_t)b * a.Hs + sy) * a.Ws + sx;
   const int lv = a.lab_bytes == 1 ? (int)((const uint8_t*)a.labels)[li] : ((const int32_t*)a.labels)[li];
@@ -215,8 +216,14 @@ static int bp_ksize(int in, int out) {
 // the `query` return; the batch operands are checked at launch.
 int rcv_launch_batch_prep(const rcv_handle* h, const rcv_op* op, hipStream_t s, OpQuery* query) {
   const int B = op->i[RCV_I_N], Hs = op->i[RCV_I_H], Ws = op->i[RCV_I_W], H = op->i[RCV_I_HO], W = op->i[RCV_I_WO];
-  const int kx = op->i[RCV_I_CIN], ky = op->i[RCV_I_COUT], lab_bytes = op->i[RCV_I_INMODE2], train = op->i[RCV_I_AUX0], mask = op->i[RCV_I_AUX1];
-  if (query) { query->n_part = 0; query->n_split = 0; query->part_bytes = 0; snprintf(query->label, sizeof(query->label), "batch_prep"); }
+  // RCV_OP_FRAME_PREP (rcv_frame_prep): the validation form for frames alone -- no label, no label table, no target
+  const bool frames_only = op->kind == RCV_OP_FRAME_PREP;
+  const int kx = op->i[RCV_I_CIN], ky = op->i[RCV_I_COUT], lab_bytes = frames_only ? 1 : op->i[RCV_I_INMODE2];
+  const int train = frames_only ? 0 : op->i[RCV_I_AUX0], mask = frames_only ? 0 : op->i[RCV_I_AUX1];
+  if (query) {
+    query->n_part = 0; query->n_split = 0; query->part_bytes = 0;
+    snprintf(query->label, sizeof(query->label), frames_only ? "frame_prep" : "batch_prep");
+  }
   RCV_CHECK_ARG(B >= 1 && H >= 1 && W >= 1 && Hs >= 1 && Ws >= 1, "batch prep: B %d, source %d x %d, output %d x %d: every size must be >= 1", B, Hs, Ws,
                 H, W);
   RCV_CHECK_ARG((long long)Hs <= 8LL * H && (long long)Ws <= 8LL * W,
@@ -228,15 +235,21 @@ int rcv_launch_batch_prep(const rcv_handle* h, const rcv_op* op, hipStream_t s, 
   const int tiles_x = ceil_div(W, BP_TC), tiles_y = ceil_div(H, BP_TR);
   RCV_CHECK_ARG((double)B * Hs * Ws < 2147483647.0 && (double)B * H * W < 2147483647.0 && (double)B * tiles_x * tiles_y < 2147483647.0,
                 "batch prep: %d images of %d x %d -> %d x %d: more than 2^31 pixels", B, Hs, Ws, H, W);
-  RCV_CHECK_ARG(op->p[RCV_P_X1] && op->p[RCV_P_X2] && op->p[RCV_P_X3] && op->p[RCV_P_X4] && op->p[RCV_P_X5],
-                "batch prep: null table (frame taps of x / y, label index of x / y, normalisation)");
+  if (frames_only)
+    RCV_CHECK_ARG(op->p[RCV_P_X1] && op->p[RCV_P_X2] && op->p[RCV_P_X5], "frame prep: null table (frame taps of x / y, normalisation)");
+  else
+    RCV_CHECK_ARG(op->p[RCV_P_X1] && op->p[RCV_P_X2] && op->p[RCV_P_X3] && op->p[RCV_P_X4] && op->p[RCV_P_X5],
+                  "batch prep: null table (frame taps of x / y, label index of x / y, normalisation)");
   if (query) return RCV_OK;
-  RCV_CHECK_ARG(op->p[RCV_P_IN] && op->p[RCV_P_IN2] && op->p[RCV_P_OUT] && op->p[RCV_P_X0], "batch prep: null operand");
+  if (frames_only) RCV_CHECK_ARG(op->p[RCV_P_IN] && op->p[RCV_P_OUT], "frame prep: null operand");
+  else RCV_CHECK_ARG(op->p[RCV_P_IN] && op->p[RCV_P_IN2] && op->p[RCV_P_OUT] && op->p[RCV_P_X0], "batch prep: null operand");
   RCV_CHECK_ARG(!train || op->p[RCV_P_IN_C], "batch prep: training mode needs the parameter rows float[B][8]");
   BpArgs a;
-  a.frames = (const uint8_t*)op->p[RCV_P_IN]; a.labels = op->p[RCV_P_IN2]; a.imgs = (float*)op->p[RCV_P_OUT]; a.tgt = (int64_t*)op->p[RCV_P_X0];
-  a.xtab = (const int32_t*)op->p[RCV_P_X1]; a.ytab = (const int32_t*)op->p[RCV_P_X2]; a.lx = (const int32_t*)op->p[RCV_P_X3];
-  a.ly = (const int32_t*)op->p[RCV_P_X4]; a.norm = (const float*)op->p[RCV_P_X5]; a.params = (const float*)op->p[RCV_P_IN_C];
+  a.frames = (const uint8_t*)op->p[RCV_P_IN]; a.imgs = (float*)op->p[RCV_P_OUT];
+  a.labels = frames_only ? nullptr : op->p[RCV_P_IN2]; a.tgt = frames_only ? nullptr : (int64_t*)op->p[RCV_P_X0];
+  a.xtab = (const int32_t*)op->p[RCV_P_X1]; a.ytab = (const int32_t*)op->p[RCV_P_X2];
+  a.lx = frames_only ? nullptr : (const int32_t*)op->p[RCV_P_X3]; a.ly = frames_only ? nullptr : (const int32_t*)op->p[RCV_P_X4];
+  a.norm = (const float*)op->p[RCV_P_X5]; a.params = frames_only ? nullptr : (const float*)op->p[RCV_P_IN_C];
   a.B = B; a.Hs = Hs; a.Ws = Ws; a.H = H; a.W = W; a.kx = kx; a.ky = ky; a.lab_bytes = lab_bytes; a.train = train; a.mask = mask;
   a.tiles_x = tiles_x; a.tiles_y = tiles_y;
   if (H == Hs && W == Ws) {

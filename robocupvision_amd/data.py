@@ -26,7 +26,7 @@ import torch
 
 from . import _lib as L
 
-__all__ = ["prepare_batch", "draw_jitter", "SSYUVDataset", "bilinear_table", "nearest_table", "norm_table"]
+__all__ = ["prepare_batch", "prepare_frames", "draw_jitter", "SSYUVDataset", "bilinear_table", "nearest_table", "norm_table"]
 
 PRECISION_BITS = 22          # Pillow's 8-bit resampling: 32 - 8 - 2
 MEAN = {False: [0.36269532, 0.41144562, 0.282713], True: [0.34190056, 0.4833289, 0.48565758]}      # dataset.py:74 (key: finetune)
@@ -155,6 +155,38 @@ def prepare_batch(frames, labels, img_size=(120, 160), finetune=False, train=Tru
                                     params.data_ptr() if train else None, 1 if train else 0, mask, imgs.data_ptr(), targets.data_ptr(),
                                     torch.cuda.current_stream(dev).cuda_stream), "rcv_batch_prep")
     return imgs, targets
+
+
+def prepare_frames(frames, img_size=(120, 160), finetune=False):
+    """``frames`` uint8 [B,Hs,Ws,3] (decoded RGB) on the HIP device -> float32 [B,3,H,W]: the validation loader's resize and
+    normalisation for frames that have no labels (detect.py:125-130), one launch (RCV_OP_FRAME_PREP).  Bit for bit the ``imgs`` of
+    ``prepare_batch(frames, labels, img_size, finetune, train=False)``; the same refusals, the one-axis-kept size among them."""
+    if not torch.is_tensor(frames):
+        raise TypeError("prepare_frames: frames must be a tensor")
+    if frames.dtype != torch.uint8:
+        raise TypeError("prepare_frames: frames must be uint8 (got %s)" % frames.dtype)
+    if frames.dim() != 4 or frames.shape[3] != 3:
+        raise ValueError("prepare_frames: frames must be [B,Hs,Ws,3] (got %s)" % (tuple(frames.shape),))
+    B, Hs, Ws, _ = frames.shape
+    H, W = int(img_size[0]), int(img_size[1])
+    if B < 1 or Hs < 1 or Ws < 1 or H < 1 or W < 1:
+        raise ValueError("prepare_frames: frames %s -> %d x %d: an empty size" % (tuple(frames.shape), H, W))
+    if (H == Hs) != (W == Ws):
+        raise ValueError("prepare_frames: %d x %d -> %d x %d keeps exactly one axis: the reference skips the resize of such a frame altogether "
+                         "(dataset.py:118-121 tests `h != Hs and w != Ws`) and feeds the network the wrong size; resize the frames first"
+                         % (Hs, Ws, H, W))
+    if frames.device.type != "cuda":
+        raise L.RcvError("prepare_frames runs on the HIP device only (frames on %s)" % frames.device)
+    if not frames.is_contiguous():
+        raise ValueError("prepare_frames: frames must be contiguous (no hidden copy of a batch)")
+    dev = frames.device
+    fx, kx, fy, ky, _, _ = _device_tables(Hs, Ws, H, W, dev)
+    norm = _device_norm(finetune, dev)
+    imgs = torch.empty(B, 3, H, W, dtype=torch.float32, device=dev)
+    h = L.handle(dev.index if dev.index is not None else torch.cuda.current_device())
+    L.check(L.load().rcv_frame_prep(h, frames.data_ptr(), B, Hs, Ws, H, W, fx.data_ptr(), kx, fy.data_ptr(), ky, norm.data_ptr(),
+                                    imgs.data_ptr(), torch.cuda.current_stream(dev).cuda_stream), "rcv_frame_prep")
+    return imgs
 
 
 def draw_jitter(B, b=0.3, c=0.3, s=0.3, h=3.1415 / 6):

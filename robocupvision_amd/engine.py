@@ -3,7 +3,8 @@
 A network is described once as a small graph (conv / pool / up / cls nodes, built by model.py from
 the module tree).  For every (input shape, train|eval) the engine lowers that graph to two cached
 arrays of `rcv_op` records -- one forward, one backward -- whose operands are persistent HBM
-buffers owned by the engine.  Running a pass is then ONE call into librcv.so (rcv_run), which
+buffers owned by the engine.  (A third variant per shape, eval-labels, is the eval plan whose
+classifier tail writes a uint8 class map and a colour image instead of logits: `Engine.predict`.)  Running a pass is then ONE call into librcv.so (rcv_run), which
 enqueues every kernel of the pass on the current HIP stream: no per-layer Python, no allocation,
 no host synchronisation, graph-capturable.
 
@@ -191,6 +192,8 @@ class Plan:
         self.dlogits_slots: List[tuple] = []
         self.logits: Optional[torch.Tensor] = None
         self.logits_slots: List[tuple] = []   # (fwd op index, slot) of the records that write the logits (inference: a fresh tensor per call)
+        self.label_op: Optional[int] = None   # eval-labels plan: fwd index of the RCV_OP_CLS_LABEL record (its outputs are fresh tensors per call)
+        self.label_shape: Optional[tuple] = None   # ... and the (N, H, W) of its class map
         self.input_grads: List[Optional[torch.Tensor]] = []
         self.n_head = 0                      # leading ops of fwd that depend on the parameters only (filter repack, eval-mode BN constants)
         self.head_key = None                 # parameter-state key the head was last run for (eval plans)
@@ -215,9 +218,19 @@ class _Lowering:
     helpers, and ``finish`` for what spans the lists (batched filter-gradient reductions, gradient-ready marks, the pack / eval head).
     ``eng`` is the Engine that owns the buffers; nothing here runs a kernel."""
 
-    def __init__(self, eng: "Engine", shapes: Sequence[tuple], training: bool):
+    def __init__(self, eng: "Engine", shapes: Sequence[tuple], training: bool, labels: bool = False):
         self.eng = eng
         self.training = training
+        # eval-labels plan (Engine.predict): the eval plan up to the classifier node, whose tail is RCV_OP_CLS_LABEL -- a uint8 class map
+        # (+ colour image) instead of logits; no logits buffer exists
+        self.labels = labels
+        if labels and training:
+            raise L.RcvError("an eval-labels plan is an inference plan")
+        if labels and (not eng.graph["nodes"] or eng.graph["nodes"][-1]["op"] != "cls"):
+            last = eng.graph["nodes"][-1]["op"] if eng.graph["nodes"] else "nothing"
+            raise L.RcvError("a class-map (eval-labels) plan needs a per-pixel classifier at the end of the graph; this graph ends in '%s'%s"
+                             % (last, {"pool_cls": " (pool_cls: the pooled patch-classification head yields one class per patch, not per pixel)",
+                                       "mat": " (fwd_mat: a block's materialised output has no classifier)"}.get(last, "")))
         g = eng.graph
         self.plan = Plan()
         self.fl = eng.flat
@@ -467,6 +480,8 @@ class _Lowering:
             raise L.RcvError("classifier input must be a materialised tensor")
         if Cin != src.C:
             raise L.RcvError("classifier: input has %d channels, weight expects %d" % (src.C, Cin))
+        if self.labels:
+            return self.fwd_cls_labels(node, src, w, b)
         logits = self.eng._alloc(self.plan, self.N, Cout, src.H, src.W)
         if tuple(w.shape[2:]) == (1, 1) and src.kind == "fused_up":
             tt, skip = src.fused
@@ -498,6 +513,36 @@ class _Lowering:
         self.plan.logits = logits
         assert self.fwd[-1].p[L.RCV_P_OUT] == logits.data_ptr()
         self.plan.logits_slots = [(len(self.fwd) - 1, L.RCV_P_OUT)]
+
+    def fwd_cls_labels(self, node: _Node, src: Value, w, b):
+        """The classifier node of an eval-labels plan: RCV_OP_CLS_LABEL in place of RCV_OP_CLS_FWD (1x1) resp. of RCV_OP_NHWC_TO_NCHW
+        behind the padded conv (3x3).  Its outputs (p[OUT] class map, p[X0] colour, p[X1] palette) are set per call by Engine.predict."""
+        Cout, Cin = w.shape[0], w.shape[1]
+        dims = dict(n=self.N, h=src.H, w=src.W, cout=Cout)
+        if tuple(w.shape[2:]) == (1, 1) and src.kind == "fused_up":
+            tt, skip = src.fused
+            self.fwd.append(L.make_op(L.OP_CLS_LABEL, L.F_FUSED_UP, cin=Cin, inmode=L.CLS_LABEL_FEATURES, aux0=skip.load_mode,
+                                 aux1=getattr(src, "fused_rch", 0), p_in=tt.data_ptr(), p_in_c=src.consts.data_ptr(),
+                                 p_x3=skip.buf.data_ptr(), p_x4=_ptr(skip.consts), p_w=w.data_ptr(), p_bias=_ptr(b), **dims))
+        elif tuple(w.shape[2:]) == (1, 1):
+            op = L.make_op(L.OP_CLS_LABEL, 0, cin=Cin, inmode=L.CLS_LABEL_FEATURES, p_w=w.data_ptr(), p_bias=_ptr(b), **dims)
+            op.p[L.RCV_P_IN] = self.bind_in(self.fwd, src, L.RCV_P_IN) or None
+            self.fwd.append(op)
+        elif tuple(w.shape[2:]) == (3, 3) and Cout <= CLS3_PAD:
+            node.t["wp"] = self.add_pack(w, Cout, Cin, True, False)
+            node.t["z"] = self.eng._alloc(self.plan, self.N, src.H, src.W, CLS3_PAD)
+            op = L.make_op(L.OP_CONV, 0, n=self.N, h=src.H, w=src.W, cin=Cin, cout=CLS3_PAD, ho=src.H, wo=src.W, stride=1, dil=1,
+                           inmode=src.load_mode, p_w=node.t["wp"].data_ptr(), p_out=node.t["z"].data_ptr())
+            op.p[L.RCV_P_IN] = self.bind_in(self.fwd, src, L.RCV_P_IN) or None
+            self.fwd.append(op)
+            self.fwd.append(L.make_op(L.OP_CLS_LABEL, 0, cin=CLS3_PAD, inmode=L.CLS_LABEL_LOGITS, p_in=node.t["z"].data_ptr(), p_bias=_ptr(b),
+                                      **dims))
+        else:
+            raise L.RcvError("classifier kernels %s with %d classes are not built (1x1, or 3x3 with <= %d classes)"
+                             % (tuple(w.shape[2:]), Cout, CLS3_PAD))
+        node.out = Value("plain", None, Cout, src.H, src.W, None, node)
+        self.plan.label_op = len(self.fwd) - 1
+        self.plan.label_shape = (self.N, src.H, src.W)
 
     def fwd_add_slice(self, node: _Node):
         d = node.d
@@ -938,6 +983,8 @@ class _Lowering:
         fwd = head + fwd
         plan.n_head = len(head)
         plan.logits_slots = [(k + len(head), sl) for (k, sl) in plan.logits_slots]
+        if plan.label_op is not None:
+            plan.label_op += len(head)
         # backward: the filter gradients (and their reductions) are off the critical path d(loss)/d(activation) chain ->
         # second HIP stream inside rcv_run (measured -4 % step time: their latency-bound phases fill the other kernels' gaps)
         if SIDE_STREAM_WGRAD:
@@ -1024,8 +1071,8 @@ class Engine:
         return t
 
     # ------------------------------------------------------------------ plan construction
-    def _build(self, shapes: Sequence[tuple], training: bool) -> Plan:
-        return _Lowering(self, shapes, training).run()
+    def _build(self, shapes: Sequence[tuple], training: bool, labels: bool = False) -> Plan:
+        return _Lowering(self, shapes, training, labels).run()
 
     # ------------------------------------------------------------------ execution
     def _param_state_key(self):
@@ -1034,12 +1081,14 @@ class Engine:
             ts += [m.running_mean, m.running_var]
         return tuple(t._version for t in ts if t is not None) + (self.flat._sig if self.flat is not None else ())
 
-    def _plan_for(self, inputs: Sequence[torch.Tensor], training: bool) -> Plan:
+    def _plan_for(self, inputs: Sequence[torch.Tensor], training: bool, labels: bool = False) -> Plan:
         self._ensure_device(inputs[0].device)
-        key = (tuple(tuple(t.shape) for t in inputs), training)
+        # three plan variants per input shape: training, eval (logits) and eval-labels (class map, Engine.predict); one cache, one budget
+        # (the key's second item stays a truth value -- True: training -- for every reader of `plans`; the labels variant is None)
+        key = (tuple(tuple(t.shape) for t in inputs), None if labels else training)
         plan = self.plans.get(key)
         if plan is None:
-            plan = self._build([tuple(t.shape) for t in inputs], training)
+            plan = self._build([tuple(t.shape) for t in inputs], training, labels)
             self.plans[key] = plan
             # every distinct (shape, mode) owns its activations (4.9 GB at 32x640x480): drop the least recently used ones beyond
             # the budget (never the plan just built, nor the one an un-finished forward/backward pair is using)
@@ -1086,25 +1135,56 @@ class Engine:
             if nbt:
                 torch._foreach_add_(nbt, 1)
         else:
-            # Inference: the packed filters and the BatchNorm constants depend on the parameters only.  They are recomputed when a
-            # kernel of this package wrote parameters / buffers (params_dirty) or a torch in-place op did (tensor version counters);
-            # otherwise the forward starts behind them (LabelProp frame pairs: 11 of 27 launches of a 0.19 ms call).
-            key = self._param_state_key()
-            if self.params_dirty or plan.head_key != key:
-                plan.fwd.run(self.handle, stream)
-                plan.head_key = self._param_state_key()
-                self.params_dirty = False
-                for pl in self.plans.values():
-                    if pl is not plan:
-                        pl.head_key = None
-            else:
-                plan.fwd.run_slice(self.handle, stream, plan.n_head, plan.fwd.n)
+            self._run_inference(plan, stream)
             if out is not plan.logits:       # the records are copied at enqueue: point them back at the engine's own buffer (profile_last re-runs the list)
                 for (idx, slot) in plan.logits_slots:
                     plan.fwd.arr[idx].p[slot] = plan.logits.data_ptr()
         self._last = (plan, [t for t in inputs])
         self._generation += 1
         return out
+
+    def _run_inference(self, plan: Plan, stream: int):
+        """The forward list of an eval or eval-labels plan.  The packed filters and the BatchNorm constants depend on the parameters
+        only.  They are recomputed when a kernel of this package wrote parameters / buffers (params_dirty) or a torch in-place op did
+        (tensor version counters); otherwise the forward starts behind them (LabelProp frame pairs: 11 of 27 launches of a 0.19 ms
+        call)."""
+        key = self._param_state_key()
+        if self.params_dirty or plan.head_key != key:
+            plan.fwd.run(self.handle, stream)
+            plan.head_key = self._param_state_key()
+            self.params_dirty = False
+            for pl in self.plans.values():
+                if pl is not plan:
+                    pl.head_key = None
+        else:
+            plan.fwd.run_slice(self.handle, stream, plan.n_head, plan.fwd.n)
+
+    def predict(self, inputs: Sequence[torch.Tensor], colour: bool = False, palette: Optional[torch.Tensor] = None):
+        """Runs the eval-labels plan: the network up to the classifier, whose tail writes the class of every pixel -- the first maximum
+        of the logits the eval plan would write, bit for bit -- as a fresh uint8 [N,H,W] tensor and, with ``colour``, palette[class] as a
+        fresh uint8 [N,H,W,3] tensor (``palette``: uint8 [8,3] on the device).  No logits are stored.  Leaves no forward in flight:
+        ``backward`` still belongs to the last ``forward``."""
+        for t in inputs:
+            if t.dtype != torch.float32 or not t.is_contiguous():
+                raise L.RcvError("engine inputs must be contiguous float32 tensors")
+        if colour and (palette is None or palette.dtype != torch.uint8 or tuple(palette.shape) != (8, 3) or not palette.is_contiguous()
+                       or palette.device != inputs[0].device):
+            raise L.RcvError("predict: the colour image needs a contiguous uint8 [8,3] palette on the input's device")
+        plan = self._plan_for(inputs, False, labels=True)
+        labels = torch.empty(plan.label_shape, dtype=torch.uint8, device=self.device)
+        col = torch.empty(plan.label_shape + (3,), dtype=torch.uint8, device=self.device) if colour else None
+        op = plan.fwd.arr[plan.label_op]
+        op.p[L.RCV_P_OUT] = labels.data_ptr()
+        op.p[L.RCV_P_X0] = col.data_ptr() if colour else None
+        op.p[L.RCV_P_X1] = palette.data_ptr() if colour else None
+        for k, t in enumerate(inputs):
+            for (is_bwd, idx, slot) in plan.input_slots[k]:
+                plan.fwd.arr[idx].p[slot] = t.data_ptr()
+        try:
+            self._run_inference(plan, torch.cuda.current_stream(self.device).cuda_stream)
+        finally:          # (the records are copied at enqueue: the cached list keeps no pointer into a caller's tensor)
+            op.p[L.RCV_P_OUT] = op.p[L.RCV_P_X0] = op.p[L.RCV_P_X1] = None
+        return (labels, col) if colour else labels
 
     def _fill_dropout(self, plan: Plan):
         """Dropout2d of the pooled head (model.py:408): a fresh keep-scale [N][C] per training forward, drawn as torch's feature dropout

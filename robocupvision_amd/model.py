@@ -107,6 +107,30 @@ class _EngineOwner:
         self.invalidate()
         return out
 
+    def predict(self, x, colour=False, palette=None):
+        """The class of every pixel, on the device, without the logits (detect.py:131-133: ``model(x)``, ``torch.max(pred, 1)``,
+        ``Colorize``).  ``x`` as for ``forward``.  Returns a fresh uint8 [N,H,W] tensor -- what ``SegmentationMetrics.update`` and
+        ``DetectionMetrics.update`` take -- or, with ``colour=True``, ``(labels, colour)`` with ``colour`` uint8 [N,H,W,3] =
+        ``palette[labels]``.  ``palette``: uint8 [k,3], k <= 8 (missing rows are black); default: the reference's five rows
+        (``labelcolormap``).  The class is the FIRST maximum of the logits ``self(x)`` writes in eval mode, bit for bit (RCV_OP_CLS_LABEL:
+        the same kernels' arithmetic with another tail).  Runs under ``torch.no_grad()``; eval mode only."""
+        from .palette import device_palette
+        if self.training:
+            raise L.RcvError("predict is an inference call and this module is in training mode: call `.eval()` first")
+        if _graph_mode(self):
+            raise L.RcvError("predict: this model is in classify mode (the pooled patch-classification head gives one class per patch, "
+                             "not a class map); build it with classify off")
+        if not hasattr(self, "_get_engine"):
+            raise L.RcvError("predict: %s has no per-pixel classifier (ROBO_UNet, PB_FCN, PB_FCN_2 and LabelProp have)" % type(self).__name__)
+        if not torch.is_tensor(x):
+            raise TypeError("predict: x must be a tensor")
+        if x.device.type != "cuda":
+            raise L.RcvError("predict runs on the HIP device only (input on %s); there is no CPU path" % x.device)
+        with torch.no_grad():
+            inputs = self._engine_inputs(x)
+            pal = device_palette(palette, x.device) if colour else None
+            return self._get_engine().predict(inputs, bool(colour), pal)
+
 
 class _BlockMixin(_EngineOwner):
     """Standalone call of a single block (NCHW in, NCHW out like the reference's blocks): the block
@@ -391,14 +415,16 @@ class ROBO_UNet(_EngineOwner, nn.Module):
             self.__dict__["_engine_mode"] = mode
         return eng
 
-    def forward(self, x):
+    def _engine_inputs(self, x):
         if x.dim() != 4 or x.shape[1] != 3:
             raise ValueError("ROBO_UNet expects float32 [B,3,H,W], got %s" % (tuple(x.shape),))
         down = 2 ** (len(self.downPart) - 1)
         if x.shape[2] % down or x.shape[3] % down:
             raise ValueError("H and W must be multiples of %d (got %dx%d)" % (down, x.shape[2], x.shape[3]))
-        x = x.to(torch.float32).contiguous()
-        return _run_engine(self._get_engine(), self.training, [x])
+        return [x.to(torch.float32).contiguous()]
+
+    def forward(self, x):
+        return _run_engine(self._get_engine(), self.training, self._engine_inputs(x))
 
     def get_computations(self, pruned=False):
         """Analytic per-layer operation counts (model.py:513-536); host arithmetic only."""
@@ -817,14 +843,16 @@ class PB_FCN(_EngineOwner, nn.Module):
             self.__dict__["_engine_mode"] = mode
         return eng
 
-    def forward(self, x):
+    def _engine_inputs(self, x):
         if x.dim() != 4 or x.shape[1] != 3:
             raise ValueError("PB_FCN expects float32 [B,3,H,W], got %s" % (tuple(x.shape),))
         down = 16 if self.noScale else 8
         if x.shape[2] % down or x.shape[3] % down:
             raise ValueError("H and W must be multiples of %d (got %dx%d)" % (down, x.shape[2], x.shape[3]))
-        x = x.to(torch.float32).contiguous()
-        return _run_engine(self._get_engine(), self.training, [x])
+        return [x.to(torch.float32).contiguous()]
+
+    def forward(self, x):
+        return _run_engine(self._get_engine(), self.training, self._engine_inputs(x))
 
 
 class PB_FCN_2(ROBO_UNet):
