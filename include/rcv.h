@@ -138,9 +138,30 @@ enum {
                              *     produced (a class outside [0, 8) is black, as Colorize leaves unmatched pixels 0); p[OUT] is not written.
                              * i[COUNT] = store shape: 0 = the library's choice, 1 = one byte / three bytes per pixel and lane, 4 = the labels
                              * and colours of four neighbouring pixels gathered into one / three dword stores (csrc/cls_label.hip)            */
-  RCV_OP_FRAME_PREP = 38    /* RCV_OP_BATCH_PREP with train = 0 for frames that have no labels (detect.py:125-130; rcv_frame_prep): the same slots
+  RCV_OP_FRAME_PREP = 38,   /* RCV_OP_BATCH_PREP with train = 0 for frames that have no labels (detect.py:125-130; rcv_frame_prep): the same slots
                              * and the same resize / normalise code; no label is read, no label table and no target: p[IN2], p[X0], p[X3], p[X4]
                              * and i[INMODE2], i[AUX0], i[AUX1] are not looked at.  p[OUT] is bit for bit what the other record writes             */
+  RCV_OP_BNN_STAGE_FWD = 39, /* one stage of the BNN-L / BNN-M-C patch classifiers (model.py:590-592, 615-618; csrc/bnn.hip), one launch:
+                             * out = relu(maxpool_{k,2}(dropout2d(conv_{KxK, pad P, stride 1}(x) + bias))).  i[N], i[H], i[W] = input plane, i[CIN]
+                             * (3 / 8 / 16), i[COUT] (4 / 8 / 16), i[AUX0] = K (3 / 5 / 8), i[COUNT] = P (0 / 1 / 3 / 4), i[AUX1] = pool k (0 = no
+                             * pool, 2, 4: k x k windows at stride 2, floor), i[HO], i[WO] = output plane, i[INMODE] = RCV_LOAD_NCHW (the network
+                             * input, 3 channels) or RCV_LOAD_PLAIN (NHWC); flags RCV_F_RELU, RCV_F_OUT_NCHW (BNN-M-C's classifier writes the
+                             * logits).  p[IN] = x, p[W] = filter [COUT][CIN][K][K] (the parameter itself), p[BIAS], p[X0] = Dropout2d keep-scale
+                             * float[N][COUT] (0 or 1/(1-p)) or NULL, p[OUT], p[X1] = uint8[N][HO][WO][COUT]: the window offset of the FIRST
+                             * maximum in row-major window order (aten's rule), or NULL where no backward follows; p[X2] = uint8[N][HO][WO]: the
+                             * FIRST maximum over the output channels of the values p[OUT] gets (the class map of `torch.max(pred, 1)`), or
+                             * NULL; with it p[OUT] may be NULL                                                                      */
+  RCV_OP_BNN_STAGE_BWD = 40, /* its backward, one launch + the fixed-order row reduction: d loss / d conv is GATHERED over the <= 4 windows
+                             * that contain a pixel (no atomics).  Slots as the forward, and p[IN] = d loss / d out, p[IN_AUX] = out (with
+                             * RCV_F_RELU), p[EPI_AUX] = x, p[OUT] = dx NHWC (RCV_LOAD_PLAIN only; NULL for the network input), p[X2] = dW
+                             * [COUT][CIN][K][K], p[X3] = db, p[PART] = i[NPART] partial rows of COUT*CIN*K*K + COUT floats                    */
+  RCV_OP_BNN_HEAD_FWD = 41,  /* BNN-L's head (model.py:593), one launch: logits = Wc relu((Wfc x + bfc) * keep) + bc per pixel.  i[N], i[H], i[W] =
+                             * head plane, i[CIN] = 16, i[COUNT] = 512 hidden units, i[COUT] = 1..8 classes; p[IN] = x NHWC, p[W] = Wfc [512][16],
+                             * p[BIAS] = bfc, p[X0] = Dropout keep-scale float[N][H][W][512] (0 or 2) or NULL, p[X1] = Wc [COUT][512], p[X2] = bc,
+                             * p[OUT] = NCHW logits or NULL, p[X3] = uint8[N][H][W] FIRST maximum of those logits or NULL (at least one of the two) */
+  RCV_OP_BNN_HEAD_BWD = 42   /* its backward, one launch + the row reduction: p[IN] = NCHW logits gradient, p[EPI_AUX] = x, p[W], p[BIAS], p[X0],
+                             * p[X1] as the forward; p[OUT] = dx NHWC [N][H][W][16], p[X2] = dWfc, p[X3] = dbfc, p[X4] = dWc, p[X5] = dbc,
+                             * p[PART] = i[NPART] partial rows (rcv_op_workspace)                                                        */
 };
 
 /* how an operand is produced from memory while it is staged (rcv_op.i[RCV_I_INMODE] etc.) */
@@ -411,6 +432,15 @@ int rcv_cls_label(rcv_handle* h, const float* x, const float* w, const float* bi
  * where the class is outside [0, 8); elem_bytes 1 = uint8, 8 = int64.                                                              */
 int rcv_colorize(rcv_handle* h, const void* classmap, int elem_bytes, int N, int H, int W, uint8_t* colour, const uint8_t* palette,
                  void* stream);
+
+/* The BNN-L / BNN-M-C patch classifiers (model.py:569-619; objDetEval.py:89-119, classVal.py).  Each call runs ONE record of the kind
+ * named (RCV_OP_BNN_STAGE_FWD / _BWD: conv -> Dropout2d -> MaxPool2d(k, 2) -> ReLU of model.py:590-592,615-618 and its
+ * aten::max_pool2d_with_indices_backward / convolution_backward; RCV_OP_BNN_HEAD_FWD / _BWD: fc -> Dropout -> ReLU -> classifier of
+ * model.py:593); the slots are documented at the kinds.                                                                          */
+int rcv_bnn_stage_fwd(rcv_handle* h, const rcv_op* op, void* stream);
+int rcv_bnn_stage_bwd(rcv_handle* h, const rcv_op* op, void* stream);
+int rcv_bnn_head_fwd(rcv_handle* h, const rcv_op* op, void* stream);
+int rcv_bnn_head_bwd(rcv_handle* h, const rcv_op* op, void* stream);
 
 /* torch.optim.SGD.step (trainer.py:176-178,221): g = grad*grad_scale + weight_decay*p; buf = step==1 ? g : momentum*buf + g;
  * p -= lr*buf.  lr_elem (may be NULL) gives a per-element learning rate (0 = parameter without a gradient: untouched). */

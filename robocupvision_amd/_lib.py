@@ -26,6 +26,7 @@ OP_LP_TAIL_FWD, OP_LP_TAIL_BWD, OP_LP_BATCH = 33, 34, 35      # LabelProp's trai
 OP_BATCH_PREP = 36          # the loader's per-image work for a whole batch (rcv.h RCV_OP_BATCH_PREP, csrc/batch_prep.hip)
 OP_CLS_LABEL = 37           # classifier tail -> uint8 class map (+ colour image), no logits (rcv.h RCV_OP_CLS_LABEL, csrc/cls_label.hip)
 OP_FRAME_PREP = 38          # OP_BATCH_PREP's validation form for frames without labels (rcv.h RCV_OP_FRAME_PREP)
+OP_BNN_STAGE_FWD, OP_BNN_STAGE_BWD, OP_BNN_HEAD_FWD, OP_BNN_HEAD_BWD = 39, 40, 41, 42      # BNN-L / BNN-M-C stages and head (rcv.h, csrc/bnn.hip)
 CLS_LABEL_FEATURES, CLS_LABEL_LOGITS, CLS_LABEL_CLASSMAP = range(3)      # i[INMODE] of OP_CLS_LABEL: the source form
 
 LOAD_PLAIN, LOAD_AFFINE, LOAD_GRAD_ENC, LOAD_GRAD_DEC, LOAD_NCHW, LOAD_AFFINE_RELU = range(6)
@@ -60,6 +61,7 @@ EXPORTS = [
     "rcv_softmax_ce_argmax_fwd", "rcv_softmax_ce_bwd", "rcv_adam_l1_step", "rcv_adam_l1_step_metrics", "rcv_confusion",
     "rcv_dice_fwd", "rcv_dice_bwd", "rcv_sgd_step", "rcv_create_planner", "rcv_adam_l1_step_pruned", "rcv_op_filter_layout",
     "rcv_object_match", "rcv_labelprop_batch", "rcv_batch_prep", "rcv_frame_prep", "rcv_cls_label", "rcv_colorize",
+    "rcv_bnn_stage_fwd", "rcv_bnn_stage_bwd", "rcv_bnn_head_fwd", "rcv_bnn_head_bwd",
 ]
 
 
@@ -106,7 +108,8 @@ def load():
         lib.rcv_frame_prep.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 3
         lib.rcv_cls_label.argtypes = [C.c_void_p] * 4 + [C.c_int] * 5 + [C.c_void_p] * 4
         lib.rcv_colorize.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 3
-        for name in ("rcv_conv3x3", "rcv_convT3x3s2", "rcv_wgrad3x3"):
+        for name in ("rcv_conv3x3", "rcv_convT3x3s2", "rcv_wgrad3x3", "rcv_bnn_stage_fwd", "rcv_bnn_stage_bwd", "rcv_bnn_head_fwd",
+                     "rcv_bnn_head_bwd"):
             getattr(lib, name).argtypes = [C.c_void_p, C.POINTER(RcvOp), C.c_void_p]
         _lib = lib
     return _lib

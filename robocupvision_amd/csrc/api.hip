@@ -119,6 +119,11 @@ static int dispatch(const rcv_handle* h, const rcv_op* op, hipStream_t s, OpQuer
       return rcv_launch_batch_prep(h, op, s, q);
     case RCV_OP_CLS_LABEL:
       return rcv_launch_cls_label(h, op, s, q);
+    case RCV_OP_BNN_STAGE_FWD:
+    case RCV_OP_BNN_STAGE_BWD:
+    case RCV_OP_BNN_HEAD_FWD:
+    case RCV_OP_BNN_HEAD_BWD:
+      return rcv_launch_bnn(h, op, s, q);
     case RCV_OP_NOP:
       if (q) { snprintf(q->label, sizeof(q->label), "nop"); q->n_part = 0; q->n_split = 0; q->part_bytes = 0; }
       return RCV_OK;
@@ -435,6 +440,23 @@ int rcv_colorize(rcv_handle* h, const void* classmap, int elem_bytes, int N, int
   op.i[RCV_I_INMODE2] = elem_bytes;
   op.p[RCV_P_IN] = (void*)classmap; op.p[RCV_P_X0] = colour; op.p[RCV_P_X1] = (void*)palette;
   return rcv_run(h, &op, 1, stream);
+}
+
+int rcv_bnn_stage_fwd(rcv_handle* h, const rcv_op* op, void* stream) {
+  RCV_CHECK_ARG(op && op->kind == RCV_OP_BNN_STAGE_FWD, "rcv_bnn_stage_fwd: record kind must be RCV_OP_BNN_STAGE_FWD");
+  return rcv_run(h, op, 1, stream);
+}
+int rcv_bnn_stage_bwd(rcv_handle* h, const rcv_op* op, void* stream) {
+  RCV_CHECK_ARG(op && op->kind == RCV_OP_BNN_STAGE_BWD, "rcv_bnn_stage_bwd: record kind must be RCV_OP_BNN_STAGE_BWD");
+  return rcv_run(h, op, 1, stream);
+}
+int rcv_bnn_head_fwd(rcv_handle* h, const rcv_op* op, void* stream) {
+  RCV_CHECK_ARG(op && op->kind == RCV_OP_BNN_HEAD_FWD, "rcv_bnn_head_fwd: record kind must be RCV_OP_BNN_HEAD_FWD");
+  return rcv_run(h, op, 1, stream);
+}
+int rcv_bnn_head_bwd(rcv_handle* h, const rcv_op* op, void* stream) {
+  RCV_CHECK_ARG(op && op->kind == RCV_OP_BNN_HEAD_BWD, "rcv_bnn_head_bwd: record kind must be RCV_OP_BNN_HEAD_BWD");
+  return rcv_run(h, op, 1, stream);
 }
 
 int rcv_sgd_step(rcv_handle* h, float* param, const float* grad, float* momentum_buf, const float* lr_elem, int64_t n, float lr,

@@ -50,6 +50,59 @@ class SegmentationMetrics:
                 "confusion_percent": (self.conf / (lab_cnt / 100.0)).cpu()}
 
 
+def patch_scores(conf) -> dict:
+    """The figures objDetEval.py prints from its confusion matrix ``conf[pred, label]`` (integers): ``acc`` = the validation accuracy
+    of objDetEval.py:156,164 (100 * #(pred == label) / #patches), and the three of objDetEval.py:171-179 over the object classes 1..3:
+    ``obj_acc`` = totAcc / total * 100 with total = sum(conf[:, 1:4]) (patches whose LABEL is an object) and totAcc = the diagonal
+    1..3, ``false_neg`` = 100 - obj_acc, ``false_pos`` = (sum(conf[1:4, :]) - totAcc) / total * 100.  Float64 on the host."""
+    c = torch.as_tensor(conf).to(torch.int64).cpu()
+    n = int(c.sum())
+    total = int(c[:, 1:4].sum())
+    tot_acc = int(c[1, 1] + c[2, 2] + c[3, 3])
+    fp = int(c[1:4, :].sum()) - tot_acc
+    nan = float("nan")
+    obj = tot_acc / total * 100 if total else nan
+    return {"acc": int(torch.diagonal(c).sum()) * 100 / n if n else nan, "obj_acc": obj, "false_neg": 100 - obj,
+            "false_pos": fp / total * 100 if total else nan, "confusion": c}
+
+
+class PatchMetrics:
+    """The confusion matrix of the patch classifiers' validation loop (objDetEval.py:155-159: ``conf[(predClass[j], labels[j])] += 1``
+    per sample, each a device read) accumulated on the device by RCV_OP_CONFUSION with one 1x1 "image" per patch; nothing is read
+    back before ``compute``."""
+
+    def __init__(self, num_class: int = 4, device="cuda"):
+        if num_class < 4 or num_class > 8:
+            raise ValueError("PatchMetrics reports the object classes 1..3: 4 <= num_class <= 8 (got %d)" % num_class)
+        self.C = num_class
+        self.device = torch.device(device)
+        self.conf = None
+
+    def reset(self):
+        self.conf = None
+
+    def update(self, pred_u8: torch.Tensor, labels: torch.Tensor):
+        """pred_u8: uint8 [B] or [B,1,1] (``BNNL.predict`` / ``BNNMC.predict`` of 32x32 patches) on the HIP device; labels: int64 [B]."""
+        if pred_u8.dtype != torch.uint8 or pred_u8.device.type != "cuda":
+            raise L.RcvError("PatchMetrics.update needs the uint8 class of every patch on the HIP device")
+        B = pred_u8.shape[0]
+        if pred_u8.numel() != B or labels.numel() != B:
+            raise ValueError("PatchMetrics.update takes one class and one label per patch: pred %s, labels %s" % (tuple(pred_u8.shape), tuple(labels.shape)))
+        labels = labels.to(pred_u8.device).to(torch.int64).contiguous()
+        counts = torch.zeros(B, self.C, self.C, dtype=torch.int32, device=pred_u8.device)
+        h = L.handle(pred_u8.device.index if pred_u8.device.index is not None else torch.cuda.current_device())
+        op = L.make_op(L.OP_CONFUSION, 0, n=B, h=1, w=1, cout=self.C, p_in=pred_u8.contiguous().data_ptr(), p_in2=labels.data_ptr(),
+                       p_out=counts.data_ptr())
+        L.OpList([op]).run(h, torch.cuda.current_stream(pred_u8.device).cuda_stream)
+        s = counts.sum(0, dtype=torch.int64)
+        self.conf = s if self.conf is None else self.conf + s
+
+    def compute(self) -> dict:
+        if self.conf is None:
+            return patch_scores(torch.zeros(self.C, self.C, dtype=torch.int64))
+        return patch_scores(self.conf)
+
+
 DEFAULT_IOU_THRESHOLDS = (0.75, 0.5, 0.25, 0.1, 0.05)     # test.py:258
 DEFAULT_DIST_THRESHOLDS = (1.25, 2.5, 5, 10, 20)          # test.py:259; test.py:261-262 doubles them for --noScale
 

@@ -21,10 +21,11 @@ import torch.nn as nn
 
 from . import _lib as L
 from .engine import Engine
+from .bnn import BNNL, BNNMC      # the reference's model.py:569-619 (kernels: csrc/bnn.hip)
 
 __all__ = ["ROBO_UNet", "CrossEntropyLoss2d", "DiceLoss", "PB_FCN", "PB_FCN_2", "LabelProp", "Conv", "Pool", "LevelDown",
            "labelprop_batch", "upSampleTransposeConv", "UltClassifier", "ConvPoolSimple", "ConvPool", "DownSampler", "Classifier", "pruneModelNew",
-           "count_zero_weights", "getParamSize"]
+           "count_zero_weights", "getParamSize", "BNNL", "BNNMC"]
 
 
 # ------------------------------------------------------------------------------------------
