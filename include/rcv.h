@@ -159,9 +159,25 @@ enum {
                              * head plane, i[CIN] = 16, i[COUNT] = 512 hidden units, i[COUT] = 1..8 classes; p[IN] = x NHWC, p[W] = Wfc [512][16],
                              * p[BIAS] = bfc, p[X0] = Dropout keep-scale float[N][H][W][512] (0 or 2) or NULL, p[X1] = Wc [COUT][512], p[X2] = bc,
                              * p[OUT] = NCHW logits or NULL, p[X3] = uint8[N][H][W] FIRST maximum of those logits or NULL (at least one of the two) */
-  RCV_OP_BNN_HEAD_BWD = 42   /* its backward, one launch + the row reduction: p[IN] = NCHW logits gradient, p[EPI_AUX] = x, p[W], p[BIAS], p[X0],
+  RCV_OP_BNN_HEAD_BWD = 42,  /* its backward, one launch + the row reduction: p[IN] = NCHW logits gradient, p[EPI_AUX] = x, p[W], p[BIAS], p[X0],
                              * p[X1] as the forward; p[OUT] = dx NHWC [N][H][W][16], p[X2] = dWfc, p[X3] = dbfc, p[X4] = dWc, p[X5] = dbc,
                              * p[PART] = i[NPART] partial rows (rcv_op_workspace)                                                        */
+  RCV_OP_CE_NORM = 43,       /* the normaliser of the weighted cross entropy, sum_p w[target_p], from the targets alone, left as partial rows:
+                             * i[N], i[H], i[W], i[COUT] = classes (1..8), p[IN2] = int64 target, p[X0] = class weights or NULL, p[PART] =
+                             * float[i[NPART]] (rcv_op_workspace), one value per workgroup.  Grid, pixel -> thread mapping and summation order
+                             * are those of RCV_OP_CLS_FWD with RCV_F_FUSED_CE: row b is bit for bit column 1 of that op's partial row b, and
+                             * the rows summed in RCV_OP_CE_FWD's finalisation order give its loss_out[1].  Runs ahead of RCV_OP_CLS_STEP   */
+  RCV_OP_CLS_STEP = 44       /* the training step's turn from forward to backward at the fused 1x1 classifier: RCV_OP_CLS_FWD and RCV_OP_CLS_BWD,
+                             * both with RCV_F_FUSED_UP | RCV_F_FUSED_CE, in ONE pass over t, the skip tensor and the targets, then one launch
+                             * for the fixed-order reductions (dW, db and the loss).  8 input channels, 1..8 classes.  Slots exactly as
+                             * RCV_OP_CLS_BWD with both flags (required; i[STATS] = RCV_STATS_BWD_DEC required): p[EPI_AUX] = t, p[EPI_C] = its
+                             * constants, p[X3] / p[X4] / i[AUX0] = the skip tensor, its constants, its load mode, p[W], p[BIAS], p[IN2] = int64
+                             * target, p[X0] = class weights or NULL, p[IN2_AUX] = d loss scalar, p[OUT] = d_up, p[X1] = dW, p[X2] = db, p[PART] =
+                             * i[NPART] partial rows (rcv_op_workspace: the backward op's layout) -- and the forward's outputs: p[RESID] = NCHW
+                             * logits, p[IN_AUX] = uint8 arg-max or NULL, p[IN2_C] = float[i[NPART]][3] loss partial rows, p[X5] = float[4]
+                             * loss_out (WRITTEN here, as RCV_OP_CE_FWD writes it), p[IN_C] = the float[i[NPART]] rows of an RCV_OP_CE_NORM
+                             * record over the same targets and weights, run before this one.  Every output and every partial row is bit
+                             * for bit what the two records write                                                                      */
 };
 
 /* how an operand is produced from memory while it is staged (rcv_op.i[RCV_I_INMODE] etc.) */

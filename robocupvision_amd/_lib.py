@@ -27,6 +27,7 @@ OP_BATCH_PREP = 36          # the loader's per-image work for a whole batch (rcv
 OP_CLS_LABEL = 37           # classifier tail -> uint8 class map (+ colour image), no logits (rcv.h RCV_OP_CLS_LABEL, csrc/cls_label.hip)
 OP_FRAME_PREP = 38          # OP_BATCH_PREP's validation form for frames without labels (rcv.h RCV_OP_FRAME_PREP)
 OP_BNN_STAGE_FWD, OP_BNN_STAGE_BWD, OP_BNN_HEAD_FWD, OP_BNN_HEAD_BWD = 39, 40, 41, 42      # BNN-L / BNN-M-C stages and head (rcv.h, csrc/bnn.hip)
+OP_CE_NORM, OP_CLS_STEP = 43, 44     # the classifier's forward + loss + backward in one pass, and its normaliser pre-pass (rcv.h, csrc/small_kernels.hip)
 CLS_LABEL_FEATURES, CLS_LABEL_LOGITS, CLS_LABEL_CLASSMAP = range(3)      # i[INMODE] of OP_CLS_LABEL: the source form
 
 LOAD_PLAIN, LOAD_AFFINE, LOAD_GRAD_ENC, LOAD_GRAD_DEC, LOAD_NCHW, LOAD_AFFINE_RELU = range(6)

@@ -4,6 +4,7 @@
 // shuffles + fixed-order LDS trees for the reductions (no float atomics).
 #include "rcv_internal.h"
 #include "cls_common.h"
+#include <type_traits>
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
@@ -258,6 +259,55 @@ __global__ void concat_kernel(const float* __restrict__ t, const float* __restri
 // (CLS_MAX_OUT and the loads that form the classifier's input -- ClsRaw, cls_load_raw, cls_form_up, cls_load_up -- are in cls_common.h,
 // shared with the class-map kernels of cls_label.hip)
 
+// The per-pixel pieces of the weighted cross entropy that cls_fwd_kernel<CE>, the training-step kernel (cls_bwd_kernel<..., ClsStepArgs>) and the
+// normaliser pre-pass (ce_norm_kernel) share, so that each of them rounds as the others do.
+// weight of a pixel's label: a label outside [0, C) (e.g. -100) is ignored, like NLLLoss's ignore_index
+__device__ __forceinline__ float ce_label_weight(int tg, int C, const float* __restrict__ cw) {
+  return (unsigned)tg < (unsigned)C ? (cw ? cw[tg] : 1.f) : 0.f;
+}
+// first maximum in class order (torch.max): strict '>', a NaN never wins
+template <int NC>
+__device__ __forceinline__ float ce_first_max(const float (&lg)[NC], int C, int& am) {
+  float mx = -INFINITY;
+  am = 0;
+#pragma unroll
+  for (int c = 0; c < NC; ++c) if (c < C && lg[c] > mx) { mx = lg[c]; am = c; }
+  return mx;
+}
+// the logit of the pixel's label (a label outside [0, C) has none: 0, and its weight is 0 too)
+template <int NC>
+__device__ __forceinline__ float ce_target_logit(const float (&lg)[NC], int C, int tg) {
+  float vt = 0.f;
+#pragma unroll
+  for (int c = 0; c < NC; ++c) if (c == tg && c < C) vt = lg[c];
+  return vt;
+}
+// one pixel's share of the three sums, from the maximum of its logits, the label's logit and se = sum_c exp(lg[c] - mx)
+// (OK: double in cls_fwd_kernel; the step kernel counts in an int, exact as well and a register less)
+template <class OK>
+__device__ __forceinline__ void ce_pixel_sums(float mx, float vt, float se, int am, int tg, int C, const float* __restrict__ cw,
+                                              double& a_nll, double& a_w, OK& a_ok) {
+  const float wt = ce_label_weight(tg, C, cw);
+  const float nll = (mx - vt) + logf(se);
+  a_nll += (double)(wt * nll);
+  a_w += (double)wt;
+  a_ok += (am == tg) ? OK(1) : OK(0);
+}
+// a workgroup's partial row: wave shuffles, then the waves through LDS in index order, rounded to float once.  w_row: the row's
+// sum of weights where ce_norm_kernel has formed it already (the same sum in the same order), in place of a_w
+__device__ __forceinline__ void ce_store_row(double a_nll, double a_w, double a_ok, float* __restrict__ row, const float* __restrict__ w_row = nullptr) {
+  __shared__ double sh[3][4];
+  a_nll = wave_sum_d(a_nll); a_w = wave_sum_d(a_w); a_ok = wave_sum_d(a_ok);
+  const int wv = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) { sh[0][wv] = a_nll; sh[1][wv] = a_w; sh[2][wv] = a_ok; }
+  __syncthreads();
+  if (threadIdx.x < 3) {
+    double t = 0.0;
+    for (int i = 0; i < (int)(blockDim.x >> 6); ++i) t += sh[threadIdx.x][i];
+    row[threadIdx.x] = (w_row && threadIdx.x == 1) ? w_row[0] : (float)t;
+  }
+}
+
 // CE: the weighted cross-entropy partial sums, the arg-max mask and the pixel-accuracy count of RCV_OP_CE_FWD are taken from the
 // logits while they are still in registers (same pixel -> thread assignment and summation order as ce_fwd_kernel: bit-identical loss).
 template <int CIN, bool FUSED, bool CE>
@@ -267,7 +317,6 @@ __global__ void cls_fwd_kernel(const float* __restrict__ x, const float* __restr
                                const int64_t* __restrict__ target, const float* __restrict__ cw, float* __restrict__ part,
                                uint8_t* __restrict__ argmax, int rch) {
   __shared__ float ws[CLS_MAX_OUT * CIN + CLS_MAX_OUT];
-  __shared__ double sh[3][4];
   for (int e = threadIdx.x; e < COUT * CIN; e += blockDim.x) ws[e] = w[e];
   for (int e = threadIdx.x; e < COUT; e += blockDim.x) ws[CLS_MAX_OUT * CIN + e] = bias ? bias[e] : 0.f;
   __syncthreads();
@@ -290,35 +339,44 @@ __global__ void cls_fwd_kernel(const float* __restrict__ x, const float* __restr
       }
     }
     if (CE) {
-      float mx = -INFINITY;
-      int am = 0;
-#pragma unroll
-      for (int c = 0; c < CLS_MAX_OUT; ++c) if (c < COUT && lg[c] > mx) { mx = lg[c]; am = c; }
+      int am;
+      const float mx = ce_first_max(lg, COUT, am);
       float se = 0.f;
 #pragma unroll
       for (int c = 0; c < CLS_MAX_OUT; ++c) if (c < COUT) se += expf(lg[c] - mx);
       const int tg = (int)target[p];
-      float vt = 0.f;
-#pragma unroll
-      for (int c = 0; c < CLS_MAX_OUT; ++c) if (c == tg && c < COUT) vt = lg[c];     // (a label in [COUT, 8) has no logit: lg[c] is unset there)
-      const float wt = (unsigned)tg < (unsigned)COUT ? (cw ? cw[tg] : 1.f) : 0.f;   // label outside [0, C) (e.g. -100): ignored, like NLLLoss's ignore_index
-      const float nll = (mx - vt) + logf(se);
-      a_nll += (double)(wt * nll);
-      a_w += (double)wt;
-      a_ok += (am == tg) ? 1.0 : 0.0;
+      ce_pixel_sums(mx, ce_target_logit(lg, COUT, tg), se, am, tg, COUT, cw, a_nll, a_w, a_ok);
       if (argmax) argmax[p] = (uint8_t)am;
     }
   }
-  if (CE) {
-    a_nll = wave_sum_d(a_nll); a_w = wave_sum_d(a_w); a_ok = wave_sum_d(a_ok);
-    const int wv = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) { sh[0][wv] = a_nll; sh[1][wv] = a_w; sh[2][wv] = a_ok; }
-    __syncthreads();
-    if (threadIdx.x < 3) {
-      double t = 0.0;
-      for (int i = 0; i < (int)(blockDim.x >> 6); ++i) t += sh[threadIdx.x][i];
-      part[(size_t)blockIdx.x * 3 + threadIdx.x] = (float)t;
-    }
+  if (CE) ce_store_row(a_nll, a_w, a_ok, part + (size_t)blockIdx.x * 3);
+}
+
+// RCV_OP_CE_NORM: the normaliser sum_p w[target_p] of the weighted cross entropy from the targets alone, as one float per workgroup:
+// grid, pixel -> thread mapping and summation order of cls_fwd_kernel<CE>'s a_w, so row b is bit for bit column 1 of that kernel's row b
+__global__ void ce_norm_kernel(const int64_t* __restrict__ target, const float* __restrict__ cw, int C, size_t total,
+                               float* __restrict__ rows) {
+  __shared__ double sh[4];
+  double a_w = 0.0;
+  // four labels in flight per lane (with one 8-byte load at a time the kernel took 40 us for 79 MB, with four 29 us); the sum keeps the
+  // pixel order of the plain loop
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  for (; p + 3 * stride < total; p += 4 * stride) {
+    const int t0 = (int)target[p], t1 = (int)target[p + stride], t2 = (int)target[p + 2 * stride], t3 = (int)target[p + 3 * stride];
+    a_w += (double)ce_label_weight(t0, C, cw);
+    a_w += (double)ce_label_weight(t1, C, cw);
+    a_w += (double)ce_label_weight(t2, C, cw);
+    a_w += (double)ce_label_weight(t3, C, cw);
+  }
+  for (; p < total; p += stride) a_w += (double)ce_label_weight((int)target[p], C, cw);
+  a_w = wave_sum_d(a_w);
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = a_w;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double t = 0.0;
+    for (int i = 0; i < (int)(blockDim.x >> 6); ++i) t += sh[i];
+    rows[blockIdx.x] = (float)t;
   }
 }
 
@@ -378,17 +436,57 @@ __global__ __launch_bounds__(256) void cls_fwd16_kernel(const float* __restrict_
 // logits are re-formed with the forward's FMA order, so the gradients are bit-identical to the unfused path).
 // Built for every class count 1..8 (trainer.py:126-132 / train.py:301: numClass = 5 - nb - ng - nr - nl; model.py:462 nClass) and
 // for 8 or 16 input channels; a thread keeps COUT x CIN filter-gradient accumulators, so the wide variants run one workgroup per SIMD set.
-template <int CIN, int COUT, bool FUSED, bool CE>
+//
+// STEP (RCV_OP_CLS_STEP; the instantiations with a trailing ClsStepArgs argument): the training step's forward and
+// backward of the classifier in ONE pass over t, r and the
+// targets.  The logits this kernel forms anyway are also stored (NCHW, nontemporal) and feed the loss sums and the arg-max exactly as in
+// cls_fwd_kernel<8, true, true>; the one thing the gradient lacks at that moment, the normaliser sum_w = loss_out[1], depends on the
+// targets alone and arrives as the rows of ce_norm_kernel, which every workgroup sums in ce_finalize_kernel's order.  Same grid, pixel ->
+// thread mapping and reductions as the two kernels: every row and every output is bit for bit theirs.
+struct ClsStepArgs {
+  float* logits;            // [N][COUT][HW]
+  uint8_t* argmax;          // [N][HW] or NULL
+  float* ce_part;           // [grid][3]
+  const float* norm_rows;   // [n_rows] (ce_norm_kernel)
+  int n_rows;
+};
+
+template <class T>
+__device__ __forceinline__ const T& cls_first_arg(const T& a) { return a; }
+
+// (one kernel text for both forms: the two-record instantiations have an empty STEP_ARGS pack -- the parent signature, and every
+// step-only statement sits in an `if constexpr (STEP)` -- so the step form costs them nothing)
+template <int CIN, int COUT, bool FUSED, bool CE, class... STEP_ARGS>
 __global__ __launch_bounds__(256, (CIN == 8 ? 2 : 1)) void cls_bwd_kernel(const float* __restrict__ up, const float* __restrict__ dl, const float* __restrict__ w,
                                float* __restrict__ dup, const float* __restrict__ t, const float* __restrict__ tc,
                                float* __restrict__ stat_part, float* __restrict__ w_part, int N, int HW, int stats,
                                const float* __restrict__ r, const float* __restrict__ rc, int mode2,
                                const int64_t* __restrict__ target, const float* __restrict__ cw, const float* __restrict__ bias,
-                               const float* __restrict__ loss_out, const float* __restrict__ grad_out) {
+                               const float* __restrict__ loss_out, const float* __restrict__ grad_out, STEP_ARGS... step_args) {
+  constexpr bool STEP = sizeof...(STEP_ARGS) != 0;
+  static_assert(!STEP || (CE && FUSED && CIN == 8), "the training-step form is the fused 8-channel classifier with its loss");
+  [[maybe_unused]] ClsStepArgs sa{};
+  if constexpr (STEP) { sa = cls_first_arg(step_args...); stats = RCV_STATS_BWD_DEC; }
   __shared__ float ws[COUT * CIN];
   __shared__ float red[4][COUT * CIN + COUT + 2 * CIN];
   for (int e = threadIdx.x; e < COUT * CIN; e += blockDim.x) ws[e] = w[e];
-  __syncthreads();
+  float sum_w = 0.f;
+  double a_nll = 0.0, a_w = 0.0;
+  int n_ok = 0;
+  if constexpr (STEP) {
+    // loss_out[1] before ce_finalize_kernel has run: its order (threads strided over the rows, wave_sum_d, the waves in index order)
+    __shared__ double shn[4];
+    double sn = 0.0;
+    for (int i = threadIdx.x; i < sa.n_rows; i += blockDim.x) sn += (double)sa.norm_rows[i];
+    sn = wave_sum_d(sn);
+    if ((threadIdx.x & 63) == 0) shn[threadIdx.x >> 6] = sn;
+    __syncthreads();
+    double tn = 0.0;
+    for (int i = 0; i < (int)(blockDim.x >> 6); ++i) tn += shn[i];
+    sum_w = (float)tn;
+  } else {
+    __syncthreads();
+  }
   float dw[COUT][CIN], db[COUT], s1[CIN], s2[CIN];
 #pragma unroll
   for (int c = 0; c < COUT; ++c) { db[c] = 0.f;
@@ -396,19 +494,25 @@ __global__ __launch_bounds__(256, (CIN == 8 ? 2 : 1)) void cls_bwd_kernel(const 
     for (int k = 0; k < CIN; ++k) dw[c][k] = 0.f; }
 #pragma unroll
   for (int k = 0; k < CIN; ++k) { s1[k] = 0.f; s2[k] = 0.f; }
+  // STEP only (the two-record kernels keep their code): the 8-class step form has no vector register to spare, so d loss / (sum of
+  // weights), which is uniform, lives in a scalar register, the label is narrowed when it is loaded, and the whole-line store below
+  // addresses from a scalar base
+  float ce_scale = 0.f;
+  if constexpr (STEP) ce_scale = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(grad_out[0] / sum_w)));
+  using label_t = typename std::conditional<STEP, int, int64_t>::type;
   const size_t total = (size_t)N * HW;
   // pixel i+1 (and its label) is requested before pixel i is worked on: unconditionally, the last iteration re-requests its own pixel
   const size_t stride = (size_t)gridDim.x * blockDim.x;
   size_t p = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   ClsRaw<CIN, FUSED> cur;
-  int64_t tcur = 0;
-  if (p < total) { cls_load_raw<CIN, FUSED>(cur, FUSED ? t : up, r, p); if (CE) tcur = target[p]; }
+  label_t tcur = 0;
+  if (p < total) { cls_load_raw<CIN, FUSED>(cur, FUSED ? t : up, r, p); if (CE) tcur = (label_t)target[p]; }
   for (; p < total; p += stride) {
     const size_t pn = p + stride < total ? p + stride : p;
     ClsRaw<CIN, FUSED> nxt;
     cls_load_raw<CIN, FUSED>(nxt, FUSED ? t : up, r, pn);
-    int64_t tnxt = 0;
-    if (CE) tnxt = target[pn];
+    label_t tnxt = 0;
+    if (CE) tnxt = (label_t)target[pn];
     const size_t n = p / HW, hw = p % HW;
     float g[COUT], u[CIN], d[CIN];
     cls_form_up<CIN, FUSED>(u, cur, tc, rc, mode2);                       // FUSED: up is re-formed from t and the skip tensor
@@ -419,14 +523,29 @@ __global__ __launch_bounds__(256, (CIN == 8 ? 2 : 1)) void cls_bwd_kernel(const 
         float lgc = bias ? bias[c] : 0.f;
 #pragma unroll
         for (int k = 0; k < CIN; ++k) lgc = fmaf(u[k], ws[c * CIN + k], lgc);
+        if constexpr (STEP) __builtin_nontemporal_store(lgc, sa.logits + (n * COUT + c) * HW + hw);
         g[c] = lgc;
         mx = fmaxf(mx, lgc);
+      }
+      const int tg = (int)tcur;
+      int am = 0;
+      float mxf = 0.f, vt = 0.f;
+      if constexpr (STEP) {      // the forward's maximum (first '>': the arg-max) and the label's logit, while g still holds the logits
+        mxf = ce_first_max(g, COUT, am);
+        vt = ce_target_logit(g, COUT, tg);
       }
       float se = 0.f;
 #pragma unroll
       for (int c = 0; c < COUT; ++c) { g[c] = expf(g[c] - mx); se += g[c]; }
-      const int tg = (int)tcur;
-      const float kf = (grad_out[0] / loss_out[1]) * ((unsigned)tg < (unsigned)COUT ? (cw ? cw[tg] : 1.f) : 0.f);
+      if constexpr (STEP) {
+        // the forward's loss terms.  Its maximum and the fmaxf one above are the same number up to the sign of a zero (a NaN wins
+        // neither), and exp(lg - mx) does not see that sign: `se` is the forward's sum, term for term
+        ce_pixel_sums(mxf, vt, se, am, tg, COUT, cw, a_nll, a_w, n_ok);
+        if (sa.argmax) sa.argmax[p] = (uint8_t)am;
+      }
+      float kf;
+      if constexpr (STEP) kf = ce_scale * ce_label_weight(tg, COUT, cw);
+      else kf = (grad_out[0] / loss_out[1]) * ((unsigned)tg < (unsigned)COUT ? (cw ? cw[tg] : 1.f) : 0.f);
       const float inv = 1.f / se;
 #pragma unroll
       for (int c = 0; c < COUT; ++c) g[c] = __fmul_rn(kf, fmaf(g[c], inv, c == tg ? -1.f : 0.f));      // explicit: same rounding as ce_bwd_kernel
@@ -446,13 +565,22 @@ __global__ __launch_bounds__(256, (CIN == 8 ? 2 : 1)) void cls_bwd_kernel(const 
       // lane l sends float4 (l&1) of pixel 32s + (l>>1), fetched from that lane by shuffles => whole-line stores.
       const int lane = threadIdx.x & 63;
       const size_t wave_p0 = p - lane;
+      float* wave_dup = dup + wave_p0 * CIN;
+      if constexpr (STEP) {
+        // (the wave's first pixel is lane 0's, and with total % 64 == 0 a wave runs whole or not at all: the store address is a scalar
+        // base plus 16 bytes per lane -- no 64-bit vector register pair per lane for it)
+        const uintptr_t wave_v = reinterpret_cast<uintptr_t>(wave_dup);
+        wave_dup = reinterpret_cast<float*>(((uintptr_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(wave_v >> 32)) << 32) |
+                                            (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)wave_v));
+      }
 #pragma unroll
       for (int sidx = 0; sidx < 2; ++sidx) {
         const int src = sidx * 32 + (lane >> 1);
         float4 lo, hi;
         lo.x = __shfl(d[0], src); lo.y = __shfl(d[1], src); lo.z = __shfl(d[2], src); lo.w = __shfl(d[3], src);
         hi.x = __shfl(d[4], src); hi.y = __shfl(d[5], src); hi.z = __shfl(d[6], src); hi.w = __shfl(d[7], src);
-        sst4(dup + (wave_p0 + sidx * 32) * CIN + lane * 4, (lane & 1) ? hi : lo);
+        if constexpr (STEP) sst4(wave_dup + sidx * 32 * CIN + lane * 4, (lane & 1) ? hi : lo);
+        else sst4(dup + (wave_p0 + sidx * 32) * CIN + lane * 4, (lane & 1) ? hi : lo);
       }
     } else {
 #pragma unroll
@@ -502,12 +630,12 @@ __global__ __launch_bounds__(256, (CIN == 8 ? 2 : 1)) void cls_bwd_kernel(const 
     if (e < COUT * CIN + COUT) w_part[(size_t)blockIdx.x * (COUT * CIN + COUT) + e] = v;
     else if (stats == RCV_STATS_BWD_DEC) stat_part[(size_t)blockIdx.x * 2 * CIN + (e - COUT * CIN - COUT)] = v;
   }
+  if constexpr (STEP) ce_store_row(a_nll, 0.0, (double)n_ok, sa.ce_part + (size_t)blockIdx.x * 3, sa.norm_rows + blockIdx.x);   // (a_w: not kept, see ce_store_row)
 }
 
-__global__ void rows_reduce_kernel(const float* __restrict__ part, int n_rows, int width, float* __restrict__ out0, int n0,
-                                   float* __restrict__ out1) {
+__device__ __forceinline__ void rows_reduce_body(const float* __restrict__ part, int n_rows, int width, float* __restrict__ out0, int n0,
+                                                 float* __restrict__ out1, int e) {
   // out0[e] (e < n0) and out1[e-n0] = sum over rows, fixed order, double accumulation
-  const int e = blockIdx.x;
   double s = 0.0, dummy = 0.0;
   for (int i = threadIdx.x; i < n_rows; i += blockDim.x) s += (double)part[(size_t)i * width + e];
   block_sum2_d(s, dummy);
@@ -515,6 +643,11 @@ __global__ void rows_reduce_kernel(const float* __restrict__ part, int n_rows, i
     if (e < n0) out0[e] = (float)s;
     else if (out1) out1[e - n0] = (float)s;
   }
+}
+
+__global__ void rows_reduce_kernel(const float* __restrict__ part, int n_rows, int width, float* __restrict__ out0, int n0,
+                                   float* __restrict__ out1) {
+  rows_reduce_body(part, n_rows, width, out0, n0, out1, blockIdx.x);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -562,7 +695,7 @@ __global__ void ce_fwd_kernel(const float* __restrict__ logits, const int64_t* _
   }
 }
 
-__global__ void ce_finalize_kernel(const float* __restrict__ part, int n_part, float* __restrict__ loss_out) {
+__device__ __forceinline__ void ce_finalize_body(const float* __restrict__ part, int n_part, float* __restrict__ loss_out) {
   __shared__ double sh[3][4];
   double s[3] = {0.0, 0.0, 0.0};
   for (int i = threadIdx.x; i < n_part; i += blockDim.x) {
@@ -579,6 +712,18 @@ __global__ void ce_finalize_kernel(const float* __restrict__ part, int n_part, f
     loss_out[2] = (float)t[2];
     loss_out[3] = (float)t[0];
   }
+}
+
+__global__ void ce_finalize_kernel(const float* __restrict__ part, int n_part, float* __restrict__ loss_out) {
+  ce_finalize_body(part, n_part, loss_out);
+}
+
+// The two reductions that follow the step kernel and depend on it alone, as one launch: workgroups [0, width) are rows_reduce_kernel's
+// (dW, db), workgroup `width` is ce_finalize_kernel's; each value in the order of the kernel it comes from.
+__global__ void cls_step_tail_kernel(const float* __restrict__ w_part, int n_rows, int width, float* __restrict__ dw, int n0,
+                                     float* __restrict__ db, const float* __restrict__ ce_part, float* __restrict__ loss_out) {
+  if ((int)blockIdx.x == width) ce_finalize_body(ce_part, n_rows, loss_out);
+  else rows_reduce_body(w_part, n_rows, width, dw, n0, db, blockIdx.x);
 }
 
 __global__ void ce_bwd_kernel(const float* __restrict__ logits, const int64_t* __restrict__ target, const float* __restrict__ cw,
@@ -1171,6 +1316,23 @@ static cls_bwd_fn cls_bwd_pick(int cout) {
   return nullptr;
 }
 
+typedef void (*cls_step_fn)(const float*, const float*, const float*, float*, const float*, const float*, float*, float*, int, int, int,
+                            const float*, const float*, int, const int64_t*, const float*, const float*, const float*, const float*, ClsStepArgs);
+
+static cls_step_fn cls_step_pick(int cout) {
+  switch (cout) {
+    case 1: return cls_bwd_kernel<8, 1, true, true, ClsStepArgs>;
+    case 2: return cls_bwd_kernel<8, 2, true, true, ClsStepArgs>;
+    case 3: return cls_bwd_kernel<8, 3, true, true, ClsStepArgs>;
+    case 4: return cls_bwd_kernel<8, 4, true, true, ClsStepArgs>;
+    case 5: return cls_bwd_kernel<8, 5, true, true, ClsStepArgs>;
+    case 6: return cls_bwd_kernel<8, 6, true, true, ClsStepArgs>;
+    case 7: return cls_bwd_kernel<8, 7, true, true, ClsStepArgs>;
+    case 8: return cls_bwd_kernel<8, 8, true, true, ClsStepArgs>;
+  }
+  return nullptr;
+}
+
 // Every refusal that depends on the SHAPE of a record (channel counts, load modes, flags) sits in front of the `query` return: what
 // rcv_op_workspace / the planner accepts, the launch accepts.  Only operand pointers and workspace row counts are checked after it.
 int rcv_launch_small(const rcv_handle* h, const rcv_op* op, hipStream_t s, OpQuery* query) {
@@ -1331,6 +1493,60 @@ int rcv_launch_small(const rcv_handle* h, const rcv_op* op, hipStream_t s, OpQue
       // dW -> p[X1] ([Cout][Cin]), db -> p[X2]
       hipLaunchKernelGGL(rows_reduce_kernel, dim3((int)wrow), dim3(256), 0, s, w_part, g, (int)wrow, (float*)op->p[RCV_P_X1], Cout * Cin,
                          (float*)op->p[RCV_P_X2]);
+      break;
+    }
+    case RCV_OP_CE_NORM: {
+      const int g = reduce_grid(h, (size_t)N * H * W, 256);      // the grid of RCV_OP_CLS_FWD with RCV_F_FUSED_CE: row b is that op's a_w of workgroup b
+      RCV_CHECK_ARG(Cout >= 1 && Cout <= CE_MAX_C, "cross entropy normaliser: %d classes unsupported (max %d)", Cout, CE_MAX_C);
+      RCV_CHECK_ARG(N > 0 && H > 0 && W > 0, "cross entropy normaliser: empty batch");
+      if (query) {
+        snprintf(query->label, sizeof(query->label), "ce_norm");
+        query->n_part = g; query->part_bytes = (size_t)g * sizeof(float);
+        return RCV_OK;
+      }
+      RCV_CHECK_ARG(op->p[RCV_P_IN2] && op->p[RCV_P_PART], "cross entropy normaliser: null operand");
+      RCV_CHECK_ARG(op->i[RCV_I_NPART] == g, "cross entropy normaliser: workspace rows %d != %d", op->i[RCV_I_NPART], g);
+      hipLaunchKernelGGL(ce_norm_kernel, dim3(g), dim3(256), 0, s, (const int64_t*)op->p[RCV_P_IN2], (const float*)op->p[RCV_P_X0], Cout,
+                         (size_t)N * H * W, (float*)op->p[RCV_P_PART]);
+      break;
+    }
+    case RCV_OP_CLS_STEP: {
+      // partial rows as RCV_OP_CLS_BWD (stats [g][2][8], then filter+bias [g][Cout*8+Cout], in p[PART]); loss rows [g][3] in p[IN2_C]
+      const int g = reduce_grid(h, (size_t)N * H * W, 256);
+      const size_t wrow = (size_t)Cout * Cin + Cout;
+      const int mode2 = op->i[RCV_I_AUX0];
+      RCV_CHECK_ARG(Cin == 8 && Cout >= 1 && Cout <= CLS_MAX_OUT, "classifier step: %d -> %d channels unsupported (8 input channels, 1..%d classes)",
+                    Cin, Cout, CLS_MAX_OUT);
+      RCV_CHECK_ARG((op->flags & RCV_F_FUSED_UP) && (op->flags & RCV_F_FUSED_CE) && op->i[RCV_I_STATS] == RCV_STATS_BWD_DEC,
+                    "classifier step: needs the fused decoder input (RCV_F_FUSED_UP), the fused loss (RCV_F_FUSED_CE) and the decoder's statistics kind");
+      RCV_CHECK_ARG(op->i[RCV_I_AUX1] == 0 || op->i[RCV_I_AUX1] == Cin, "classifier step: %d skip channels for %d inputs", op->i[RCV_I_AUX1], Cin);
+      RCV_CHECK_ARG(mode2 == RCV_LOAD_PLAIN || mode2 == RCV_LOAD_AFFINE || mode2 == RCV_LOAD_AFFINE_RELU, "classifier step: skip load mode %d", mode2);
+      if (query) {
+        snprintf(query->label, sizeof(query->label), "cls_step");
+        query->n_part = g;
+        query->part_bytes = (size_t)g * (2 * Cin + wrow) * sizeof(float);
+        return RCV_OK;
+      }
+      const float* r = (const float*)op->p[RCV_P_X3]; const float* rc = (const float*)op->p[RCV_P_X4];
+      RCV_CHECK_ARG(op->p[RCV_P_EPI_AUX] && op->p[RCV_P_EPI_C] && r && (mode2 == RCV_LOAD_PLAIN || rc) && op->p[RCV_P_W] && op->p[RCV_P_IN2] &&
+                    op->p[RCV_P_IN2_AUX], "classifier step: null input operand");
+      RCV_CHECK_ARG(op->p[RCV_P_OUT] && op->p[RCV_P_RESID] && op->p[RCV_P_PART] && op->p[RCV_P_IN2_C] && op->p[RCV_P_IN_C] && op->p[RCV_P_X1] &&
+                    op->p[RCV_P_X5], "classifier step: null output or workspace operand");
+      RCV_CHECK_ARG(op->i[RCV_I_NPART] == g, "classifier step: workspace rows %d != %d", op->i[RCV_I_NPART], g);
+      float* stat_part = (float*)op->p[RCV_P_PART];
+      float* w_part = stat_part + (size_t)g * 2 * Cin;
+      ClsStepArgs sa;
+      sa.logits = (float*)op->p[RCV_P_RESID]; sa.argmax = (uint8_t*)op->p[RCV_P_IN_AUX]; sa.ce_part = (float*)op->p[RCV_P_IN2_C];
+      sa.norm_rows = (const float*)op->p[RCV_P_IN_C]; sa.n_rows = g;
+      // (no `up` / dlogits / loss_out operands: the decoder's raw tensors are the input, the loss gradient is formed in the kernel)
+      hipLaunchKernelGGL(cls_step_pick(Cout), dim3(g), dim3(256), 0, s, (const float*)nullptr, (const float*)nullptr, (const float*)op->p[RCV_P_W],
+                         (float*)op->p[RCV_P_OUT], (const float*)op->p[RCV_P_EPI_AUX], (const float*)op->p[RCV_P_EPI_C], stat_part, w_part, N, H * W,
+                         (int)RCV_STATS_BWD_DEC, r, rc, mode2, (const int64_t*)op->p[RCV_P_IN2], (const float*)op->p[RCV_P_X0],
+                         (const float*)op->p[RCV_P_BIAS], (const float*)nullptr, (const float*)op->p[RCV_P_IN2_AUX], sa);
+      RCV_HIP(hipGetLastError());
+      // dW -> p[X1], db -> p[X2], loss_out -> p[X5]: one launch, the extra workgroup finalises the loss
+      hipLaunchKernelGGL(cls_step_tail_kernel, dim3((int)wrow + 1), dim3(256), 0, s, (const float*)w_part, g, (int)wrow, (float*)op->p[RCV_P_X1],
+                         Cout * Cin, (float*)op->p[RCV_P_X2], (const float*)sa.ce_part, (float*)op->p[RCV_P_X5]);
       break;
     }
     case RCV_OP_CE_FWD: {

@@ -1247,6 +1247,11 @@ class Engine:
             rch = i[L.RCV_I_AUX1] if op.flags & L.F_FUSED_UP else 0      # (LabelProp's tail: a narrower skip, and its gradient written too)
             src = cin + ((rch or cin) if op.flags & L.F_FUSED_UP else 0)
             nbytes = 4.0 * px * (src + cin + rch + (0 if op.flags & L.F_FUSED_CE else cout)) + (px * 8.0 if op.flags & L.F_FUSED_CE else 0.0)
+        elif k == L.OP_CLS_STEP:
+            flops = 2.0 * 3 * cin * cout * px        # logits + data gradient + filter gradient
+            nbytes = 4.0 * px * (cin + (i[L.RCV_I_AUX1] or cin) + cout + cin) + px * 9.0      # t, skip, logits, d_up; label + arg-max
+        elif k == L.OP_CE_NORM:
+            nbytes = px * 8.0
         elif k in (L.OP_CE_FWD, L.OP_DICE_FWD):
             nbytes = px * (4.0 * cout + 8 + 1)
         elif k in (L.OP_CE_BWD, L.OP_DICE_BWD):
@@ -1287,6 +1292,8 @@ class Engine:
         plan, _inputs = self._last
         stream = torch.cuda.current_stream(self.device).cuda_stream
         ce = plan.ce if (with_loss and plan.ce) else None
+        if ce:
+            ce = ce.get("ran") or ce             # the lists the last forward_ce really ran (two classifier records, or the one-record step form)
         lists = [ce["fwd"] if ce else plan.fwd]
         bwd = ce["bwd"] if ce else plan.bwd
         if bwd is not None and bwd.n:
@@ -1376,7 +1383,7 @@ class Engine:
             best = min(range(len(ms)), key=lambda k: ms[k])
             plan.side_mode = self.SIDE_MODES[best if ms[best] < 0.97 * ms[0] else 0]
         plan.side_on = plan.side_mode != "off"
-        for lst in (plan.bwd, plan.ce["bwd"] if plan.ce else None):
+        for lst in (plan.bwd, plan.ce["bwd"] if plan.ce else None, plan.ce["step"]["bwd"] if plan.ce and plan.ce["step"] else None):
             if lst is not None:
                 self._set_side(lst, plan.side_mode)
 
@@ -1431,11 +1438,46 @@ class Engine:
         plan.ce = {"fwd": L.OpList(fops), "bwd": L.OpList(bops), "kf": kf[0], "kb": kb[0], "loss_out": loss_out, "argmax": argmax}
         plan.ce["fwd"].labels(self.handle)          # (plan-time validation, as in _build)
         plan.ce["bwd"].labels(self.handle)
+        plan.ce["step"] = self._cls_step_variant(plan, fops, bops, f, b)
         return plan.ce
 
-    def forward_ce(self, inputs: Sequence[torch.Tensor], targets: torch.Tensor, weight: Optional[torch.Tensor]):
+    def _cls_step_variant(self, plan: Plan, fops, bops, f: L.RcvOp, b: L.RcvOp):
+        """Third variant, for a forward that a backward follows at once (Trainer.step): the two classifier records of the fused-loss
+        lists meet in ONE record, RCV_OP_CLS_STEP, which reads t, the skip tensor and the targets once.  The forward list ends in the
+        normaliser pre-pass (RCV_OP_CE_NORM) and that record; the backward list keeps its length and indices with RCV_OP_NOP in slot
+        0, so bwd_marks, the side-stream flags and every index into the list stay valid.  The pre-pass sits directly in front of the
+        fused record: on one stream its cost is the same anywhere in the list, and there no index of the forward list moves.  The
+        library's side stream was NOT tried for it (rcv_run joins that stream at the end of the list, behind the record that needs
+        the rows: it would take a join point inside the list); neither was the head of the list measured against this place.
+        None (only the two-record lists exist) for LabelProp's tail or a residual on the gradient."""
+        if f.kind != L.OP_CLS_FWD or b.kind != L.OP_CLS_BWD or (b.flags & L.F_RESID):
+            return None
+        if any((is_bwd, idx) in ((False, len(fops) - 1), (True, 0)) for slots in plan.input_slots for (is_bwd, idx, _slot) in slots):
+            return None                              # (a graph input bound into the records this variant replaces: not a fused classifier)
+        if f.i[L.RCV_I_CIN] != 8 or b.i[L.RCV_I_STATS] != L.STATS_BWD_DEC or f.i[L.RCV_I_AUX1] not in (0, 8):
+            return None
+        norm = L.make_op(L.OP_CE_NORM, 0, n=f.i[L.RCV_I_N], h=f.i[L.RCV_I_H], w=f.i[L.RCV_I_W], cout=f.i[L.RCV_I_COUT])
+        self._workspace(plan, norm)
+        st = L.RcvOp.from_buffer_copy(b)            # slots as the backward record; the forward's outputs in slots it leaves free
+        st.kind = L.OP_CLS_STEP
+        st.p[L.RCV_P_RESID] = f.p[L.RCV_P_OUT]      # logits
+        st.p[L.RCV_P_IN_AUX] = f.p[L.RCV_P_X2]      # arg-max
+        st.p[L.RCV_P_IN2_C] = f.p[L.RCV_P_PART]     # loss partial rows (same row count: one grid)
+        st.p[L.RCV_P_IN_C] = norm.p[L.RCV_P_PART]
+        if f.i[L.RCV_I_NPART] != st.i[L.RCV_I_NPART] or norm.i[L.RCV_I_NPART] != st.i[L.RCV_I_NPART]:
+            return None
+        sf = L.OpList([L.RcvOp.from_buffer_copy(o) for o in fops[:-1]] + [norm, st])
+        sb = L.OpList([L.make_op(L.OP_NOP, 0)] + [L.RcvOp.from_buffer_copy(o) for o in bops[1:]])
+        sf.labels(self.handle)
+        sb.labels(self.handle)
+        return {"fwd": sf, "bwd": sb, "knorm": sf.n - 2, "kstep": sf.n - 1}
+
+    def forward_ce(self, inputs: Sequence[torch.Tensor], targets: torch.Tensor, weight: Optional[torch.Tensor], step: bool = False):
         """Training forward with CrossEntropyLoss2d(weight) fused into the classifier op.  Returns (logits, loss_out[4], argmax) --
-        loss_out as RCV_OP_CE_FWD: [loss, sum_w, #correct, sum_w*nll] -- or None when this graph has no such fast path."""
+        loss_out as RCV_OP_CE_FWD: [loss, sum_w, #correct, sum_w*nll] -- or None when this graph has no such fast path.
+        step: the caller runs backward_ce right after this call (Trainer.step); the classifier's backward is then done by the
+        forward's last record where that variant exists (_cls_step_variant) -- the gradients of the classifier and of the decoder
+        output are already written when this call's work completes, backward_ce does the rest."""
         for t in inputs:
             if t.dtype != torch.float32 or not t.is_contiguous():
                 raise L.RcvError("engine inputs must be contiguous float32 tensors")
@@ -1451,10 +1493,21 @@ class Engine:
                 (ce["bwd"] if is_bwd else ce["fwd"]).arr[idx].p[slot] = t.data_ptr()
                 (plan.bwd if is_bwd else plan.fwd).arr[idx].p[slot] = t.data_ptr()      # keeps the plain lists usable (profile_last)
         wptr = None if weight is None else weight.data_ptr()
-        for op in (ce["fwd"].arr[ce["kf"]], ce["bwd"].arr[ce["kb"]]):
+        st = ce["step"] if step else None
+        if st:
+            lists = st
+            for k, t in enumerate(inputs):
+                for (is_bwd, idx, slot) in plan.input_slots[k]:      # (never the records the variant replaced: they read no graph input)
+                    (st["bwd"] if is_bwd else st["fwd"]).arr[idx].p[slot] = t.data_ptr()
+            loss_ops = (st["fwd"].arr[st["knorm"]], st["fwd"].arr[st["kstep"]])
+        else:
+            lists = ce
+            loss_ops = (ce["fwd"].arr[ce["kf"]], ce["bwd"].arr[ce["kb"]])
+        for op in loss_ops:
             op.p[L.RCV_P_IN2] = targets.data_ptr()
             op.p[L.RCV_P_X0] = wptr
-        ce["fwd"].run(self.handle, torch.cuda.current_stream(self.device).cuda_stream)
+        ce["ran"] = lists
+        lists["fwd"].run(self.handle, torch.cuda.current_stream(self.device).cuda_stream)
         self.params_dirty = True
         nbt = [m.num_batches_tracked for m in self.bn_modules if m.num_batches_tracked is not None]
         if nbt:
@@ -1467,5 +1520,5 @@ class Engine:
     def backward_ce(self):
         """Backward of the loss produced by the last forward_ce (d loss = 1): fills the flat gradient buffer."""
         plan, _inputs = self._last
-        self._run_backward(plan, plan.ce["bwd"])
+        self._run_backward(plan, plan.ce["ran"]["bwd"])
         return plan

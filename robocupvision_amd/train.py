@@ -109,6 +109,8 @@ class Trainer:
         self.metrics = torch.zeros(4, dtype=torch.float64, device=dev)     # loss, reg, correct, steps
         self.distributed = distributed
         self.fuse_loss = fuse_loss and not os.environ.get("RCV_NO_FUSED_LOSS")
+        # RCV_NO_FUSED_CLS_STEP=1: the classifier's forward + loss and its backward stay two records (the A/B switch of RCV_OP_CLS_STEP)
+        self.fuse_cls_step = not os.environ.get("RCV_NO_FUSED_CLS_STEP")
         self.world = 1
         self.exchange: Optional[GradExchange] = None
         self.force_collectives = bool(int(os.environ.get("RCV_FORCE_COLLECTIVES", "0")))   # exercise the path at world size 1
@@ -167,7 +169,8 @@ class Trainer:
             if w is not None and w.device != imgs.device:
                 w = w.to(imgs.device)
                 crit.weight = w
-            fused = eng.forward_ce(ins, targets.to(torch.int64).contiguous(), w)
+            # (step=True: backward_ce follows at once, so the classifier's forward, loss and backward run as one record where built)
+            fused = eng.forward_ce(ins, targets.to(torch.int64).contiguous(), w, step=self.fuse_cls_step)
         if fused is not None:
             pred, out, argmax = fused
             crit.last_stats, crit.last_argmax = out, argmax
