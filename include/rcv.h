@@ -167,7 +167,7 @@ enum {
                              * float[i[NPART]] (rcv_op_workspace), one value per workgroup.  Grid, pixel -> thread mapping and summation order
                              * are those of RCV_OP_CLS_FWD with RCV_F_FUSED_CE: row b is bit for bit column 1 of that op's partial row b, and
                              * the rows summed in RCV_OP_CE_FWD's finalisation order give its loss_out[1].  Runs ahead of RCV_OP_CLS_STEP   */
-  RCV_OP_CLS_STEP = 44       /* the training step's turn from forward to backward at the fused 1x1 classifier: RCV_OP_CLS_FWD and RCV_OP_CLS_BWD,
+  RCV_OP_CLS_STEP = 44,      /* the training step's turn from forward to backward at the fused 1x1 classifier: RCV_OP_CLS_FWD and RCV_OP_CLS_BWD,
                              * both with RCV_F_FUSED_UP | RCV_F_FUSED_CE, in ONE pass over t, the skip tensor and the targets, then one launch
                              * for the fixed-order reductions (dW, db and the loss).  8 input channels, 1..8 classes.  Slots exactly as
                              * RCV_OP_CLS_BWD with both flags (required; i[STATS] = RCV_STATS_BWD_DEC required): p[EPI_AUX] = t, p[EPI_C] = its
@@ -178,7 +178,28 @@ enum {
                              * loss_out (WRITTEN here, as RCV_OP_CE_FWD writes it), p[IN_C] = the float[i[NPART]] rows of an RCV_OP_CE_NORM
                              * record over the same targets and weights, run before this one.  Every output and every partial row is bit
                              * for bit what the two records write                                                                      */
+  RCV_OP_PRUNE = 45          /* the magnitude-pruning mask builders (model.py:45-57 pruneModelNew, :621-642 pruneModel, :644-672 pruneModel2) for
+                             * every weight tensor of a model in ONE launch (rcv_prune; csrc/prune.hip): p[IN] = rcv_prune_job[i[COUNT]] in
+                             * device memory, i[AUX0] = the rule (RCV_PRUNE_*).  One workgroup per job, integer counts only: nothing is reduced
+                             * across workgroups and no result depends on scheduling.  The weights are zeroed in place, the masks and the
+                             * result rows of the jobs are written                                                                     */
 };
+
+/* i[RCV_I_AUX0] of RCV_OP_PRUNE: how the threshold of a tensor is chosen */
+enum {
+  RCV_PRUNE_MAX_RATIO = 0,   /* pruneModelNew: thresh = fp32(max|w| * fp32(ratio)); zero |w| < thresh; mask = |w| < thresh                   */
+  RCV_PRUNE_STD_SEARCH = 1,  /* pruneModel: thresh starts at the sample standard deviation (float64 accumulation, two passes, rounded to fp32)
+                              * and is stepped by fp32(1.025) / fp32(0.975) until lower <= 100 * #(|w| < thresh) / #(w != 0) <= upper; at most
+                              * RCV_PRUNE_MAX_ITER steps (the reference's loop need not terminate)                                      */
+  RCV_PRUNE_SMALLEST_K = 2   /* pruneModel2: zero the `amount` smallest |w| (exact radix select on the bit pattern; among equal magnitudes at
+                              * the boundary the LOWEST flat indices go: torch.topk leaves that choice open); mask = (w == 0) afterwards  */
+};
+#define RCV_PRUNE_MAX_ITER 4096
+/* rcv_prune_job.result[3] */
+#define RCV_PRUNE_ST_OK       0
+#define RCV_PRUNE_ST_NO_END   1   /* rule 1: the search did not settle within RCV_PRUNE_MAX_ITER steps; the tensor is left untouched  */
+#define RCV_PRUNE_ST_ALL_ZERO 2   /* rule 1: no non-zero weight (the reference's ZeroDivisionError); untouched                          */
+#define RCV_PRUNE_ST_BAD_JOB  3   /* a job rcv_prune_check refuses reached the device; untouched                                       */
 
 /* how an operand is produced from memory while it is staged (rcv_op.i[RCV_I_INMODE] etc.) */
 enum {
@@ -340,6 +361,20 @@ typedef struct rcv_reduce_job {
   int32_t nsplit, CB, CA, first_block;
 } rcv_reduce_job;
 
+/* One row of the RCV_OP_PRUNE job table (device memory): one weight tensor.  `w` needs 4-byte alignment only (a view into the engine's
+ * flat parameter buffer starts anywhere), `mask` none.  The kernel fills `thresh` and `result`; a caller reads the whole table back
+ * in one copy. */
+typedef struct rcv_prune_job {
+  float*   w;          /* n weights, zeroed in place                                                                                 */
+  uint8_t* mask;       /* n bytes out: 1 = pruned                                                                                    */
+  int64_t  n;
+  int64_t  amount;     /* rule 2: how many to zero, 0 <= amount <= n (int(n * r), computed by the host as model.py:649-660)          */
+  double   lower, upper;   /* rule 1: the window in per cent                                                                         */
+  float    ratio;      /* rule 0                                                                                                     */
+  float    thresh;     /* out: the threshold used (rule 2: the selected boundary magnitude, 0 when amount == 0)                      */
+  int64_t  result[4];  /* out: { rules 0 / 1: #(|w| < thresh), rule 2: #zeroed by this call; #(w != 0) before; search steps; status } */
+} rcv_prune_job;
+
 /* ------------------------------------------------------------------------------------------ */
 /* Named entry points (each = fill one record + rcv_run).  Reference call sites they replace:  */
 /* ------------------------------------------------------------------------------------------ */
@@ -462,6 +497,24 @@ int rcv_bnn_head_bwd(rcv_handle* h, const rcv_op* op, void* stream);
  * p -= lr*buf.  lr_elem (may be NULL) gives a per-element learning rate (0 = parameter without a gradient: untouched). */
 int rcv_sgd_step(rcv_handle* h, float* param, const float* grad, float* momentum_buf, const float* lr_elem /*may be NULL*/,
                  int64_t n, float lr, float momentum, float weight_decay, int step, float grad_scale, void* stream);
+
+/* The same with the prune mask of trainer.py:220-226 / labelPropTrain.py:201-206 / pruner.py:196-202 (`param.grad[indices] = 0` between
+ * backward and optimizer.step()): uint8 per element, non-zero = the stored gradient counts as 0, g = weight_decay*p.  The momentum
+ * buffer is not masked (a carried-over buffer keeps moving a pruned weight, as under torch.optim.SGD).  As an op record the mask is
+ * p[RCV_P_X5], the slot RCV_OP_ADAM_L1 uses.  NULL: bit for bit rcv_sgd_step. */
+int rcv_sgd_step_pruned(rcv_handle* h, float* param, const float* grad, float* momentum_buf, const float* lr_elem /*may be NULL*/,
+                        const uint8_t* prune_mask /*may be NULL*/, int64_t n, float lr, float momentum, float weight_decay, int step,
+                        float grad_scale, void* stream);
+
+/* The mask builders of the reference's prune stage for a whole model in one launch (RCV_OP_PRUNE): pruneModelNew (model.py:45-57, rule
+ * RCV_PRUNE_MAX_RATIO), pruneModel (model.py:621-642, RCV_PRUNE_STD_SEARCH) and pruneModel2 (model.py:644-672, RCV_PRUNE_SMALLEST_K) --
+ * per tensor two or three `.item()` host syncs in the reference (two per step of pruneModel's search), none here.  `jobs` is DEVICE
+ * memory, one row per parameter with dim() > 1; the rows' `thresh` / `result` are outputs (read them back after the stream has run:
+ * a status != 0 is that tensor's refusal).  rcv_prune_check validates the same table in HOST memory before it is uploaded and refuses
+ * what the reference refuses before it computes anything: amount > n (torch.topk's error), n < 2 under rule 1 (std is NaN), and
+ * null / misaligned pointers, n outside [1, 2^31), a ratio or window that is not finite.  Neither call synchronises. */
+int rcv_prune_check(const rcv_prune_job* host_jobs, int n_jobs, int rule);
+int rcv_prune(rcv_handle* h, rcv_prune_job* jobs, int n_jobs, int rule, void* stream);
 
 /* As an op record, p[RCV_P_IN_AUX] (may be NULL) is a device int32 holding the 1-based step number: it overrides `step` (the
  * bias corrections are then formed on the device), so that a captured graph of the whole training step can be replayed.

@@ -28,6 +28,10 @@ OP_CLS_LABEL = 37           # classifier tail -> uint8 class map (+ colour image
 OP_FRAME_PREP = 38          # OP_BATCH_PREP's validation form for frames without labels (rcv.h RCV_OP_FRAME_PREP)
 OP_BNN_STAGE_FWD, OP_BNN_STAGE_BWD, OP_BNN_HEAD_FWD, OP_BNN_HEAD_BWD = 39, 40, 41, 42      # BNN-L / BNN-M-C stages and head (rcv.h, csrc/bnn.hip)
 OP_CE_NORM, OP_CLS_STEP = 43, 44     # the classifier's forward + loss + backward in one pass, and its normaliser pre-pass (rcv.h, csrc/small_kernels.hip)
+OP_PRUNE = 45               # the three mask builders of the prune stage, one workgroup per weight tensor (rcv.h RCV_OP_PRUNE, csrc/prune.hip)
+PRUNE_MAX_RATIO, PRUNE_STD_SEARCH, PRUNE_SMALLEST_K = range(3)      # i[AUX0] of OP_PRUNE: pruneModelNew / pruneModel / pruneModel2
+PRUNE_MAX_ITER = 4096
+PRUNE_ST_OK, PRUNE_ST_NO_END, PRUNE_ST_ALL_ZERO, PRUNE_ST_BAD_JOB = range(4)
 CLS_LABEL_FEATURES, CLS_LABEL_LOGITS, CLS_LABEL_CLASSMAP = range(3)      # i[INMODE] of OP_CLS_LABEL: the source form
 
 LOAD_PLAIN, LOAD_AFFINE, LOAD_GRAD_ENC, LOAD_GRAD_DEC, LOAD_NCHW, LOAD_AFFINE_RELU = range(6)
@@ -55,6 +59,11 @@ class RcvReduceJob(C.Structure):      # struct rcv_reduce_job of include/rcv.h
                 ("CA", C.c_int32), ("first_block", C.c_int32)]
 
 
+class RcvPruneJob(C.Structure):       # struct rcv_prune_job of include/rcv.h
+    _fields_ = [("w", C.c_void_p), ("mask", C.c_void_p), ("n", C.c_int64), ("amount", C.c_int64), ("lower", C.c_double),
+                ("upper", C.c_double), ("ratio", C.c_float), ("thresh", C.c_float), ("result", C.c_int64 * 4)]
+
+
 EXPORTS = [
     "rcv_create", "rcv_destroy", "rcv_last_error", "rcv_version", "rcv_num_cus", "rcv_op_workspace", "rcv_run",
     "rcv_run_timed", "rcv_op_kernel_label", "rcv_run_ex", "rcv_join_side",
@@ -63,6 +72,7 @@ EXPORTS = [
     "rcv_dice_fwd", "rcv_dice_bwd", "rcv_sgd_step", "rcv_create_planner", "rcv_adam_l1_step_pruned", "rcv_op_filter_layout",
     "rcv_object_match", "rcv_labelprop_batch", "rcv_batch_prep", "rcv_frame_prep", "rcv_cls_label", "rcv_colorize",
     "rcv_bnn_stage_fwd", "rcv_bnn_stage_bwd", "rcv_bnn_head_fwd", "rcv_bnn_head_bwd",
+    "rcv_sgd_step_pruned", "rcv_prune_check", "rcv_prune",
 ]
 
 
@@ -109,6 +119,10 @@ def load():
         lib.rcv_frame_prep.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 3
         lib.rcv_cls_label.argtypes = [C.c_void_p] * 4 + [C.c_int] * 5 + [C.c_void_p] * 4
         lib.rcv_colorize.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 3
+        lib.rcv_sgd_step.argtypes = [C.c_void_p] * 5 + [C.c_int64, C.c_float, C.c_float, C.c_float, C.c_int, C.c_float, C.c_void_p]
+        lib.rcv_sgd_step_pruned.argtypes = [C.c_void_p] * 6 + [C.c_int64, C.c_float, C.c_float, C.c_float, C.c_int, C.c_float, C.c_void_p]
+        lib.rcv_prune_check.argtypes = [C.POINTER(RcvPruneJob), C.c_int, C.c_int]
+        lib.rcv_prune.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         for name in ("rcv_conv3x3", "rcv_convT3x3s2", "rcv_wgrad3x3", "rcv_bnn_stage_fwd", "rcv_bnn_stage_bwd", "rcv_bnn_head_fwd",
                      "rcv_bnn_head_bwd"):
             getattr(lib, name).argtypes = [C.c_void_p, C.POINTER(RcvOp), C.c_void_p]

@@ -124,6 +124,8 @@ static int dispatch(const rcv_handle* h, const rcv_op* op, hipStream_t s, OpQuer
     case RCV_OP_BNN_HEAD_FWD:
     case RCV_OP_BNN_HEAD_BWD:
       return rcv_launch_bnn(h, op, s, q);
+    case RCV_OP_PRUNE:
+      return rcv_launch_prune(h, op, s, q);
     case RCV_OP_NOP:
       if (q) { snprintf(q->label, sizeof(q->label), "nop"); q->n_part = 0; q->n_split = 0; q->part_bytes = 0; }
       return RCV_OK;
@@ -468,6 +470,49 @@ int rcv_sgd_step(rcv_handle* h, float* param, const float* grad, float* momentum
   op.i[RCV_I_COUNT] = (int32_t)(uint32_t)n; op.i[RCV_I_AUX0] = step;
   op.f[0] = lr; op.f[1] = momentum; op.f[2] = weight_decay; op.f[5] = grad_scale;
   op.p[RCV_P_IN] = param; op.p[RCV_P_IN2] = (void*)grad; op.p[RCV_P_X0] = momentum_buf; op.p[RCV_P_X2] = (void*)lr_elem;
+  return rcv_run(h, &op, 1, stream);
+}
+
+int rcv_sgd_step_pruned(rcv_handle* h, float* param, const float* grad, float* momentum_buf, const float* lr_elem,
+                        const uint8_t* prune_mask, int64_t n, float lr, float momentum, float weight_decay, int step, float grad_scale,
+                        void* stream) {
+  RCV_CHECK_ARG(n > 0 && n < ((int64_t)1 << 32), "rcv_sgd_step_pruned: n out of range");
+  rcv_op op;
+  memset(&op, 0, sizeof(op));
+  op.kind = RCV_OP_SGD;
+  op.i[RCV_I_COUNT] = (int32_t)(uint32_t)n; op.i[RCV_I_AUX0] = step;
+  op.f[0] = lr; op.f[1] = momentum; op.f[2] = weight_decay; op.f[5] = grad_scale;
+  op.p[RCV_P_IN] = param; op.p[RCV_P_IN2] = (void*)grad; op.p[RCV_P_X0] = momentum_buf; op.p[RCV_P_X2] = (void*)lr_elem;
+  op.p[RCV_P_X5] = (void*)prune_mask;
+  return rcv_run(h, &op, 1, stream);
+}
+
+int rcv_prune_check(const rcv_prune_job* jobs, int n_jobs, int rule) {
+  RCV_CHECK_ARG(rule >= RCV_PRUNE_MAX_RATIO && rule <= RCV_PRUNE_SMALLEST_K, "rcv_prune: rule %d unknown (0 = pruneModelNew, 1 = pruneModel, 2 = pruneModel2)", rule);
+  RCV_CHECK_ARG(jobs && n_jobs > 0 && n_jobs <= 65535, "rcv_prune: %d jobs (1..65535) or a null table", n_jobs);
+  for (int j = 0; j < n_jobs; ++j) {
+    const rcv_prune_job& b = jobs[j];
+    RCV_CHECK_ARG(b.w && b.mask, "rcv_prune: job %d: null pointer", j);
+    RCV_CHECK_ARG(((uintptr_t)b.w & 3) == 0, "rcv_prune: job %d: weights are not 4-byte aligned", j);
+    RCV_CHECK_ARG(b.n >= 1 && b.n < ((int64_t)1 << 31), "rcv_prune: job %d: %lld elements (1 .. 2^31 - 1)", j, (long long)b.n);
+    if (rule == RCV_PRUNE_MAX_RATIO) RCV_CHECK_ARG(b.ratio == b.ratio && b.ratio - b.ratio == 0.f, "rcv_prune: job %d: ratio is not finite", j);
+    if (rule == RCV_PRUNE_STD_SEARCH) {
+      RCV_CHECK_ARG(b.n >= 2, "rcv_prune: job %d: the standard deviation of %lld element is NaN (pruneModel needs two)", j, (long long)b.n);
+      RCV_CHECK_ARG(b.lower - b.lower == 0.0 && b.upper - b.upper == 0.0, "rcv_prune: job %d: the window [lower, upper] is not finite", j);
+    }
+    if (rule == RCV_PRUNE_SMALLEST_K)
+      RCV_CHECK_ARG(b.amount >= 0 && b.amount <= b.n, "rcv_prune: job %d: amount %lld out of range for %lld elements (torch.topk: k not in range)", j,
+                    (long long)b.amount, (long long)b.n);
+  }
+  return RCV_OK;
+}
+
+int rcv_prune(rcv_handle* h, rcv_prune_job* jobs, int n_jobs, int rule, void* stream) {
+  rcv_op op;
+  memset(&op, 0, sizeof(op));
+  op.kind = RCV_OP_PRUNE;
+  op.i[RCV_I_COUNT] = n_jobs; op.i[RCV_I_AUX0] = rule;
+  op.p[RCV_P_IN] = jobs;
   return rcv_run(h, &op, 1, stream);
 }
 

@@ -1159,13 +1159,15 @@ __global__ void adam_l1_kernel(float* __restrict__ p, const float* __restrict__ 
 }
 
 // torch.optim.SGD with momentum and weight decay (trainer.py:176-178), dampening 0, no nesterov
+// prune (may be NULL): the mask of trainer.py:220-226 / pruner.py:196-202, `param.grad[indices] = 0` between backward and step(): the stored
+// gradient of a masked element counts as 0 (the weight-decay term and the momentum buffer are what torch.optim.SGD makes of that)
 __global__ void sgd_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf, const float* __restrict__ lr_elem,
-                           size_t n, float lr, float momentum, float wd, float grad_scale, int first) {
+                           const uint8_t* __restrict__ prune, size_t n, float lr, float momentum, float wd, float grad_scale, int first) {
   for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (size_t)gridDim.x * blockDim.x) {
     const float step = lr_elem ? lr_elem[e] : lr;
     if (step == 0.f) continue;                       // parameter outside the graph (grad None in PyTorch): untouched
     const float pv = p[e];
-    const float gr = fmaf(wd, pv, g[e] * grad_scale);
+    const float gr = fmaf(wd, pv, (prune && prune[e]) ? 0.f : g[e] * grad_scale);
     const float b = first ? gr : fmaf(momentum, buf[e], gr);
     buf[e] = b;
     p[e] = pv - step * b;
@@ -1650,8 +1652,8 @@ int rcv_launch_small(const rcv_handle* h, const rcv_op* op, hipStream_t s, OpQue
       const size_t n = (size_t)(uint32_t)op->i[RCV_I_COUNT];
       RCV_CHECK_ARG(op->p[RCV_P_IN] && op->p[RCV_P_IN2] && op->p[RCV_P_X0] && n > 0 && op->i[RCV_I_AUX0] >= 1, "sgd: bad operand");
       hipLaunchKernelGGL(sgd_kernel, dim3(stream_grid(h, n, 256)), dim3(256), 0, s, (float*)op->p[RCV_P_IN], (const float*)op->p[RCV_P_IN2],
-                         (float*)op->p[RCV_P_X0], (const float*)op->p[RCV_P_X2], n, op->f[0], op->f[1], op->f[2], op->f[5],
-                         op->i[RCV_I_AUX0] == 1 ? 1 : 0);
+                         (float*)op->p[RCV_P_X0], (const float*)op->p[RCV_P_X2], (const uint8_t*)op->p[RCV_P_X5], n, op->f[0], op->f[1],
+                         op->f[2], op->f[5], op->i[RCV_I_AUX0] == 1 ? 1 : 0);
       break;
     }
     case RCV_OP_MEMSET: {

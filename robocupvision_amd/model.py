@@ -25,7 +25,7 @@ from .bnn import BNNL, BNNMC      # the reference's model.py:569-619 (kernels: c
 
 __all__ = ["ROBO_UNet", "CrossEntropyLoss2d", "DiceLoss", "PB_FCN", "PB_FCN_2", "LabelProp", "Conv", "Pool", "LevelDown",
            "labelprop_batch", "upSampleTransposeConv", "UltClassifier", "ConvPoolSimple", "ConvPool", "DownSampler", "Classifier", "pruneModelNew",
-           "count_zero_weights", "getParamSize", "BNNL", "BNNMC"]
+           "count_zero_weights", "getParamSize", "BNNL", "BNNMC", "pruneModel", "pruneModel2"]
 
 
 # ------------------------------------------------------------------------------------------
@@ -688,18 +688,163 @@ def labelprop_batch(images, labels, num_class=5):
 # ------------------------------------------------------------------------------------------
 # host-side helpers of the module surface (model.py:45-74) -- scalar bookkeeping, not hot path
 # ------------------------------------------------------------------------------------------
+class PruneError(L.RcvError, ZeroDivisionError):
+    """A tensor the prune rules cannot handle.  The reference dies with a ZeroDivisionError on a tensor without a non-zero weight
+    (model.py:52, 629): callers that catch that keep working."""
+
+
+def _prune_on_device(big, rule, ratio=0.0, lower=0.0, upper=0.0, amounts=None):
+    """RCV_OP_PRUNE over the weight tensors ``big`` (device, fp32, contiguous): one launch, one workgroup per tensor, and ONE
+    device-to-host copy of the job table at the end -- the only synchronisation of the call.  Returns (masks, rows): the masks are
+    views of one uint8 buffer.  When the tensors are views of one flat buffer (the engine's layout) that buffer mirrors it element
+    for element, so the optimizers take it as their flat prune mask as it is (optim._adopt_flat_mask)."""
+    import ctypes as C
+    dev = big[0].device
+    datas = []
+    for k, p in enumerate(big):
+        d = p.data
+        if d.device != dev or d.dtype != torch.float32 or not d.is_contiguous():
+            raise L.RcvError("prune: parameter %d must be a contiguous fp32 tensor on %s (got %s, %s)" % (k, dev, d.dtype, d.device))
+        datas.append(d)
+    base = datas[0].untyped_storage().data_ptr()
+    flat = all(d.untyped_storage().data_ptr() == base for d in datas)
+    if flat:
+        total = datas[0].untyped_storage().nbytes() // 4
+        offs = [(d.data_ptr() - base) // 4 for d in datas]
+    else:
+        offs, total = [], 0
+        for d in datas:
+            offs.append(total)
+            total += d.numel()
+    buf = torch.zeros(total, dtype=torch.uint8, device=dev)
+    table = (L.RcvPruneJob * len(big))()
+    for k, d in enumerate(datas):
+        j = table[k]
+        j.w, j.mask, j.n = d.data_ptr(), buf.data_ptr() + offs[k], d.numel()
+        j.amount = 0 if amounts is None else amounts[k]
+        j.lower, j.upper, j.ratio = float(lower), float(upper), float(ratio)
+    lib = L.load()
+    if lib.rcv_prune_check(table, len(big), rule) != 0:
+        raise L.RcvError("librcv rcv_prune refused (parameter index = job index): %s" % lib.rcv_last_error().decode("utf-8", "replace"))
+    h = L.handle(dev.index if dev.index is not None else torch.cuda.current_device())
+    jobs = torch.frombuffer(bytearray(bytes(table)), dtype=torch.uint8).to(dev)
+    with torch.cuda.device(dev):
+        L.check(lib.rcv_prune(h, jobs.data_ptr(), len(big), rule, torch.cuda.current_stream(dev).cuda_stream), "rcv_prune")
+    rows = (L.RcvPruneJob * len(big)).from_buffer_copy(jobs.cpu().numpy().tobytes())
+    _prune_check_rows(rows, rule)
+    masks = [buf[o:o + d.numel()].view(d.shape).view(torch.bool) for o, d in zip(offs, datas)]
+    return masks, rows
+
+
+def _prune_check_rows(rows, rule):
+    """The per-tensor refusals only the data can decide (rcv_prune_job.result[3])."""
+    for k, r in enumerate(rows):
+        st = int(r.result[3])
+        if st == L.PRUNE_ST_NO_END:
+            raise L.RcvError("pruneModel: parameter %d: the threshold search did not settle in %d steps (the window [lower, upper] is "
+                             "narrower than one 2.5 %% step of the threshold moves the pruned share); the tensor is untouched"
+                             % (k, L.PRUNE_MAX_ITER))
+        if st == L.PRUNE_ST_ALL_ZERO or (rule != L.PRUNE_SMALLEST_K and st == L.PRUNE_ST_OK and int(r.result[1]) == 0):
+            raise PruneError("prune: parameter %d has no non-zero weight (float division by zero in the reference)" % k)
+        if st != L.PRUNE_ST_OK:
+            raise L.RcvError("prune: parameter %d: the job was refused on the device (status %d)" % (k, st))
+
+
 def pruneModelNew(params, ratio=0.01):
-    """Magnitude pruning masks (model.py:45-57): zero weights below ratio*max|w|, return the masks."""
+    """Magnitude pruning masks (model.py:45-57): zero weights below ratio*max|w|, return the masks.  Parameters on the HIP device
+    are handled by one RCV_OP_PRUNE launch (rule 0) and one copy back, instead of three host syncs per tensor."""
+    big = [p for p in params if p.dim() > 1]
+    if big and big[0].device.type == "cuda":
+        masks, rows = _prune_on_device(big, L.PRUNE_MAX_RATIO, ratio=ratio)
+        for r in rows:
+            print("Pruned %f%% of the weights" % (float(r.result[0]) / float(r.result[1]) * 100))
+        return masks
     indices = []
-    for param in params:
-        if param.dim() > 1:
-            with torch.no_grad():
-                thresh = torch.max(torch.abs(param)) * ratio
-                mask = torch.abs(param) < thresh
-                print("Pruned %f%% of the weights" % (float(torch.sum(mask)) / float(torch.sum(param != 0)) * 100))
-                param[mask] = 0
-                indices.append(torch.abs(param) < thresh)
+    for param in big:
+        with torch.no_grad():
+            thresh = torch.max(torch.abs(param)) * ratio
+            mask = torch.abs(param) < thresh
+            print("Pruned %f%% of the weights" % (float(torch.sum(mask)) / float(torch.sum(param != 0)) * 100))
+            param[mask] = 0
+            indices.append(torch.abs(param) < thresh)
     return indices
+
+
+def pruneModel(params, lower=73, upper=77):
+    """model.py:621-642: per weight tensor, a threshold that starts at the tensor's standard deviation and is stepped by 2.5 % until
+    between ``lower`` and ``upper`` per cent of the non-zero weights lie below it; those are zeroed.  Returns the masks.
+
+    Fixed here where the reference leaves it open: the standard deviation is the fp32 rounding of the float64 two-pass value; the
+    search is cut off after 4096 steps (the reference's loop need not end) with an RcvError that names the parameter; a tensor
+    with fewer than two elements, or without a non-zero weight, is refused (PruneError, a ZeroDivisionError as in the reference)."""
+    big = [p for p in params if p.dim() > 1]
+    if big and big[0].device.type == "cuda":
+        masks, rows = _prune_on_device(big, L.PRUNE_STD_SEARCH, lower=lower, upper=upper)
+        for r in rows:
+            print("Pruned %f%% of the weights" % (float(r.result[0]) / float(r.result[1]) * 100))
+        return masks
+    indices = []
+    for k, param in enumerate(big):
+        param = param.data
+        if param.numel() < 2:
+            raise L.RcvError("pruneModel: parameter %d has %d element: its standard deviation is NaN" % (k, param.numel()))
+        d = param.double()
+        thresh = torch.sqrt(((d - d.mean()) ** 2).sum() / (param.numel() - 1)).float()
+        nonzero = float(torch.sum(param != 0))
+        if nonzero == 0:
+            raise PruneError("prune: parameter %d has no non-zero weight (float division by zero in the reference)" % k)
+        for _ in range(L.PRUNE_MAX_ITER):
+            num = float(torch.sum(torch.abs(param) < thresh)) / nonzero * 100
+            if num < lower:
+                thresh *= 1.025
+            elif num > upper:
+                thresh *= 0.975
+            else:
+                break
+        else:
+            raise L.RcvError("pruneModel: parameter %d: the threshold search did not settle in %d steps; the tensor is untouched"
+                             % (k, L.PRUNE_MAX_ITER))
+        print("Pruned %f%% of the weights" % (float(torch.sum(torch.abs(param) < thresh)) / nonzero * 100))
+        param[torch.abs(param) < thresh] = 0
+        indices.append(torch.abs(param) < thresh)
+    return indices
+
+
+def pruneModel2(params, ratio, lT, hT):
+    """model.py:644-672 (pruner.py:158-209): zero the ``int(n * r)`` smallest-magnitude weights of every weight tensor, r = 0 below
+    100 elements, 0.8 * ratio below ``lT``, 1.05 * ratio above ``hT``; the mask is ``param == 0`` afterwards, so weights pruned in
+    earlier rounds are in it.  Among equal magnitudes at the boundary the LOWEST flat indices go (torch.topk leaves that open)."""
+    big = [p for p in params if p.dim() > 1]
+    rs, amounts = [], []
+    for k, param in enumerate(big):
+        r = ratio
+        if getParamSize(param) < 100:
+            r = 0
+        elif getParamSize(param) < lT:
+            r = ratio * 0.8
+        if getParamSize(param) > hT:
+            r = ratio * 1.05
+        amount = int(param.numel() * r)
+        if amount > param.numel() or amount < 0:
+            raise L.RcvError("pruneModel2: parameter %d: amount %d out of range for %d elements (torch.topk: k not in range)"
+                             % (k, amount, param.numel()))
+        rs.append(r)
+        amounts.append(amount)
+    if big and big[0].device.type == "cuda":
+        masks, _ = _prune_on_device(big, L.PRUNE_SMALLEST_K, amounts=amounts)
+    else:
+        masks = []
+        for param, amount in zip(big, amounts):
+            flat = param.data.reshape(-1)
+            if not param.data.is_contiguous():
+                raise L.RcvError("pruneModel2: parameters must be contiguous")
+            if amount > 0:
+                idx = torch.sort(torch.abs(flat), stable=True)[1][:amount]
+                flat[idx] = 0.0
+            masks.append(param.data == 0.0)
+    for param, amount, r in zip(big, amounts, rs):
+        print("Pruned %d of %d weights (%.3f%%)" % (amount, param.numel(), r))
+    return masks
 
 
 def count_zero_weights(model):

@@ -23,6 +23,38 @@ def reference_param_groups(model, lr: float, transfer: int = 0):
             {"params": list(model.segmenter.parameters())}]
 
 
+def _adopt_flat_mask(masks, fl) -> Optional[torch.Tensor]:
+    """The device mask builders (model.pruneModel / pruneModel2 / pruneModelNew on device parameters) return views of ONE uint8
+    buffer; when the parameters already had the engine's flat layout that buffer mirrors ``fl.data`` element for element and IS the
+    flat prune mask.  Returns it, or None for any other list of masks."""
+    big = [k for k, p in enumerate(fl.params) if p.dim() > 1]
+    if not masks or len(big) != len(masks):
+        return None
+    st = masks[0].untyped_storage()
+    if masks[0].device != fl.data.device or st.nbytes() != fl.numel:
+        return None
+    for k, m in zip(big, masks):
+        if m.dtype != torch.bool or not m.is_contiguous() or m.untyped_storage().data_ptr() != st.data_ptr() \
+                or m.data_ptr() - st.data_ptr() != fl.offsets[k] or m.numel() != fl.params[k].numel():
+            return None
+    return torch.empty(0, dtype=torch.uint8, device=fl.data.device).set_(st, 0, (fl.numel,))
+
+
+def _flat_prune_mask(masks, fl) -> torch.Tensor:
+    """uint8 per element of the flat parameter buffer (1 = pruned) from one boolean mask per parameter with dim() > 1."""
+    t = _adopt_flat_mask(masks, fl)
+    if t is not None:
+        return t
+    big = [k for k, p in enumerate(fl.params) if p.dim() > 1]
+    if len(big) != len(masks):
+        raise L.RcvError("prune mask list has %d entries, the model has %d parameters with dim() > 1" % (len(masks), len(big)))
+    t = torch.zeros(fl.numel, dtype=torch.uint8, device=fl.data.device)
+    for k, m in zip(big, masks):
+        p = fl.params[k]
+        t[fl.offsets[k]:fl.offsets[k] + p.numel()] = m.to(device=fl.data.device, dtype=torch.uint8).reshape(-1)
+    return t
+
+
 class AdamL1(torch.optim.Optimizer):
     """torch.optim.Adam(betas=(.9,.999), eps=1e-8) + gradient of ``decay*sum|p|``, fused.
 
@@ -103,14 +135,7 @@ class AdamL1(torch.optim.Optimizer):
         prune_ptr = 0
         if self._prune_src is not None:
             if self._prune_flat is None or self._prune_flat.numel() != fl.numel or self._prune_flat.device != fl.data.device:
-                big = [k for k, p in enumerate(fl.params) if p.dim() > 1]
-                if len(big) != len(self._prune_src):
-                    raise L.RcvError("prune mask list has %d entries, the model has %d parameters with dim() > 1" % (len(self._prune_src), len(big)))
-                t = torch.zeros(fl.numel, dtype=torch.uint8, device=fl.data.device)
-                for k, m in zip(big, self._prune_src):
-                    p = fl.params[k]
-                    t[fl.offsets[k]:fl.offsets[k] + p.numel()] = m.to(device=fl.data.device, dtype=torch.uint8).reshape(-1)
-                self._prune_flat = t
+                self._prune_flat = _flat_prune_mask(self._prune_src, fl)
             prune_ptr = self._prune_flat.data_ptr()
         self._t += 1
         if self._step_dev is not None:
@@ -150,7 +175,17 @@ class SGD(torch.optim.Optimizer):
         self._lr_elem: Optional[torch.Tensor] = None
         self._lr_key = None
         self._t = 0
+        self._prune_src = None            # list of boolean masks (parameters with dim() > 1, parameters() order) or None
+        self._prune_flat: Optional[torch.Tensor] = None
         super().__init__([{"params": list(model.parameters())}], dict(lr=lr, momentum=momentum, weight_decay=weight_decay))
+
+    def set_prune_mask(self, masks):
+        """trainer.py:220-226 / labelPropTrain.py:201-206 / pruner.py:196-202 inside the fused step: ``masks`` = what pruneModel /
+        pruneModel2 / pruneModelNew returned for ``model.parameters()`` (True = pruned weight).  The launch takes the stored gradient
+        of a masked element as 0 -- what ``param.grad[indices] = 0`` between backward and ``optimizer.step()`` leaves for
+        torch.optim.SGD: the weight-decay term and a carried-over momentum buffer still act.  None switches it off."""
+        self._prune_src = None if masks is None else list(masks)
+        self._prune_flat = None
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -177,8 +212,13 @@ class SGD(torch.optim.Optimizer):
                         t[fl.offsets[k]:fl.offsets[k] + p.numel()] = lr
                 self._lr_elem, self._lr_key = t, lr
             lr_elem_ptr = self._lr_elem.data_ptr()
+        prune_ptr = 0
+        if self._prune_src is not None:
+            if self._prune_flat is None or self._prune_flat.numel() != fl.numel or self._prune_flat.device != fl.data.device:
+                self._prune_flat = _flat_prune_mask(self._prune_src, fl)
+            prune_ptr = self._prune_flat.data_ptr()
         self._t += 1
         op = L.make_op(L.OP_SGD, 0, count=fl.numel, aux0=self._t, f0=lr, f1=g["momentum"], f2=g["weight_decay"], f5=self.grad_scale,
-                       p_in=fl.data.data_ptr(), p_in2=fl.grad.data_ptr(), p_x0=self._buf.data_ptr(), p_x2=lr_elem_ptr)
+                       p_in=fl.data.data_ptr(), p_in2=fl.grad.data_ptr(), p_x0=self._buf.data_ptr(), p_x2=lr_elem_ptr, p_x5=prune_ptr)
         L.OpList([op]).run(eng.handle, torch.cuda.current_stream(fl.data.device).cuda_stream)
         eng.params_dirty = True

@@ -149,6 +149,22 @@ class Trainer:
         if hasattr(self.optimizer, "set_prune_mask"):
             self.optimizer.set_prune_mask(self.prune_indices)
 
+    def prune(self, rule="pruneModelNew", **kw):
+        """The prune stage in one call: run a mask builder of ``model`` (``rule`` = "pruneModelNew" | "pruneModel" | "pruneModel2",
+        or the function itself; ``kw`` = its arguments after ``params``) over ``self.model.parameters()``, drop the engine's cached
+        packed filters (the builders write through ``.data``, which no version counter sees) and hand the masks to the optimizer
+        (``set_prune_indices``).  Returns the masks."""
+        from . import model as M
+        builders = {"pruneModelNew": M.pruneModelNew, "pruneModel": M.pruneModel, "pruneModel2": M.pruneModel2}
+        fn = builders.get(rule, rule)
+        if not callable(fn):
+            raise ValueError("Trainer.prune: rule must be one of %s or a callable, got %r" % (sorted(builders), rule))
+        masks = fn(self.model.parameters(), **kw)
+        if hasattr(self.model, "invalidate"):
+            self.model.invalidate()
+        self.set_prune_indices(masks)
+        return masks
+
     def step(self, imgs: torch.Tensor, targets: torch.Tensor) -> torch.Tensor:
         """One train.py:43-74 iteration; returns the logits tensor (engine-owned, valid until the next forward)."""
         model, opt, crit = self.model, self.optimizer, self.criterion
