@@ -178,11 +178,19 @@ enum {
                              * loss_out (WRITTEN here, as RCV_OP_CE_FWD writes it), p[IN_C] = the float[i[NPART]] rows of an RCV_OP_CE_NORM
                              * record over the same targets and weights, run before this one.  Every output and every partial row is bit
                              * for bit what the two records write                                                                      */
-  RCV_OP_PRUNE = 45          /* the magnitude-pruning mask builders (model.py:45-57 pruneModelNew, :621-642 pruneModel, :644-672 pruneModel2) for
+  RCV_OP_PRUNE = 45,         /* the magnitude-pruning mask builders (model.py:45-57 pruneModelNew, :621-642 pruneModel, :644-672 pruneModel2) for
                              * every weight tensor of a model in ONE launch (rcv_prune; csrc/prune.hip): p[IN] = rcv_prune_job[i[COUNT]] in
                              * device memory, i[AUX0] = the rule (RCV_PRUNE_*).  One workgroup per job, integer counts only: nothing is reduced
                              * across workgroups and no result depends on scheduling.  The weights are zeroed in place, the masks and the
                              * result rows of the jobs are written                                                                     */
+  RCV_OP_OBJECTS = 46        /* the objects of a class map (rcv_find_objects; csrc/objects.hip): per image and class 1..C-1 the 8-connected
+                             * components that pass the class's area rules, largest first.  i[N], i[H], i[W], i[COUT] = C (2..8), i[COUNT] = M
+                             * = max_objects (1..16), i[INMODE] = element bytes of p[IN] (1 = uint8, 8 = int64), i[AUX0] = kernel form (0 = the
+                             * library's choice by shape, 1 = the general multi-launch form, 2 = the single-launch form with the union-find in
+                             * LDS, refused where the plane does not fit; both forms write identical bytes); p[IN] = class map [N][H][W],
+                             * p[OUT] = rows int32 [N][C-1][M][8], p[X0] = counts int32 [N][C-1][4], p[X1] = HOST double[C-1] min_ratio, p[X2] =
+                             * HOST int32[C-1] min_area, p[X3] = HOST int32[C-1] cap (the three read when enqueued), p[PART] = workspace,
+                             * i[NPART] = its size in 256-byte units (filled by rcv_op_workspace)                                       */
 };
 
 /* i[RCV_I_AUX0] of RCV_OP_PRUNE: how the threshold of a tensor is chosen */
@@ -441,6 +449,21 @@ int rcv_confusion(rcv_handle* h, const uint8_t* argmax, const int64_t* target, i
  * threshold arrays are host memory, read before the call returns.  ws: rcv_op_workspace bytes of the RCV_OP_OBJECT_MATCH record.  */
 int rcv_object_match(rcv_handle* h, const void* pred, int pred_bytes, const void* target, int target_bytes, int N, int C, int H, int W,
                      const double* iou_thr, const double* dist_thr, int K, int32_t* counts, void* ws, size_t ws_bytes, void* stream);
+
+/* The objects of a class map, on the device (RCV_OP_OBJECTS): what test.py:43-67 gets from cv2.connectedComponents + cv2.boundingRect + the
+ * box centre, with the per-class rules of DBConvert.py:47-102.  classmap [N][H][W] (elem_bytes 1 = uint8, 8 = int64: what predict
+ * returns); a pixel is of class v when 1 <= v < C, anything else is background.  Components are 8-connected and numbered per (image,
+ * class) by their first 2x2 block in raster order (`rank`, the order of rcv_object_match).  Per class c = 1..C-1 (arrays indexed c-1, HOST
+ * memory, read before the call returns): A = components with area > min_area[c] (strict, DBConvert.py:55); amax = the largest area in
+ * A (0 if empty); Q = members of A with (double)area >= (double)amax * min_ratio[c] (one fp64 multiply, one compare); Q sorted by area
+ * descending, ties by rank ascending; the first min(|Q|, cap[c]) are emitted.  rows int32 [N][C-1][M][8] = { x, y, w, h, area, rank,
+ * 2x + w, 2y + h } (x, y, w, h = cv2.boundingRect; the last two = twice the box centre of test.py:59), zero past the emitted count;
+ * counts int32 [N][C-1][4] = { components of the class, |A|, |Q|, emitted }.  Every byte of both is written by every call; area is the
+ * PIXEL count (not cv2.contourArea).  2 <= C <= 8, 1 <= M <= 16, 0 <= cap[c] <= M, min_area[c] >= 0, min_ratio[c] in [0, 1]; rows and
+ * counts 16-byte aligned.  ws: rcv_op_workspace bytes of the RCV_OP_OBJECTS record.  No host synchronisation.                       */
+int rcv_find_objects(rcv_handle* h, const void* classmap, int elem_bytes, int N, int C, int H, int W, const int32_t* min_area,
+                     const double* min_ratio, const int32_t* cap, int M, int32_t* rows, int32_t* counts, void* workspace,
+                     size_t workspace_bytes, void* stream);
 
 /* The batch assembly of labelPropTrain.py:162-193 in one launch: for every frame pair b, inputs[2b] = [Ya, Yb, Ya - Yb,
  * labelToPred(label_b)], targets[2b] = label_a, and the swapped sample at 2b + 1; Y = channel 0 of a frame, labelToPred

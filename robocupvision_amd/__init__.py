@@ -23,7 +23,8 @@ def __getattr__(name):
     if name in ("colorize", "Colorize", "labelcolormap"):
         from . import palette
         return getattr(palette, name)
-    if name == "Segmenter":
-        from .infer import Segmenter
-        return Segmenter
+    # ... and the objects of a class map (test.py:43-67, DBConvert.py:47-102): find_objects
+    if name in ("Segmenter", "find_objects", "Objects", "DBCONVERT"):
+        from . import infer
+        return getattr(infer, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -126,6 +126,8 @@ static int dispatch(const rcv_handle* h, const rcv_op* op, hipStream_t s, OpQuer
       return rcv_launch_bnn(h, op, s, q);
     case RCV_OP_PRUNE:
       return rcv_launch_prune(h, op, s, q);
+    case RCV_OP_OBJECTS:
+      return rcv_launch_objects(h, op, s, q);
     case RCV_OP_NOP:
       if (q) { snprintf(q->label, sizeof(q->label), "nop"); q->n_part = 0; q->n_split = 0; q->part_bytes = 0; }
       return RCV_OK;
@@ -384,6 +386,23 @@ int rcv_object_match(rcv_handle* h, const void* pred, int pred_bytes, const void
   const int rc = rcv_op_workspace(h, &op, &need);
   if (rc) return rc;
   RCV_CHECK_ARG(ws_bytes >= need, "rcv_object_match: workspace of %zu bytes given, %zu needed (rcv_op_workspace)", ws_bytes, need);
+  return rcv_run(h, &op, 1, stream);
+}
+
+int rcv_find_objects(rcv_handle* h, const void* classmap, int elem_bytes, int N, int C, int H, int W, const int32_t* min_area,
+                     const double* min_ratio, const int32_t* cap, int M, int32_t* rows, int32_t* counts, void* workspace,
+                     size_t workspace_bytes, void* stream) {
+  rcv_op op;
+  memset(&op, 0, sizeof(op));
+  op.kind = RCV_OP_OBJECTS;
+  op.i[RCV_I_N] = N; op.i[RCV_I_H] = H; op.i[RCV_I_W] = W; op.i[RCV_I_COUT] = C; op.i[RCV_I_COUNT] = M; op.i[RCV_I_INMODE] = elem_bytes;
+  op.p[RCV_P_IN] = (void*)classmap; op.p[RCV_P_OUT] = rows; op.p[RCV_P_X0] = counts; op.p[RCV_P_PART] = workspace;
+  op.p[RCV_P_X1] = (void*)min_ratio; op.p[RCV_P_X2] = (void*)min_area; op.p[RCV_P_X3] = (void*)cap;
+  size_t need = 0;
+  const int rc = rcv_op_workspace(h, &op, &need);
+  if (rc) return rc;
+  RCV_CHECK_ARG(workspace_bytes >= need, "rcv_find_objects: workspace of %zu bytes given, %zu needed (rcv_op_workspace)", workspace_bytes,
+                need);
   return rcv_run(h, &op, 1, stream);
 }
 

@@ -19,29 +19,17 @@
 // Integer atomics only; every output is a pure function of the inputs (the hash-table layout depends on scheduling, but the matcher
 // takes the MINIMUM qualifying rank of a candidate list, so the order of the lists does not matter).  No host synchronisation.
 #include <math.h>
-#include "rcv_internal.h"
+#include "objdet_stages.h"
 
 namespace {
 
-constexpr int OD_TILE = 256;    // 2x2 blocks per workgroup of the per-block kernels
 constexpr int OD_MAXK = 8;
-constexpr int OD_MAXC = 8;
-constexpr int OD_MAX_BLOCKS = 1 << 17;   // 2x2 blocks per plane (a 512 x 1024 plane); bounds the matcher's LDS (24 B per 64 blocks)
 constexpr int OD_NO_MATCH = 0x7fffffff;
-
-struct OdGeo {
-  int N, H, W, C, Wb, NB, QP, tiles;   // NB = 2x2 blocks per plane, QP = 4 * NB (block-major pixel slots), tiles = ceil(NB / OD_TILE)
-  int pbytes, tbytes;                  // element size of pred / target: 1 (uint8) or 8 (int64)
-  uint32_t hmask;                      // pair hash capacity - 1
-};
 
 struct OdThr {
   double t[OD_MAXK];   // IoU thresholds, fp64 as given
   int s[OD_MAXK];      // distance thresholds as integer limits on s = dX^2 + dY^2 (X = x0 + x1 + 1): pass iff s <= s[k]
 };
-
-// component table entry (int[8] per gid): bounding box first (one 16-byte load), then area and the candidate list of a pred component
-enum { CX0 = 0, CX1, CY0, CY1, CAREA, CCNT, COFF, CCUR };
 
 struct OdWs {
   uint64_t* hkey;   // [cap] pair key (pred gid + 1) << 32 | target gid; 0 = empty
@@ -80,76 +68,6 @@ static size_t od_layout(const OdGeo& g, uint64_t cap, char* base, OdWs* w) {
   return off;
 }
 
-__device__ __forceinline__ int od_cls(uint32_t cw, int i) { return (int)((cw >> (8 * i)) & 255u); }
-
-// index of the first pixel of block word cw with the class of pixel i
-__device__ __forceinline__ int od_rep(uint32_t cw, int i) {
-  const int c = od_cls(cw, i);
-  int j = 0;
-  while (od_cls(cw, j) != c) ++j;
-  return j;
-}
-
-__device__ __forceinline__ int od_ld(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-__device__ __forceinline__ int od_find_live(const int* L, int a) {     // during the merge: parents change under our feet
-  int b = od_ld(L + a);
-  while (b != a) { a = b; b = od_ld(L + a); }
-  return a;
-}
-
-// Playne & Hawick's lock-free union: link the larger root under the smaller; a failed link (the root got a parent meanwhile)
-// continues from that parent.  Labels only decrease and always point inside the component, so the loop ends.
-__device__ void od_union(int* L, int a, int b) {
-  while (true) {
-    a = od_find_live(L, a);
-    b = od_find_live(L, b);
-    if (a == b) return;
-    if (a > b) { const int t = a; a = b; b = t; }
-    const int old = atomicMin(L + b, a);
-    if (old == b) return;
-    b = old;
-  }
-}
-
-__device__ __forceinline__ int od_popc_below(uint64_t m) {
-  return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-}
-
-__device__ __forceinline__ int od_wave_min(int v) {
-  for (int o = 32; o; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
-  return v;
-}
-__device__ __forceinline__ int od_wave_max(int v) {
-  for (int o = 32; o; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
-  return v;
-}
-__device__ __forceinline__ int od_wave_sum(int v) {
-  for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-// exclusive scan of one int per thread over the workgroup (blockDim.x a multiple of 64, at most 1024); sh = 16 ints of LDS
-__device__ int od_block_scan(int v, int* sh, int* total) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  int x = v;
-  for (int o = 1; o < 64; o <<= 1) {
-    const int y = __shfl_up(x, o, 64);
-    if (lane >= o) x += y;
-  }
-  if (lane == 63) sh[wv] = x;
-  __syncthreads();
-  int before = 0, tot = 0;
-  for (int w = 0; w < nw; ++w) {
-    const int s = sh[w];
-    if (w < wv) before += s;
-    tot += s;
-  }
-  __syncthreads();
-  *total = tot;
-  return before + x - v;
-}
-
 __device__ __forceinline__ uint32_t od_hash(uint64_t k) {
   k ^= k >> 33; k *= 0xff51afd7ed558ccdull; k ^= k >> 33; k *= 0xc4ceb9fe1a85ec53ull; k ^= k >> 33;
   return (uint32_t)k;
@@ -170,7 +88,8 @@ __device__ void od_insert(uint64_t* keys, int* cnt, uint32_t hmask, uint64_t key
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------
-// 1 init: grid (tiles, 2N) x OD_TILE, one thread per 2x2 block
+// Stages 1-6 are the bodies of objdet_stages.h over 2N planes (plane 2n = pred, 2n + 1 = target of image n).
+// 1 init: grid (tiles, 2N) x OD_TILE, one thread per 2x2 block; clears the pair hash table
 __global__ __launch_bounds__(OD_TILE) void od_init_kernel(const void* __restrict__ pred, const void* __restrict__ target, OdGeo g,
                                                           uint32_t* __restrict__ cls, int* __restrict__ L, uint4* __restrict__ hclear,
                                                           size_t hwords) {
@@ -179,176 +98,43 @@ __global__ __launch_bounds__(OD_TILE) void od_init_kernel(const void* __restrict
   for (size_t i = tid; i < hwords; i += nthr) hclear[i] = make_uint4(0u, 0u, 0u, 0u);
   const int pl = blockIdx.y, b = blockIdx.x * OD_TILE + threadIdx.x;
   if (b >= g.NB) return;
-  const int n = pl >> 1;
   const bool tgt = pl & 1;
-  const int bytes = tgt ? g.tbytes : g.pbytes;
-  const void* src = tgt ? target : pred;
-  const int by = b / g.Wb, bx = b - by * g.Wb;
-  uint32_t cw = 0;
-  for (int i = 0; i < 4; ++i) {
-    const int y = 2 * by + (i >> 1), x = 2 * bx + (i & 1);
-    if (y >= g.H || x >= g.W) continue;
-    const size_t idx = ((size_t)n * g.H + y) * g.W + x;
-    const long long v = bytes == 1 ? (long long)((const uint8_t*)src)[idx] : (long long)((const int64_t*)src)[idx];
-    if (v >= 1 && v < g.C) cw |= (uint32_t)v << (8 * i);
-  }
-  cls[(size_t)pl * g.NB + b] = cw;
-  int4 l;
-  l.x = 4 * b + od_rep(cw, 0); l.y = 4 * b + od_rep(cw, 1); l.z = 4 * b + od_rep(cw, 2); l.w = 4 * b + od_rep(cw, 3);
-  *reinterpret_cast<int4*>(L + (size_t)pl * g.QP + 4 * b) = l;
+  od_init_block(g, tgt ? target : pred, tgt ? g.tbytes : g.pbytes, pl >> 1, b, cls + (size_t)pl * g.NB, L + (size_t)pl * g.QP);
 }
 
-// 2 merge: the raster-backward neighbours (left, up-left, up, up-right) of every pixel cover every 8-neighbour edge once; edges inside
-// the block were joined by init
+// 2 merge
 __global__ __launch_bounds__(OD_TILE) void od_merge_kernel(OdGeo g, const uint32_t* __restrict__ cls, int* L) {
   const int pl = blockIdx.y, b = blockIdx.x * OD_TILE + threadIdx.x;
   if (b >= g.NB) return;
-  const uint32_t* cp = cls + (size_t)pl * g.NB;
-  const uint32_t cw = cp[b];
-  if (!cw) return;
-  int* Lp = L + (size_t)pl * g.QP;
-  const int by = b / g.Wb, bx = b - by * g.Wb;
-  const int dy[4] = {0, -1, -1, -1}, dx[4] = {-1, -1, 0, 1};
-  for (int i = 0; i < 4; ++i) {
-    const int c = od_cls(cw, i);
-    if (!c) continue;
-    const int y = 2 * by + (i >> 1), x = 2 * bx + (i & 1);
-    const int rep = 4 * b + od_rep(cw, i);
-    for (int e = 0; e < 4; ++e) {
-      const int ny = y + dy[e], nx = x + dx[e];
-      if (ny < 0 || nx < 0 || nx >= g.W) continue;
-      const int nb = (ny >> 1) * g.Wb + (nx >> 1);
-      if (nb == b) continue;
-      const int ni = (ny & 1) * 2 + (nx & 1);
-      if (od_cls(cp[nb], ni) != c) continue;
-      od_union(Lp, rep, 4 * nb + ni);
-    }
-  }
+  od_merge_block(g, b, cls + (size_t)pl * g.NB, L + (size_t)pl * g.QP);
 }
 
-// 3 count: path compression; roots per class in this tile -> tcnt
+// 3 count
 __global__ __launch_bounds__(OD_TILE) void od_count_kernel(OdGeo g, const uint32_t* __restrict__ cls, int* L, int* __restrict__ tcnt) {
   __shared__ int wc[OD_TILE / 64][OD_MAXC];
-  const int pl = blockIdx.y, b = blockIdx.x * OD_TILE + threadIdx.x;
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const uint32_t cw = b < g.NB ? cls[(size_t)pl * g.NB + b] : 0u;
-  uint32_t roots = 0;   // bit c: this block holds the root of a class-c component (at most one per class)
-  if (cw) {
-    int* Lp = L + (size_t)pl * g.QP;
-    int4 l = *reinterpret_cast<const int4*>(Lp + 4 * b);
-    int lv[4] = {l.x, l.y, l.z, l.w};
-    for (int i = 0; i < 4; ++i) {
-      const int c = od_cls(cw, i);
-      if (!c) continue;
-      int a = lv[i];
-      while (true) { const int p = Lp[a]; if (p == a) break; a = p; }
-      lv[i] = a;
-      if (a == 4 * b + i) roots |= 1u << c;
-    }
-    *reinterpret_cast<int4*>(Lp + 4 * b) = make_int4(lv[0], lv[1], lv[2], lv[3]);
-  }
-  for (int c = 1; c < g.C; ++c) {
-    const uint64_t m = __ballot((roots >> c) & 1u);
-    if (lane == 0) wc[wv][c] = __popcll(m);
-  }
-  __syncthreads();
-  if ((int)threadIdx.x < OD_MAXC) {
-    const int c = threadIdx.x;
-    int s = 0;
-    if (c >= 1 && c < g.C)
-      for (int w = 0; w < OD_TILE / 64; ++w) s += wc[w][c];
-    tcnt[((size_t)pl * g.tiles + blockIdx.x) * OD_MAXC + c] = s;
-  }
+  const int pl = blockIdx.y;
+  od_count_tile(g, blockIdx.x * OD_TILE + threadIdx.x, blockIdx.x, threadIdx.x, cls + (size_t)pl * g.NB, L + (size_t)pl * g.QP,
+                tcnt + (size_t)pl * g.tiles * OD_MAXC, wc);
 }
 
-// 4 plane: grid 2N x 256
+// 4 plane: grid 2N x 256; nPred / nTrue into the output
 __global__ __launch_bounds__(256) void od_plane_kernel(OdGeo g, int K, const int* __restrict__ tcnt, int* __restrict__ toff,
                                                        int* __restrict__ pc, int* __restrict__ counts) {
   __shared__ int sh[16];
   __shared__ int tot[OD_MAXC];
-  const int pl = blockIdx.x;
-  for (int c = 1; c < g.C; ++c) {
-    int carry = 0;
-    for (int t0 = 0; t0 < g.tiles; t0 += 256) {
-      const int t = t0 + threadIdx.x;
-      const size_t at = ((size_t)pl * g.tiles + t) * OD_MAXC + c;
-      const int v = t < g.tiles ? tcnt[at] : 0;
-      int total;
-      const int ex = od_block_scan(v, sh, &total);
-      if (t < g.tiles) toff[at] = carry + ex;
-      carry += total;
-    }
-    if (threadIdx.x == 0) tot[c] = carry;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const int n = pl >> 1, row = 2 + 2 * K;
-    int base = 0;
-    for (int c = 1; c < g.C; ++c) {
-      pc[pl * 16 + c] = tot[c];
-      pc[pl * 16 + 8 + c] = base;
-      base += tot[c];
-      counts[((size_t)n * (g.C - 1) + c - 1) * row + (pl & 1)] = tot[c];
-    }
-  }
+  const int pl = blockIdx.x, row = 2 + 2 * K;
+  od_plane_scan<256>(g, tcnt + (size_t)pl * g.tiles * OD_MAXC, toff + (size_t)pl * g.tiles * OD_MAXC, pc + pl * 16,
+                     counts + (size_t)(pl >> 1) * (g.C - 1) * row + (pl & 1), row, sh, tot);
 }
 
-// 5 rank: R[root] = rank in block order among the roots of its class; the component's table entry is initialised
+// 5 rank
 __global__ __launch_bounds__(OD_TILE) void od_rank_kernel(OdGeo g, const uint32_t* __restrict__ cls, const int* __restrict__ L,
                                                           const int* __restrict__ toff, const int* __restrict__ pc, int* __restrict__ R,
                                                           int* __restrict__ comp) {
   __shared__ int wc[OD_TILE / 64][OD_MAXC];
-  const int pl = blockIdx.y, b = blockIdx.x * OD_TILE + threadIdx.x;
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const uint32_t cw = b < g.NB ? cls[(size_t)pl * g.NB + b] : 0u;
-  const int* Lp = L + (size_t)pl * g.QP;
-  int rootq[OD_MAXC];
-  uint32_t roots = 0;
-  if (cw) {
-    const int4 l = *reinterpret_cast<const int4*>(Lp + 4 * b);
-    const int lv[4] = {l.x, l.y, l.z, l.w};
-    for (int i = 0; i < 4; ++i) {
-      const int c = od_cls(cw, i);
-      if (c && lv[i] == 4 * b + i) { roots |= 1u << c; rootq[c] = 4 * b + i; }
-    }
-  }
-  int below[OD_MAXC];
-  for (int c = 1; c < g.C; ++c) {
-    const uint64_t m = __ballot((roots >> c) & 1u);
-    below[c] = od_popc_below(m);
-    if (lane == 0) wc[wv][c] = __popcll(m);
-  }
-  __syncthreads();
-  for (int c = 1; c < g.C; ++c) {
-    if (!((roots >> c) & 1u)) continue;
-    int rank = toff[((size_t)pl * g.tiles + blockIdx.x) * OD_MAXC + c] + below[c];
-    for (int w = 0; w < wv; ++w) rank += wc[w][c];
-    R[(size_t)pl * g.QP + rootq[c]] = rank;
-    int* e = comp + ((size_t)pl * g.QP + pc[pl * 16 + 8 + c] + rank) * 8;
-    *reinterpret_cast<int4*>(e) = make_int4(0x7fffffff, -1, 0x7fffffff, -1);
-    *reinterpret_cast<int4*>(e + 4) = make_int4(0, 0, 0, 0);
-  }
-}
-
-// area + bounding box of one group of pixels into its component; when every active lane of the wave hits the same component the wave
-// reduces first and one lane does the atomics (a large blob would otherwise serialise thousands of atomics on one address)
-__device__ void od_add_box(bool act, int gid, int area, int x0, int x1, int y0, int y1, int* comp) {
-  const uint64_t am = __ballot(act);
-  if (!am) return;
-  const int lead = __ffsll((unsigned long long)am) - 1;
-  const int lg = __shfl(gid, lead, 64);
-  if (__ballot(act && gid == lg) == am) {
-    const int a = od_wave_sum(act ? area : 0);
-    const int ax0 = od_wave_min(act ? x0 : 0x7fffffff), ax1 = od_wave_max(act ? x1 : -1);
-    const int ay0 = od_wave_min(act ? y0 : 0x7fffffff), ay1 = od_wave_max(act ? y1 : -1);
-    if ((int)(threadIdx.x & 63) == lead) {
-      int* e = comp + (size_t)lg * 8;
-      atomicMin(e + CX0, ax0); atomicMax(e + CX1, ax1); atomicMin(e + CY0, ay0); atomicMax(e + CY1, ay1); atomicAdd(e + CAREA, a);
-    }
-  } else if (act) {
-    int* e = comp + (size_t)gid * 8;
-    atomicMin(e + CX0, x0); atomicMax(e + CX1, x1); atomicMin(e + CY0, y0); atomicMax(e + CY1, y1); atomicAdd(e + CAREA, area);
-  }
+  const int pl = blockIdx.y;
+  od_rank_tile(g, blockIdx.x * OD_TILE + threadIdx.x, blockIdx.x, threadIdx.x, cls + (size_t)pl * g.NB, L + (size_t)pl * g.QP,
+               toff + (size_t)pl * g.tiles * OD_MAXC, pc + pl * 16, R + (size_t)pl * g.QP, comp + (size_t)pl * g.QP * 8, wc);
 }
 
 __device__ void od_add_pair(bool act, uint64_t key, int v, uint64_t* keys, int* cnt, uint32_t hmask) {
@@ -364,7 +150,8 @@ __device__ void od_add_pair(bool act, uint64_t key, int v, uint64_t* keys, int* 
   }
 }
 
-// 6 stats: grid (tiles, 2N); every thread of a wave runs the (uniform) slot loops, so the wave-level aggregation sees all lanes
+// 6 stats: grid (tiles, 2N); area + bounding box per component, and the overlap pixels per (pred component, target component) pair into
+// an integer hash table (aggregated per 2x2 block)
 __global__ __launch_bounds__(OD_TILE) void od_stats_kernel(OdGeo g, const uint32_t* __restrict__ cls, const int* __restrict__ L,
                                                            const int* __restrict__ R, const int* __restrict__ pc, int* comp, uint64_t* hkey,
                                                            int* hcnt) {
@@ -375,22 +162,7 @@ __global__ __launch_bounds__(OD_TILE) void od_stats_kernel(OdGeo g, const uint32
   int4 l = make_int4(0, 0, 0, 0);
   if (cw) l = *reinterpret_cast<const int4*>(L + pbase + 4 * b);
   const int lv[4] = {l.x, l.y, l.z, l.w};
-  const int by = in ? b / g.Wb : 0, bx = in ? b - by * g.Wb : 0;
-  // slot i: the pixels of the class of pixel i, when pixel i is the first of its class in the block
-  for (int i = 0; i < 4; ++i) {
-    const int c = od_cls(cw, i);
-    const bool act = c != 0 && od_rep(cw, i) == i;
-    int gid = 0, area = 0, x0 = 0x7fffffff, x1 = -1, y0 = 0x7fffffff, y1 = -1;
-    if (act) {
-      gid = (int)(pbase + pc[pl * 16 + 8 + c] + R[pbase + lv[i]]);
-      for (int j = i; j < 4; ++j) {
-        if (od_cls(cw, j) != c) continue;
-        const int y = 2 * by + (j >> 1), x = 2 * bx + (j & 1);
-        ++area; x0 = min(x0, x); x1 = max(x1, x); y0 = min(y0, y); y1 = max(y1, y);
-      }
-    }
-    od_add_box(act, gid, area, x0, x1, y0, y1, comp);
-  }
+  od_stats_boxes(g, in, b, cw, lv, pbase, R + pbase, pc + pl * 16, comp);
   if (pl & 1) return;        // (uniform per workgroup) pairs are counted from the pred planes
   const uint32_t tw = in ? cls[(size_t)(pl + 1) * g.NB + b] : 0u;
   uint32_t both = 0;         // class bytes of the pixels where pred == target (>= 1)

@@ -4,22 +4,185 @@
     labels, colour = seg(frames)                         # frames uint8 [B,Hs,Ws,3] on the HIP device
 
 ``labels`` uint8 [B,H,W] is what ``SegmentationMetrics.update`` / ``DetectionMetrics.update`` take; ``colour`` uint8 [B,H,W,3] is
-``Colorize`` of every map, HWC as detect.py:133 permutes it (cv2.imwrite reads it as BGR).  File writing stays with the caller."""
+``Colorize`` of every map, HWC as detect.py:133 permutes it (cv2.imwrite reads it as BGR).  File writing stays with the caller.
+
+What a user then does with a class map -- find the ball, the robots, the goal posts in it (test.py:43-67: components, cv2.boundingRect,
+the box centre; DBConvert.py:47-102: the per-class area rules of the detection data set) -- is ``find_objects``, one op on the device:
+
+    objs = find_objects(labels, **DBCONVERT)             # Objects: rows / counts stay on the device
+    seg = Segmenter(model, objects=DBCONVERT)            # labels, colour, objs = seg(frames)
+    objs.to_list()                                       # the one host copy: per image [(class, x, y, w, h, area), ...]"""
 from __future__ import annotations
+
+import ctypes
+from collections import OrderedDict
+
+import torch
 
 from . import _lib as L
 from .data import prepare_frames
 from .palette import device_palette
 
-__all__ = ["Segmenter"]
+__all__ = ["Segmenter", "find_objects", "Objects", "ObjectsRecord", "DBCONVERT"]
+
+
+class _Rules(dict):
+    """Keyword arguments of ``find_objects`` with a docstring of their own."""
+
+    def __init__(self, doc, **kw):
+        super().__init__(**kw)
+        self.__doc__ = doc
+
+
+DBCONVERT = _Rules(
+    """The per-class rules of DBConvert.py:52-100 for the five-class maps (classes 1..4: ball, robot, goal post, line), as keywords of
+    ``find_objects`` / ``Segmenter(objects=...)``: minimum area (25, 200, 30, -), minimum share of the class's largest blob (0.05, 0.05,
+    0.2, -), at most (6, 5, 2, 0) boxes; lines give no boxes.  Two known differences from that script: (1) area is the PIXEL area of
+    the 8-connected component, not ``cv2.contourArea`` of its outline (the polygon area through the pixel centres, smaller by about
+    half the perimeter); (2) where a class has more blobs than its cap, the LARGEST are kept (area descending, ties by component number),
+    not the first of the script's walk over the contours in ascending area.""",
+    num_class=5, min_area=(25, 200, 30, 0), min_ratio=(0.05, 0.05, 0.2, 0.0), max_objects=(6, 5, 2, 0))
+
+
+def _per_class(v, n, what, conv):
+    if isinstance(v, (list, tuple)):
+        if len(v) != n:
+            raise L.RcvError("find_objects: %s has %d entries, one per class 1..%d expected" % (what, len(v), n))
+        seq = list(v)
+    else:
+        seq = [v] * n
+    try:
+        return [conv(x) for x in seq]
+    except (TypeError, ValueError) as e:
+        raise L.RcvError("find_objects: %s: %s" % (what, e)) from None
+
+
+def _as_int(x):
+    if isinstance(x, bool) or int(x) != x:
+        raise ValueError("%r is not an integer" % (x,))
+    if not -(1 << 31) <= int(x) < (1 << 31):
+        raise ValueError("%r does not fit 32 bits" % (x,))
+    return int(x)
+
+
+class ObjectsRecord:
+    """One RCV_OP_OBJECTS record and the host arrays (min_ratio double[C-1], min_area / cap int32[C-1]) it points to, kept alive with
+    it.  ``form``: 0 = the library routes by shape, 1 / 2 force the general / the single-launch LDS kernels (tests and A/B timing)."""
+
+    def __init__(self, N: int, H: int, W: int, num_class: int = 5, min_area=0, min_ratio=0.0, max_objects=8, elem_bytes: int = 1,
+                 form: int = 0):
+        try:
+            num_class = _as_int(num_class)
+        except (TypeError, ValueError) as e:
+            raise L.RcvError("find_objects: num_class: %s" % e) from None
+        nc = min(max(num_class - 1, 0), 64)      # (the library refuses num_class outside 2..8)
+        area = _per_class(min_area, nc, "min_area", _as_int)
+        ratio = _per_class(min_ratio, nc, "min_ratio", float)
+        cap = _per_class(max_objects, nc, "max_objects", _as_int)
+        self.C = num_class
+        # a per-class sequence gives the caps and M is its maximum (at least one row); a scalar is both
+        self.M = max([1] + cap) if isinstance(max_objects, (list, tuple)) else _per_class(max_objects, 1, "max_objects", _as_int)[0]
+        self.min_area = (ctypes.c_int32 * max(nc, 1))(*area)
+        self.min_ratio = (ctypes.c_double * max(nc, 1))(*ratio)
+        self.cap = (ctypes.c_int32 * max(nc, 1))(*cap)
+        self.op = L.make_op(L.OP_OBJECTS, 0, n=N, h=H, w=W, cout=num_class, count=self.M, inmode=elem_bytes, aux0=form,
+                            p_x1=ctypes.addressof(self.min_ratio), p_x2=ctypes.addressof(self.min_area), p_x3=ctypes.addressof(self.cap))
+
+    def workspace_bytes(self, h) -> int:
+        """rcv_op_workspace: refuses the record (RcvError with the library's message) exactly as an enqueue would."""
+        return L.op_workspace(h, self.op)
+
+
+class Objects:
+    """The result of ``find_objects``: two int32 device tensors, ``rows`` [N, C-1, M, 8] = {x, y, w, h, area, rank, 2x+w, 2y+h} (zero
+    past the emitted count) and ``counts`` [N, C-1, 4] = {components of the class, |A|, |Q|, emitted}; index 0 of the class axis is
+    class 1.  The properties are views / device arithmetic; nothing here synchronises except ``to_list``."""
+
+    def __init__(self, rows: torch.Tensor, counts: torch.Tensor):
+        self.rows, self.counts = rows, counts
+
+    @property
+    def boxes(self):           # [N, C-1, M, 4] x, y, w, h (cv2.boundingRect)
+        return self.rows[..., 0:4]
+
+    @property
+    def area(self):            # [N, C-1, M] pixels
+        return self.rows[..., 4]
+
+    @property
+    def rank(self):            # [N, C-1, M] component number within (image, class), first-2x2-block order
+        return self.rows[..., 5]
+
+    @property
+    def count(self):           # [N, C-1] emitted rows
+        return self.counts[..., 3]
+
+    @property
+    def centres(self):         # [N, C-1, M, 2] float64 (x + w/2, y + h/2): test.py:59's predCent
+        return self.rows[..., 6:8].to(torch.float64) / 2
+
+    def to_list(self):
+        """One host copy: per image the list of (class, x, y, w, h, area), classes ascending, each class largest first."""
+        N, Cm1, M, _ = self.rows.shape
+        host = torch.cat([self.rows.reshape(-1), self.counts.reshape(-1)]).cpu()
+        rows = host[:N * Cm1 * M * 8].reshape(N, Cm1, M, 8).tolist()
+        counts = host[N * Cm1 * M * 8:].reshape(N, Cm1, 4).tolist()
+        return [[(c + 1,) + tuple(rows[n][c][k][0:5]) for c in range(Cm1) for k in range(counts[n][c][3])] for n in range(N)]
+
+
+_WORKSPACES = OrderedDict()      # (device, N, H, W) -> workspace tensor, the few most recent shapes
+_WORKSPACES_KEPT = 8
+
+
+def _workspace(dev, shape, nbytes):
+    key = (dev,) + tuple(shape)
+    ws = _WORKSPACES.get(key)
+    if ws is None or ws.numel() < nbytes:
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    _WORKSPACES[key] = ws
+    _WORKSPACES.move_to_end(key)
+    while len(_WORKSPACES) > _WORKSPACES_KEPT:
+        _WORKSPACES.popitem(last=False)
+    return ws
+
+
+def find_objects(class_map: torch.Tensor, num_class: int = 5, min_area=0, min_ratio=0.0, max_objects=8, _form: int = 0) -> Objects:
+    """The objects of every class map of a batch (RCV_OP_OBJECTS, rcv.h rcv_find_objects): class_map uint8 or int64 [N,H,W] on the HIP
+    device, exactly what ``predict`` returns; a pixel is of class v when 1 <= v < num_class.  Per class c (scalars, or sequences of
+    length num_class-1 for classes 1..): keep the 8-connected components with area > min_area (strict), of those the ones with
+    area >= largest * min_ratio (fp64), and emit the max_objects largest (ties: lower component number first).  A per-class
+    max_objects sequence gives the caps; the row count M of the result is its maximum.  Enqueued on the current stream, nothing
+    synchronises; the workspace is cached per shape (calls on one shape from several streams at once must not overlap).
+    ``_form`` forces a kernel form (ObjectsRecord) -- for tests."""
+    if not isinstance(class_map, torch.Tensor) or class_map.dim() != 3:
+        raise L.RcvError("find_objects: class_map must be a [N,H,W] tensor")
+    eb = {torch.uint8: 1, torch.int64: 8}.get(class_map.dtype)
+    if eb is None:
+        raise L.RcvError("find_objects: dtype %s unsupported (torch.uint8 or torch.int64)" % class_map.dtype)
+    N, H, W = class_map.shape
+    rec = ObjectsRecord(N, H, W, num_class, min_area, min_ratio, max_objects, eb, _form)
+    if class_map.device.type != "cuda":
+        rec.workspace_bytes(L.planner_handle())       # bad arguments are refused with the library's message first
+        raise L.RcvError("find_objects needs the class map on the HIP device (there is no CPU path)")
+    dev = class_map.device
+    h = L.handle(dev.index if dev.index is not None else torch.cuda.current_device())
+    ws = _workspace(dev, (N, H, W), rec.workspace_bytes(h))
+    class_map = class_map.contiguous()
+    rows = torch.empty(N, rec.C - 1, rec.M, 8, dtype=torch.int32, device=dev)
+    counts = torch.empty(N, rec.C - 1, 4, dtype=torch.int32, device=dev)
+    op = rec.op
+    op.p[L.RCV_P_IN], op.p[L.RCV_P_OUT], op.p[L.RCV_P_X0], op.p[L.RCV_P_PART] = class_map.data_ptr(), rows.data_ptr(), counts.data_ptr(), ws.data_ptr()
+    L.OpList([op]).run(h, torch.cuda.current_stream(dev).cuda_stream)
+    return Objects(rows, counts)
 
 
 class Segmenter:
     """``Segmenter(model)(frames)`` = ``model.predict(prepare_frames(frames, img_size, finetune), colour=True, palette=palette)``.
     ``model``: a ROBO_UNet, PB_FCN, PB_FCN_2 (segmentation mode) on the HIP device; it is put in eval mode here, once -- a caller
-    that trains it afterwards calls ``.eval()`` again before the next frame."""
+    that trains it afterwards calls ``.eval()`` again before the next frame.  ``objects``: a dict of ``find_objects`` keywords (e.g.
+    ``DBCONVERT``); the call then returns ``(labels, colour, objects)`` with the ``Objects`` of the labels."""
 
-    def __init__(self, model, img_size=(120, 160), finetune=False, palette=None):
+    def __init__(self, model, img_size=(120, 160), finetune=False, palette=None, objects=None):
         if not hasattr(model, "predict"):
             raise TypeError("Segmenter: model must be one of this package's networks (it has no predict)")
         if getattr(model, "classify", False):
@@ -31,6 +194,12 @@ class Segmenter:
         self._device_palettes = {}          # device -> the palette padded to uint8 [8,3], uploaded once
         if palette is not None:
             device_palette(palette, "cpu")          # a wrong palette is refused at construction
+        self._objects = None
+        if objects is not None:
+            if not isinstance(objects, dict) or not set(objects) <= {"num_class", "min_area", "min_ratio", "max_objects"}:
+                raise L.RcvError("Segmenter: objects must be a dict of find_objects keywords (num_class, min_area, min_ratio, max_objects)")
+            self._objects = dict(objects)
+            ObjectsRecord(1, 1, 1, **self._objects).workspace_bytes(L.planner_handle())       # wrong rules are refused at construction
 
     def __call__(self, frames):
         imgs = prepare_frames(frames, self.img_size, self.finetune)
@@ -39,4 +208,7 @@ class Segmenter:
             pal = self._device_palettes.get(imgs.device)
             if pal is None:
                 pal = self._device_palettes[imgs.device] = device_palette(self._palette, imgs.device)
-        return self.model.predict(imgs, colour=True, palette=pal)
+        labels, colour = self.model.predict(imgs, colour=True, palette=pal)
+        if self._objects is None:
+            return labels, colour
+        return labels, colour, find_objects(labels, **self._objects)
