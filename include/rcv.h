@@ -183,7 +183,7 @@ enum {
                              * device memory, i[AUX0] = the rule (RCV_PRUNE_*).  One workgroup per job, integer counts only: nothing is reduced
                              * across workgroups and no result depends on scheduling.  The weights are zeroed in place, the masks and the
                              * result rows of the jobs are written                                                                     */
-  RCV_OP_OBJECTS = 46        /* the objects of a class map (rcv_find_objects; csrc/objects.hip): per image and class 1..C-1 the 8-connected
+  RCV_OP_OBJECTS = 46,       /* the objects of a class map (rcv_find_objects; csrc/objects.hip): per image and class 1..C-1 the 8-connected
                              * components that pass the class's area rules, largest first.  i[N], i[H], i[W], i[COUT] = C (2..8), i[COUNT] = M
                              * = max_objects (1..16), i[INMODE] = element bytes of p[IN] (1 = uint8, 8 = int64), i[AUX0] = kernel form (0 = the
                              * library's choice by shape, 1 = the general multi-launch form, 2 = the single-launch form with the union-find in
@@ -191,6 +191,17 @@ enum {
                              * p[OUT] = rows int32 [N][C-1][M][8], p[X0] = counts int32 [N][C-1][4], p[X1] = HOST double[C-1] min_ratio, p[X2] =
                              * HOST int32[C-1] min_area, p[X3] = HOST int32[C-1] cap (the three read when enqueued), p[PART] = workspace,
                              * i[NPART] = its size in 256-byte units (filled by rcv_op_workspace)                                       */
+  RCV_OP_RGB_PREP = 47       /* the loader of trainer.py:75-123 (and pruner.py, labelPropTrain.py, tester.py, makeLPImages.py, classTrainer.py,
+                             * objDetEval.py) for a whole batch (rcv_rgb_prep; csrc/rgb_prep.hip): Scale, the two flips, torchvision's PIL
+                             * ColorJitter, rgb2yuv, ToTensor, Normalize([.5,0,0],[.5,.5,.5]), and the label's Scale, flips and maskLabel.
+                             * i[N] = B, i[H] / i[W] = source Hs / Ws, i[HO] / i[WO] = output H / W, i[CIN] / i[COUT] = taps per output column /
+                             * row of the frame tables, i[INMODE2] = label element bytes (1 = uint8, 4 = int32; 0 = no labels: the patch chain),
+                             * i[AUX0] = train (0 / 1), i[AUX1] = maskLabel flags, i[COUNT] = 1 when a parameter row may hold a contrast
+                             * operation (the statistics launch runs), 0 promises that none does (a row that does anyway blends towards 0);
+                             * p[IN] = frames uint8[B][Hs][Ws][3], p[IN2] = labels [B][Hs][Ws], p[X1] / p[X2] = frame tables of x / y, p[X3] / p[X4] =
+                             * label index tables of x / y (the four as RCV_OP_BATCH_PREP), p[IN_C] = parameter rows float[B][12] (train only),
+                             * p[OUT] = imgs float[B][3][H][W], p[X0] = targets int64[B][H][W], p[PART] = uint32[i[NPART]]: one partial sum of L
+                             * per workgroup of the statistics launch (i[NPART] filled by rcv_op_workspace; 0 unless train and i[COUNT])     */
 };
 
 /* i[RCV_I_AUX0] of RCV_OP_PRUNE: how the threshold of a tensor is chosen */
@@ -496,6 +507,33 @@ int rcv_batch_prep(rcv_handle* h, const uint8_t* frames, const void* labels, int
  * bit for bit what rcv_batch_prep(train = 0) writes for the same frames and tables.                                                */
 int rcv_frame_prep(rcv_handle* h, const uint8_t* frames, int B, int Hs, int Ws, int H, int W, const int32_t* frame_x, int kx,
                    const int32_t* frame_y, int ky, const float* norm, float* imgs, void* stream);
+
+/* RCV_OP_RGB_PREP: the RGB loader of trainer.py:75-123 (SSDataSet with Scale / HorizontalFlip / VerticalFlip / torchvision's PIL
+ * ColorJitter / ToYUV / ToTensor / Normalize([.5,0,0],[.5,.5,.5]); the same chain feeds pruner.py, labelPropTrain.py, tester.py,
+ * makeLPImages.py, classTrainer.py and objDetEval.py) for a whole batch, on the caller's stream.  frames, labels, the four tables, imgs
+ * and targets are rcv_batch_prep's; labels == NULL (then label_bytes = 0, label_x / label_y / targets are not looked at) is the patch
+ * chain, which has no label plane.  Per image, in this order:
+ *   1. resize: Pillow's 8-bit BILINEAR (frame) / NEAREST (label) from the tables; equal sizes leave the bytes as they are;
+ *   2. with train != 0 the row params[b] = {hflip, vflip, n_ops, op0, op1, op2, op3, f_brightness, f_contrast, f_saturation, hue_shift,
+ *      0}: x mirrored when hflip != 0, y mirrored when vflip != 0 (frame and label alike), then the first n_ops (0..4) operations in the
+ *      row's order on the uint8 RGB pixel, as Pillow computes them (0 = brightness, 1 = contrast, 2 = saturation, 3 = hue; any other code
+ *      does nothing).  Image.blend(d, x, f) per byte, fp32 with separately rounded multiply and add: t = d + f (x - d); 0 if t <= 0, 255
+ *      if t >= 255, else t truncated.  brightness = blend(0, x, f); contrast = blend(m, x, f), m = floor((2 sum L + n) / (2 n)) over the
+ *      n pixels of the image as it stands when the operation runs; saturation = blend(L, x, f); L = (19595 R + 38470 G + 7471 B + 32768)
+ *      >> 16.  hue = Pillow's convert("HSV"), H = (H + hue_shift) & 255, convert("RGB"), with every rounding where Pillow has it
+ *      (csrc/rgb_prep.hip lists them); the round trip is taken for hue_shift = 0 as well.
+ *   3. c = byte / 255.0 in fp64; y, u, v = the rows {0.299, 0.587, 0.114}, {-0.14714119, -0.28886916, 0.43601035}, {0.61497538,
+ *      -0.51496512, -0.10001026} times (r, g, b), each product rounded, summed left to right (no fused multiply-add); imgs =
+ *      ((y - 0.5) / 0.5, u / 0.5, v / 0.5) rounded once to fp32.
+ *   4. label: gather, mirrors, maskLabel (mask_flags as rcv_batch_prep), widened to int64.
+ * Contrast depends on the whole image: with stats != 0 a first launch leaves one integer partial sum of L per workgroup in `workspace`
+ * (rcv_op_workspace bytes of the record; nothing to zero, no atomics) and the main launch sums its image's partials in a fixed order;
+ * stats == 0 promises that no row holds a contrast operation and skips that launch (validation mode takes neither).  Exact: integers,
+ * and fp32 / fp64 operations with the roundings above.  No random numbers and no trigonometry on the device.                      */
+int rcv_rgb_prep(rcv_handle* h, const uint8_t* frames, const void* labels /*may be NULL*/, int label_bytes, int B, int Hs, int Ws, int H, int W,
+                 const int32_t* frame_x, int kx, const int32_t* frame_y, int ky, const int32_t* label_x, const int32_t* label_y,
+                 const float* params /*NULL unless train*/, int train, int stats, int mask_flags, float* imgs, int64_t* targets,
+                 void* workspace, size_t workspace_bytes, void* stream);
 
 /* RCV_OP_CLS_LABEL, source form 0 without the fused decoder input: labels uint8[N][H][W] = first arg-max over c of
  * (bias[c] + sum_k x[p][k] w[c][k]) (detect.py:131-132), colour uint8[N][H][W][3] = palette[label] (detect.py:133 Colorize) or NULL;

@@ -16,7 +16,8 @@ def __getattr__(name):
     if name == "data":
         import importlib
         return importlib.import_module(".data", __name__)
-    if name in ("prepare_batch", "prepare_frames", "draw_jitter", "SSYUVDataset"):
+    # ... and the RGB loader of trainer.py / pruner.py: prepare_rgb_batch / draw_color_jitter / SSDataSet
+    if name in ("prepare_batch", "prepare_frames", "draw_jitter", "SSYUVDataset", "prepare_rgb_batch", "draw_color_jitter", "SSDataSet"):
         from . import data
         return getattr(data, name)
     # class maps and colour masks on the device (detect.py): palette.py, infer.py

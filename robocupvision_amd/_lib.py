@@ -30,6 +30,7 @@ OP_BNN_STAGE_FWD, OP_BNN_STAGE_BWD, OP_BNN_HEAD_FWD, OP_BNN_HEAD_BWD = 39, 40, 4
 OP_CE_NORM, OP_CLS_STEP = 43, 44     # the classifier's forward + loss + backward in one pass, and its normaliser pre-pass (rcv.h, csrc/small_kernels.hip)
 OP_PRUNE = 45               # the three mask builders of the prune stage, one workgroup per weight tensor (rcv.h RCV_OP_PRUNE, csrc/prune.hip)
 OP_OBJECTS = 46             # boxes, areas and centres of the components of a class map (rcv.h RCV_OP_OBJECTS, csrc/objects.hip)
+OP_RGB_PREP = 47            # the RGB loader of trainer.py / pruner.py for a whole batch: PIL ColorJitter, rgb2yuv (rcv.h RCV_OP_RGB_PREP, csrc/rgb_prep.hip)
 PRUNE_MAX_RATIO, PRUNE_STD_SEARCH, PRUNE_SMALLEST_K = range(3)      # i[AUX0] of OP_PRUNE: pruneModelNew / pruneModel / pruneModel2
 PRUNE_MAX_ITER = 4096
 PRUNE_ST_OK, PRUNE_ST_NO_END, PRUNE_ST_ALL_ZERO, PRUNE_ST_BAD_JOB = range(4)
@@ -73,7 +74,7 @@ EXPORTS = [
     "rcv_dice_fwd", "rcv_dice_bwd", "rcv_sgd_step", "rcv_create_planner", "rcv_adam_l1_step_pruned", "rcv_op_filter_layout",
     "rcv_object_match", "rcv_labelprop_batch", "rcv_batch_prep", "rcv_frame_prep", "rcv_cls_label", "rcv_colorize",
     "rcv_bnn_stage_fwd", "rcv_bnn_stage_bwd", "rcv_bnn_head_fwd", "rcv_bnn_head_bwd",
-    "rcv_sgd_step_pruned", "rcv_prune_check", "rcv_prune", "rcv_find_objects",
+    "rcv_sgd_step_pruned", "rcv_prune_check", "rcv_prune", "rcv_find_objects", "rcv_rgb_prep",
 ]
 
 
@@ -121,6 +122,8 @@ def load():
         lib.rcv_batch_prep.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p, C.c_int, C.c_void_p, C.c_int] + \
             [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.rcv_frame_prep.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 3
+        lib.rcv_rgb_prep.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p, C.c_int, C.c_void_p, C.c_int] + \
+            [C.c_void_p] * 3 + [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         lib.rcv_cls_label.argtypes = [C.c_void_p] * 4 + [C.c_int] * 5 + [C.c_void_p] * 4
         lib.rcv_colorize.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 3
         lib.rcv_sgd_step.argtypes = [C.c_void_p] * 5 + [C.c_int64, C.c_float, C.c_float, C.c_float, C.c_int, C.c_float, C.c_void_p]

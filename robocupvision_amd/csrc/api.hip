@@ -117,6 +117,8 @@ static int dispatch(const rcv_handle* h, const rcv_op* op, hipStream_t s, OpQuer
     case RCV_OP_BATCH_PREP:
     case RCV_OP_FRAME_PREP:
       return rcv_launch_batch_prep(h, op, s, q);
+    case RCV_OP_RGB_PREP:
+      return rcv_launch_rgb_prep(h, op, s, q);
     case RCV_OP_CLS_LABEL:
       return rcv_launch_cls_label(h, op, s, q);
     case RCV_OP_BNN_STAGE_FWD:
@@ -438,6 +440,25 @@ int rcv_frame_prep(rcv_handle* h, const uint8_t* frames, int B, int Hs, int Ws, 
   op.i[RCV_I_N] = B; op.i[RCV_I_H] = Hs; op.i[RCV_I_W] = Ws; op.i[RCV_I_HO] = H; op.i[RCV_I_WO] = W; op.i[RCV_I_CIN] = kx; op.i[RCV_I_COUT] = ky;
   op.p[RCV_P_IN] = (void*)frames; op.p[RCV_P_OUT] = imgs; op.p[RCV_P_X1] = (void*)frame_x; op.p[RCV_P_X2] = (void*)frame_y;
   op.p[RCV_P_X5] = (void*)norm;
+  return rcv_run(h, &op, 1, stream);
+}
+
+int rcv_rgb_prep(rcv_handle* h, const uint8_t* frames, const void* labels, int label_bytes, int B, int Hs, int Ws, int H, int W,
+                 const int32_t* frame_x, int kx, const int32_t* frame_y, int ky, const int32_t* label_x, const int32_t* label_y,
+                 const float* params, int train, int stats, int mask_flags, float* imgs, int64_t* targets, void* workspace,
+                 size_t workspace_bytes, void* stream) {
+  rcv_op op;
+  memset(&op, 0, sizeof(op));
+  op.kind = RCV_OP_RGB_PREP;
+  op.i[RCV_I_N] = B; op.i[RCV_I_H] = Hs; op.i[RCV_I_W] = Ws; op.i[RCV_I_HO] = H; op.i[RCV_I_WO] = W; op.i[RCV_I_CIN] = kx; op.i[RCV_I_COUT] = ky;
+  op.i[RCV_I_INMODE2] = labels ? label_bytes : 0; op.i[RCV_I_AUX0] = train; op.i[RCV_I_AUX1] = mask_flags; op.i[RCV_I_COUNT] = stats;
+  op.p[RCV_P_IN] = (void*)frames; op.p[RCV_P_IN2] = (void*)labels; op.p[RCV_P_OUT] = imgs; op.p[RCV_P_X0] = targets;
+  op.p[RCV_P_X1] = (void*)frame_x; op.p[RCV_P_X2] = (void*)frame_y; op.p[RCV_P_X3] = (void*)label_x; op.p[RCV_P_X4] = (void*)label_y;
+  op.p[RCV_P_IN_C] = (void*)params; op.p[RCV_P_PART] = workspace;
+  size_t need = 0;
+  const int rc = rcv_op_workspace(h, &op, &need);
+  if (rc) return rc;
+  RCV_CHECK_ARG(workspace_bytes >= need, "rcv_rgb_prep: workspace of %zu bytes given, %zu needed (rcv_op_workspace)", workspace_bytes, need);
   return rcv_run(h, &op, 1, stream);
 }
 
