@@ -1,0 +1,95 @@
+"""Shapes, load modes and record builders of the dilated and decoder-order cases of tests/test_gpu_kernels.py: the conv / transposed-conv
+/ filter-gradient records that PB_FCN, PB_FCN_2 and LabelProp emit in training (engine.py bwd_conv / bwd_up; model.py ConvPoolSimple /
+ConvPool) and the ROBO-UNet / U-Net step does not -- dilation 2 on NHWC operands, the `bn_relu` order (gathered operand
+RCV_LOAD_AFFINE_RELU, gradient RCV_LOAD_GRAD_DEC) and the `relu` order (RCV_LOAD_PLAIN, RCV_LOAD_GRAD_ENC with the rows (1, 0, 0)).
+
+Records only, no tensors and no device: tests/test_lib_abi.py plans every one of them on the planning handle and pins the kernel
+labels they reach, so that a planner change which moves them onto another kernel shows there and not as a silent loss of coverage."""
+from robocupvision_amd import _lib as L
+
+# (N, H, W, Cin, Cout, stride, dilation): the smallest planes that still reach each kernel, its ragged edges and its
+# several-tiles-per-workgroup path; label -> shapes as the planner answers for 256 CUs (layout 0)
+DILATED_CONV_LABELS = {
+    (2, 37, 53, 64, 128, 1, 2): "conv_dma<1,5,4,1,4>", (2, 37, 53, 128, 64, 1, 2): "conv_dma<1,5,4,1,4>",
+    (3, 5, 7, 128, 64, 1, 2): "conv_dma<1,5,4,1,4>", (2, 3, 4, 64, 64, 1, 2): "conv_dma<1,5,4,1,4>",
+    (2, 30, 40, 64, 32, 1, 2): "conv_mfma<1,5,2,2,8>",
+    (2, 33, 47, 16, 16, 1, 2): "convs_mfma<1,5,16>", (2, 33, 47, 8, 16, 1, 2): "convs_mfma<1,5,8>",
+    (2, 33, 47, 32, 16, 1, 2): "convs_mfma<1,3,32>",
+    (1, 2, 2, 32, 32, 1, 2): "convs_mfma<2,3,32>",          # every off-centre tap lies in the padding
+}
+DILATED_CONV_SHAPES = list(DILATED_CONV_LABELS)
+STRIDE2_DILATED_CONV_SHAPES = [(2, 24, 40, 64, 64, 2, 2), (2, 33, 47, 16, 32, 2, 2)]
+STRIDE2_CONV_SHAPES = [(2, 48, 64, 16, 32, 2, 1), (2, 30, 40, 32, 64, 2, 1), (2, 14, 18, 64, 128, 2, 1), (2, 48, 64, 8, 16, 2, 1)]
+STRIDE1_CONV_SHAPES = [(4, 30, 40, 64, 64, 1, 1), (4, 30, 40, 32, 32, 1, 1), (2, 37, 53, 16, 16, 1, 1)]
+CONV_RECORD_SHAPES = DILATED_CONV_SHAPES + STRIDE2_DILATED_CONV_SHAPES + STRIDE2_CONV_SHAPES + STRIDE1_CONV_SHAPES
+
+# load mode of the gathered operand -> (RCV_LOAD_*, flags, statistics).  The two gradient loads as the data-gradient launches carry them
+# (a residual: the skip tensor's share); the two activation loads with the statistics of the training forward -- without statistics most
+# of these planes go to conv_small.
+CONV_RECORD_MODES = {
+    "grad_dec": (L.LOAD_GRAD_DEC, L.F_RESID, L.STATS_NONE),
+    "grad_enc_relu": (L.LOAD_GRAD_ENC, L.F_RESID, L.STATS_NONE),        # constants (1, 0, 0): relu(conv) without a BatchNorm
+    "affine_relu": (L.LOAD_AFFINE_RELU, L.F_BIAS, L.STATS_FWD),
+    "plain": (L.LOAD_PLAIN, L.F_BIAS, L.STATS_FWD),
+}
+TCONV_RECORD_MODES = {"grad_dec": L.LOAD_GRAD_DEC, "affine_relu": L.LOAD_AFFINE_RELU, "plain": L.LOAD_PLAIN}
+
+
+def conv_layouts(Cin, Cout, s, d):
+    """Filter layouts (rcv_op_filter_layout) a conv record of this shape is run under: 0 plain, 2 Winograd, 3 / 5 split-bf16 -- at
+    dilation 1 what test_gpu_kernels._conv_layouts enumerates; no Winograd and no split-bf16 kernel takes dilation 2."""
+    if d != 1:
+        return [0]
+    return [0] + ([2] if (s == 1 and Cin % 16 == 0 and Cin >= 32 and Cout >= 64) else []) + \
+        ([3] if (s == 1 and Cin % 32 == 0 and Cin >= 64 and Cout >= 64) or (Cin in (8, 16, 32) and Cout <= 32) else []) + \
+        ([5] if (s == 2 and Cin % 16 == 0 and Cin >= 32 and Cout >= 64) else [])
+
+
+def conv_record(shape, mode_name, layout, **ptrs):
+    N, H, W, Cin, Cout, s, d = shape
+    mode, flags, stats = CONV_RECORD_MODES[mode_name]
+    return L.make_op(L.OP_CONV, flags, n=N, h=H, w=W, cin=Cin, cout=Cout, ho=(H - 1) // s + 1, wo=(W - 1) // s + 1, stride=s, dil=d,
+                     inmode=mode, stats=stats, aux0=layout, **ptrs)
+
+
+def tconv_record(shape, mode_name, layout, **ptrs):
+    N, H, W, Cin, Cout = shape
+    return L.make_op(L.OP_TCONV, L.F_BIAS, n=N, h=H, w=W, cin=Cin, cout=Cout, ho=2 * H, wo=2 * W, stride=2, dil=1,
+                     inmode=TCONV_RECORD_MODES[mode_name], aux0=layout, **ptrs)
+
+
+# ------------------------------------------------------------------------------------------ filter gradients
+# (gathered, pointwise) load modes -> (RCV_LOAD_* of the gathered operand, of the pointwise operand, flags)
+WGRAD_RECORD_PAIRS = {
+    "affine_relu,grad_dec": (L.LOAD_AFFINE_RELU, L.LOAD_GRAD_DEC, 0),     # a bn_relu conv after a bn_relu producer: bias ahead of a BatchNorm
+    "plain,grad_enc_relu": (L.LOAD_PLAIN, L.LOAD_GRAD_ENC, 0),           # ConvPool.conv1: constants (1, 0, 0)
+    "affine,grad_dec": (L.LOAD_AFFINE, L.LOAD_GRAD_DEC, L.F_BIAS),       # a bn_relu conv after a relu_bn producer; here with the bias sums
+}
+# run-time-geometry wgrad_mfma tiles (no split-bf16 kernel takes dilation 2)
+DILATED_WGRAD_SHAPES = DILATED_CONV_SHAPES + STRIDE2_DILATED_CONV_SHAPES + [(2, 37, 53, 128, 128, 1, 2)]
+DILATED_WGRAD_LABELS = {"wgrad_mfma<2,2,2,2,1,f0>", "wgrad_mfma<2,2,1,2,2,f0>", "wgrad_mfma<1,1,1,1,4,f0>", "wgrad_mfma<1,1,1,1,4,f5>",
+                        "wgrad_mfma<1,2,1,1,4,f0>", "wgrad_mfma<2,2,1,1,4,f0>", "wgrad_mfma<2,1,1,1,4,f0>"}
+# dilation 1, each under flags 0 (the split-bf16 kernel where the planner has one) and under RCV_F_MFMA_FP32 (always wgrad_mfma);
+# shape -> (label under flags 0, label under RCV_F_MFMA_FP32) as the planner answers for 256 CUs: the last two planes are too small for a
+# split-bf16 kernel and stay on the fp32 matrix instruction either way
+MATRIX_WGRAD_LABELS = {(4, 15, 20, 64, 64, 1, 1): ("wgrad_bf3<8>", "wgrad_mfma<2,2,2,2,1,f0>"),
+                       (4, 15, 20, 128, 128, 1, 1): ("wgrad_bf3<8>", "wgrad_mfma<2,2,2,2,1,f0>"),
+                       (8, 64, 128, 16, 16, 1, 1): ("wgradn_bf3<16,1>", "wgrad_mfma<1,1,1,1,4,f0>"),
+                       (8, 128, 128, 16, 32, 2, 1): ("wgradn_bf3<8,2>", "wgrad_mfma<2,1,1,1,4,f0>"),
+                       (4, 30, 40, 32, 64, 2, 1): ("wgrad_mfma<2,2,2,1,2,f0>", "wgrad_mfma<2,2,2,1,2,f0>"),
+                       (3, 14, 18, 64, 128, 2, 1): ("wgrad_mfma<2,2,2,2,1,f0>", "wgrad_mfma<2,2,2,2,1,f0>")}
+MATRIX_WGRAD_SHAPES = list(MATRIX_WGRAD_LABELS)
+
+
+def wgrad_kernel(shape, matrix_flags):
+    """The kernel family (label ahead of '<') a filter-gradient record of these cases runs on."""
+    if shape not in MATRIX_WGRAD_LABELS:
+        return "wgrad_mfma"
+    return MATRIX_WGRAD_LABELS[shape][1 if matrix_flags & L.F_MFMA_FP32 else 0].split("<")[0]
+
+
+def wgrad_record(shape, pair, matrix_flags=0, **ptrs):
+    N, H, W, Cin, Cout, s, d = shape
+    gmode, pmode, flags = WGRAD_RECORD_PAIRS[pair]
+    return L.make_op(L.OP_WGRAD, flags | matrix_flags, n=N, h=H, w=W, cin=Cin, ho=(H - 1) // s + 1, wo=(W - 1) // s + 1, cout=Cout,
+                     stride=s, dil=d, inmode=gmode, inmode2=pmode, **ptrs)

@@ -234,6 +234,10 @@ TCONV_STATS_SHAPES = [(3, 7, 9, 128, 64), (1, 33, 21, 64, 32), (2, 24, 32, 32, 1
 # NCHW-image first layers and the tiny dilated planes (the latter leave conv_small when statistics are requested)
 IMAGE_STATS_SHAPES = [(3, 37, 53, 4, 16, 1, 1), (1, 33, 47, 3, 16, 2, 1), (2, 40, 56, 3, 8, 1, 2), (2, 24, 40, 2, 32, 1, 2), (2, 48, 64, 3, 8, 1, 1)]
 TINY_STATS_SHAPES = [(2, 15, 20, 32, 64, 1, 2), (1, 7, 9, 128, 64, 1, 1), (3, 9, 11, 16, 48, 2, 1), (2, 5, 3, 20, 36, 1, 2)]
+# dilation 2 on NHWC operands (LabelProp conv1..3, PB_FCN conv4..8, ConvPool.conv1): conv_dma, conv_mfma and the run-time-pitch branch
+# of convs_mfma, ragged planes, several tiles per workgroup, stride 2, and a plane whose off-centre taps all lie in the padding
+DILATED_STATS_SHAPES = [(2, 37, 53, 64, 64, 1, 2), (2, 30, 40, 64, 32, 1, 2), (2, 33, 47, 16, 16, 1, 2), (2, 33, 47, 32, 16, 1, 2),
+                        (3, 5, 7, 128, 64, 1, 2), (2, 33, 47, 16, 32, 2, 2), (1, 2, 2, 32, 32, 1, 2)]
 # (statistics kind, flags): F_BIAS = 1, F_RELU = 2, F_RESID = 4.  Sensitivity: every variant of the convs (the input under the centre
 # tap makes the two removed pixels non-zero in every channel); of the transposed convs, whose odd output pixels no centre tap reaches,
 # the variants with a residual (which does the same there).

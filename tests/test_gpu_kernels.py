@@ -2,7 +2,13 @@
 and the load transforms of the step (BatchNorm apply, BatchNorm + ReLU backward), on planes that are large, tiny and ragged.
 
 Bars (max error relative to the largest entry of the fp64 result): convolutions 3e-6 (direct) / 2e-6 (Winograd), filter gradients 5e-7,
-bias gradients 5e-7.  Measured (scripts/experiments/conv_check.py, wgrad_check.py): <= 1.1e-6, <= 4.9e-7, <= 1.7e-7, <= 1.5e-7."""
+bias gradients 5e-7.  Measured (scripts/experiments/conv_check.py, wgrad_check.py): <= 1.1e-6, <= 4.9e-7, <= 1.7e-7, <= 1.5e-7.
+
+The records only PB_FCN, PB_FCN_2 and LabelProp emit in training -- dilation 2 on NHWC operands (also at stride 2), the loads of the
+conv -> BatchNorm -> ReLU order (RCV_LOAD_AFFINE_RELU, RCV_LOAD_GRAD_DEC) and of relu(conv) without a BatchNorm (RCV_LOAD_PLAIN,
+RCV_LOAD_GRAD_ENC with the rows (1, 0, 0)), the fp32-instruction filter gradients under RCV_F_MFMA_FP32 with these loads -- are the
+cases of tests/conv_record_cases.py, at the same bars; measured <= 1.41e-6 (convolutions, dilation 2, 128 input channels), <= 3.3e-7
+(Winograd), <= 1.35e-7 (filter gradients), <= 6.1e-8 (bias gradients); per kernel label in the docstrings of the tests."""
 import os
 import sys
 
@@ -14,6 +20,8 @@ import torch.nn.functional as F
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
+
+import conv_record_cases as RC      # noqa: E402  (tests/conv_record_cases.py: the dilated and decoder-order records)
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
@@ -31,6 +39,8 @@ def _load_fp64(mode, x, aux, c, L):
         return C[0] * torch.where(A * C[3] + C[4] > 0, X, torch.zeros((), dtype=torch.float64)) + C[1] + C[2] * A
     if mode == L.LOAD_AFFINE:          # v = x*c0 + c1
         return X * C[0] + C[1]
+    if mode == L.LOAD_AFFINE_RELU:     # v = max(x*c0 + c1, 0)
+        return torch.clamp_min(X * C[0] + C[1], 0.0)
     return X
 
 
@@ -89,6 +99,78 @@ def test_conv_kernels_vs_fp64(N, H, W, Cin, Cout, s, mode_name):
         err = float((out.double().cpu() - ref).abs().max() / ref.abs().max())
         print(".%s %s: max error %.3e" % (label, (N, H, W, Cin, Cout), err))
         assert err <= (2e-6 if wino == 2 else 3e-6), (label, err)
+
+
+def _relu_grad_rows(C):
+    """The constants of RCV_LOAD_GRAD_ENC behind relu(conv) without a BatchNorm (engine.py bwd_conv): v = aux > 0 ? 1*x + 0 + 0*aux : 0."""
+    c = torch.zeros(5, C)
+    c[0] = 1.0
+    return c
+
+
+@pytest.mark.parametrize("shape", RC.CONV_RECORD_SHAPES, ids=lambda s: "-".join(map(str, s)))
+@pytest.mark.parametrize("mode_name", list(RC.CONV_RECORD_MODES))
+def test_dilated_and_decoder_order_conv_records_vs_fp64(shape, mode_name):
+    """The conv records of PB_FCN / PB_FCN_2 / LabelProp in training that the cases above do not build (tests/conv_record_cases.py):
+    dilation 2 on NHWC operands -- conv_dma<1,5,4,1,4>, conv_mfma<1,5,2,2,8>, convs_mfma<1,5,16> / <1,5,8> / <1,3,32> / <2,3,32> (the
+    run-time-pitch branch of convs_mfma), also at stride 2 -- and, at every shape and under every filter layout of _conv_layouts (so that
+    conv_bf3, conv2_bf3, convn_bf3 and conv_wino see them too), the loads of the `bn_relu` and `relu` orders: RCV_LOAD_GRAD_DEC (random
+    c0..c4) and RCV_LOAD_GRAD_ENC with the rows (1, 0, 0), both with a residual; RCV_LOAD_AFFINE_RELU and RCV_LOAD_PLAIN with the bias and
+    RCV_STATS_FWD of the training forward (NaN-prefilled partial rows; without statistics most of these planes run on conv_small).  The
+    masks are decided in float64 from the fp32 operands: the kernel's single fmaf has the sign of that exact expression.
+    Bars: 3e-6 (2e-6 Winograd) of the largest entry of the fp64 result; the float64 sum of the partial rows within
+    close(rtol=1e-4, floor=1.0) of the float64 sums.
+    Measured (MI355X, largest over the four modes).  Dilation 2: conv_dma<1,5,4,1,4> 1.41e-6 (128 -> 64 channels, plain; 8.8e-7 at
+    stride 2), conv_mfma<1,5,2,2,8> 1.02e-6, convs_mfma<1,5,16> 3.7e-7, <1,5,8> 2.3e-7, <1,3,32> 5.8e-7, <2,3,32> 7.0e-8, <2,2,16>
+    (stride 2) 3.7e-7.  Dilation 1: conv_dma<1,5,4,1,4> 1.03e-6, conv_wino<64,80> 3.3e-7, conv_bf3<64,160> 8.3e-7, conv2_bf3<64,160>
+    6.1e-7, convs_mfma<2,3,32> 5.9e-7, <1,5,16> 4.6e-7, <2,2,16> 3.8e-7, <1,3,8> 2.5e-7, convn_bf3<32,2,3> 5.8e-7, <16,2,3> 3.1e-7,
+    <16,1,5> 2.8e-7, <8,1,3> 1.5e-7.  By mode: grad_dec 1.24e-6, grad_enc (1, 0, 0) 7.6e-7, affine_relu 1.13e-6, plain 1.41e-6."""
+    from robocupvision_amd import _lib as L
+    from test_gpu_blocks import close
+    h = L.handle(0)
+    N, H, W, Cin, Cout, s, d = shape
+    mode, flags, stats = RC.CONV_RECORD_MODES[mode_name]
+    gen = torch.Generator().manual_seed(4000 + H * W + Cin + 7 * d)
+    Ho, Wo = (H - 1) // s + 1, (W - 1) // s + 1
+    x, xa, c = _rand(gen, N, H, W, Cin), _rand(gen, N, H, W, Cin), _rand(gen, 5, Cin, scale=0.5)
+    w, resid, bias = _rand(gen, Cout, Cin, 3, 3, scale=0.1), _rand(gen, N, Ho, Wo, Cout), _rand(gen, Cout)
+    if mode_name == "grad_enc_relu":
+        c = _relu_grad_rows(Cin)
+    ref = F.conv2d(_load_fp64(mode, x, xa, c, L).permute(0, 3, 1, 2), w.double(), stride=s, padding=d, dilation=d).permute(0, 2, 3, 1)
+    ref = ref + (resid.double() if flags & L.F_RESID else bias.double())
+    ref_rows = torch.stack([ref.sum((0, 1, 2)), (ref * ref).sum((0, 1, 2))])
+    xd, xad, cd, wd, rd, bd = (v.to(DEV) for v in (x, xa, c, w, resid, bias))
+    for layout in RC.conv_layouts(Cin, Cout, s, d):
+        rp, cp, nfl = _pack_dims(Cin, Cout, layout)
+        wp = torch.zeros(nfl, device=DEV)
+        job = L.RcvPackJob()
+        job.src, job.dst, job.D0, job.D1 = wd.data_ptr(), wp.data_ptr(), Cout, Cin
+        job.rows_from_d1, job.flip, job.rows_pad, job.cols_pad, job.merged = 1, 0, rp, cp, layout
+        table = torch.frombuffer(bytearray(bytes((L.RcvPackJob * 1)(job))), dtype=torch.uint8).to(DEV)
+        out = torch.full((N, Ho, Wo, Cout), float("nan"), device=DEV)
+        pack = L.make_op(L.OP_PACK, 0, count=1, aux0=16 * rp * cp, p_in=table.data_ptr())
+        conv = RC.conv_record(shape, mode_name, layout, p_in=xd.data_ptr(), p_in_aux=xad.data_ptr(), p_in_c=cd.data_ptr(), p_w=wp.data_ptr(),
+                             p_out=out.data_ptr(), p_resid=rd.data_ptr(), p_bias=bd.data_ptr())
+        part = None
+        if stats != L.STATS_NONE:
+            nbytes = L.op_workspace(h, conv)
+            n_part = conv.i[L.RCV_I_NPART]
+            assert n_part > 0 and nbytes == n_part * 2 * Cout * 4
+            part = torch.full((n_part, 2, Cout), float("nan"), device=DEV)
+            conv.p[L.RCV_P_PART] = part.data_ptr()
+        lst = L.OpList([pack, conv])
+        label = lst.labels(h)[1]
+        assert label.startswith("conv_wino") == (layout == 2) and ("_bf3" in label) == (layout in (3, 5)), label
+        assert not label.startswith("conv_small"), label
+        if shape in RC.DILATED_CONV_LABELS:      # (the tiling itself is pinned for 256 CUs by tests/test_lib_abi.py)
+            assert label.split("<")[0] == RC.DILATED_CONV_LABELS[shape].split("<")[0], label
+        lst.run(h, torch.cuda.current_stream().cuda_stream)
+        torch.cuda.synchronize()
+        err = float((out.double().cpu() - ref).abs().max() / ref.abs().max())
+        print(".%s %s %s: max error %.3e" % (label, shape, mode_name, err))
+        assert err <= (2e-6 if layout == 2 else 3e-6), (label, err)
+        if part is not None:
+            close(part.double().cpu().sum(0), ref_rows, "%s %s %s partial rows" % (label, shape, mode_name), rtol=1e-4, floor=1.0)
 
 
 @pytest.mark.parametrize("N,H,W,Cin,Cout,s,d", [(2, 48, 64, 3, 8, 1, 1), (2, 120, 160, 3, 16, 1, 1), (3, 37, 53, 4, 16, 1, 1), (2, 48, 64, 3, 16, 2, 1),
@@ -183,6 +265,61 @@ def test_filter_gradient_kernels_vs_fp64(N, H, W, Cin, Cout, s, modes):
     assert e <= 5e-7 and eb <= 5e-7, (lst.labels(h)[0], e, eb)
 
 
+@pytest.mark.parametrize("shape", RC.DILATED_WGRAD_SHAPES + RC.MATRIX_WGRAD_SHAPES, ids=lambda s: "-".join(map(str, s)))
+@pytest.mark.parametrize("pair", list(RC.WGRAD_RECORD_PAIRS))
+def test_dilated_and_decoder_order_filter_gradients_vs_fp64(shape, pair):
+    """The filter-gradient records of PB_FCN / PB_FCN_2 / LabelProp that the cases above do not build (tests/conv_record_cases.py).
+    (gathered, pointwise) loads: (RCV_LOAD_AFFINE_RELU, RCV_LOAD_GRAD_DEC) -- a conv -> BatchNorm -> ReLU layer behind another one --,
+    (RCV_LOAD_PLAIN, RCV_LOAD_GRAD_ENC with the rows (1, 0, 0)) -- relu(conv) without a BatchNorm -- and (RCV_LOAD_AFFINE,
+    RCV_LOAD_GRAD_DEC), the last with the bias sums.  Dilation 2 (stride 1 and 2) on the run-time-geometry tiles wgrad_mfma<2,2,2,2,1,f0>,
+    <2,2,1,2,2,f0>, <1,1,1,1,4,f0>, <1,1,1,1,4,f5>, <1,2,1,1,4,f0>, <2,2,1,1,4,f0>, <2,1,1,1,4,f0>; dilation 1 twice, as the planner
+    routes it (wgrad_bf3<8>, wgradn_bf3<16,1>, wgradn_bf3<8,2> where a split-bf16 kernel exists) and under RCV_F_MFMA_FP32 (the
+    fp32-instruction kernels behind every shape the split-bf16 kernels decline).  Bars: 5e-7 of the largest entry of the fp64 result
+    on dw and on db.
+    Measured (MI355X, largest over the three pairs; dw / db): wgrad_mfma<2,2,2,2,1,f0> 1.13e-7 / 6.1e-8, <2,2,1,2,2,f0> 5.3e-8 / 4.8e-8,
+    <1,1,1,1,4,f0> 9.3e-8 / 4.0e-8, <1,1,1,1,4,f5> 7.0e-8 / 2.2e-8, <1,2,1,1,4,f0> 7.6e-8 / 1.7e-8, <2,2,1,1,4,f0> 7.8e-8 / 3.4e-8,
+    <2,1,1,1,4,f0> 7.8e-8 / 3.4e-8, <2,2,2,1,2,f0> 5.1e-8 / 2.8e-8; wgrad_bf3<8> 1.32e-7 / 6.1e-8, wgradn_bf3<16,1> 1.35e-7 / 4.0e-8,
+    wgradn_bf3<8,2> 1.03e-7 / 2.6e-8."""
+    from robocupvision_amd import _lib as L
+    h = L.handle(0)
+    N, H, W, Cin, Cout, s, d = shape
+    gmode, pmode, flags = RC.WGRAD_RECORD_PAIRS[pair]
+    gen = torch.Generator().manual_seed(6000 + H * W + Cout + 7 * d)
+    Ho, Wo = (H - 1) // s + 1, (W - 1) // s + 1
+    G, P, Pa = _rand(gen, N, H, W, Cin), _rand(gen, N, Ho, Wo, Cout), _rand(gen, N, Ho, Wo, Cout)
+    gc, pc = torch.rand(5, Cin, generator=gen) + 0.5, _rand(gen, 5, Cout, scale=0.5)
+    if gmode == L.LOAD_AFFINE_RELU:      # shifts of both signs: part of every channel is clamped
+        gc[1] = _rand(gen, Cin, scale=0.5)
+    if pair == "plain,grad_enc_relu":
+        pc = _relu_grad_rows(Cout)
+    x64, gy64 = _load_fp64(gmode, G, G, gc, L), _load_fp64(pmode, P, Pa, pc, L)
+    ref = torch.nn.grad.conv2d_weight(x64.permute(0, 3, 1, 2), (Cout, Cin, 3, 3), gy64.permute(0, 3, 1, 2), stride=s, padding=d, dilation=d)
+    refb = gy64.sum((0, 1, 2))
+    Gd, Pd, Pad, gcd, pcd = (v.to(DEV) for v in (G, P, Pa, gc, pc))
+    has_bias = bool(flags & L.F_BIAS)
+    for matrix_flags in ((0,) if d != 1 else (0, L.F_MFMA_FP32)):
+        dw = torch.full((Cout, Cin, 3, 3), float("nan"), device=DEV)
+        db = torch.full((Cout,), float("nan"), device=DEV)
+        op = RC.wgrad_record(shape, pair, matrix_flags, p_in=Gd.data_ptr(), p_in_c=gcd.data_ptr(), p_in2=Pd.data_ptr(),
+                             p_in2_aux=Pad.data_ptr(), p_in2_c=pcd.data_ptr())
+        nb = L.op_workspace(h, op)
+        part = torch.zeros(max(nb // 4, 4), device=DEV)
+        op.p[L.RCV_P_PART] = part.data_ptr()
+        red = L.make_op(L.OP_WGRAD_REDUCE, 0, cin=Cin, cout=Cout, nsplit=op.i[L.RCV_I_NSPLIT], p_part=part.data_ptr(), p_out=dw.data_ptr(),
+                        p_bias=db.data_ptr() if has_bias else 0)
+        lst = L.OpList([op, red])
+        label = lst.labels(h)[0]
+        # a split-bf16 kernel exactly where the planner has one for the shape, never under RCV_F_MFMA_FP32, never at dilation 2
+        want = RC.wgrad_kernel(shape, matrix_flags)
+        assert label.split("<")[0] == want and ("_bf3" in label) == ("_bf3" in want), (label, want)
+        lst.run(h, torch.cuda.current_stream().cuda_stream)
+        torch.cuda.synchronize()
+        e = float((dw.double().cpu() - ref).abs().max() / ref.abs().max())
+        eb = float((db.double().cpu() - refb).abs().max() / refb.abs().max()) if has_bias else 0.0
+        print(".%s %s %s: max error %.3e (bias %.3e)" % (label, shape, pair, e, eb))
+        assert e <= 5e-7 and eb <= 5e-7, (label, e, eb)
+
+
 @pytest.mark.parametrize("N,H,W,Cin,Cout,s,d", [(2, 48, 64, 3, 8, 1, 1), (2, 40, 56, 3, 8, 1, 2), (2, 48, 64, 3, 16, 1, 1), (2, 37, 53, 4, 16, 1, 1),
                                                (2, 48, 64, 3, 32, 1, 1), (2, 48, 64, 4, 8, 1, 1), (1, 96, 128, 3, 16, 2, 1), (3, 24, 40, 2, 8, 1, 1)])
 @pytest.mark.parametrize("two", [False, True])
@@ -223,14 +360,18 @@ TCONV_SHAPES = [(2, 15, 20, 128, 64), (2, 30, 40, 64, 32), (2, 60, 80, 32, 16), 
 
 
 @pytest.mark.parametrize("N,H,W,Cin,Cout", TCONV_SHAPES)
-@pytest.mark.parametrize("mode_name", ["affine", "grad_enc"])
+@pytest.mark.parametrize("mode_name", ["affine", "grad_enc"] + list(RC.TCONV_RECORD_MODES))
 def test_transposed_conv_kernels_vs_fp64(N, H, W, Cin, Cout, mode_name):
     """ConvTranspose2d(k3, s2, p1, output_padding 1) in its three kernel forms (all-parity LDS-DMA tile, merged-parity narrow tile,
-    phase-split fallback) -- the forward of the decoder blocks and the data gradient of the stride-2 convs: 3e-6 of the fp64 result."""
+    phase-split fallback) -- the forward of the decoder blocks and the data gradient of the stride-2 convs: 3e-6 of the fp64 result.
+    Load modes: BatchNorm apply and the BatchNorm + ReLU backward of the U-Net step; RCV_LOAD_GRAD_DEC (the data gradient of
+    ConvPoolSimple(..., stride 2): conv -> BatchNorm -> ReLU), RCV_LOAD_AFFINE_RELU and RCV_LOAD_PLAIN (a decoder block behind such a conv,
+    behind relu(conv)).  Measured under the three latter modes (MI355X): tconva_dma<1,5,4,1,4> 8.8e-7, tconva_dma<1,5,2,2,4> 6.2e-7,
+    tconvms_mfma<4,3,32> 4.8e-7, <4,3,16> 2.6e-7, <2,5,16> 2.2e-7, tconvn_bf3<32,4,3> 2.8e-7, <16,2,5> 1.6e-7."""
     from robocupvision_amd import _lib as L
     from robocupvision_amd.engine import MERGED_TCONV_MAX_COUT
     h = L.handle(0)
-    mode = {"grad_enc": L.LOAD_GRAD_ENC, "affine": L.LOAD_AFFINE}[mode_name]
+    mode = dict(RC.TCONV_RECORD_MODES, grad_enc=L.LOAD_GRAD_ENC, affine=L.LOAD_AFFINE)[mode_name]
     gen = torch.Generator().manual_seed(3000 + H * W + Cin)
     x, xa, c = _rand(gen, N, H, W, Cin), _rand(gen, N, H, W, Cin), _rand(gen, 5, Cin, scale=0.5)
     w, bias = _rand(gen, Cin, Cout, 3, 3, scale=0.1), _rand(gen, Cout)
@@ -258,7 +399,7 @@ def test_transposed_conv_kernels_vs_fp64(N, H, W, Cin, Cout, mode_name):
         lst.run(h, torch.cuda.current_stream().cuda_stream)
         torch.cuda.synchronize()
         err = float((out.double().cpu() - ref).abs().max() / ref.abs().max())
-        print(".%s %s: max error %.3e" % (label, (N, H, W, Cin, Cout), err))
+        print(".%s %s %s: max error %.3e" % (label, (N, H, W, Cin, Cout), mode_name, err))
         assert err <= 3e-6, (label, err)
 
 
@@ -338,9 +479,7 @@ def test_tiny_plane_conv_vs_fp64(N, H, W, Cin, Cout, s, d, mode_name, flags):
 # ------------------------------------------------------------------------------------------ epilogue statistics
 def _conv_layouts(Cin, Cout, s):
     """The filter layouts test_conv_kernels_vs_fp64 enumerates for a shape."""
-    return [0] + ([2] if (s == 1 and Cin % 16 == 0 and Cin >= 32 and Cout >= 64) else []) + \
-        ([3] if (s == 1 and Cin % 32 == 0 and Cin >= 64 and Cout >= 64) or (Cin in (8, 16, 32) and Cout <= 32) else []) + \
-        ([5] if (s == 2 and Cin % 16 == 0 and Cin >= 32 and Cout >= 64) else [])
+    return RC.conv_layouts(Cin, Cout, s, 1)
 
 
 def _stats_case_on_device(c, layout, merged, labels, variants=None, randn=False):
@@ -403,7 +542,7 @@ def _stats_case_on_device(c, layout, merged, labels, variants=None, randn=False)
             what, bad.shape[0], bad[0].tolist(), float(rows[tuple(bad[0])]), float(ref[tuple(bad[0].tolist())]))
 
 
-@pytest.mark.parametrize("family", ["conv", "tconv", "image", "tiny"])
+@pytest.mark.parametrize("family", ["conv", "tconv", "image", "tiny", "dilated"])
 def test_epilogue_statistics_exact(family):
     """The per-workgroup partial rows of RCV_STATS_FWD (with F_BIAS|F_RELU, without flags, with F_BIAS|F_RESID), RCV_STATS_BWD_ENC and
     RCV_STATS_BWD_DEC (both with F_RESID; p[EPI_C] = (c0, c1, mean), pixels with e*c0 + c1 == 0 masked) of every conv / transposed
@@ -414,11 +553,14 @@ def test_epilogue_statistics_exact(family):
     convs_mfma<2,3,32> / <1,5,16> / <1,3,16> / <1,3,8> / <1,5,8> / <2,2,16>, convn_bf3<32,2,3> / <16,1,5> / <8,1,5> / <16,2,3> (conv);
     tconva_dma<1,5,4,1,4> / <1,5,2,2,4>, tconvms_mfma<4,3,32> / <4,3,16> / <2,5,16>, tconvn_bf3<32,4,3> / <16,2,5> (tconv); conv_first<1> /
     <2> (RCV_STATS_FWD without a residual), convs_mfma<1,5,4> / <2,5,4> (NCHW image); the tiny dilated planes leave conv_small, which
-    takes no statistics, for conv_dma<1,5,4,1,4>, conv_mfma<1,5,1,2,8> / <1,5,1,2,4>."""
+    takes no statistics, for conv_dma<1,5,4,1,4>, conv_mfma<1,5,1,2,8> / <1,5,1,2,4>; dilation 2 on NHWC operands (ragged planes, several
+    tiles per workgroup, stride 2, a 2 x 2 plane whose off-centre taps all lie in the padding): conv_dma<1,5,4,1,4>,
+    conv_mfma<1,5,2,2,8>, convs_mfma<1,5,16> / <1,3,32> / <2,2,16> / <2,3,32> (dilated)."""
     import small_ops_cases as K
     from robocupvision_amd.engine import MERGED_TCONV_MAX_COUT
     labels = set()
-    shapes = dict(conv=K.CONV_STATS_SHAPES, tconv=K.TCONV_STATS_SHAPES, image=K.IMAGE_STATS_SHAPES, tiny=K.TINY_STATS_SHAPES)[family]
+    shapes = dict(conv=K.CONV_STATS_SHAPES, tconv=K.TCONV_STATS_SHAPES, image=K.IMAGE_STATS_SHAPES, tiny=K.TINY_STATS_SHAPES,
+                  dilated=K.DILATED_STATS_SHAPES)[family]
     for shape in shapes:
         c = K.build_conv_stats(shape, transposed=family == "tconv", nchw=family == "image")
         if family == "conv":
@@ -432,7 +574,8 @@ def test_epilogue_statistics_exact(family):
             _stats_case_on_device(c, 0, False, labels)
     print(".epilogue statistics %s: labels %s" % (family, sorted(labels)))
     expected = dict(conv={"conv_dma", "conv_mfma", "conv_wino", "conv_bf3", "conv2_bf3", "convs_mfma", "convn_bf3"},
-                    tconv={"tconva_dma", "tconvms_mfma", "tconvn_bf3"}, image={"conv_first", "convs_mfma"}, tiny={"conv_dma", "conv_mfma"})[family]
+                    tconv={"tconva_dma", "tconvms_mfma", "tconvn_bf3"}, image={"conv_first", "convs_mfma"}, tiny={"conv_dma", "conv_mfma"},
+                    dilated={"conv_dma", "conv_mfma", "convs_mfma"})[family]
     assert labels == expected, (family, sorted(labels))
 
 

@@ -111,3 +111,78 @@ def test_planner_accepts_every_layer_shape_of_the_networks():
                                    inmode=L.LOAD_AFFINE, stats=L.STATS_FWD)
                     assert L.op_workspace(h, op) >= 0
     assert {"wgrad_mfma", "wgrad_first", "conv_dma", "convs_mfma"} <= labels, labels
+
+
+def test_planner_routes_the_dilated_and_decoder_order_records():
+    """Planner pin (no GPU) of the dilated and decoder-order cases of tests/test_gpu_kernels.py (tests/conv_record_cases.py) and of the
+    dilated integer-grid statistics cases (tests/small_ops_cases.py): every record gets a plan, a workspace size and a label for 256 and
+    for 64 CUs, and at 256 CUs the kernels reached are the ones written here -- a planner change that moves these cases onto another
+    kernel shows as a failure of this test, not as a silent loss of coverage of the kernel they were chosen for."""
+    import conv_record_cases as RC
+    import small_ops_cases as K
+    from robocupvision_amd.engine import MERGED_TCONV_MAX_COUT
+    from test_gpu_kernels import TCONV_SHAPES
+
+    def plan(h, op, statistics=False):
+        nbytes = L.op_workspace(h, op)
+        if op.kind == L.OP_WGRAD:
+            assert nbytes > 0 and op.i[L.RCV_I_NSPLIT] >= 1
+        elif statistics:
+            assert op.i[L.RCV_I_NPART] > 0 and nbytes == op.i[L.RCV_I_NPART] * 2 * op.i[L.RCV_I_COUT] * 4
+        else:
+            assert nbytes == 0
+        label = L.OpList([op]).labels(h)[0]
+        assert "<" in label, label
+        return label
+
+    reached = {}
+    for cus in (256, 64):
+        h = L.planner_handle(cus)
+        conv, tconv, wgrad, stats = set(), set(), set(), set()
+        # 1. conv records: every shape x load mode x filter layout
+        for shape in RC.CONV_RECORD_SHAPES:
+            N, H, W, Cin, Cout, s, d = shape
+            for mode_name, (_, _, st) in RC.CONV_RECORD_MODES.items():
+                for layout in RC.conv_layouts(Cin, Cout, s, d):
+                    label = plan(h, RC.conv_record(shape, mode_name, layout), st != L.STATS_NONE)
+                    assert label.startswith("conv_wino") == (layout == 2) and ("_bf3" in label) == (layout in (3, 5)), (shape, label)
+                    if cus == 256 and shape in RC.DILATED_CONV_LABELS:
+                        assert label == RC.DILATED_CONV_LABELS[shape], (shape, mode_name, label)
+                    conv.add(label.split("<")[0])
+        for shape in TCONV_SHAPES:
+            merged = 1 if shape[4] <= MERGED_TCONV_MAX_COUT else 0
+            for layout in [merged] + ([4] if merged and (shape[3], (4 * shape[4] + 15) // 16 * 16) in ((16, 32), (32, 64)) else []):
+                for mode_name in RC.TCONV_RECORD_MODES:
+                    label = plan(h, RC.tconv_record(shape, mode_name, layout))
+                    assert ("_bf3" in label) == (layout == 4), (shape, label)
+                    tconv.add(label.split("<")[0])
+        # 2. filter-gradient records: the dilated ones, and dilation 1 as routed and under RCV_F_MFMA_FP32
+        dilated = set()
+        for pair in RC.WGRAD_RECORD_PAIRS:
+            for shape in RC.DILATED_WGRAD_SHAPES:
+                label = plan(h, RC.wgrad_record(shape, pair))
+                assert label.startswith("wgrad_mfma<"), (shape, label)
+                dilated.add(label)
+                wgrad.add(label.split("<")[0])
+            for shape in RC.MATRIX_WGRAD_SHAPES:
+                for k, matrix_flags in enumerate((0, L.F_MFMA_FP32)):
+                    label = plan(h, RC.wgrad_record(shape, pair, matrix_flags))
+                    if cus == 256:
+                        assert label == RC.MATRIX_WGRAD_LABELS[shape][k], (shape, pair, matrix_flags, label)
+                        assert label.split("<")[0] == RC.wgrad_kernel(shape, matrix_flags)
+                    assert not (matrix_flags and "_bf3" in label), (shape, label)
+                    wgrad.add(label.split("<")[0])
+        if cus == 256:
+            assert dilated == RC.DILATED_WGRAD_LABELS, sorted(dilated)
+        # 3. the dilated integer-grid statistics cases, every variant
+        for shape in K.DILATED_STATS_SHAPES:
+            N, H, W, Cin, Cout, s, d = shape
+            for kind, flags in K.STATS_VARIANTS:
+                op = L.make_op(L.OP_CONV, flags, n=N, h=H, w=W, cin=Cin, cout=Cout, ho=(H - 1) // s + 1, wo=(W - 1) // s + 1, stride=s, dil=d,
+                               inmode=L.LOAD_AFFINE, aux0=0, stats=kind)
+                stats.add(plan(h, op, True).split("<")[0])
+        reached[cus] = dict(conv=conv, tconv=tconv, wgrad=wgrad, stats=stats)
+    assert reached[256] == dict(conv={"conv_dma", "conv_mfma", "convs_mfma", "conv_wino", "conv_bf3", "conv2_bf3", "convn_bf3"},
+                                tconv={"tconva_dma", "tconvms_mfma", "tconvn_bf3"},
+                                wgrad={"wgrad_mfma", "wgrad_bf3", "wgradn_bf3"},
+                                stats={"conv_dma", "conv_mfma", "convs_mfma"}), reached[256]

@@ -270,9 +270,10 @@ def test_bwd_stats_cases_are_exact_and_sensitive():
     K.check_bwd_stats(K.build_bwd_stats(plane, 16, 8, 8, second_item=cap))
 
 
-@pytest.mark.parametrize("family", ["conv", "tconv", "image", "tiny"])
+@pytest.mark.parametrize("family", ["conv", "tconv", "image", "tiny", "dilated"])
 def test_conv_statistics_cases_are_exact(family):
-    shapes = dict(conv=K.CONV_STATS_SHAPES, tconv=K.TCONV_STATS_SHAPES, image=K.IMAGE_STATS_SHAPES, tiny=K.TINY_STATS_SHAPES)[family]
+    shapes = dict(conv=K.CONV_STATS_SHAPES, tconv=K.TCONV_STATS_SHAPES, image=K.IMAGE_STATS_SHAPES, tiny=K.TINY_STATS_SHAPES,
+                  dilated=K.DILATED_STATS_SHAPES)[family]
     for shape in shapes:
         K.check_conv_stats(K.build_conv_stats(shape, transposed=family == "tconv", nchw=family == "image"))
 
