@@ -3,7 +3,6 @@
 #include <stdarg.h>
 #include <string.h>
 #include "rcv_internal.h"
-#include "conv_common.h"
 
 static thread_local char g_err[512] = "";
 
@@ -212,13 +211,7 @@ static int run_ops(rcv_handle* h, const rcv_op* ops, int n, void* stream, bool j
 
 extern "C" {
 
-int rcv_op_filter_layout(const rcv_handle* h, const rcv_op* op, int force) {
-  if (!h || !op) return 0;
-  if (force == 0 && convn_bf3_wanted(h, op)) return op->kind == RCV_OP_TCONV ? 4 : 3;     // split-bf16 layouts, narrow layers (convn_bf3.hip)
-  if (op->kind != RCV_OP_CONV) return 0;
-  if (force == 0 && conv_bf3_wanted(h, op)) return op->i[RCV_I_STRIDE] == 2 ? 5 : 3;      // split-bf16 layout (conv_bf3.hip); force: the Winograd layout where it exists
-  return conv_wino_wanted(h, op, force != 0) ? 2 : 0;
-}
+int rcv_op_filter_layout(const rcv_handle* h, const rcv_op* op, int force) { return h && op ? rcv_filter_layout(h, op, force) : 0; }
 
 int rcv_op_kernel_label(const rcv_handle* h, const rcv_op* op, char* buf, int size) {
   RCV_CHECK_ARG(h && op && buf && size > 0, "rcv_op_kernel_label: bad arguments");

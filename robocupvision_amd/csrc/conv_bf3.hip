@@ -289,13 +289,14 @@ static bool c3_geometry(const rcv_handle* h, const rcv_op* op, C3Geom* g) {
   return found;
 }
 
-bool conv_bf3_wanted(const rcv_handle* h, const rcv_op* op) {
-  if (RCV_ENV("RCV_NO_BF3") || (op->flags & RCV_F_MFMA_FP32)) return false;
+// The split-bf16 layout to pack this record's filter in (3: stride 1, 5: stride 2); 0: it stays on the other kernels (force: the Winograd layout where it exists)
+static int conv_bf3_layout(const rcv_handle* h, const rcv_op* op, int force) {
+  if (force || RCV_ENV("RCV_NO_BF3") || (op->flags & RCV_F_MFMA_FP32)) return 0;
   const int N = op->i[RCV_I_N], H = op->i[RCV_I_H], W = op->i[RCV_I_W], Cin = op->i[RCV_I_CIN], Cout = op->i[RCV_I_COUT];
   const int S = op->i[RCV_I_STRIDE];
-  if (op->kind != RCV_OP_CONV || (S != 1 && S != 2) || op->i[RCV_I_DIL] != 1) return false;
-  if (op->i[RCV_I_INMODE] == RCV_LOAD_NCHW || Cout % 4 || Cout < 64) return false;
-  if (S == 1 ? (Cin % 32 || Cin < 64) : (Cin % 16 || Cin < 32 || RCV_ENV("RCV_NO_BF3S2") != nullptr)) return false;      // stride 2: layout 5, 16-channel chunks
+  if (op->kind != RCV_OP_CONV || (S != 1 && S != 2) || op->i[RCV_I_DIL] != 1) return 0;
+  if (op->i[RCV_I_INMODE] == RCV_LOAD_NCHW || Cout % 4 || Cout < 64) return 0;
+  if (S == 1 ? (Cin % 32 || Cin < 64) : (Cin % 16 || Cin < 32 || RCV_ENV("RCV_NO_BF3S2") != nullptr)) return 0;      // stride 2: layout 5, 16-channel chunks
   if (S == 2 && !RCV_ENV("RCV_BF3S2_ALL")) {
     // Stride 2 only in the FORWARD pass.  Op by op conv2_bf3 beats conv_dma on all four stride-2 launches of the step (32 -> 64: 91 -> 79 us
     // forward, 115 -> 110 as the data gradient of the mirrored transposed conv; 64 -> 128: 77 -> 58, 89 -> 72), but with the backward
@@ -303,25 +304,25 @@ bool conv_bf3_wanted(const rcv_handle* h, const rcv_op* op) {
     // workgroup keep the side stream's filter-gradient workgroups off the CUs that conv_dma's tiles share with them.  Forward only:
     // 5.485 -> 5.468 ms.
     const int m = op->i[RCV_I_INMODE];
-    if (m == RCV_LOAD_GRAD_ENC || m == RCV_LOAD_GRAD_DEC) return false;
+    if (m == RCV_LOAD_GRAD_ENC || m == RCV_LOAD_GRAD_DEC) return 0;
   }
-  if ((long long)N * H * W * Cin >= (1ll << 31)) return false;
+  if ((long long)N * H * W * Cin >= (1ll << 31)) return 0;
   if (RCV_ENV("RCV_BF3_FWD")) {        // experiments build: forward launches only (what the two-stream step makes of the backward ones)
     const int m = op->i[RCV_I_INMODE];
-    if (m == RCV_LOAD_GRAD_ENC || m == RCV_LOAD_GRAD_DEC) return false;
+    if (m == RCV_LOAD_GRAD_ENC || m == RCV_LOAD_GRAD_DEC) return 0;
   }
   C3Geom g;
-  if (!c3_geometry(h, op, &g)) return false;
+  if (!c3_geometry(h, op, &g)) return 0;
   // the grid must cover most of the chip (one 512-thread workgroup per CU): small planes stay on the other kernels
-  return (long)g.total * 4 >= (long)h->num_cus * 3;
+  return (long)g.total * 4 >= (long)h->num_cus * 3 ? (S == 2 ? 5 : 3) : 0;
 }
 
-bool conv_bf3_supported(const rcv_handle* h, const rcv_op* op, int kind) {
+static bool conv_bf3_supported(const rcv_handle* h, const rcv_op* op, int kind) {
   // the record carries a filter packed in a split layout (rcv_op_filter_layout): 3 = stride 1, 5 = stride 2 (16-channel chunks)
   return kind == KIND_GATHER && ((op->i[RCV_I_AUX0] == 3 && op->i[RCV_I_STRIDE] == 1) || (op->i[RCV_I_AUX0] == 5 && op->i[RCV_I_STRIDE] == 2));
 }
 
-int conv_bf3_plan(const rcv_handle* h, const rcv_op* op, ConvPlan* pl) {
+static int conv_bf3_plan(const rcv_handle* h, const rcv_op* op, int kind, ConvPlan* pl) {
   const int Cin = op->i[RCV_I_CIN], Cout = op->i[RCV_I_COUT];
   const int S = op->i[RCV_I_STRIDE];
   RCV_CHECK_ARG(op->kind == RCV_OP_CONV && (S == 1 || S == 2) && op->i[RCV_I_DIL] == 1 && Cin % (S == 1 ? 32 : 16) == 0 && Cout % 4 == 0 &&
@@ -330,19 +331,23 @@ int conv_bf3_plan(const rcv_handle* h, const rcv_op* op, ConvPlan* pl) {
                 op->i[RCV_I_DIL], Cin, Cout);
   C3Geom g;
   RCV_CHECK_ARG(c3_geometry(h, op, &g), "split-bf16 conv: no tile fits %dx%d", op->i[RCV_I_HO], op->i[RCV_I_WO]);
-  pl->kind = KIND_GATHER; pl->narrow = 0; pl->dma = 0; pl->first = 0; pl->wino = 0; pl->small = 0; pl->bf3 = 1;
-  pl->CK = S == 1 ? 32 : 16; pl->CoutV = Cout; pl->CoutP = round_up(Cout, 16);
+  pl->kind = kind; pl->path = CONV_BF3;
+  pl->CK = S == 1 ? 32 : 16; pl->xpitch_ck = pl->CK; pl->CoutV = Cout; pl->CoutP = round_up(Cout, 16);
   pl->R = g.TH; pl->Wt = g.TW; pl->IH = g.IH; pl->IW = g.IW; pl->tiles_x = g.tiles_x; pl->tiles_y = g.tiles_y;
-  pl->n_co_tiles = g.n_co_tiles; pl->n_phases = 1; pl->total_tiles = g.total; pl->grid = g.total;
+  pl->n_co_tiles = g.n_co_tiles; pl->n_phases = 1; pl->total_tiles = g.total; pl->grid = g.total; pl->n_part = op->i[RCV_I_N] * g.tiles_x * g.tiles_y;
   pl->WN = g.WN; pl->WM = 2;
   pl->xl_floats = round_up(g.IH * g.IW * (S == 1 ? C3_PITCH : C3_PITCH / 2), 16) / 4; pl->wl_floats = 0;
   pl->lds = g.lds;
   return RCV_OK;
 }
 
-int conv_bf3_launch(const ConvPlan& pl, const ConvArgs& a, hipStream_t s) {
+static void conv_bf3_label(const ConvPlan& pl, const rcv_op* op, char* buf, size_t n) { snprintf(buf, n, "conv%s_bf3<64,%d>", op->i[RCV_I_STRIDE] == 2 ? "2" : "", 32 * pl.WN); }
+
+static int conv_bf3_launch(const ConvPlan& pl, const ConvArgs& a, hipStream_t s) {
   const bool two = a.in_mode == RCV_LOAD_GRAD_ENC || a.in_mode == RCV_LOAD_GRAD_DEC;
   if (a.stride == 2) return two ? conv_launch_with_lds<conv2_bf3_kernel<5, true>>(pl, a, s) : conv_launch_with_lds<conv2_bf3_kernel<5, false>>(pl, a, s);
   if (pl.WN == 10) return two ? conv_launch_with_lds<conv_bf3_kernel<10, true>>(pl, a, s) : conv_launch_with_lds<conv_bf3_kernel<10, false>>(pl, a, s);
   return two ? conv_launch_with_lds<conv_bf3_kernel<5, true>>(pl, a, s) : conv_launch_with_lds<conv_bf3_kernel<5, false>>(pl, a, s);
 }
+
+RCV_HOST_ROW(ConvFamily, kConvBf3, "conv_bf3", conv_bf3_supported, conv_bf3_plan, conv_bf3_launch, conv_bf3_label, conv_bf3_layout, 1u << 3 | 1u << 5);

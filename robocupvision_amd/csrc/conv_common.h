@@ -1,4 +1,4 @@
-// Shared declarations of the convolution kernels (conv_mfma.hip: general; convs_mfma.hip: narrow layers).
+// Shared declarations of the convolution kernel families (dispatch: conv_dispatch.hip).
 #pragma once
 #include "load_xform.h"
 
@@ -57,21 +57,34 @@ __device__ __forceinline__ TileInfo decode_tile(const ConvArgs& a, int t, int CO
   return ti;
 }
 
+// Kernel families in order of precedence: ConvPlan::path is the row of kConvFamilies (conv_dispatch.hip)
+enum { CONVN_BF3 = 0, CONV_BF3, CONV_WINO, CONV_FIRST, CONV_NARROW, CONV_SMALL, CONV_MFMA, CONV_DMA, CONV_NUM_FAMILIES };
+
 struct ConvPlan {
   int kind, tile, CK, R, Wt, tiles_x, tiles_y, IH, IW;
   int CoutV, CoutP, n_co_tiles, n_phases, total_tiles, grid;
   size_t lds;
   int wl_floats, xl_floats;
-  int narrow;            // 1: convs_mfma.hip (persistent, filter resident in LDS)
-  int dma;               // 1: conv_dma_kernel (filter chunks by LDS-DMA, double buffered)
-  int xk;                // conv_dma_kernel: channels per staged input chunk
-  int WM, WN, XMAX;      // narrow kernel template selection
-  int first;             // 1: conv_first.hip (3 -> 8 channel first layer on the vector ALU)
+  int path;              // the family that runs the record (CONV_*)
+  int n_part;            // statistics rows of a launch: one per pixel tile and parity, or one per workgroup of a persistent kernel
+  int xpitch_ck;         // channel count of a staged input pixel (conv_xpitch)
+  int xk;                // conv_dma_kernel, conv_wino_kernel: channels per staged input chunk
+  int WM, WN, XMAX;      // template selection of the families with several instantiations
   int dev;               // device of the handle the plan belongs to (per-device kernel attributes)
-  int wino;              // 1: conv_wino.hip (Winograd F(2x2,3x3) for the wide stride-1 layers)
-  int bf3;               // 1: conv_bf3.hip (wide stride-1 layers: fp32 products on the bf16 matrix pipe, filter in the split layout); 2: convn_bf3.hip (narrow layers)
-  int small;             // 1: conv_small.hip (inference on planes of a few hundred pixels: one MFMA block per workgroup, K split over its waves)
 };
+
+// One kernel family: a row of kConvFamilies, defined next to its kernels.  The first row whose `supported` accepts a record plans it
+// (`plan` fills every field above but `dev`); the packer asks the same rows, in the same order, through `layout`.
+struct ConvFamily {
+  const char* name;
+  bool (*supported)(const rcv_handle*, const rcv_op*, int kind);   // nullptr: reached through another row's plan
+  int (*plan)(const rcv_handle*, const rcv_op*, int kind, ConvPlan*);
+  int (*launch)(const ConvPlan&, const ConvArgs&, hipStream_t);
+  void (*label)(const ConvPlan&, const rcv_op*, char* buf, size_t n);
+  int (*layout)(const rcv_handle*, const rcv_op*, int force);      // filter layout this family asks the packer for (0: none / plain); nullptr where there is none
+  unsigned layouts;      // bit L: the family reads a filter packed in layout L = 2..5 (RCV_I_AUX0); such a record runs on one of these rows or not at all
+};
+extern const ConvFamily kConvnBf3, kConvBf3, kConvWino, kConvFirst, kConvNarrow, kConvSmall, kConvMfma, kConvDma;
 
 // 512-thread launch of a kernel whose grid and dynamic LDS are the plan's (rcv_launch_with_lds)
 template <auto KERN>
@@ -92,36 +105,3 @@ static inline void tile_halo(int kind, int R, int Wt, int s, int d, int* IH, int
   if (kind == KIND_GATHER) { *IH = (R - 1) * s + 2 * d + 1; *IW = (Wt - 1) * s + 2 * d + 1; }
   else { *IH = R + 1; *IW = Wt + 1; }
 }
-
-// Winograd kernel (conv_wino.hip)
-bool conv_wino_supported(const rcv_handle* h, const rcv_op* op, int kind);
-bool conv_wino_wanted(const rcv_handle* h, const rcv_op* op, bool force);
-int conv_wino_plan(const rcv_handle* h, const rcv_op* op, ConvPlan* pl);
-int conv_wino_launch(const ConvPlan& pl, const ConvArgs& a, hipStream_t s);
-
-// split-bf16 kernel (conv_bf3.hip)
-bool conv_bf3_wanted(const rcv_handle* h, const rcv_op* op);
-bool conv_bf3_supported(const rcv_handle* h, const rcv_op* op, int kind);
-int conv_bf3_plan(const rcv_handle* h, const rcv_op* op, ConvPlan* pl);
-int conv_bf3_launch(const ConvPlan& pl, const ConvArgs& a, hipStream_t s);
-
-// split-bf16 narrow-layer kernel (convn_bf3.hip)
-bool convn_bf3_wanted(const rcv_handle* h, const rcv_op* op);
-bool convn_bf3_supported(const rcv_handle* h, const rcv_op* op, int kind);
-int convn_bf3_plan(const rcv_handle* h, const rcv_op* op, int kind, ConvPlan* pl);
-int convn_bf3_launch(const ConvPlan& pl, const ConvArgs& a, hipStream_t s);
-
-// tiny-plane inference kernel (conv_small.hip)
-bool conv_small_supported(const rcv_handle* h, const rcv_op* op, int kind);
-int conv_small_plan(const rcv_handle* h, const rcv_op* op, ConvPlan* pl);
-int conv_small_launch(const ConvPlan& pl, const ConvArgs& a, hipStream_t s);
-
-// first-layer kernel (conv_first.hip)
-bool conv_first_supported(const rcv_op* op, int kind);
-int conv_first_plan(const rcv_handle* h, const rcv_op* op, ConvPlan* pl);
-int conv_first_launch(const ConvPlan& pl, const ConvArgs& a, hipStream_t s);
-
-// narrow-layer kernel (convs_mfma.hip)
-bool convs_supported(const rcv_handle* h, const rcv_op* op, int kind, int CinP, int CoutV);
-int convs_make_plan(const rcv_handle* h, const rcv_op* op, int kind, ConvPlan* pl);
-int convs_launch(const ConvPlan& pl, const ConvArgs& a, bool two, hipStream_t s);

@@ -205,29 +205,33 @@ __global__ __launch_bounds__(256) void conv_first_kernel(const ConvArgs a, int t
 // --------------------------------------------------------------------------------------------
 // host side
 // --------------------------------------------------------------------------------------------
-bool conv_first_supported(const rcv_op* op, int kind) {
+static bool conv_first_supported(const rcv_handle* h, const rcv_op* op, int kind) {
   if (RCV_ENV("RCV_NO_CONV_FIRST")) return false;
   const int d = op->i[RCV_I_DIL], st = op->i[RCV_I_STATS];
   return kind == KIND_GATHER && op->i[RCV_I_INMODE] == RCV_LOAD_NCHW && op->i[RCV_I_CIN] <= 4 && op->i[RCV_I_COUT] == 8 &&
          op->i[RCV_I_STRIDE] == 1 && (d == 1 || d == 2) && (st == RCV_STATS_NONE || st == RCV_STATS_FWD) && !(op->flags & RCV_F_RESID);
 }
 
-int conv_first_plan(const rcv_handle* h, const rcv_op* op, ConvPlan* pl) {
-  pl->kind = KIND_GATHER; pl->narrow = 0; pl->dma = 0; pl->first = 1;
-  pl->CK = 4; pl->CoutV = 8; pl->CoutP = 16;
+static int conv_first_plan(const rcv_handle* h, const rcv_op* op, int kind, ConvPlan* pl) {
+  pl->kind = kind; pl->path = CONV_FIRST;
+  pl->CK = 4; pl->xpitch_ck = 4; pl->CoutV = 8; pl->CoutP = 16;
   pl->R = 16; pl->Wt = 64;
   pl->tiles_x = ceil_div(op->i[RCV_I_W], 64); pl->tiles_y = ceil_div(op->i[RCV_I_H], 16);
   pl->n_co_tiles = 1; pl->n_phases = 1;
   pl->total_tiles = op->i[RCV_I_N] * pl->tiles_x * pl->tiles_y;
   const int cap = h->num_cus * 4;                   // persistent: ~20 KB of LDS and < 128 registers, several workgroups per CU
-  pl->grid = pl->total_tiles < cap ? pl->total_tiles : cap;
+  pl->grid = pl->total_tiles < cap ? pl->total_tiles : cap; pl->n_part = pl->grid;
   pl->lds = 0;
   return RCV_OK;
 }
 
-int conv_first_launch(const ConvPlan& pl, const ConvArgs& a, hipStream_t s) {
+static void conv_first_label(const ConvPlan& pl, const rcv_op* op, char* buf, size_t n) { snprintf(buf, n, "conv_first<%d>", op->i[RCV_I_DIL]); }
+
+static int conv_first_launch(const ConvPlan& pl, const ConvArgs& a, hipStream_t s) {
   if (a.dil == 1) hipLaunchKernelGGL(conv_first_kernel<1>, dim3(pl.grid), dim3(256), 0, s, a, pl.tiles_x, pl.tiles_y, pl.total_tiles);
   else hipLaunchKernelGGL(conv_first_kernel<2>, dim3(pl.grid), dim3(256), 0, s, a, pl.tiles_x, pl.tiles_y, pl.total_tiles);
   RCV_HIP(hipGetLastError());
   return RCV_OK;
 }
+
+RCV_HOST_ROW(ConvFamily, kConvFirst, "conv_first", conv_first_supported, conv_first_plan, conv_first_launch, conv_first_label, nullptr, 0);

@@ -591,7 +591,7 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64) void conv_dma_kernel(const C
 }
 
 // --------------------------------------------------------------------------------------------
-// Host side: tiling choice and launch
+// Host side: tiling choice and launch of the general kernel (validation, plan cache and ConvArgs: conv_dispatch.hip)
 // --------------------------------------------------------------------------------------------
 template <int WM, int WN, int WAVES_M, int WAVES_N, int KIND, int XMAX = 4>
 static int launch_dma(const ConvArgs& a, dim3 grid, size_t lds, hipStream_t s, int dev) {
@@ -694,43 +694,18 @@ static bool plan_tile(int kind, int TH, int TW, int PIX, int s, int d, int cap, 
   return best_tiles >= 0;
 }
 
-static int make_plan(const rcv_handle* h, const rcv_op* op, ConvPlan* pl) {
+static bool conv_mfma_supported(const rcv_handle* h, const rcv_op* op, int kind) { return true; }     // the last row: takes what no other family does
+
+static int conv_mfma_plan(const rcv_handle* h, const rcv_op* op, int kind, ConvPlan* pl) {
   const bool transposed = op->kind == RCV_OP_TCONV;
   const int N = op->i[RCV_I_N], H = op->i[RCV_I_H], W = op->i[RCV_I_W];
   const int Cin = op->i[RCV_I_CIN], Cout = op->i[RCV_I_COUT];
   const int Ho = op->i[RCV_I_HO], Wo = op->i[RCV_I_WO];
   const int s = op->i[RCV_I_STRIDE], d = op->i[RCV_I_DIL];
-  RCV_CHECK_ARG(N > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0, "conv: empty shape N=%d H=%d W=%d Cin=%d Cout=%d", N, H, W, Cin, Cout);
-  RCV_CHECK_ARG(Cout % 4 == 0, "conv: Cout=%d must be a multiple of 4", Cout);
   const int mode = op->i[RCV_I_INMODE];
-  if (mode == RCV_LOAD_NCHW) RCV_CHECK_ARG(Cin <= 4, "conv: NCHW input supports Cin<=4 (got %d)", Cin);
-  else RCV_CHECK_ARG(Cin % 4 == 0, "conv: Cin=%d must be a multiple of 4 for NHWC operands", Cin);
-  if (transposed) {
-    RCV_CHECK_ARG(Ho == 2 * H && Wo == 2 * W, "tconv: output must be 2x input (%dx%d -> %dx%d)", H, W, Ho, Wo);
-    pl->kind = op->i[RCV_I_AUX0] ? KIND_TMERGED : KIND_TPHASE;     // AUX0 = 1 (or 4: split-bf16): filter is packed in the merged layout
-    RCV_CHECK_ARG(pl->kind == KIND_TPHASE || 4 * Cout <= 128, "tconv: merged layout needs Cout <= 32 (got %d)", Cout);
-  } else {
-    RCV_CHECK_ARG((s == 1 || s == 2) && (d == 1 || d == 2), "conv: stride %d dilation %d unsupported", s, d);
-    RCV_CHECK_ARG(Ho == (H - 1) / s + 1 && Wo == (W - 1) / s + 1, "conv: bad output size %dx%d for input %dx%d stride %d", Ho, Wo, H, W, s);
-    pl->kind = KIND_GATHER;
-  }
   const int CinP = round_up(Cin, 4);
-  pl->narrow = 0;
-  pl->dma = 0;
-  pl->first = 0;
-  pl->wino = 0;
-  pl->small = 0;
-  pl->bf3 = 0;
-  if (convn_bf3_supported(h, op, pl->kind)) return convn_bf3_plan(h, op, pl->kind, pl);
-  if (conv_bf3_supported(h, op, pl->kind)) return conv_bf3_plan(h, op, pl);
-  RCV_CHECK_ARG(op->i[RCV_I_AUX0] < 3 || op->i[RCV_I_AUX0] > 5, "conv: a filter packed in a split-bf16 layout needs a record one of the split-bf16 kernels runs");
-  if (conv_wino_supported(h, op, pl->kind)) return conv_wino_plan(h, op, pl);
-  RCV_CHECK_ARG(transposed || op->i[RCV_I_AUX0] != 2, "conv: a filter packed in the Winograd layout needs stride 1 / dilation 1");
-  if (conv_first_supported(op, pl->kind)) return conv_first_plan(h, op, pl);
-  if (convs_supported(h, op, pl->kind, CinP, pl->kind == KIND_TMERGED ? 4 * Cout : Cout)) return convs_make_plan(h, op, pl->kind, pl);
-  if (conv_small_supported(h, op, pl->kind)) return conv_small_plan(h, op, pl);
+  pl->kind = kind;
   pl->CK = (CinP % 8 == 0) ? 8 : 4;
-  const int Q = pl->CK / 4;
   pl->CoutV = pl->kind == KIND_TMERGED ? 4 * Cout : Cout;
   pl->CoutP = round_up(pl->CoutV, 16);
   const int TH = transposed ? H : Ho, TW = transposed ? W : Wo;
@@ -740,7 +715,6 @@ static int make_plan(const rcv_handle* h, const rcv_op* op, ConvPlan* pl) {
   // (Cin = 32 with more than 32 output channels: the 32 -> 64 stride-2 conv and its twin; staged 16 channels at a time they read
   // 64 of the 128 bytes of a pixel record per pass instead of the 32 of the general kernel's 8-channel chunks)
   const bool use_dma = mode != RCV_LOAD_NCHW && Cin >= 32 && CinP % 8 == 0 && (long long)N * H * W * Cin < (1ll << 31) && !RCV_ENV("RCV_NO_DMA");
-  (void)Q;
   long best = -1;
   bool best_dma = false;
   pl->tile = -1;
@@ -793,10 +767,10 @@ static int make_plan(const rcv_handle* h, const rcv_op* op, ConvPlan* pl) {
   tile_halo(pl->kind, pl->R, pl->Wt, s, d, &pl->IH, &pl->IW);
   const int ntaps = pl->kind == KIND_GATHER ? 9 : 4;
   const bool tall5 = pl->tile == 5 && pl->kind == KIND_TPHASE && !RCV_ENV("RCV_NO_TALL");
-  pl->dma = use_dma && (pl->tile == 0 || pl->tile == 1 || pl->tile == 4 || tall5) && pl->IH * pl->IW <= tc.nt() * 2;
-  pl->xk = 0;
+  const bool dma = use_dma && (pl->tile == 0 || pl->tile == 1 || pl->tile == 4 || tall5) && pl->IH * pl->IW <= tc.nt() * 2;
+  pl->path = dma ? CONV_DMA : CONV_MFMA;
   size_t floats;
-  if (pl->dma) {
+  if (dma) {
     pl->CK = 4;
     const int taps_dma = (pl->kind == KIND_TPHASE && (pl->tile == 4 || pl->tile == 5) && !RCV_ENV("RCV_NO_TALL")) ? 9 : ntaps;   // KIND_TALL below
     pl->wl_floats = ntaps * 4 * tc.cot();
@@ -827,7 +801,8 @@ static int make_plan(const rcv_handle* h, const rcv_op* op, ConvPlan* pl) {
   pl->n_phases = pl->kind == KIND_TPHASE ? 4 : 1;
   const int n_pix_tiles = N * pl->tiles_x * pl->tiles_y;
   pl->total_tiles = n_pix_tiles * pl->n_co_tiles * pl->n_phases;
-  if (pl->kind == KIND_TPHASE && pl->dma && (pl->tile == 4 || pl->tile == 5) && !RCV_ENV("RCV_NO_TALL")) {
+  pl->n_part = n_pix_tiles * pl->n_phases; pl->xpitch_ck = dma ? pl->xk : pl->CK;
+  if (pl->kind == KIND_TPHASE && dma && (pl->tile == 4 || pl->tile == 5) && !RCV_ENV("RCV_NO_TALL")) {
     // all four output parities in one workgroup (KIND_TALL): one staging of the input and nine taps per chunk instead of four
     // workgroups with 1/2/2/4 taps each paying the whole per-chunk overhead; n_phases stays 4: the statistics rows are per parity
     pl->kind = KIND_TALL;
@@ -840,95 +815,27 @@ static int make_plan(const rcv_handle* h, const rcv_op* op, ConvPlan* pl) {
   return RCV_OK;
 }
 
-int rcv_launch_conv(const rcv_handle* h, const rcv_op* op, hipStream_t s, OpQuery* query) {
-  ConvPlan pl;
-  if (!rcv_plan_get(h, op, &pl)) {
-    memset(&pl, 0, sizeof(pl));
-    const int rc = make_plan(h, op, &pl);
-    if (rc) return rc;
-    pl.dev = h->device;
-    rcv_plan_put(h, op, pl);
-  }
-  const int Cout = op->i[RCV_I_COUT];
-  const int n_pix_tiles = op->i[RCV_I_N] * pl.tiles_x * pl.tiles_y;
-  const int n_part = (pl.narrow || pl.first || pl.bf3 == 2) ? pl.grid : n_pix_tiles * pl.n_phases;
-  if (query) {
-    static const char* kn[] = {"conv", "tconv", "tconvm", "tconva"};
-    if (pl.bf3 == 2) {
-      snprintf(query->label, sizeof(query->label), "%sn_bf3<%d,%d,%d>", pl.kind == KIND_TMERGED ? "tconv" : "conv", pl.CK, pl.WM, pl.WN);
-    } else if (pl.bf3) {
-      snprintf(query->label, sizeof(query->label), "conv%s_bf3<64,%d>", op->i[RCV_I_STRIDE] == 2 ? "2" : "", 32 * pl.WN);
-    } else if (pl.wino) {
-      snprintf(query->label, sizeof(query->label), "conv_wino<64,%d>", 16 * pl.WN);
-    } else if (pl.small) {
-      snprintf(query->label, sizeof(query->label), "conv_small<%d>", op->i[RCV_I_DIL]);
-    } else if (pl.first) {
-      snprintf(query->label, sizeof(query->label), "conv_first<%d>", op->i[RCV_I_DIL]);
-    } else if (pl.narrow) {
-      snprintf(query->label, sizeof(query->label), "%ss_mfma<%d,%d,%d>", kn[pl.kind], pl.WM, pl.WN, pl.CK);
-    } else {
-      const TileCfg& tc = kTiles[pl.tile];
-      snprintf(query->label, sizeof(query->label), "%s_%s<%d,%d,%d,%d,%d>", kn[pl.kind], pl.dma ? "dma" : "mfma", tc.WM, tc.WN, tc.WAVES_M,
-               tc.WAVES_N, pl.CK);
-    }
-    query->n_part = op->i[RCV_I_STATS] != RCV_STATS_NONE ? n_part : 0;
-    query->n_split = 0;
-    query->part_bytes = (size_t)query->n_part * 2 * Cout * sizeof(float);
-    return RCV_OK;
-  }
-  ConvArgs a;
-  a.in = (const float*)op->p[RCV_P_IN];
-  a.in_aux = (const float*)op->p[RCV_P_IN_AUX];
-  a.in_c = (const float*)op->p[RCV_P_IN_C];
-  a.w = (const float*)op->p[RCV_P_W];
-  a.bias = (const float*)op->p[RCV_P_BIAS];
-  a.out = (float*)op->p[RCV_P_OUT];
-  a.resid = (const float*)op->p[RCV_P_RESID];
-  a.epi_aux = (const float*)op->p[RCV_P_EPI_AUX];
-  a.epi_c = (const float*)op->p[RCV_P_EPI_C];
-  a.part = (float*)op->p[RCV_P_PART];
-  a.N = op->i[RCV_I_N]; a.H = op->i[RCV_I_H]; a.W = op->i[RCV_I_W];
-  a.Cin = op->i[RCV_I_CIN]; a.Cout = Cout; a.Ho = op->i[RCV_I_HO]; a.Wo = op->i[RCV_I_WO];
-  a.CinP = round_up(a.Cin, 4); a.CoutP = pl.CoutP; a.CoutV = pl.CoutV;
-  a.stride = op->i[RCV_I_STRIDE]; a.dil = op->i[RCV_I_DIL];
-  a.R = pl.R; a.Wt = pl.Wt; a.tiles_x = pl.tiles_x; a.tiles_y = pl.tiles_y; a.IH = pl.IH; a.IW = pl.IW;
-  a.n_pix_tiles = n_pix_tiles; a.n_co_tiles = pl.n_co_tiles; a.n_sub = pl.n_co_tiles * (pl.kind == KIND_TALL ? 1 : pl.n_phases);
-  a.total_tiles = pl.total_tiles; a.nchunks = a.CinP / pl.CK;      // (conv_bf3: CK = 32, Cin % 32 == 0)
-  a.in_mode = op->i[RCV_I_INMODE]; a.stats = op->i[RCV_I_STATS]; a.flags = op->flags;
-  a.wl_floats = pl.wl_floats; a.xl_floats = pl.xl_floats;
-  a.xk = pl.xk;
-  a.xpitch = conv_xpitch((pl.dma || pl.wino) ? pl.xk : pl.CK, pl.kind == KIND_GATHER ? a.stride : 1);
-  a.fdWt = make_fastdiv(pl.Wt); a.fdIW = make_fastdiv(pl.IW);
-  a.fdTX = make_fastdiv(pl.tiles_x); a.fdTY = make_fastdiv(pl.tiles_y);
-#ifdef RCV_STAMPS
-  a.stamps = (unsigned long long*)op->p[RCV_P_X5];
-#endif
-  RCV_CHECK_ARG(a.in && a.w && a.out, "conv: null operand");
-  RCV_CHECK_ARG(a.in_mode == RCV_LOAD_PLAIN || a.in_mode == RCV_LOAD_NCHW || a.in_c, "conv: load mode %d needs constants", a.in_mode);
-  RCV_CHECK_ARG(!(a.in_mode == RCV_LOAD_GRAD_ENC || a.in_mode == RCV_LOAD_GRAD_DEC) || a.in_aux, "conv: gradient load needs aux tensor");
-  RCV_CHECK_ARG(!(a.flags & RCV_F_BIAS) || a.bias, "conv: bias flag without bias");
-  RCV_CHECK_ARG(!(a.flags & RCV_F_RESID) || a.resid, "conv: resid flag without tensor");
-  RCV_CHECK_ARG(a.stats == RCV_STATS_NONE || a.part, "conv: statistics requested without workspace");
-  RCV_CHECK_ARG(a.stats == RCV_STATS_NONE || op->i[RCV_I_NPART] == n_part, "conv: workspace rows %d != %d", op->i[RCV_I_NPART], n_part);
-  RCV_CHECK_ARG(!(a.stats == RCV_STATS_BWD_ENC || a.stats == RCV_STATS_BWD_DEC) || a.epi_aux, "conv: backward statistics need epi_aux");
-  RCV_CHECK_ARG(!(a.stats == RCV_STATS_BWD_ENC || a.stats == RCV_STATS_BWD_DEC) || a.epi_c, "conv: backward statistics need epi_c (scale, shift, mean)");
-  if (pl.bf3 == 2) return convn_bf3_launch(pl, a, s);
-  if (pl.bf3) return conv_bf3_launch(pl, a, s);
-  if (pl.wino) return conv_wino_launch(pl, a, s);
-  if (pl.first) return conv_first_launch(pl, a, s);
-  if (pl.small) return conv_small_launch(pl, a, s);
-  if (pl.narrow) return convs_launch(pl, a, a.in_mode == RCV_LOAD_GRAD_ENC || a.in_mode == RCV_LOAD_GRAD_DEC, s);
+static void conv_mfma_label(const ConvPlan& pl, const rcv_op* op, char* buf, size_t n) {
+  static const char* kn[] = {"conv", "tconv", "tconvm", "tconva"};
+  const TileCfg& tc = kTiles[pl.tile];
+  snprintf(buf, n, "%s_%s<%d,%d,%d,%d,%d>", kn[pl.kind], pl.path == CONV_DMA ? "dma" : "mfma", tc.WM, tc.WN, tc.WAVES_M, tc.WAVES_N, pl.CK);
+}
+
+static int conv_mfma_launch(const ConvPlan& pl, const ConvArgs& a, hipStream_t s) {
   const dim3 grid(pl.grid);
-  if (pl.dma) {
+  if (pl.path == CONV_DMA) {
     if (pl.kind == KIND_TALL)
-      return pl.tile == 4 ? launch_dma<1, 5, 4, 1, KIND_TALL>(a, grid, pl.lds, s, h->device) : launch_dma<1, 5, 2, 2, KIND_TALL>(a, grid, pl.lds, s, h->device);
-    if (pl.kind == KIND_TPHASE) return launch_dma_tile<KIND_TPHASE>(pl.tile, a, grid, pl.lds, s, h->device);
-    if (pl.kind == KIND_TMERGED) return launch_dma_tile<KIND_TMERGED>(pl.tile, a, grid, pl.lds, s, h->device);
-    return launch_dma_tile<KIND_GATHER>(pl.tile, a, grid, pl.lds, s, h->device);
+      return pl.tile == 4 ? launch_dma<1, 5, 4, 1, KIND_TALL>(a, grid, pl.lds, s, pl.dev) : launch_dma<1, 5, 2, 2, KIND_TALL>(a, grid, pl.lds, s, pl.dev);
+    if (pl.kind == KIND_TPHASE) return launch_dma_tile<KIND_TPHASE>(pl.tile, a, grid, pl.lds, s, pl.dev);
+    if (pl.kind == KIND_TMERGED) return launch_dma_tile<KIND_TMERGED>(pl.tile, a, grid, pl.lds, s, pl.dev);
+    return launch_dma_tile<KIND_GATHER>(pl.tile, a, grid, pl.lds, s, pl.dev);
   }
   if (pl.kind == KIND_TPHASE)
-    return pl.CK == 8 ? launch_tile<8, KIND_TPHASE>(pl.tile, a, grid, pl.lds, s, h->device) : launch_tile<4, KIND_TPHASE>(pl.tile, a, grid, pl.lds, s, h->device);
+    return pl.CK == 8 ? launch_tile<8, KIND_TPHASE>(pl.tile, a, grid, pl.lds, s, pl.dev) : launch_tile<4, KIND_TPHASE>(pl.tile, a, grid, pl.lds, s, pl.dev);
   if (pl.kind == KIND_TMERGED)
-    return pl.CK == 8 ? launch_tile<8, KIND_TMERGED>(pl.tile, a, grid, pl.lds, s, h->device) : launch_tile<4, KIND_TMERGED>(pl.tile, a, grid, pl.lds, s, h->device);
-  return pl.CK == 8 ? launch_tile<8, KIND_GATHER>(pl.tile, a, grid, pl.lds, s, h->device) : launch_tile<4, KIND_GATHER>(pl.tile, a, grid, pl.lds, s, h->device);
+    return pl.CK == 8 ? launch_tile<8, KIND_TMERGED>(pl.tile, a, grid, pl.lds, s, pl.dev) : launch_tile<4, KIND_TMERGED>(pl.tile, a, grid, pl.lds, s, pl.dev);
+  return pl.CK == 8 ? launch_tile<8, KIND_GATHER>(pl.tile, a, grid, pl.lds, s, pl.dev) : launch_tile<4, KIND_GATHER>(pl.tile, a, grid, pl.lds, s, pl.dev);
 }
+
+RCV_HOST_ROW(ConvFamily, kConvMfma, "conv_mfma", conv_mfma_supported, conv_mfma_plan, conv_mfma_launch, conv_mfma_label, nullptr, 0);
+RCV_HOST_ROW(ConvFamily, kConvDma, "conv_dma", nullptr, conv_mfma_plan, conv_mfma_launch, conv_mfma_label, nullptr, 0);     // (chosen inside conv_mfma_plan)

@@ -79,7 +79,7 @@ __global__ __launch_bounds__(CS_NW * 64) void conv_small_kernel(const ConvArgs a
 // --------------------------------------------------------------------------------------------
 // host side
 // --------------------------------------------------------------------------------------------
-bool conv_small_supported(const rcv_handle* h, const rcv_op* op, int kind) {
+static bool conv_small_supported(const rcv_handle* h, const rcv_op* op, int kind) {
   if (RCV_ENV("RCV_NO_CONV_SMALL")) return false;
   const int mode = op->i[RCV_I_INMODE], Cin = op->i[RCV_I_CIN], Cout = op->i[RCV_I_COUT];
   const long px = (long)op->i[RCV_I_N] * op->i[RCV_I_HO] * op->i[RCV_I_WO];
@@ -89,20 +89,22 @@ bool conv_small_supported(const rcv_handle* h, const rcv_op* op, int kind) {
          Cout % 4 == 0 && Cout >= 16 && px * ceil_div(Cout, 16) <= (long)16 * 4 * h->num_cus && px <= 4096;
 }
 
-int conv_small_plan(const rcv_handle* h, const rcv_op* op, ConvPlan* pl) {
+static int conv_small_plan(const rcv_handle* h, const rcv_op* op, int kind, ConvPlan* pl) {
   const int Cout = op->i[RCV_I_COUT];
   const int px = op->i[RCV_I_N] * op->i[RCV_I_HO] * op->i[RCV_I_WO];
-  pl->kind = KIND_GATHER; pl->narrow = 0; pl->dma = 0; pl->first = 0; pl->wino = 0; pl->small = 1;
-  pl->CK = 4; pl->CoutV = Cout; pl->CoutP = round_up(Cout, 16);
+  pl->kind = kind; pl->path = CONV_SMALL;
+  pl->CK = 4; pl->xpitch_ck = 4; pl->CoutV = Cout; pl->CoutP = round_up(Cout, 16);
   pl->R = 1; pl->Wt = 16; pl->tiles_x = ceil_div(px, 16); pl->tiles_y = 1;
   pl->n_co_tiles = pl->CoutP / 16; pl->n_phases = 1;
   pl->total_tiles = pl->tiles_x * pl->n_co_tiles;
-  pl->grid = pl->total_tiles;
+  pl->grid = pl->total_tiles; pl->n_part = op->i[RCV_I_N] * pl->tiles_x;       // (n_part is never asked for: no record with statistics comes here)
   pl->lds = 0;
   return RCV_OK;
 }
 
-int conv_small_launch(const ConvPlan& pl, const ConvArgs& a, hipStream_t s) {
+static void conv_small_label(const ConvPlan& pl, const rcv_op* op, char* buf, size_t n) { snprintf(buf, n, "conv_small<%d>", op->i[RCV_I_DIL]); }
+
+static int conv_small_launch(const ConvPlan& pl, const ConvArgs& a, hipStream_t s) {
   const int px = a.N * a.Ho * a.Wo;
   const dim3 block(CS_NW * 64);
   if (a.in_mode == RCV_LOAD_PLAIN) hipLaunchKernelGGL(conv_small_kernel<RCV_LOAD_PLAIN>, dim3(pl.grid), block, 0, s, a, pl.n_co_tiles, px);
@@ -111,3 +113,5 @@ int conv_small_launch(const ConvPlan& pl, const ConvArgs& a, hipStream_t s) {
   RCV_HIP(hipGetLastError());
   return RCV_OK;
 }
+
+RCV_HOST_ROW(ConvFamily, kConvSmall, "conv_small", conv_small_supported, conv_small_plan, conv_small_launch, conv_small_label, nullptr, 0);

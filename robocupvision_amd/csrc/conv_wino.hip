@@ -351,29 +351,11 @@ __global__ __launch_bounds__(W_NT) void conv_wino_kernel(const ConvArgs a) {
 // --------------------------------------------------------------------------------------------
 // host side
 // --------------------------------------------------------------------------------------------
-bool conv_wino_supported(const rcv_handle* h, const rcv_op* op, int kind) {
-  if (kind != KIND_GATHER || op->i[RCV_I_AUX0] != 2) return false;     // AUX0 == 2: the filter was packed in the Winograd layout
-  (void)h;
-  return true;
+static bool conv_wino_supported(const rcv_handle* h, const rcv_op* op, int kind) {
+  return kind == KIND_GATHER && op->i[RCV_I_AUX0] == 2;     // AUX0 == 2: the filter was packed in the Winograd layout
 }
 
-// Would this op run on the Winograd kernel if its filter were packed for it?  (The engine asks before it lays out the filter.)
-bool conv_wino_wanted(const rcv_handle* h, const rcv_op* op, bool force) {
-  const int N = op->i[RCV_I_N], H = op->i[RCV_I_H], W = op->i[RCV_I_W], Cin = op->i[RCV_I_CIN], Cout = op->i[RCV_I_COUT];
-  if (op->kind != RCV_OP_CONV || op->i[RCV_I_STRIDE] != 1 || op->i[RCV_I_DIL] != 1) return false;
-  if (op->i[RCV_I_INMODE] == RCV_LOAD_NCHW || Cin % 16 || Cin < 32 || Cout % 4 || Cout < 64) return false;     // (32 and 48 input channels: measured 20-26 % faster than the direct kernel)
-  if ((long long)N * H * W * Cin >= (1ll << 31)) return false;
-  if (force) return true;
-  ConvPlan pl;
-  memset(&pl, 0, sizeof(pl));
-  rcv_op o2 = *op;
-  o2.i[RCV_I_AUX0] = 2;
-  if (conv_wino_plan(h, &o2, &pl) != RCV_OK) return false;
-  // the grid must cover the chip (one 512-thread workgroup per CU): small planes stay on the direct kernel
-  return (long)pl.grid * 4 >= (long)h->num_cus * 3;
-}
-
-int conv_wino_plan(const rcv_handle* h, const rcv_op* op, ConvPlan* pl) {
+static int conv_wino_plan(const rcv_handle* h, const rcv_op* op, int kind, ConvPlan* pl) {
   const int N = op->i[RCV_I_N], Ho = op->i[RCV_I_HO], Wo = op->i[RCV_I_WO], Cin = op->i[RCV_I_CIN], Cout = op->i[RCV_I_COUT];
   RCV_CHECK_ARG(op->i[RCV_I_STRIDE] == 1 && op->i[RCV_I_DIL] == 1 && Cin % 16 == 0 && Cout % 4 == 0,
                 "winograd conv: needs stride 1, dilation 1, Cin %% 16 == 0 (got s%d d%d Cin %d Cout %d)", op->i[RCV_I_STRIDE], op->i[RCV_I_DIL], Cin, Cout);
@@ -405,12 +387,12 @@ int conv_wino_plan(const rcv_handle* h, const rcv_op* op, ConvPlan* pl) {
     const int b3 = plan_blocks(48, &r3, &w3);
     if (b3 > 0 && (long)N * b3 * n_co * 4 >= (long)h->num_cus * 3) { best = b3; bR = r3; bW = w3; pl->WN = 3; }
   }
-  pl->kind = KIND_GATHER; pl->tile = 0; pl->CK = 4; pl->narrow = 0; pl->dma = 0; pl->first = 0; pl->wino = 1;
+  pl->kind = kind; pl->path = CONV_WINO; pl->tile = 0; pl->CK = 4;
   pl->R = bR; pl->Wt = bW; pl->tiles_x = ceil_div(TW, bW); pl->tiles_y = ceil_div(TH, bR);
   pl->IH = 2 * bR + 2; pl->IW = 2 * bW + 2;
   pl->CoutV = Cout; pl->CoutP = round_up(Cout, 16);
   pl->n_co_tiles = ceil_div(pl->CoutP, W_COT); pl->n_phases = 1;
-  pl->xk = W_XK;
+  pl->xk = W_XK; pl->xpitch_ck = W_XK;
   pl->xl_floats = round_up(pl->IH * pl->IW * conv_xpitch(W_XK, 1), 4);
   pl->wl_floats = 0;
   size_t floats = 2 * (size_t)W_UBUF + 2 * (size_t)(16 * W_CK * 16 * pl->WN) + 2 * (size_t)pl->xl_floats + 5 * (size_t)round_up(Cin, 4);
@@ -418,12 +400,30 @@ int conv_wino_plan(const rcv_handle* h, const rcv_op* op, ConvPlan* pl) {
   if (floats < exch) floats = exch;
   pl->lds = floats * sizeof(float);
   RCV_CHECK_ARG(pl->lds <= (size_t)h->max_lds, "winograd conv: tile needs %zu B of LDS (limit %d)", pl->lds, h->max_lds);
-  pl->total_tiles = N * pl->tiles_x * pl->tiles_y * pl->n_co_tiles;
+  pl->n_part = N * pl->tiles_x * pl->tiles_y; pl->total_tiles = pl->n_part * pl->n_co_tiles;
   pl->grid = pl->total_tiles;
   return RCV_OK;
 }
 
-int conv_wino_launch(const ConvPlan& pl, const ConvArgs& a, hipStream_t s) {
+// Would this op run on the Winograd kernel if its filter were packed for it?  (The engine asks before it lays out the filter.)
+static int conv_wino_layout(const rcv_handle* h, const rcv_op* op, int force) {
+  const int N = op->i[RCV_I_N], H = op->i[RCV_I_H], W = op->i[RCV_I_W], Cin = op->i[RCV_I_CIN], Cout = op->i[RCV_I_COUT];
+  if (op->kind != RCV_OP_CONV || op->i[RCV_I_STRIDE] != 1 || op->i[RCV_I_DIL] != 1) return 0;
+  if (op->i[RCV_I_INMODE] == RCV_LOAD_NCHW || Cin % 16 || Cin < 32 || Cout % 4 || Cout < 64) return 0;     // (32 and 48 input channels: measured 20-26 % faster than the direct kernel)
+  if ((long long)N * H * W * Cin >= (1ll << 31)) return 0;
+  if (force) return 2;
+  ConvPlan pl;
+  memset(&pl, 0, sizeof(pl));
+  rcv_op o2 = *op;
+  o2.i[RCV_I_AUX0] = 2;
+  if (conv_wino_plan(h, &o2, KIND_GATHER, &pl) != RCV_OK) return 0;
+  // the grid must cover the chip (one 512-thread workgroup per CU): small planes stay on the direct kernel
+  return (long)pl.grid * 4 >= (long)h->num_cus * 3 ? 2 : 0;
+}
+
+static void conv_wino_label(const ConvPlan& pl, const rcv_op* op, char* buf, size_t n) { snprintf(buf, n, "conv_wino<64,%d>", 16 * pl.WN); }
+
+static int conv_wino_launch(const ConvPlan& pl, const ConvArgs& a, hipStream_t s) {
   const bool two = a.in_mode == RCV_LOAD_GRAD_ENC || a.in_mode == RCV_LOAD_GRAD_DEC;
 #define WINO_LAUNCH(TWO_, TB_)                                                         \
   do {                                                                                 \
@@ -438,3 +438,5 @@ int conv_wino_launch(const ConvPlan& pl, const ConvArgs& a, hipStream_t s) {
   RCV_HIP(hipGetLastError());
   return RCV_OK;
 }
+
+RCV_HOST_ROW(ConvFamily, kConvWino, "conv_wino", conv_wino_supported, conv_wino_plan, conv_wino_launch, conv_wino_label, conv_wino_layout, 1u << 2);

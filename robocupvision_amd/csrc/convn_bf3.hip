@@ -296,18 +296,18 @@ static bool n3_geometry(const rcv_handle* h, const rcv_op* op, int kind, N3Geom*
 }
 
 // Would this record run here if its filter were packed in the split layout?  (rcv_op_filter_layout: 3 for a conv, 4 for a merged transposed conv)
-bool convn_bf3_wanted(const rcv_handle* h, const rcv_op* op) {
-  if (RCV_ENV("RCV_NO_BF3") || RCV_ENV("RCV_NO_BF3N") || (op->flags & RCV_F_MFMA_FP32)) return false;
+static int convn_bf3_layout(const rcv_handle* h, const rcv_op* op, int force) {
+  if (force || RCV_ENV("RCV_NO_BF3") || RCV_ENV("RCV_NO_BF3N") || (op->flags & RCV_F_MFMA_FP32)) return 0;
   const int kind = op->kind == RCV_OP_CONV ? KIND_GATHER : (op->kind == RCV_OP_TCONV ? KIND_TMERGED : -1);
-  if (kind < 0 || !n3_shape_ok(op, kind)) return false;
-  if ((long long)op->i[RCV_I_N] * op->i[RCV_I_H] * op->i[RCV_I_W] * op->i[RCV_I_CIN] >= (1ll << 31)) return false;
+  if (kind < 0 || !n3_shape_ok(op, kind)) return 0;
+  if ((long long)op->i[RCV_I_N] * op->i[RCV_I_H] * op->i[RCV_I_W] * op->i[RCV_I_CIN] >= (1ll << 31)) return 0;
   N3Geom g;
-  if (!n3_geometry(h, op, kind, &g)) return false;
-  if ((long)g.total * 2 < (long)h->num_cus) return false;   // small planes stay on the other kernels
-  if (RCV_ENV("RCV_BF3N_ALL")) return true;
+  if (!n3_geometry(h, op, kind, &g)) return 0;
+  if ((long)g.total * 2 < (long)h->num_cus) return 0;   // small planes stay on the other kernels
+  if (RCV_ENV("RCV_BF3N_ALL")) return kind == KIND_GATHER ? 3 : 4;
   if (RCV_ENV("RCV_BF3N_FWD")) {       // experiments build: forward launches only
     const int m0 = op->i[RCV_I_INMODE];
-    if (m0 == RCV_LOAD_GRAD_ENC || m0 == RCV_LOAD_GRAD_DEC) return false;
+    if (m0 == RCV_LOAD_GRAD_ENC || m0 == RCV_LOAD_GRAD_DEC) return 0;
   }
   // Where this kernel is the faster one (op by op at the shapes of the 640 x 480 step, scripts/experiments/exp_r3_n3ops.sh): the layers
   // whose fp32 form is matrix-pipe bound -- 32 -> 32 (133 -> 86 us forward, 157 -> 107 data gradient), 16 -> 16 (136 -> 125, 186 -> 170),
@@ -315,27 +315,27 @@ bool convn_bf3_wanted(const rcv_handle* h, const rcv_op* op) {
   // convs: 102 -> 127, 115 -> 164 us) stream better through convs_mfma.hip, whose two workgroups per CU keep more loads in flight.
   const int Cin = op->i[RCV_I_CIN], m = op->i[RCV_I_INMODE];
   const bool two = m == RCV_LOAD_GRAD_ENC || m == RCV_LOAD_GRAD_DEC;
-  if (kind == KIND_GATHER) return Cin == 32 || (Cin == 16 && op->i[RCV_I_STRIDE] == 1);
-  return Cin == 32 && two;
+  if (kind == KIND_GATHER) return (Cin == 32 || (Cin == 16 && op->i[RCV_I_STRIDE] == 1)) ? 3 : 0;
+  return (Cin == 32 && two) ? 4 : 0;
 }
 
-bool convn_bf3_supported(const rcv_handle* h, const rcv_op* op, int kind) {
+static bool convn_bf3_supported(const rcv_handle* h, const rcv_op* op, int kind) {
   const int aux = op->i[RCV_I_AUX0];
   return ((kind == KIND_GATHER && aux == 3) || (kind == KIND_TMERGED && aux == 4)) && op->i[RCV_I_CIN] <= 32;
 }
 
-int convn_bf3_plan(const rcv_handle* h, const rcv_op* op, int kind, ConvPlan* pl) {
+static int convn_bf3_plan(const rcv_handle* h, const rcv_op* op, int kind, ConvPlan* pl) {
   RCV_CHECK_ARG(n3_shape_ok(op, kind) && !(op->flags & RCV_F_MFMA_FP32), "split-bf16 narrow conv: shape %d -> %d (stride %d, dilation %d) not built",
                 op->i[RCV_I_CIN], op->i[RCV_I_COUT], op->i[RCV_I_STRIDE], op->i[RCV_I_DIL]);
   N3Geom g;
   RCV_CHECK_ARG(n3_geometry(h, op, kind, &g), "split-bf16 narrow conv: no tile fits");
   const int Cout = op->i[RCV_I_COUT];
-  pl->kind = kind; pl->narrow = 0; pl->dma = 0; pl->first = 0; pl->wino = 0; pl->small = 0; pl->bf3 = 2;
-  pl->CK = op->i[RCV_I_CIN];
+  pl->kind = kind; pl->path = CONVN_BF3;
+  pl->CK = op->i[RCV_I_CIN]; pl->xpitch_ck = pl->CK;
   pl->CoutV = kind == KIND_TMERGED ? 4 * Cout : Cout; pl->CoutP = round_up(pl->CoutV, 16);
   pl->WM = pl->CoutP / 16; pl->WN = g.WN;
   pl->R = g.R; pl->Wt = g.Wt; pl->IH = g.IH; pl->IW = g.IW; pl->tiles_x = g.tiles_x; pl->tiles_y = g.tiles_y;
-  pl->n_co_tiles = 1; pl->n_phases = 1; pl->total_tiles = g.total; pl->grid = g.grid;
+  pl->n_co_tiles = 1; pl->n_phases = 1; pl->total_tiles = g.total; pl->grid = g.grid; pl->n_part = g.grid;
   pl->xl_floats = g.xl_bytes / 4; pl->wl_floats = 0; pl->lds = g.lds;
   return RCV_OK;
 }
@@ -346,7 +346,9 @@ static int n3_launch_wn(const ConvPlan& pl, const ConvArgs& a, bool two, hipStre
   return two ? conv_launch_with_lds<convn_bf3_kernel<CIN, WM, 3, KIND, true>>(pl, a, s) : conv_launch_with_lds<convn_bf3_kernel<CIN, WM, 3, KIND, false>>(pl, a, s);
 }
 
-int convn_bf3_launch(const ConvPlan& pl, const ConvArgs& a, hipStream_t s) {
+static void convn_bf3_label(const ConvPlan& pl, const rcv_op* op, char* buf, size_t n) { snprintf(buf, n, "%sn_bf3<%d,%d,%d>", pl.kind == KIND_TMERGED ? "tconv" : "conv", pl.CK, pl.WM, pl.WN); }
+
+static int convn_bf3_launch(const ConvPlan& pl, const ConvArgs& a, hipStream_t s) {
   const bool two = a.in_mode == RCV_LOAD_GRAD_ENC || a.in_mode == RCV_LOAD_GRAD_DEC;
   if (pl.kind == KIND_TMERGED) {
     if (a.Cin == 16) return n3_launch_wn<16, 2, KIND_TMERGED>(pl, a, two, s);
@@ -361,3 +363,5 @@ int convn_bf3_launch(const ConvPlan& pl, const ConvArgs& a, hipStream_t s) {
     default: return n3_launch_wn<32, 2, KIND_GATHER>(pl, a, two, s);
   }
 }
+
+RCV_HOST_ROW(ConvFamily, kConvnBf3, "convn_bf3", convn_bf3_supported, convn_bf3_plan, convn_bf3_launch, convn_bf3_label, convn_bf3_layout, 1u << 3 | 1u << 4);

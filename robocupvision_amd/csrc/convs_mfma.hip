@@ -539,8 +539,8 @@ static inline bool narrow_wn_built(int WN, int CK, int WM) {
   return WN == 5 || (WN == 3 && CK >= 8) || (WN == 2 && CK == 16);
 }
 
-bool convs_supported(const rcv_handle* h, const rcv_op* op, int kind, int CinP, int CoutV) {
-  (void)h;
+static bool convs_supported(const rcv_handle* h, const rcv_op* op, int kind) {
+  const int CinP = round_up(op->i[RCV_I_CIN], 4), CoutV = kind == KIND_TMERGED ? 4 * op->i[RCV_I_COUT] : op->i[RCV_I_COUT];
   if (RCV_ENV("RCV_NO_NARROW")) return false;
   if (op->i[RCV_I_H] >= 16384 || op->i[RCV_I_W] >= 16384 || op->i[RCV_I_HO] >= 16384 || op->i[RCV_I_WO] >= 16384) return false;   // packed 16-bit tile coordinates
   // 32-bit byte offsets from the tensor bases: input and output stay below 4 GiB
@@ -552,14 +552,14 @@ bool convs_supported(const rcv_handle* h, const rcv_op* op, int kind, int CinP, 
   return round_up(CoutV, 16) <= 32;
 }
 
-int convs_make_plan(const rcv_handle* h, const rcv_op* op, int kind, ConvPlan* pl) {
+static int convs_plan(const rcv_handle* h, const rcv_op* op, int kind, ConvPlan* pl) {
   const int N = op->i[RCV_I_N], H = op->i[RCV_I_H], W = op->i[RCV_I_W];
   const int Cin = op->i[RCV_I_CIN], Cout = op->i[RCV_I_COUT];
   const int Ho = op->i[RCV_I_HO], Wo = op->i[RCV_I_WO];
   const int s = op->i[RCV_I_STRIDE], d = op->i[RCV_I_DIL];
   const int CinP = round_up(Cin, 4);
-  pl->kind = kind; pl->narrow = 1; pl->dma = 0; pl->first = 0;
-  pl->CK = CinP;
+  pl->kind = kind; pl->path = CONV_NARROW;
+  pl->CK = CinP; pl->xpitch_ck = CinP;
   pl->CoutV = kind == KIND_TMERGED ? 4 * Cout : Cout;
   pl->CoutP = round_up(pl->CoutV, 16);
   pl->WM = pl->CoutP / 16; pl->XMAX = kNarrowXMAX;
@@ -615,7 +615,7 @@ int convs_make_plan(const rcv_handle* h, const rcv_op* op, int kind, ConvPlan* p
   if (const char* ev = RCV_ENV("RCV_CONVS_OCC")) { const int o = atoi(ev); if (o >= 1 && o <= 4) occ = o; }
   const int resident = h->num_cus * occ;
   const int per = ceil_div(pl->total_tiles, resident);
-  pl->grid = ceil_div(pl->total_tiles, per);
+  pl->grid = ceil_div(pl->total_tiles, per); pl->n_part = pl->grid;
   return RCV_OK;
 }
 
@@ -662,8 +662,13 @@ static int convs_launch_wm4(const ConvPlan& pl, const ConvArgs& a, bool two, hip
   }
 }
 
-int convs_launch(const ConvPlan& pl, const ConvArgs& a, bool two, hipStream_t s) {
+static void convs_label(const ConvPlan& pl, const rcv_op* op, char* buf, size_t n) { snprintf(buf, n, "%ss_mfma<%d,%d,%d>", pl.kind == KIND_TMERGED ? "tconvm" : "conv", pl.WM, pl.WN, pl.CK); }
+
+static int convs_launch(const ConvPlan& pl, const ConvArgs& a, hipStream_t s) {
+  const bool two = a.in_mode == RCV_LOAD_GRAD_ENC || a.in_mode == RCV_LOAD_GRAD_DEC;
   if (pl.WM == 4) return convs_launch_wm4(pl, a, two, s);
   if (pl.kind == KIND_GATHER) return pl.WM == 1 ? convs_launch_ck<1, KIND_GATHER>(pl, a, two, s) : convs_launch_ck<2, KIND_GATHER>(pl, a, two, s);
   return pl.WM == 1 ? convs_launch_ck<1, KIND_TMERGED>(pl, a, two, s) : convs_launch_ck<2, KIND_TMERGED>(pl, a, two, s);
 }
+
+RCV_HOST_ROW(ConvFamily, kConvNarrow, "convs_mfma", convs_supported, convs_plan, convs_launch, convs_label, nullptr, 0);

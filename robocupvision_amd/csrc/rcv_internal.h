@@ -134,6 +134,13 @@ static int rcv_launch_with_lds(const Args& a, dim3 grid, size_t lds, int dev, hi
 }
 #endif
 
+// A row of a kernel-family table (conv_common.h, wgrad_common.h): host data; the device pass must not see it (it would emit it, host function names and all)
+#ifdef __HIP_DEVICE_COMPILE__
+#define RCV_HOST_ROW(type, name, ...)
+#else
+#define RCV_HOST_ROW(type, name, ...) extern const type name = {__VA_ARGS__}
+#endif
+
 // ---- launchers implemented in the .hip files; each validates, picks a tiling and enqueues ----
 // `query` != nullptr: do not launch, only fill tiling dependent outputs (n_part / n_split / bytes).
 struct OpQuery {
@@ -144,6 +151,7 @@ struct OpQuery {
 };
 int rcv_launch_conv(const rcv_handle* h, const rcv_op* op, hipStream_t s, OpQuery* query);
 int rcv_launch_wgrad(const rcv_handle* h, const rcv_op* op, hipStream_t s, OpQuery* query);
+int rcv_filter_layout(const rcv_handle* h, const rcv_op* op, int force);     // rcv_op_filter_layout (conv_dispatch.hip)
 int rcv_launch_small(const rcv_handle* h, const rcv_op* op, hipStream_t s, OpQuery* query);
 int rcv_launch_pool_cls(const rcv_handle* h, const rcv_op* op, hipStream_t s, OpQuery* query);
 int rcv_launch_objdet(const rcv_handle* h, const rcv_op* op, hipStream_t s, OpQuery* query);

@@ -249,7 +249,7 @@ __global__ __launch_bounds__(512) void wgrad_bf3_kernel(const WgradArgs a) {
 // --------------------------------------------------------------------------------------------
 // host side
 // --------------------------------------------------------------------------------------------
-bool wgrad_bf3_supported(const rcv_handle* h, const rcv_op* op) {
+static bool wgrad_bf3_supported(const rcv_handle* h, const rcv_op* op) {
   if (RCV_ENV("RCV_NO_BF3") || (op->flags & RCV_F_MFMA_FP32)) return false;
   const int CA = op->i[RCV_I_CIN], CB = op->i[RCV_I_COUT];
   return op->i[RCV_I_STRIDE] == 1 && op->i[RCV_I_DIL] == 1 && op->i[RCV_I_INMODE] != RCV_LOAD_NCHW && CA % 64 == 0 && CB % 64 == 0 &&
@@ -257,30 +257,35 @@ bool wgrad_bf3_supported(const rcv_handle* h, const rcv_op* op) {
 }
 
 // pixel tile (8 x 8 or 4 x 16: the one that wastes fewer pixel slots on this plane) and the pixel split
-void wgrad_bf3_geometry(const rcv_handle* h, const rcv_op* op, int* tw, int* tiles_x, int* tiles_y, int* nsplit, int* nctiles) {
+static int wgrad_bf3_plan(const rcv_handle* h, const rcv_op* op, WPlan* pl) {
   const int N = op->i[RCV_I_N], Hp = op->i[RCV_I_HO], Wp = op->i[RCV_I_WO];
   const long s8 = (long)ceil_div(Hp, 8) * ceil_div(Wp, 8), s16 = (long)ceil_div(Hp, 4) * ceil_div(Wp, 16);
   int TW = s16 < s8 ? 16 : 8;
   if (const char* ev = RCV_ENV("RCV_BF3_TW")) { const int v = atoi(ev); if (v == 8 || v == 16) TW = v; }
-  *tw = TW;
-  *tiles_x = ceil_div(Wp, TW); *tiles_y = ceil_div(Hp, 64 / TW);
+  pl->path = WGRAD_BF3; pl->geom = TW;
+  pl->R = 64 / TW; pl->Wt = TW; pl->Wt4 = TW; pl->IH = pl->R + 2; pl->IW = TW + 2;
+  pl->tiles_x = ceil_div(Wp, TW); pl->tiles_y = ceil_div(Hp, pl->R);
   const int ctiles = (op->i[RCV_I_COUT] / 64) * (op->i[RCV_I_CIN] / 64);
-  const int ntiles = N * *tiles_x * *tiles_y;
+  const int ntiles = N * pl->tiles_x * pl->tiles_y;
   int ns = h->num_cus / ctiles;                      // two 70+ KB buffers: one workgroup per CU
   if (ns < 1) ns = 1;
   if (ns > ntiles) ns = ntiles;
-  *nsplit = ceil_div(ntiles, ceil_div(ntiles, ns));  // equal tile counts per workgroup
-  *nctiles = ctiles;
+  pl->nsplit = ceil_div(ntiles, ceil_div(ntiles, ns));  // equal tile counts per workgroup
+  pl->nctiles = ctiles; pl->grid = dim3(pl->nsplit * ctiles, 1, 1);
+  return RCV_OK;
 }
+
+static void wgrad_bf3_label(const WPlan& pl, const rcv_op* op, char* buf, size_t n) { snprintf(buf, n, "wgrad_bf3<%d>", pl.geom); }
 
 template <int TW, bool GTWO>
 static int b3_launch_inst(const WgradArgs& a, dim3 grid, hipStream_t s, int dev) {
   return rcv_launch_with_lds<wgrad_bf3_kernel<TW, GTWO>>(a, grid, 2 * (size_t)B3Geom<TW>::BUF, dev, s);
 }
 
-int wgrad_bf3_launch(const rcv_handle* h, const WgradArgs& a, int tw, hipStream_t s) {
+static int wgrad_bf3_launch(const rcv_handle* h, const WPlan& pl, const WgradArgs& a, hipStream_t s) {
   const bool g_two = a.g_mode == RCV_LOAD_GRAD_ENC || a.g_mode == RCV_LOAD_GRAD_DEC;
-  const dim3 grid(a.nsplit * a.nctiles);
-  if (tw == 8) return g_two ? b3_launch_inst<8, true>(a, grid, s, h->device) : b3_launch_inst<8, false>(a, grid, s, h->device);
-  return g_two ? b3_launch_inst<16, true>(a, grid, s, h->device) : b3_launch_inst<16, false>(a, grid, s, h->device);
+  if (pl.geom == 8) return g_two ? b3_launch_inst<8, true>(a, pl.grid, s, h->device) : b3_launch_inst<8, false>(a, pl.grid, s, h->device);
+  return g_two ? b3_launch_inst<16, true>(a, pl.grid, s, h->device) : b3_launch_inst<16, false>(a, pl.grid, s, h->device);
 }
+
+RCV_HOST_ROW(WgradFamily, kWgradBf3, "wgrad_bf3", wgrad_bf3_supported, wgrad_bf3_plan, wgrad_bf3_launch, wgrad_bf3_label);

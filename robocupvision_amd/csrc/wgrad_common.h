@@ -1,4 +1,4 @@
-// Shared declarations of the filter-gradient kernels (wgrad_mfma.hip: matrix cores; wgrad_first.hip: first layer on the vector ALU).
+// Shared declarations of the filter-gradient kernel families (dispatch: conv_dispatch.hip).
 #pragma once
 #include "load_xform.h"
 
@@ -20,17 +20,16 @@ struct WgradArgs {
 // padded gathered-channel count of the partial-filter layout [split][tap][CBP][CAP] (shared by the kernels and RCV_OP_WGRAD_REDUCE)
 static inline int wgrad_cap(int CA) { return CA <= 4 ? 4 : round_up(CA, 16); }
 
-// first-layer kernel (wgrad_first.hip)
-bool wgrad_first_supported(const rcv_op* op);
-int wgrad_first_nsplit(const rcv_handle* h, const rcv_op* op);
-int wgrad_first_launch(const rcv_handle* h, const WgradArgs& a, hipStream_t s);
-
-// wide stride-1 layers on the bf16 matrix pipe (wgrad_bf3.hip)
-bool wgrad_bf3_supported(const rcv_handle* h, const rcv_op* op);
-void wgrad_bf3_geometry(const rcv_handle* h, const rcv_op* op, int* tw, int* tiles_x, int* tiles_y, int* nsplit, int* nctiles);
-int wgrad_bf3_launch(const rcv_handle* h, const WgradArgs& a, int tw, hipStream_t s);
-
-// narrow layers on the bf16 matrix pipe (wgradn_bf3.hip)
-bool wgradn_bf3_supported(const rcv_handle* h, const rcv_op* op);
-void wgradn_bf3_geometry(const rcv_handle* h, const rcv_op* op, int* th, int* tiles_x, int* tiles_y, int* ngroups);
-int wgradn_bf3_launch(const rcv_handle* h, const WgradArgs& a, int th, int ngroups, hipStream_t s);
+// Kernel families in order of precedence: WPlan::path is the row of kWgradFamilies (conv_dispatch.hip: it fills CAP / CBP, `plan` the rest).
+// `geom`: the tile width of wgrad_bf3, the tile rows of wgradn_bf3; `tile`: the row of wgrad_mfma's tile table.
+enum { WGRAD_FIRST = 0, WGRAD_BF3, WGRADN_BF3, WGRAD_MFMA, WGRAD_NUM_FAMILIES };
+struct WPlan { int path; int geom; int nctiles; int tile; int R, Wt, Wt4, tiles_x, tiles_y, IH, IW, SP, SG, nsplit, pl_floats, gl_floats; size_t lds; dim3 grid; int CAP, CBP; };
+struct WgradFamily {      // one row, defined next to its kernels; the first row whose `supported` accepts a record plans it
+  const char* name;
+  bool (*supported)(const rcv_handle*, const rcv_op*);
+  int (*plan)(const rcv_handle*, const rcv_op*, WPlan*);
+  int (*launch)(const rcv_handle*, const WPlan&, const WgradArgs&, hipStream_t);
+  void (*label)(const WPlan&, const rcv_op*, char* buf, size_t n);
+};
+extern const WgradFamily kWgradFirst, kWgradBf3, kWgradnBf3, kWgradMfma;
+int wgrad_reduce_launch(const rcv_handle* h, const rcv_op* op, hipStream_t s);      // RCV_OP_WGRAD_REDUCE[_BATCH] (wgrad_mfma.hip)

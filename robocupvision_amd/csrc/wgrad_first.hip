@@ -160,7 +160,7 @@ __global__ __launch_bounds__(384) void wgrad_first_kernel(const WgradArgs a, int
 // --------------------------------------------------------------------------------------------
 // host side
 // --------------------------------------------------------------------------------------------
-bool wgrad_first_supported(const rcv_op* op) {
+static bool wgrad_first_supported(const rcv_handle* h, const rcv_op* op) {
   if (RCV_ENV("RCV_NO_WGRAD_FIRST")) return false;
   const int d = op->i[RCV_I_DIL];
   return op->i[RCV_I_INMODE] == RCV_LOAD_NCHW && op->i[RCV_I_CIN] <= 3 && op->i[RCV_I_COUT] == 8 && op->i[RCV_I_STRIDE] == 1 &&
@@ -174,21 +174,25 @@ static inline int wf_tiles(const rcv_op* op, int* tx, int* ty) {
   return op->i[RCV_I_N] * *tx * *ty;
 }
 
-int wgrad_first_nsplit(const rcv_handle* h, const rcv_op* op) {
-  int tx, ty;
-  const int ntiles = wf_tiles(op, &tx, &ty);
-  int nsplit = h->num_cus * wf_occ();                // persistent workgroups of six waves (24 KB of LDS each)
+static int wgrad_first_plan(const rcv_handle* h, const rcv_op* op, WPlan* pl) {
+  const int d = op->i[RCV_I_DIL];
+  const int ntiles = wf_tiles(op, &pl->tiles_x, &pl->tiles_y);
+  int nsplit = h->num_cus * wf_occ();                // persistent workgroups of six waves (24 KB of LDS each), one partial row per workgroup
   if (nsplit > ntiles) nsplit = ntiles;
-  return ceil_div(ntiles, ceil_div(ntiles, nsplit)); // equal tile counts per workgroup
+  pl->nsplit = ceil_div(ntiles, ceil_div(ntiles, nsplit)); // equal tile counts per workgroup
+  pl->path = WGRAD_FIRST; pl->nctiles = 1; pl->grid = dim3(pl->nsplit, 1, 1);
+  pl->R = 8; pl->Wt = 64; pl->Wt4 = 64; pl->IH = 8 + 2 * d; pl->IW = 64 + 2 * d; pl->SP = 8; pl->SG = 1;
+  return RCV_OK;
 }
 
-int wgrad_first_launch(const rcv_handle* h, const WgradArgs& a, hipStream_t s) {
-  const int tiles_x = ceil_div(a.Wp, 64), tiles_y = ceil_div(a.Hp, 8);
-  const int total = a.N * tiles_x * tiles_y;
-  (void)h;
+static void wgrad_first_label(const WPlan& pl, const rcv_op* op, char* buf, size_t n) { snprintf(buf, n, "wgrad_first<%d>", op->i[RCV_I_DIL]); }
+
+static int wgrad_first_launch(const rcv_handle* h, const WPlan& pl, const WgradArgs& a, hipStream_t s) {
   const dim3 g(a.nsplit), b(384);
-  if (a.dil == 1) hipLaunchKernelGGL((wgrad_first_kernel<1>), g, b, 0, s, a, tiles_x, tiles_y, total);
-  else hipLaunchKernelGGL((wgrad_first_kernel<2>), g, b, 0, s, a, tiles_x, tiles_y, total);
+  if (a.dil == 1) hipLaunchKernelGGL((wgrad_first_kernel<1>), g, b, 0, s, a, a.tiles_x, a.tiles_y, a.ntiles);
+  else hipLaunchKernelGGL((wgrad_first_kernel<2>), g, b, 0, s, a, a.tiles_x, a.tiles_y, a.ntiles);
   RCV_HIP(hipGetLastError());
   return RCV_OK;
 }
+
+RCV_HOST_ROW(WgradFamily, kWgradFirst, "wgrad_first", wgrad_first_supported, wgrad_first_plan, wgrad_first_launch, wgrad_first_label);

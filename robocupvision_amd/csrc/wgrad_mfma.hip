@@ -514,7 +514,7 @@ static int wlaunch_inst(const WgradArgs& a, bool gtwo, dim3 grid, size_t lds, hi
     RCV_ENSURE_LDS(kern, lds, dev, configured);
     hipLaunchKernelGGL(kern, grid, dim3(NT), lds, s, a);
   } else if (a.g_mode == RCV_LOAD_NCHW) {
-    constexpr bool CAN = NBF == 2 || (NBF == 0 && WN * WAVES_N == 1);       // tiles the planner gives an NCHW image (wmake_plan)
+    constexpr bool CAN = NBF == 2 || (NBF == 0 && WN * WAVES_N == 1);       // tiles the planner gives an NCHW image (wgrad_mfma_plan)
     if constexpr (CAN) {
       auto kern = wgrad_mfma_kernel<WM, WN, WAVES_M, WAVES_N, WAVES_K, NBF, SPEC, false, true>;
       static size_t configured[RCV_MAX_DEVICES];
@@ -534,49 +534,17 @@ static int wlaunch_inst(const WgradArgs& a, bool gtwo, dim3 grid, size_t lds, hi
   return RCV_OK;
 }
 
-struct WPlan { int first; int bf3; int nctiles; int tile; int R, Wt, Wt4, tiles_x, tiles_y, IH, IW, SP, SG, nsplit, pl_floats, gl_floats; size_t lds; dim3 grid; int CAP, CBP; };
+static bool wgrad_mfma_supported(const rcv_handle* h, const rcv_op* op) { return true; }     // the last row: takes what no other family does
 
-static int wmake_plan(const rcv_handle* h, const rcv_op* op, WPlan* pl) {
-  const int N = op->i[RCV_I_N], H = op->i[RCV_I_H], W = op->i[RCV_I_W];
-  const int CA = op->i[RCV_I_CIN], CB = op->i[RCV_I_COUT];
+static int wgrad_mfma_plan(const rcv_handle* h, const rcv_op* op, WPlan* pl) {
+  const int N = op->i[RCV_I_N], CA = op->i[RCV_I_CIN], CB = op->i[RCV_I_COUT];
   const int Hp = op->i[RCV_I_HO], Wp = op->i[RCV_I_WO];
   const int s = op->i[RCV_I_STRIDE], d = op->i[RCV_I_DIL];
-  RCV_CHECK_ARG(N > 0 && H > 0 && W > 0 && CA > 0 && CB > 0, "wgrad: empty shape");
-  RCV_CHECK_ARG((s == 1 || s == 2) && (d == 1 || d == 2), "wgrad: stride %d dilation %d unsupported", s, d);
-  RCV_CHECK_ARG(Hp == (H - 1) / s + 1 && Wp == (W - 1) / s + 1, "wgrad: pointwise plane %dx%d does not match %dx%d / %d", Hp, Wp, H, W, s);
-  RCV_CHECK_ARG(CB % 4 == 0, "wgrad: pointwise channels %d must be a multiple of 4", CB);
-  RCV_CHECK_ARG((size_t)N * H * W * CA < (1ull << 31) && (size_t)N * Hp * Wp * CB < (1ull << 31), "wgrad: operand exceeds 2^31 elements (32-bit offsets)");
   const bool nchw = op->i[RCV_I_INMODE] == RCV_LOAD_NCHW;
-  if (nchw) RCV_CHECK_ARG(CA <= 4, "wgrad: NCHW gathered operand supports <=4 channels");
-  else RCV_CHECK_ARG(CA % 4 == 0, "wgrad: gathered channels %d must be a multiple of 4", CA);
-  pl->CAP = wgrad_cap(CA); pl->CBP = round_up(CB, 16);
   int cbt_want = pl->CBP >= 64 ? 64 : (pl->CBP >= 32 ? 32 : 16);
   int cat_want = pl->CAP >= 64 ? 64 : (pl->CAP >= 32 ? 32 : 16);
   if (const char* ev = RCV_ENV("RCV_WGRAD_CT")) { const int c = atoi(ev); if (c == 16 || c == 32) { if (cbt_want > c) cbt_want = c; if (cat_want > c) cat_want = c; } }
-  pl->tile = -1;
-  pl->first = 0;
-  if (wgrad_first_supported(op)) {      // first layer: vector-ALU kernel (wgrad_first.hip), one partial row per persistent workgroup
-    pl->first = 1;
-    pl->nsplit = wgrad_first_nsplit(h, op);
-    pl->nctiles = 1; pl->lds = 0; pl->grid = dim3(pl->nsplit, 1, 1);
-    pl->R = 8; pl->Wt = 64; pl->Wt4 = 64; pl->tiles_x = ceil_div(Wp, 64); pl->tiles_y = ceil_div(Hp, 8);
-    pl->IH = 8 + 2 * d; pl->IW = 64 + 2 * d; pl->SP = 8; pl->SG = 1; pl->pl_floats = 0; pl->gl_floats = 0;
-    return RCV_OK;
-  }
-  pl->bf3 = 0;
-  if (wgrad_bf3_supported(h, op)) {     // wide stride-1 layers: fp32 products on the bf16 matrix pipe (wgrad_bf3.hip)
-    wgrad_bf3_geometry(h, op, &pl->bf3, &pl->tiles_x, &pl->tiles_y, &pl->nsplit, &pl->nctiles);
-    pl->lds = 0; pl->grid = dim3(pl->nsplit * pl->nctiles, 1, 1);
-    pl->R = 64 / pl->bf3; pl->Wt = pl->bf3; pl->Wt4 = pl->bf3; pl->IH = pl->R + 2; pl->IW = pl->bf3 + 2; pl->SP = 0; pl->SG = 0; pl->pl_floats = 0; pl->gl_floats = 0;
-    return RCV_OK;
-  }
-  if (wgradn_bf3_supported(h, op)) {    // narrow layers, the same arithmetic (wgradn_bf3.hip): bf3 = -(tile rows), four splits per workgroup
-    int th, ng;
-    wgradn_bf3_geometry(h, op, &th, &pl->tiles_x, &pl->tiles_y, &ng);
-    pl->bf3 = -th; pl->nsplit = 4 * ng; pl->nctiles = 1; pl->lds = 0; pl->grid = dim3(ng, 1, 1);
-    pl->R = th; pl->Wt = 16; pl->Wt4 = 16; pl->IH = (th - 1) * s + 3; pl->IW = 15 * s + 3; pl->SP = 0; pl->SG = 0; pl->pl_floats = 0; pl->gl_floats = 0;
-    return RCV_OK;
-  }
+  pl->path = WGRAD_MFMA; pl->tile = -1;
   // (an NCHW image with 4 channels does not fit the 2-block folded tile and the 5-block one carries no NCHW path: 16 x 16 tile)
   const bool fold = CA <= 8 && cbt_want == 16 && !(nchw && 9 * CA > 32) && !RCV_ENV("RCV_NO_FOLD");
   if (fold) pl->tile = 9 * CA <= 32 ? 7 : 8;
@@ -693,89 +661,14 @@ static int wmake_plan(const rcv_handle* h, const rcv_op* op, WPlan* pl) {
   return RCV_OK;
 }
 
-int rcv_launch_wgrad(const rcv_handle* h, const rcv_op* op, hipStream_t s, OpQuery* query) {
-  if (op->kind == RCV_OP_WGRAD_REDUCE_BATCH) {
-    if (query) { snprintf(query->label, sizeof(query->label), "wgrad_reduce_batch"); query->n_part = 0; query->n_split = 0; query->part_bytes = 0; return RCV_OK; }
-    const int njobs = op->i[RCV_I_COUNT], blocks = op->i[RCV_I_NPART];
-    RCV_CHECK_ARG(op->p[RCV_P_IN] && njobs >= 1 && njobs <= 64 && blocks >= 1, "wgrad_reduce_batch: needs a job table (1..64 rows) and the block count");
-    hipLaunchKernelGGL(wgrad_reduce_batch_kernel, dim3(blocks), dim3(256), 0, s, (const rcv_reduce_job*)op->p[RCV_P_IN], njobs);
-    RCV_HIP(hipGetLastError());
-    return RCV_OK;
-  }
-  if (op->kind == RCV_OP_WGRAD_REDUCE) {
-    if (query) { snprintf(query->label, sizeof(query->label), "wgrad_reduce"); query->n_part = 0; query->n_split = 0; query->part_bytes = 0; return RCV_OK; }
-    const int CA = op->i[RCV_I_CIN], CB = op->i[RCV_I_COUT], nsplit = op->i[RCV_I_NSPLIT];
-    const int CAP = wgrad_cap(CA), CBP = round_up(CB, 16);
-    const float* part = (const float*)op->p[RCV_P_PART];
-    float* dw = (float*)op->p[RCV_P_OUT];
-    float* db = (float*)op->p[RCV_P_BIAS];
-    RCV_CHECK_ARG(part && dw && nsplit > 0, "wgrad_reduce: null operand");
-    const float* pb = db ? part + (size_t)nsplit * 9 * CBP * CAP : nullptr;
-    const int total = 9 * CBP * CAP + (db ? CBP : 0);
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(ceil_div(total, 64)), dim3(256), 0, s, part, pb, dw, db, nsplit, CB, CA, CBP, CAP);
-    RCV_HIP(hipGetLastError());
-    return RCV_OK;
-  }
-  WPlan pl;
-  if (!rcv_plan_get(h, op, &pl)) {
-    memset(&pl, 0, sizeof(pl));
-    const int rc = wmake_plan(h, op, &pl);
-    if (rc) return rc;
-    rcv_plan_put(h, op, pl);
-  }
-  {   // load-mode refusals belong to the shape of the record: in front of the query return (what the planner accepts, the launch accepts)
-    const int gm = op->i[RCV_I_INMODE], pm = op->i[RCV_I_INMODE2];
-    const bool g2 = gm == RCV_LOAD_GRAD_ENC || gm == RCV_LOAD_GRAD_DEC, p2 = pm == RCV_LOAD_GRAD_ENC || pm == RCV_LOAD_GRAD_DEC;
-    RCV_CHECK_ARG(pm != RCV_LOAD_NCHW, "wgrad: pointwise operand cannot be NCHW");
-    RCV_CHECK_ARG(!(g2 && p2), "wgrad: at most one operand may be a gradient (two-tensor) load");
-  }
-  if (query && pl.first) {
-    snprintf(query->label, sizeof(query->label), "wgrad_first<%d>", op->i[RCV_I_DIL]);
-    query->n_part = 0;
-    query->n_split = pl.nsplit;
-    query->part_bytes = (size_t)pl.nsplit * (9 * (size_t)pl.CBP * pl.CAP + pl.CBP) * sizeof(float);
-    return RCV_OK;
-  }
-  if (query && pl.bf3) {
-    if (pl.bf3 > 0) snprintf(query->label, sizeof(query->label), "wgrad_bf3<%d>", pl.bf3);
-    else snprintf(query->label, sizeof(query->label), "wgradn_bf3<%d,%d>", -pl.bf3, op->i[RCV_I_STRIDE]);
-    query->n_part = 0;
-    query->n_split = pl.nsplit;
-    query->part_bytes = (size_t)pl.nsplit * (9 * (size_t)pl.CBP * pl.CAP + pl.CBP) * sizeof(float);
-    return RCV_OK;
-  }
-  if (query) {
-    const WTile& wt = kWT[pl.tile];
-    snprintf(query->label, sizeof(query->label), "wgrad_mfma<%d,%d,%d,%d,%d,f%d>", wt.WM, wt.WN, wt.WAVES_M, wt.WAVES_N, wt.WAVES_K, wt.NBF);
-    query->n_part = 0;
-    query->n_split = pl.nsplit;
-    query->part_bytes = (size_t)pl.nsplit * (9 * (size_t)pl.CBP * pl.CAP + pl.CBP) * sizeof(float);
-    return RCV_OK;
-  }
-  WgradArgs a;
-  a.g = (const float*)op->p[RCV_P_IN]; a.g_aux = (const float*)op->p[RCV_P_IN_AUX]; a.g_c = (const float*)op->p[RCV_P_IN_C];
-  a.p = (const float*)op->p[RCV_P_IN2]; a.p_aux = (const float*)op->p[RCV_P_IN2_AUX]; a.p_c = (const float*)op->p[RCV_P_IN2_C];
-  a.part = (float*)op->p[RCV_P_PART];
-  a.g_mode = op->i[RCV_I_INMODE]; a.p_mode = op->i[RCV_I_INMODE2];
-  a.N = op->i[RCV_I_N]; a.H = op->i[RCV_I_H]; a.W = op->i[RCV_I_W]; a.Hp = op->i[RCV_I_HO]; a.Wp = op->i[RCV_I_WO];
-  a.CA = op->i[RCV_I_CIN]; a.CB = op->i[RCV_I_COUT]; a.CAP = pl.CAP; a.CBP = pl.CBP;
-  a.stride = op->i[RCV_I_STRIDE]; a.dil = op->i[RCV_I_DIL];
-  a.R = pl.R; a.Wt = pl.Wt; a.Wt4 = pl.Wt4; a.tiles_x = pl.tiles_x; a.tiles_y = pl.tiles_y;
-  a.ntiles = a.N * pl.tiles_x * pl.tiles_y; a.IH = pl.IH; a.IW = pl.IW; a.SP = pl.SP; a.SG = pl.SG;
-  a.dbg = op->flags; a.nsplit = pl.nsplit; a.nctiles = pl.nctiles; a.pl_floats = pl.pl_floats; a.gl_floats = pl.gl_floats;
-  a.fdWt4 = make_fastdiv(pl.Wt4); a.fdIW = make_fastdiv(pl.IW);
-  RCV_CHECK_ARG(a.g && a.p && a.part, "wgrad: null operand");
-  RCV_CHECK_ARG(op->i[RCV_I_NSPLIT] == pl.nsplit, "wgrad: workspace splits %d != %d", op->i[RCV_I_NSPLIT], pl.nsplit);
-  RCV_CHECK_ARG(a.g_mode == RCV_LOAD_PLAIN || a.g_mode == RCV_LOAD_NCHW || a.g_c, "wgrad: gathered load mode %d needs constants", a.g_mode);
-  RCV_CHECK_ARG(a.p_mode == RCV_LOAD_PLAIN || a.p_c, "wgrad: pointwise load mode %d needs constants", a.p_mode);
+
+static void wgrad_mfma_label(const WPlan& pl, const rcv_op* op, char* buf, size_t n) {
+  const WTile& wt = kWT[pl.tile];
+  snprintf(buf, n, "wgrad_mfma<%d,%d,%d,%d,%d,f%d>", wt.WM, wt.WN, wt.WAVES_M, wt.WAVES_N, wt.WAVES_K, wt.NBF);
+}
+
+static int wgrad_mfma_launch(const rcv_handle* h, const WPlan& pl, const WgradArgs& a, hipStream_t s) {
   const bool g_two = a.g_mode == RCV_LOAD_GRAD_ENC || a.g_mode == RCV_LOAD_GRAD_DEC;
-  const bool p_two = a.p_mode == RCV_LOAD_GRAD_ENC || a.p_mode == RCV_LOAD_GRAD_DEC;
-  RCV_CHECK_ARG(!g_two || a.g_aux, "wgrad: gathered gradient load needs aux");
-  RCV_CHECK_ARG(!p_two || a.p_aux, "wgrad: pointwise gradient load needs aux");
-  a.part_bias = (op->flags & RCV_F_BIAS) ? a.part + (size_t)pl.nsplit * 9 * pl.CBP * pl.CAP : nullptr;
-  if (pl.first) return wgrad_first_launch(h, a, s);
-  if (pl.bf3 < 0) return wgradn_bf3_launch(h, a, -pl.bf3, (int)pl.grid.x, s);
-  if (pl.bf3) return wgrad_bf3_launch(h, a, pl.bf3, s);
   switch (pl.tile) {
     case 0: return wlaunch_inst<2, 2, 2, 2, 1, 0, true>(a, g_two, pl.grid, pl.lds, s, h->device);
     case 1: return wlaunch_inst<2, 2, 2, 1, 2, 0, true>(a, g_two, pl.grid, pl.lds, s, h->device);
@@ -787,4 +680,26 @@ int rcv_launch_wgrad(const rcv_handle* h, const rcv_op* op, hipStream_t s, OpQue
     case 7: return wlaunch_inst<1, 1, 1, 1, 4, 2, false>(a, g_two, pl.grid, pl.lds, s, h->device);
     default: return wlaunch_inst<1, 1, 1, 1, 4, 5, false>(a, g_two, pl.grid, pl.lds, s, h->device);
   }
+}
+
+RCV_HOST_ROW(WgradFamily, kWgradMfma, "wgrad_mfma", wgrad_mfma_supported, wgrad_mfma_plan, wgrad_mfma_launch, wgrad_mfma_label);
+
+int wgrad_reduce_launch(const rcv_handle* h, const rcv_op* op, hipStream_t s) {
+  if (op->kind == RCV_OP_WGRAD_REDUCE_BATCH) {
+    const int njobs = op->i[RCV_I_COUNT], blocks = op->i[RCV_I_NPART];
+    RCV_CHECK_ARG(op->p[RCV_P_IN] && njobs >= 1 && njobs <= 64 && blocks >= 1, "wgrad_reduce_batch: needs a job table (1..64 rows) and the block count");
+    hipLaunchKernelGGL(wgrad_reduce_batch_kernel, dim3(blocks), dim3(256), 0, s, (const rcv_reduce_job*)op->p[RCV_P_IN], njobs);
+    RCV_HIP(hipGetLastError());
+    return RCV_OK;
+  }
+  const int CA = op->i[RCV_I_CIN], CB = op->i[RCV_I_COUT], nsplit = op->i[RCV_I_NSPLIT];
+  const int CAP = wgrad_cap(CA), CBP = round_up(CB, 16);
+  const float* part = (const float*)op->p[RCV_P_PART];
+  float *dw = (float*)op->p[RCV_P_OUT], *db = (float*)op->p[RCV_P_BIAS];
+  RCV_CHECK_ARG(part && dw && nsplit > 0, "wgrad_reduce: null operand");
+  const float* pb = db ? part + (size_t)nsplit * 9 * CBP * CAP : nullptr;
+  const int total = 9 * CBP * CAP + (db ? CBP : 0);
+  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(ceil_div(total, 64)), dim3(256), 0, s, part, pb, dw, db, nsplit, CB, CA, CBP, CAP);
+  RCV_HIP(hipGetLastError());
+  return RCV_OK;
 }

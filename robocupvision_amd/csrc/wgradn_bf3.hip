@@ -249,7 +249,7 @@ static inline size_t w3_buf(int cbt, int cat, int s, int th) {
   return ((size_t)3 * ih * iw * w3_gpitch(cat) + (size_t)3 * th * 16 * w3_ppitch(cbt) + 15) / 16 * 16;
 }
 
-bool wgradn_bf3_supported(const rcv_handle* h, const rcv_op* op) {
+static bool wgradn_bf3_supported(const rcv_handle* h, const rcv_op* op) {
   if (RCV_ENV("RCV_NO_BF3") || RCV_ENV("RCV_NO_BF3W") || (op->flags & RCV_F_MFMA_FP32)) return false;
   const int CA = op->i[RCV_I_CIN], CB = op->i[RCV_I_COUT], s = op->i[RCV_I_STRIDE];
   if (op->i[RCV_I_DIL] != 1 || op->i[RCV_I_INMODE] == RCV_LOAD_NCHW || (s != 1 && s != 2)) return false;
@@ -267,17 +267,21 @@ bool wgradn_bf3_supported(const rcv_handle* h, const rcv_op* op) {
 }
 
 // tile rows (16 where two buffers of it fit, else 8), tile counts and the workgroup count; n_split = 4 per workgroup (one per consumer wave)
-void wgradn_bf3_geometry(const rcv_handle* h, const rcv_op* op, int* th, int* tiles_x, int* tiles_y, int* ngroups) {
+static int wgradn_bf3_plan(const rcv_handle* h, const rcv_op* op, WPlan* pl) {
   const int CA = op->i[RCV_I_CIN], CB = op->i[RCV_I_COUT], s = op->i[RCV_I_STRIDE];
   int TH = (s == 1 && w3_ct(CB) == 16 && w3_ct(CA) == 16 && 2 * w3_buf(16, 16, 1, 16) <= (size_t)h->max_lds) ? 16 : 8;
   if (const char* ev = RCV_ENV("RCV_BF3W_TH")) { const int v = atoi(ev); if (v == 8) TH = 8; }
-  *th = TH;
-  *tiles_x = ceil_div(op->i[RCV_I_WO], 16); *tiles_y = ceil_div(op->i[RCV_I_HO], TH);
-  const long tiles = (long)op->i[RCV_I_N] * *tiles_x * *tiles_y;
+  pl->path = WGRADN_BF3; pl->geom = TH;
+  pl->R = TH; pl->Wt = 16; pl->Wt4 = 16; pl->IH = (TH - 1) * s + 3; pl->IW = 15 * s + 3;
+  pl->tiles_x = ceil_div(op->i[RCV_I_WO], 16); pl->tiles_y = ceil_div(op->i[RCV_I_HO], TH);
+  const long tiles = (long)op->i[RCV_I_N] * pl->tiles_x * pl->tiles_y;
   int g = tiles < h->num_cus ? (int)tiles : h->num_cus;
   g = ceil_div((int)tiles, ceil_div((int)tiles, g));                      // equal tile counts per workgroup
-  *ngroups = g;
+  pl->nsplit = 4 * g; pl->nctiles = 1; pl->grid = dim3(g, 1, 1);
+  return RCV_OK;
 }
+
+static void wgradn_bf3_label(const WPlan& pl, const rcv_op* op, char* buf, size_t n) { snprintf(buf, n, "wgradn_bf3<%d,%d>", pl.geom, op->i[RCV_I_STRIDE]); }
 
 template <int CBT, int CAT, int S, int TH, bool GTWO>
 static int w3_launch_inst(const WgradArgs& a, int ngroups, hipStream_t s, int dev) {
@@ -298,7 +302,10 @@ static int w3_launch_s(const WgradArgs& a, int th, bool g_two, int ngroups, hipS
   return w3_launch_th<32, 32, S>(a, th, g_two, ngroups, s, dev);
 }
 
-int wgradn_bf3_launch(const rcv_handle* h, const WgradArgs& a, int th, int ngroups, hipStream_t s) {
+static int wgradn_bf3_launch(const rcv_handle* h, const WPlan& pl, const WgradArgs& a, hipStream_t s) {
   const bool g_two = a.g_mode == RCV_LOAD_GRAD_ENC || a.g_mode == RCV_LOAD_GRAD_DEC;
-  return a.stride == 1 ? w3_launch_s<1>(a, th, g_two, ngroups, s, h->device) : w3_launch_s<2>(a, th, g_two, ngroups, s, h->device);
+  const int ngroups = (int)pl.grid.x;
+  return a.stride == 1 ? w3_launch_s<1>(a, pl.geom, g_two, ngroups, s, h->device) : w3_launch_s<2>(a, pl.geom, g_two, ngroups, s, h->device);
 }
+
+RCV_HOST_ROW(WgradFamily, kWgradnBf3, "wgradn_bf3", wgradn_bf3_supported, wgradn_bf3_plan, wgradn_bf3_launch, wgradn_bf3_label);

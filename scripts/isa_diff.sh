@@ -2,7 +2,8 @@
 # usage: scripts/isa_diff.sh BASE_REV [JOBS]
 # Compiles every csrc/*.hip of BASE_REV and of the working tree device-only to gfx950 assembly (the Makefile's flags) and prints, per
 # file, the number of differing lines -- ignoring the lines with __hip_cuid_, a hash of the source text -- and, per kernel, the
-# register / spill / scratch figures that changed.  Exit status 0: identical device code everywhere.  Needs hipcc, no GPU.
+# register / spill / scratch figures that changed.  A file that only the working tree has and that defines no kernel is reported as
+# "host only".  Exit status 0: identical device code everywhere.  Needs hipcc, no GPU.
 set -euo pipefail
 BASE=${1:?usage: scripts/isa_diff.sh BASE_REV [JOBS]}
 JOBS=${2:-8}
@@ -31,6 +32,7 @@ meta() {
 status=0
 for name in $(cd "$T/asm" && ls base head | grep '\.s$' | sort -u); do
   b="$T/asm/base/$name"; h="$T/asm/head/$name"
+  if [ ! -f "$b" ] && ! grep -q '\.amdhsa_kernel' "$h"; then echo "${name%.s}.hip: host only"; continue; fi      # a new file without kernels
   if [ ! -f "$b" ] || [ ! -f "$h" ]; then echo "${name%.s}.hip: only in $([ -f "$b" ] && echo "$BASE" || echo "the working tree")"; status=1; continue; fi
   n=$(diff <(grep -v __hip_cuid_ "$b") <(grep -v __hip_cuid_ "$h") | grep -c '^[<>]' || true)
   echo "${name%.s}.hip: $n differing lines"

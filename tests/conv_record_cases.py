@@ -58,6 +58,34 @@ def tconv_record(shape, mode_name, layout, **ptrs):
                      inmode=TCONV_RECORD_MODES[mode_name], aux0=layout, **ptrs)
 
 
+# ------------------------------------------------------------------------------------------ the layer shapes of the networks
+NETWORK_PLANES = [(32, 480, 640), (64, 120, 160), (32, 240, 320), (2, 48, 64), (1, 32, 48), (3, 37, 53), (1, 9, 11), (5, 130, 70)]
+NETWORK_CHANNELS = [(3, 8), (8, 8), (8, 16), (16, 16), (16, 32), (32, 32), (32, 64), (64, 64), (64, 128), (128, 128), (128, 64), (24, 40), (4, 12)]
+
+
+def network_layer_records():
+    """(what, record) for every conv / transposed-conv / filter-gradient record the ROBO-UNet, U-Net and PB_FCN graphs produce at the
+    BASELINE sizes and at ragged / tiny planes; what: "conv", "wgrad", "wgrad_nchw" (the image as the gathered operand) or "tconv".
+    The sweep of tests/test_lib_abi.py and of scripts/plan_dump.py."""
+    for (n, H, W) in NETWORK_PLANES:
+        for (ci, co) in NETWORK_CHANNELS:
+            for s in (1, 2):
+                for d in ((1, 2) if s == 1 else (1,)):
+                    Ho, Wo = (H - 1) // s + 1, (W - 1) // s + 1
+                    if ci >= 4:
+                        for mode in (L.LOAD_AFFINE, L.LOAD_GRAD_ENC):
+                            yield "conv", L.make_op(L.OP_CONV, L.F_BIAS, n=n, h=H, w=W, cin=ci, cout=co, ho=Ho, wo=Wo, stride=s, dil=d,
+                                                    inmode=mode, stats=L.STATS_FWD)
+                        yield "wgrad", L.make_op(L.OP_WGRAD, L.F_BIAS, n=n, h=H, w=W, cin=ci, ho=Ho, wo=Wo, cout=co, stride=s, dil=d,
+                                                 inmode=L.LOAD_AFFINE, inmode2=L.LOAD_GRAD_ENC)
+                    elif d == 1 or s == 1:
+                        yield "wgrad_nchw", L.make_op(L.OP_WGRAD, L.F_BIAS, n=n, h=H, w=W, cin=ci, ho=Ho, wo=Wo, cout=co, stride=s, dil=d,
+                                                      inmode=L.LOAD_NCHW, inmode2=L.LOAD_GRAD_ENC)
+            if ci >= 4 and co % 4 == 0:
+                yield "tconv", L.make_op(L.OP_TCONV, L.F_BIAS, n=n, h=H, w=W, cin=ci, cout=co, ho=2 * H, wo=2 * W, stride=2, dil=1,
+                                         inmode=L.LOAD_AFFINE, stats=L.STATS_FWD)
+
+
 # ------------------------------------------------------------------------------------------ filter gradients
 # (gathered, pointwise) load modes -> (RCV_LOAD_* of the gathered operand, of the pointwise operand, flags)
 WGRAD_RECORD_PAIRS = {
