@@ -191,7 +191,7 @@ enum {
                              * p[OUT] = rows int32 [N][C-1][M][8], p[X0] = counts int32 [N][C-1][4], p[X1] = HOST double[C-1] min_ratio, p[X2] =
                              * HOST int32[C-1] min_area, p[X3] = HOST int32[C-1] cap (the three read when enqueued), p[PART] = workspace,
                              * i[NPART] = its size in 256-byte units (filled by rcv_op_workspace)                                       */
-  RCV_OP_RGB_PREP = 47       /* the loader of trainer.py:75-123 (and pruner.py, labelPropTrain.py, tester.py, makeLPImages.py, classTrainer.py,
+  RCV_OP_RGB_PREP = 47,      /* the loader of trainer.py:75-123 (and pruner.py, labelPropTrain.py, tester.py, makeLPImages.py, classTrainer.py,
                              * objDetEval.py) for a whole batch (rcv_rgb_prep; csrc/rgb_prep.hip): Scale, the two flips, torchvision's PIL
                              * ColorJitter, rgb2yuv, ToTensor, Normalize([.5,0,0],[.5,.5,.5]), and the label's Scale, flips and maskLabel.
                              * i[N] = B, i[H] / i[W] = source Hs / Ws, i[HO] / i[WO] = output H / W, i[CIN] / i[COUT] = taps per output column /
@@ -202,6 +202,17 @@ enum {
                              * label index tables of x / y (the four as RCV_OP_BATCH_PREP), p[IN_C] = parameter rows float[B][12] (train only),
                              * p[OUT] = imgs float[B][3][H][W], p[X0] = targets int64[B][H][W], p[PART] = uint32[i[NPART]]: one partial sum of L
                              * per workgroup of the statistics launch (i[NPART] filled by rcv_op_workspace; 0 unless train and i[COUNT])     */
+  RCV_OP_FARNEBACK = 48,     /* dense optical flow of B frame pairs by Farnebaeck's polynomial expansion (rcv_farneback_flow; csrc/flow.hip;
+                             * transform.py:185-187 optFlow).  i[N] = B, i[H], i[W], i[CIN] = bytes per pixel of the frames (1 = gray, 3 = RGB:
+                             * gray = (4899 R + 9617 G + 1868 B + 8192) >> 14 is formed on load), i[COUNT] = levels (0..4), i[AUX0] = winsize
+                             * (odd, 1..15), i[AUX1] = iterations (1..64), i[STRIDE] = poly_n (5 or 7), i[DIL] = cv2's flags word (0 only),
+                             * f[0] = pyr_scale (0.5 only), f[1] = poly_sigma; p[IN] = prev uint8[B][H][W](x3), p[IN2] = next, p[OUT] = flow
+                             * float[B][2][H][W] (channel 0 = dx along columns, 1 = dy along rows), p[PART] = workspace, i[NPART] = its size in
+                             * 256-byte units (filled by rcv_op_workspace)                                                              */
+  RCV_OP_REMAP_LABELS = 49   /* a class map moved through a flow (rcv_update_labels; csrc/flow.hip; transform.py:189-198 updateLabels): out[y][x]
+                             * = in[rint(y + flow[1])][rint(x + flow[0])] inside the plane, 0 outside; fp32 sums, rint = half to even.  i[N],
+                             * i[H], i[W], i[INMODE] = element bytes (1 = uint8, 8 = int64); p[IN] = class map [N][H][W], p[IN2] = flow
+                             * float[N][2][H][W], p[OUT] = class map [N][H][W] (not p[IN])                                              */
 };
 
 /* i[RCV_I_AUX0] of RCV_OP_PRUNE: how the threshold of a tensor is chosen */
@@ -475,6 +486,24 @@ int rcv_object_match(rcv_handle* h, const void* pred, int pred_bytes, const void
 int rcv_find_objects(rcv_handle* h, const void* classmap, int elem_bytes, int N, int C, int H, int W, const int32_t* min_area,
                      const double* min_ratio, const int32_t* cap, int M, int32_t* rows, int32_t* counts, void* workspace,
                      size_t workspace_bytes, void* stream);
+
+/* Dense optical flow on the device (RCV_OP_FARNEBACK): what transform.py:185-187 optFlow gets from cv2.calcOpticalFlowFarneback(prev,
+ * next, None, pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags), for B frame pairs at once.  prev / next uint8
+ * [B][H][W] (channels = 1) or [B][H][W][3] RGB (channels = 3); flow float[B][2][H][W], channel 0 = dx (columns), 1 = dy (rows), the
+ * layout optFlow's transpose((2,0,1)) returns: next(x) = prev(x - d) gives +d.  The algorithm is Farnebaeck's (2003) with OpenCV's parameter
+ * meanings, stated operation by operation in tests/farneback_restatement.py and DESIGN §4.11 (the project's own contract: agreement with
+ * cv2 bit for bit is not claimed).  Refused: flags != 0 (no initial flow, no Gaussian window), pyr_scale != 0.5, even winsize or
+ * winsize > 15, poly_n other than 5 or 7, levels > 4.  fp32; every window is summed in a fixed tap order, so the result does not depend
+ * on batch position or run.  ws: rcv_op_workspace bytes of the record, 256-byte aligned.  No host synchronisation.                 */
+int rcv_farneback_flow(rcv_handle* h, const uint8_t* prev, const uint8_t* next, int channels, int B, int H, int W, float pyr_scale,
+                       int levels, int winsize, int iterations, int poly_n, float poly_sigma, int flags, float* flow, void* workspace,
+                       size_t workspace_bytes, void* stream);
+
+/* RCV_OP_REMAP_LABELS: what transform.py:189-198 updateLabels gets from cv2.remap(labels, col + flow[0], row + flow[1], INTER_NEAREST,
+ * BORDER_CONSTANT, 0) for N class maps (elem_bytes 1 = uint8, 8 = int64) and their flows float[N][2][H][W]: the source pixel is
+ * (rint(row + flow[1]), rint(col + flow[0])), sums in fp32, halves to even; 0 where it lies outside the plane (or is NaN).  out must
+ * not be labels.                                                                                                                 */
+int rcv_update_labels(rcv_handle* h, const void* labels, int elem_bytes, const float* flow, int N, int H, int W, void* out, void* stream);
 
 /* The batch assembly of labelPropTrain.py:162-193 in one launch: for every frame pair b, inputs[2b] = [Ya, Yb, Ya - Yb,
  * labelToPred(label_b)], targets[2b] = label_a, and the swapped sample at 2b + 1; Y = channel 0 of a frame, labelToPred

@@ -28,4 +28,11 @@ def __getattr__(name):
     if name in ("Segmenter", "find_objects", "Objects", "DBCONVERT"):
         from . import infer
         return getattr(infer, name)
+    # label propagation by dense optical flow (test.py:135-140 --lProp; transform.py:185-198): flow.py
+    if name == "flow":
+        import importlib
+        return importlib.import_module(".flow", __name__)
+    if name in ("farneback_flow", "update_labels", "propagate_labels", "rgb_to_gray", "optFlow", "updateLabels"):
+        from . import flow
+        return getattr(flow, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

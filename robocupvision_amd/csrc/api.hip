@@ -129,6 +129,9 @@ static int dispatch(const rcv_handle* h, const rcv_op* op, hipStream_t s, OpQuer
       return rcv_launch_prune(h, op, s, q);
     case RCV_OP_OBJECTS:
       return rcv_launch_objects(h, op, s, q);
+    case RCV_OP_FARNEBACK:
+    case RCV_OP_REMAP_LABELS:
+      return rcv_launch_flow(h, op, s, q);
     case RCV_OP_NOP:
       if (q) { snprintf(q->label, sizeof(q->label), "nop"); q->n_part = 0; q->n_split = 0; q->part_bytes = 0; }
       return RCV_OK;
@@ -398,6 +401,33 @@ int rcv_find_objects(rcv_handle* h, const void* classmap, int elem_bytes, int N,
   if (rc) return rc;
   RCV_CHECK_ARG(workspace_bytes >= need, "rcv_find_objects: workspace of %zu bytes given, %zu needed (rcv_op_workspace)", workspace_bytes,
                 need);
+  return rcv_run(h, &op, 1, stream);
+}
+
+int rcv_farneback_flow(rcv_handle* h, const uint8_t* prev, const uint8_t* next, int channels, int B, int H, int W, float pyr_scale,
+                       int levels, int winsize, int iterations, int poly_n, float poly_sigma, int flags, float* flow, void* workspace,
+                       size_t workspace_bytes, void* stream) {
+  rcv_op op;
+  memset(&op, 0, sizeof(op));
+  op.kind = RCV_OP_FARNEBACK;
+  op.i[RCV_I_N] = B; op.i[RCV_I_H] = H; op.i[RCV_I_W] = W; op.i[RCV_I_CIN] = channels; op.i[RCV_I_COUNT] = levels; op.i[RCV_I_AUX0] = winsize;
+  op.i[RCV_I_AUX1] = iterations; op.i[RCV_I_STRIDE] = poly_n; op.i[RCV_I_DIL] = flags;
+  op.f[0] = pyr_scale; op.f[1] = poly_sigma;
+  op.p[RCV_P_IN] = (void*)prev; op.p[RCV_P_IN2] = (void*)next; op.p[RCV_P_OUT] = flow; op.p[RCV_P_PART] = workspace;
+  size_t need = 0;
+  const int rc = rcv_op_workspace(h, &op, &need);
+  if (rc) return rc;
+  RCV_CHECK_ARG(workspace_bytes >= need, "rcv_farneback_flow: workspace of %zu bytes given, %zu needed (rcv_op_workspace)", workspace_bytes,
+                need);
+  return rcv_run(h, &op, 1, stream);
+}
+
+int rcv_update_labels(rcv_handle* h, const void* labels, int elem_bytes, const float* flow, int N, int H, int W, void* out, void* stream) {
+  rcv_op op;
+  memset(&op, 0, sizeof(op));
+  op.kind = RCV_OP_REMAP_LABELS;
+  op.i[RCV_I_N] = N; op.i[RCV_I_H] = H; op.i[RCV_I_W] = W; op.i[RCV_I_INMODE] = elem_bytes;
+  op.p[RCV_P_IN] = (void*)labels; op.p[RCV_P_IN2] = (void*)flow; op.p[RCV_P_OUT] = out;
   return rcv_run(h, &op, 1, stream);
 }
 
