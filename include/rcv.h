@@ -209,10 +209,21 @@ enum {
                              * f[0] = pyr_scale (0.5 only), f[1] = poly_sigma; p[IN] = prev uint8[B][H][W](x3), p[IN2] = next, p[OUT] = flow
                              * float[B][2][H][W] (channel 0 = dx along columns, 1 = dy along rows), p[PART] = workspace, i[NPART] = its size in
                              * 256-byte units (filled by rcv_op_workspace)                                                              */
-  RCV_OP_REMAP_LABELS = 49   /* a class map moved through a flow (rcv_update_labels; csrc/flow.hip; transform.py:189-198 updateLabels): out[y][x]
+  RCV_OP_REMAP_LABELS = 49,  /* a class map moved through a flow (rcv_update_labels; csrc/flow.hip; transform.py:189-198 updateLabels): out[y][x]
                              * = in[rint(y + flow[1])][rint(x + flow[0])] inside the plane, 0 outside; fp32 sums, rint = half to even.  i[N],
                              * i[H], i[W], i[INMODE] = element bytes (1 = uint8, 8 = int64); p[IN] = class map [N][H][W], p[IN2] = flow
                              * float[N][2][H][W], p[OUT] = class map [N][H][W] (not p[IN])                                              */
+  RCV_OP_OBJECT_PATCHES = 50 /* the boxes of an RCV_OP_OBJECTS result cut out of the full-resolution frames and brought to the patch
+                             * classifiers' input (rcv_object_patches; csrc/patches.hip): Pillow's 8-bit BILINEAR resize of every box, then
+                             * rgb2yuv + Normalize([.5,0,0],[.5,.5,.5]), one launch, one workgroup per slot.  i[N], i[H] / i[W] = Hs / Ws of the
+                             * frames, i[HO] / i[WO] = H / W of the class map the boxes live in (1..Hs / 1..Ws), i[COUT] = C - 1 (classes with
+                             * boxes), i[COUNT] = M (rows per class), i[AUX0] / i[AUX1] = patch Sh / Sw (1..64 each), i[CIN] = margin >= 0 in
+                             * class-map pixels; p[IN] = frames uint8[N][Hs][Ws][3], p[IN2] = rows int32[N][C-1][M][8] (columns 0..3 = x, y,
+                             * w, h are read), p[X0] = counts int32[N][C-1][4] (column 3 = emitted is read), p[OUT] = images float
+                             * [N (C-1) M][3][Sh][Sw], p[X1] = bytes uint8[N (C-1) M][Sh][Sw][3] or NULL; both outputs are written for every
+                             * slot (zeros past the emitted count: nothing needs pre-zeroing).  No workspace.  Refused when planned: a count
+                             * < 1, a patch side outside 1..64, margin < 0, a map larger than the frames, W Ws or H Hs past 32 bits,
+                             * coefficient tables (2 + ceil(in / out) 2 + 1 int32 per output index and axis) beyond the LDS of a workgroup */
 };
 
 /* i[RCV_I_AUX0] of RCV_OP_PRUNE: how the threshold of a tensor is chosen */
@@ -486,6 +497,28 @@ int rcv_object_match(rcv_handle* h, const void* pred, int pred_bytes, const void
 int rcv_find_objects(rcv_handle* h, const void* classmap, int elem_bytes, int N, int C, int H, int W, const int32_t* min_area,
                      const double* min_ratio, const int32_t* cap, int M, int32_t* rows, int32_t* counts, void* workspace,
                      size_t workspace_bytes, void* stream);
+
+/* Object patches on the device (RCV_OP_OBJECT_PATCHES): the step between rcv_find_objects and the patch classifiers (the verifiers of
+ * objDetEval.py / classVal.py / classTrainer.py).  frames uint8 [N][Hs][Ws][3]; rows / counts: what rcv_find_objects wrote for N class
+ * maps of H x W with C classes and M rows per class (only x, y, w, h of a row and `emitted` of counts are read).  Slot (n, c, k), P =
+ * N (C-1) M of them in the order of rows, is valid iff k < min(emitted, M).  For a valid slot:
+ *   1. the box in map pixels, every value clamped where it is used (no row content can address outside the frame):
+ *      x0 = clamp(x - margin, 0, W - 1), x1 = clamp(x + w + margin, x0 + 1, W); y0, y1 likewise with H;
+ *   2. the box in frame pixels, fp64, one correctly rounded division each: fx0 = (x0 Ws) / W, fx1 = (x1 Ws) / W, fy0 = (y0 Hs) / H,
+ *      fy1 = (y1 Hs) / H;
+ *   3. Pillow's Image.resize((Sw, Sh), BILINEAR, box = (fx0, fy0, fx1, fy1)) of frame n: per axis precompute_coeffs with the box offset
+ *      in fp64 (scale = (in1 - in0) / out, support = max(scale, 1), center = in0 + (xx + 0.5) scale, xmin = max(int(center - support +
+ *      0.5), 0), xmax = min(int(center + support + 0.5), inSize); triangle weights summed left to right, each divided by the sum, then
+ *      int(0.5 + w 2^22)); the horizontal pass first, the vertical pass second, each from 2^21, int32 sums, >> 22, clipped to a byte.
+ *      (Pillow itself takes the box as C floats: it agrees byte for byte wherever the four corners are exact in fp32, as they are for
+ *      frames of 480 x 640 and maps of 120 x 160; elsewhere this contract is what Pillow computes from the unrounded corners.)
+ *   4. step 3 of rcv_rgb_prep: c = byte / 255.0 in fp64, y / u / v rows, products rounded, summed left to right, ((y - 0.5) / 0.5,
+ *      u / 0.5, v / 0.5) rounded once to fp32.
+ * images float [P][3][Sh][Sw]; bytes uint8 [P][Sh][Sw][3] (the result of step 3) or NULL.  An invalid slot is zero in both; every
+ * element of both is written by every call.  1 <= Sh, Sw <= 64, margin >= 0, 1 <= H <= Hs, 1 <= W <= Ws; rows, counts and images
+ * 4-byte aligned.  Exact: integers and correctly rounded fp64.  No workspace, no host synchronisation.                           */
+int rcv_object_patches(rcv_handle* h, const uint8_t* frames, int N, int Hs, int Ws, const int32_t* rows, const int32_t* counts, int C,
+                       int M, int H, int W, int Sh, int Sw, int margin, float* images, uint8_t* bytes /*may be NULL*/, void* stream);
 
 /* Dense optical flow on the device (RCV_OP_FARNEBACK): what transform.py:185-187 optFlow gets from cv2.calcOpticalFlowFarneback(prev,
  * next, None, pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags), for B frame pairs at once.  prev / next uint8

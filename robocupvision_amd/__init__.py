@@ -28,6 +28,13 @@ def __getattr__(name):
     if name in ("Segmenter", "find_objects", "Objects", "DBCONVERT"):
         from . import infer
         return getattr(infer, name)
+    # ... and the patches of those objects, cut out of the full-resolution frames for the patch classifiers: patches.py
+    if name == "patches":
+        import importlib
+        return importlib.import_module(".patches", __name__)
+    if name in ("object_patches", "classify_objects", "classify_patches", "Patches"):
+        from . import patches
+        return getattr(patches, name)
     # label propagation by dense optical flow (test.py:135-140 --lProp; transform.py:185-198): flow.py
     if name == "flow":
         import importlib

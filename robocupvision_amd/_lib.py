@@ -32,6 +32,7 @@ OP_PRUNE = 45               # the three mask builders of the prune stage, one wo
 OP_OBJECTS = 46             # boxes, areas and centres of the components of a class map (rcv.h RCV_OP_OBJECTS, csrc/objects.hip)
 OP_RGB_PREP = 47            # the RGB loader of trainer.py / pruner.py for a whole batch: PIL ColorJitter, rgb2yuv (rcv.h RCV_OP_RGB_PREP, csrc/rgb_prep.hip)
 OP_FARNEBACK, OP_REMAP_LABELS = 48, 49      # dense optical flow and the label remap through it (rcv.h RCV_OP_FARNEBACK / RCV_OP_REMAP_LABELS, csrc/flow.hip)
+OP_OBJECT_PATCHES = 50      # the boxes of OP_OBJECTS cut out of the frames -> 32x32 YUV patches (rcv.h RCV_OP_OBJECT_PATCHES, csrc/patches.hip)
 PRUNE_MAX_RATIO, PRUNE_STD_SEARCH, PRUNE_SMALLEST_K = range(3)      # i[AUX0] of OP_PRUNE: pruneModelNew / pruneModel / pruneModel2
 PRUNE_MAX_ITER = 4096
 PRUNE_ST_OK, PRUNE_ST_NO_END, PRUNE_ST_ALL_ZERO, PRUNE_ST_BAD_JOB = range(4)
@@ -76,7 +77,7 @@ EXPORTS = [
     "rcv_object_match", "rcv_labelprop_batch", "rcv_batch_prep", "rcv_frame_prep", "rcv_cls_label", "rcv_colorize",
     "rcv_bnn_stage_fwd", "rcv_bnn_stage_bwd", "rcv_bnn_head_fwd", "rcv_bnn_head_bwd",
     "rcv_sgd_step_pruned", "rcv_prune_check", "rcv_prune", "rcv_find_objects", "rcv_rgb_prep",
-    "rcv_farneback_flow", "rcv_update_labels",
+    "rcv_farneback_flow", "rcv_update_labels", "rcv_object_patches",
 ]
 
 
@@ -119,6 +120,8 @@ def load():
         lib.rcv_find_objects.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.POINTER(C.c_int32), C.POINTER(C.c_double),
                                                                                   C.POINTER(C.c_int32), C.c_int, C.c_void_p, C.c_void_p,
                                                                                   C.c_void_p, C.c_size_t, C.c_void_p]
+        lib.rcv_object_patches.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 7 + \
+            [C.c_void_p] * 3
         lib.rcv_farneback_flow.argtypes = [C.c_void_p] * 3 + [C.c_int] * 4 + [C.c_float] + [C.c_int] * 4 + [C.c_float, C.c_int, C.c_void_p, C.c_void_p,
                                                                                                           C.c_size_t, C.c_void_p]
         lib.rcv_update_labels.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]

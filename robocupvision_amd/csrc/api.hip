@@ -132,6 +132,8 @@ static int dispatch(const rcv_handle* h, const rcv_op* op, hipStream_t s, OpQuer
     case RCV_OP_FARNEBACK:
     case RCV_OP_REMAP_LABELS:
       return rcv_launch_flow(h, op, s, q);
+    case RCV_OP_OBJECT_PATCHES:
+      return rcv_launch_object_patches(h, op, s, q);
     case RCV_OP_NOP:
       if (q) { snprintf(q->label, sizeof(q->label), "nop"); q->n_part = 0; q->n_split = 0; q->part_bytes = 0; }
       return RCV_OK;
@@ -401,6 +403,21 @@ int rcv_find_objects(rcv_handle* h, const void* classmap, int elem_bytes, int N,
   if (rc) return rc;
   RCV_CHECK_ARG(workspace_bytes >= need, "rcv_find_objects: workspace of %zu bytes given, %zu needed (rcv_op_workspace)", workspace_bytes,
                 need);
+  return rcv_run(h, &op, 1, stream);
+}
+
+int rcv_object_patches(rcv_handle* h, const uint8_t* frames, int N, int Hs, int Ws, const int32_t* rows, const int32_t* counts, int C,
+                       int M, int H, int W, int Sh, int Sw, int margin, float* images, uint8_t* bytes, void* stream) {
+  rcv_op op;
+  memset(&op, 0, sizeof(op));
+  op.kind = RCV_OP_OBJECT_PATCHES;
+  op.i[RCV_I_N] = N; op.i[RCV_I_H] = Hs; op.i[RCV_I_W] = Ws; op.i[RCV_I_HO] = H; op.i[RCV_I_WO] = W; op.i[RCV_I_COUT] = C - 1;
+  op.i[RCV_I_COUNT] = M; op.i[RCV_I_AUX0] = Sh; op.i[RCV_I_AUX1] = Sw; op.i[RCV_I_CIN] = margin;
+  op.p[RCV_P_IN] = (void*)frames; op.p[RCV_P_IN2] = (void*)rows; op.p[RCV_P_X0] = (void*)counts; op.p[RCV_P_OUT] = images;
+  op.p[RCV_P_X1] = bytes;
+  size_t need = 0;
+  const int rc = rcv_op_workspace(h, &op, &need);      // (no workspace: the record's refusals, on any handle)
+  if (rc) return rc;
   return rcv_run(h, &op, 1, stream);
 }
 

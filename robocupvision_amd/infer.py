@@ -11,7 +11,12 @@ the box centre; DBConvert.py:47-102: the per-class area rules of the detection d
 
     objs = find_objects(labels, **DBCONVERT)             # Objects: rows / counts stay on the device
     seg = Segmenter(model, objects=DBCONVERT)            # labels, colour, objs = seg(frames)
-    objs.to_list()                                       # the one host copy: per image [(class, x, y, w, h, area), ...]"""
+    objs.to_list()                                       # the one host copy: per image [(class, x, y, w, h, area), ...]
+
+and the boxes go on to the patch classifiers without leaving the device (``patches.py``: ``object_patches``, ``classify_objects``):
+
+    seg = Segmenter(model, objects=DBCONVERT, patches={}, classifier=BNNMC().to(dev))
+    labels, colour, objs, cut, classes = seg(frames)     # cut.images float32 [P,3,32,32]; classes uint8 [B,C-1,M], 255 = no object"""
 from __future__ import annotations
 
 import ctypes
@@ -22,6 +27,7 @@ import torch
 from . import _lib as L
 from .data import prepare_frames
 from .palette import device_palette
+from .patches import check_keywords, classify_patches, object_patches
 
 __all__ = ["Segmenter", "find_objects", "Objects", "ObjectsRecord", "DBCONVERT"]
 
@@ -180,9 +186,13 @@ class Segmenter:
     """``Segmenter(model)(frames)`` = ``model.predict(prepare_frames(frames, img_size, finetune), colour=True, palette=palette)``.
     ``model``: a ROBO_UNet, PB_FCN, PB_FCN_2 (segmentation mode) on the HIP device; it is put in eval mode here, once -- a caller
     that trains it afterwards calls ``.eval()`` again before the next frame.  ``objects``: a dict of ``find_objects`` keywords (e.g.
-    ``DBCONVERT``); the call then returns ``(labels, colour, objects)`` with the ``Objects`` of the labels."""
+    ``DBCONVERT``); the call then returns ``(labels, colour, objects)`` with the ``Objects`` of the labels.  ``patches``: a dict of
+    the ``object_patches`` keywords size / margin / return_bytes (needs ``objects``; the map size is ``img_size``); the call then
+    returns ``(labels, colour, objects, patches)`` with the ``Patches`` cut out of the full-resolution frames.  ``classifier``: a
+    patch classifier for ``classify_objects`` (needs ``patches``; put in eval mode here); the call then returns ``(labels, colour,
+    objects, patches, classes)`` with the uint8 [N,C-1,M] class of every found object, 255 where a slot holds none."""
 
-    def __init__(self, model, img_size=(120, 160), finetune=False, palette=None, objects=None):
+    def __init__(self, model, img_size=(120, 160), finetune=False, palette=None, objects=None, patches=None, classifier=None):
         if not hasattr(model, "predict"):
             raise TypeError("Segmenter: model must be one of this package's networks (it has no predict)")
         if getattr(model, "classify", False):
@@ -200,6 +210,18 @@ class Segmenter:
                 raise L.RcvError("Segmenter: objects must be a dict of find_objects keywords (num_class, min_area, min_ratio, max_objects)")
             self._objects = dict(objects)
             ObjectsRecord(1, 1, 1, **self._objects).workspace_bytes(L.planner_handle())       # wrong rules are refused at construction
+        self._patches = None
+        self._classifier = None
+        if patches is not None:
+            if self._objects is None:
+                raise L.RcvError("Segmenter: patches needs objects (the boxes to cut out)")
+            self._patches = check_keywords(patches, self.img_size, "Segmenter")
+        if classifier is not None:
+            if self._patches is None:
+                raise L.RcvError("Segmenter: classifier needs patches (a dict of object_patches keywords, {} for 32x32 patches)")
+            if not isinstance(classifier, torch.nn.Module):
+                raise TypeError("Segmenter: classifier must be a module (BNNL, BNNMC, PB_FCN(classify=1), PB_FCN_2(True))")
+            self._classifier = classifier.eval()
 
     def __call__(self, frames):
         imgs = prepare_frames(frames, self.img_size, self.finetune)
@@ -211,4 +233,10 @@ class Segmenter:
         labels, colour = self.model.predict(imgs, colour=True, palette=pal)
         if self._objects is None:
             return labels, colour
-        return labels, colour, find_objects(labels, **self._objects)
+        objs = find_objects(labels, **self._objects)
+        if self._patches is None:
+            return labels, colour, objs
+        cut = object_patches(frames, objs, map_size=self.img_size, **self._patches)
+        if self._classifier is None:
+            return labels, colour, objs, cut
+        return labels, colour, objs, cut, classify_patches(cut, self._classifier)
