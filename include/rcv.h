@@ -469,7 +469,8 @@ int rcv_dice_bwd(rcv_handle* h, const float* logits, const int64_t* target, cons
 /* train.py:23-27,52-55 (decay * L1 -> gradient decay*sign(p)) + torch.optim.Adam.step            *
  * (train.py:67,357-363) over one flat fp32 buffer; lr is per element group via lr_scale[].      */
 /* Per-image confusion matrices from the arg-max mask (uint8) and the labels (int64): replaces the Python
- * mask loops of valid() (train.py:136-153).  counts is int32 [N][C][C] indexed [n][pred][label]; the call ADDS.   */
+ * mask loops of valid() (train.py:136-153).  counts is int32 [N][C][C] indexed [n][pred][label]; the call ADDS.  A pixel with
+ * pred >= C or a label outside [0, C) -- as the int64 it is: -100, 255, 2^32 + c -- is counted nowhere.  Any N >= 1.          */
 int rcv_confusion(rcv_handle* h, const uint8_t* argmax, const int64_t* target, int N, int C, int H, int W,
                   int32_t* counts, void* stream);
 

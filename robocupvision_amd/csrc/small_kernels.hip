@@ -1089,9 +1089,9 @@ __global__ void adam_l1_kernel(float* __restrict__ p, const float* __restrict__ 
   }
   __syncthreads();
   const float bc1 = s_bc[0], bc2_sqrt = s_bc[1];
-  float asum = 0.f;
+  double asum = 0.0;                                  // double from the first addition: sum|p| is then good to a few 2^-53 of itself
   auto update = [&](float pv, float gv, float& mv, float& vv, float lre, bool pruned) -> float {
-    if (MET) asum += fabsf(pv);                       // l1reg(model) runs over every parameter, stepped or not
+    if (MET) asum += (double)fabsf(pv);               // l1reg(model) runs over every parameter, stepped or not
     if (lre == 0.f) return pv;                        // parameter without a gradient (outside the graph / the groups): untouched, as under torch.optim.Adam
     const float sg = pv > 0.f ? 1.f : (pv < 0.f ? -1.f : 0.f);
     float gr = fmaf(decay, sg, gv * grad_scale);
@@ -1127,7 +1127,7 @@ __global__ void adam_l1_kernel(float* __restrict__ p, const float* __restrict__ 
   if (MET) {
     __shared__ int is_last;
     unsigned* ticket = reinterpret_cast<unsigned*>(part + gridDim.x);
-    double a = (double)asum, dummy = 0.0;
+    double a = asum, dummy = 0.0;
     block_sum2_d(a, dummy);
     if (threadIdx.x == 0) {
       // The row and the ticket are both device-scope atomics, i.e. performed at the memory side of the (per-XCD, mutually
@@ -1198,21 +1198,26 @@ __global__ void add_slice_kernel(float* __restrict__ x, int C, const float* __re
   }
 }
 
-// counts[n][pred][label] += 1: per-block LDS histogram (integer atomics: order independent), then one global add per bin
+// counts[n][pred][label] += 1: per-block LDS histogram (integer atomics: order independent), then one global add per bin.
+// A label outside [0, C) -- decided on the int64 value, so 2^32 + c is no class either -- or a prediction >= C counts nowhere.
+// gridDim.y = min(N, 65535): the images beyond a grid dimension fold onto its rows (PatchMetrics: one 1x1 image per patch).
 __global__ void confusion_kernel(const uint8_t* __restrict__ pred, const int64_t* __restrict__ target, int* __restrict__ counts,
-                                 int HW, int C) {
+                                 int HW, int C, int N) {
   __shared__ int hist[64];
-  if (threadIdx.x < 64) hist[threadIdx.x] = 0;
-  __syncthreads();
-  const int n = blockIdx.y;
-  const uint8_t* pp = pred + (size_t)n * HW;
-  const int64_t* tt = target + (size_t)n * HW;
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < HW; i += gridDim.x * blockDim.x) {
-    const int p = pp[i], t = (int)tt[i];
-    if (p < C && t >= 0 && t < C) atomicAdd(&hist[p * C + t], 1);
+  for (int n = blockIdx.y; n < N; n += gridDim.y) {
+    if (threadIdx.x < 64) hist[threadIdx.x] = 0;
+    __syncthreads();
+    const uint8_t* pp = pred + (size_t)n * HW;
+    const int64_t* tt = target + (size_t)n * HW;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < HW; i += gridDim.x * blockDim.x) {
+      const int p = pp[i];
+      const int64_t t = tt[i];
+      if (p < C && t >= 0 && t < (int64_t)C) atomicAdd(&hist[p * C + (int)t], 1);
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < C * C && hist[threadIdx.x]) atomicAdd(&counts[(size_t)n * C * C + threadIdx.x], hist[threadIdx.x]);
+    __syncthreads();                                     // the next image of this row clears the histogram
   }
-  __syncthreads();
-  if ((int)threadIdx.x < C * C && hist[threadIdx.x]) atomicAdd(&counts[(size_t)n * C * C + threadIdx.x], hist[threadIdx.x]);
 }
 
 // out = f(in): a block's output as a plain NHWC tensor (block-level module calls, LabelProp tail)
@@ -1679,8 +1684,8 @@ int rcv_launch_small(const rcv_handle* h, const rcv_op* op, hipStream_t s, OpQue
       RCV_CHECK_ARG(op->p[RCV_P_IN] && op->p[RCV_P_IN2] && op->p[RCV_P_OUT], "confusion: null operand");
       int gx = ceil_div(H * W, 256 * 8);
       if (gx > 64) gx = 64;
-      hipLaunchKernelGGL(confusion_kernel, dim3(gx, N), dim3(256), 0, s, (const uint8_t*)op->p[RCV_P_IN], (const int64_t*)op->p[RCV_P_IN2],
-                         (int*)op->p[RCV_P_OUT], H * W, Cout);
+      hipLaunchKernelGGL(confusion_kernel, dim3(gx, N < 65535 ? N : 65535), dim3(256), 0, s, (const uint8_t*)op->p[RCV_P_IN],
+                         (const int64_t*)op->p[RCV_P_IN2], (int*)op->p[RCV_P_OUT], H * W, Cout, N);
       break;
     }
     case RCV_OP_MATERIALIZE: {

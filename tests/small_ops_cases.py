@@ -4,7 +4,11 @@ conv cases; nothing from the library, so that tests/test_small_ops.py can assert
 
   * every reduction's sum of |terms| is an integer multiple of its quantum q below 2^24 q (exact in fp32 in any order);
   * removing the last pixel, or the first pixel of the second grid pass, changes EVERY entry of every reduced result (the inputs
-    are forced so that those pixels carry non-zero terms in every channel)."""
+    are forced so that those pixels carry non-zero terms in every channel).
+
+Further down: the seeded Adam + L1 cases with an fp32 emulation of the kernel's expression order and its wrong variants, the
+hand-made partial filters of the reduction tests (layout of include/rcv.h, rcv_reduce_job) with the kernel's order of additions
+restated in fp32, and the planes and labels of the confusion tests."""
 import numpy as np
 
 import small_ops_restatement as R
@@ -341,3 +345,290 @@ def check_conv_stats(c):
             assert_sensitive(lambda k: (R.stats(kind, v, c["e"], c["ec"], k),), c["npix"], 0, "conv statistics kind %d" % kind)
     z = R._f(c["e"]) * R._f(c["ec"])[0] + R._f(c["ec"])[1]
     assert (z == 0).any() and (z < 0).any()
+
+
+# ------------------------------------------------------------------------------------------ Adam + L1
+ADAM_HYPER = dict(lr=2e-3, b1=0.9, b2=0.999, eps=1e-8, decay=1e-3)
+ADAM_T = (1, 2, 10, 1000, 100000)
+ADAM_GS = (1.0, 1.0 / 8, 1.0 / 3)
+f32 = np.float32
+
+
+def adam_big_n(num_cus):
+    """An element count beyond one grid pass of adam_l1_kernel (2 workgroups per CU x 256 threads x 4 elements), with a scalar tail:
+    the vector loop makes a second pass in several workgroups and n % 4 == 3."""
+    return 2 * num_cus * WG * 4 + 5003
+
+
+def adam_cases(num_cus):
+    """(n, t, grad_scale): every n, every t, every grad_scale with the large n; not the full product."""
+    big = adam_big_n(num_cus)
+    assert big % 4 == 3 and big // 4 > 2 * num_cus * WG
+    g1, g8, g3 = ADAM_GS
+    return [(1, 1, g1), (3, 2, g8), (4, 10, g3), (5, 1000, g1), (255, 100000, g8), (1027, 1, g3), (1027, 1000, g1), (100003, 2, g1),
+            (100003, 10, g8), (100003, 100000, g3), (big, 1, g1), (big, 1000, g8), (big, 100000, g3)]
+
+
+def _logu(rng, n, lo, hi):
+    return 10.0 ** rng.uniform(np.log10(lo), np.log10(hi), n)
+
+
+def build_adam(n, t, gs):
+    """fp32 operands spanning what training produces: |g| log-uniform in 1e-10..1 with random sign and exact zeros (i % 11 == 3),
+    p over 1e-6..1 with exact +0 (i % 13 == 5) and -0 (i % 13 == 6), m and v of the spread of g and g^2 (zero at t = 1, and where
+    i % 22 == 3: there g = m = v = 0), lr_elem in stretches of 7 (one stretch in five 0, two lr, two 10 lr), a prune mask over a
+    quarter of the elements."""
+    rng = np.random.default_rng(31000 + n % 9973 + 17 * t + int(1000 * gs))
+    i = np.arange(n)
+    sgn = lambda: rng.choice([-1.0, 1.0], n)
+    g = _logu(rng, n, 1e-10, 1.0) * sgn()
+    p = _logu(rng, n, 1e-6, 1.0) * sgn()
+    mag = _logu(rng, n, 1e-10, 1.0)
+    m = mag * rng.uniform(0.1, 1.0, n) * sgn()
+    v = mag * mag * rng.uniform(0.5, 2.0, n)
+    g[i % 11 == 3] = 0.0
+    p[i % 13 == 5] = 0.0
+    p[i % 13 == 6] = -0.0
+    if t == 1:
+        m[:], v[:] = 0.0, 0.0
+    m[i % 22 == 3], v[i % 22 == 3] = 0.0, 0.0
+    lr = f32(ADAM_HYPER["lr"])
+    lre = np.array([0.0, lr, lr, 10 * lr, 10 * lr], f32)[((i // 7) + 1) % 5]
+    prune = (rng.random(n) < 0.25).astype(np.uint8)
+    c = dict(n=n, t=t, gs=f32(gs), p=p.astype(f32), g=g.astype(f32), m=m.astype(f32), v=v.astype(f32), lr_elem=lre, prune=prune)
+    c.update({k: f32(x) for k, x in ADAM_HYPER.items()})
+    return c
+
+
+ADAM_FORMS = ("plain", "lr_elem", "lr_elem+prune")
+
+
+def adam_form(c, form):
+    """(lr_elem, prune) of the three record forms."""
+    return (None if form == "plain" else c["lr_elem"]), (c["prune"] if form.endswith("prune") else None)
+
+
+def adam_reference(c, form, decay=None):
+    lre, pr = adam_form(c, form)
+    return R.adam_l1_step(c["p"], c["g"], c["m"], c["v"], c["t"], c["lr"], c["b1"], c["b2"], c["eps"], c["decay"] if decay is None else decay,
+                          c["gs"], lre, pr)
+
+
+def _fma(a, b, c):
+    """fp32 fma: the product of two fp32 values is exact in float64 (the sum is rounded twice: at 53 bits, then at 24)."""
+    return (np.asarray(a, np.float64) * np.asarray(b, np.float64) + np.asarray(c, np.float64)).astype(f32)
+
+
+# the wrong kernels tests/test_small_ops.py shows to leave the bound: name -> the share of the live elements (lr_elem != 0, form "lr_elem+prune") that it must put outside TWICE the bound in at least one
+# case of n >= 1027: half of the largest share test_small_ops.py prints
+ADAM_MUTANTS = {"eps_before_bc2": 0.36,       # eps added before the division by bc2_sqrt
+                "eps_inside_sqrt": 0.44,      # sqrt(v' + eps)
+                "bc_t_minus_1": 0.49,         # bias corrections of step t - 1
+                "gs_on_decay": 0.31,          # (g + decay sign(p)) * grad_scale
+                "l1_on_pruned": 0.11,         # a pruned element keeps gr = decay sign(p)
+                "sign0_is_1": 0.06,           # sign(+-0) = 1
+                "v_with_gr": 0.36}            # v' = b2 v + (1 - b2) gr
+
+
+def adam_emulate(c, form, contract=0, variant=None):
+    """adam_l1_kernel's expression order in fp32 numpy -> (p', m', v').  contract: 0 = every product rounded (but the kernel's own
+    fmaf), 1 / 2 = the two ways a compiler contracts a b + c d into an fma, and p - step r.  variant: one of ADAM_MUTANTS."""
+    p, g, m, v = c["p"], c["g"], c["m"], c["v"]
+    lr, b1, b2, eps, decay, gs = (c[k] for k in ("lr", "b1", "b2", "eps", "decay", "gs"))
+    lre, pr = adam_form(c, form)
+    lre = np.full(c["n"], lr, f32) if lre is None else lre
+    t = c["t"] - 1 if variant == "bc_t_minus_1" else c["t"]
+    with np.errstate(all="ignore"):
+        bc1, bc2s = f32(1.0 - np.float64(b1) ** t), f32(np.sqrt(1.0 - np.float64(b2) ** t))
+        sg = np.sign(p).astype(f32)
+        if variant == "sign0_is_1":
+            sg = np.where(p == 0, f32(1), sg)
+        gr = _fma(decay, sg, g) * gs if variant == "gs_on_decay" else _fma(decay, sg, g * gs)
+        if pr is not None:
+            gr = np.where(pr != 0, decay * sg if variant == "l1_on_pruned" else f32(0), gr)
+        o1, o2 = f32(1) - b1, f32(1) - b2
+        s1 = o2 * gr
+        s2 = s1 if variant == "v_with_gr" else s1 * gr
+        if contract == 0:
+            m1, v1 = b1 * m + o1 * gr, b2 * v + s2
+        elif contract == 1:
+            m1, v1 = _fma(b1, m, o1 * gr), _fma(b2, v, s2)
+        else:
+            m1, v1 = _fma(o1, gr, b1 * m), (b2 * v + s2 if variant == "v_with_gr" else _fma(s1, gr, b2 * v))
+        if variant == "eps_before_bc2":
+            den = (np.sqrt(v1) + eps) / bc2s
+        elif variant == "eps_inside_sqrt":
+            den = np.sqrt(v1 + eps) / bc2s
+        else:
+            den = np.sqrt(v1) / bc2s + eps
+        step, r = lre / bc1, m1 / den
+        p1 = p - step * r if contract == 0 else _fma(-step, r, p)
+    live = lre != 0
+    assert p1.dtype == f32 and m1.dtype == f32 and v1.dtype == f32
+    return np.where(live, p1, p), np.where(live, m1, m), np.where(live, v1, v)
+
+
+def adam_ratios(got, ref, bound):
+    """Largest error / bound of each of (p, m, v), and the elements outside `factor` x the bound."""
+    out = []
+    for a, r, b in zip(got, ref, bound):
+        err = np.abs(np.asarray(a, np.float64) - r)
+        out.append(np.where(err > 0, err / np.maximum(b, 1e-300), 0.0))
+    return out
+
+
+def adam_metrics_inputs(n, seed=0):
+    """p on the grid k / 8, |k| <= 16 (sum|p| exact in double and in fp32 partial sums in any order), a third of the elements with
+    lr_elem == 0, a quarter pruned."""
+    rng = np.random.default_rng(32000 + seed + n % 9973)
+    p = (rng.integers(-16, 17, n) / 8.0).astype(f32)
+    lre = np.where(np.arange(n) % 3 == 1, f32(0), f32(ADAM_HYPER["lr"])).astype(f32)
+    return dict(n=n, p=p, g=rng.standard_normal(n).astype(f32), m=(rng.standard_normal(n) * 0.1).astype(f32),
+                v=(rng.random(n) * 0.01).astype(f32), lr_elem=lre, prune=(np.arange(n) % 4 == 2).astype(np.uint8))
+
+
+# ------------------------------------------------------------------------------------------ filter-gradient reductions
+REDUCE_NSPLIT = (1, 2, 15, 16, 17, 32, 48, 49, 63, 64, 65, 112, 113, 129, 200)
+REDUCE_SHAPES = ((8, 3), (8, 4), (16, 8), (5, 16))         # (CB, CA): every nsplit, with and without the bias row
+REDUCE_WIDE = ((64, 32), (1, 49, 65, 200))                  # with the bias row
+
+
+def reduce_pads(CB, CA):
+    """include/rcv.h (rcv_reduce_job): CAP = CA <= 4 ? 4 : round16(CA), CBP = round16(CB)."""
+    return (CB + 15) // 16 * 16, (4 if CA <= 4 else (CA + 15) // 16 * 16)
+
+
+def reduce_blocks(CB, CA, with_bias):
+    CBP, CAP = reduce_pads(CB, CA)
+    return (9 * CBP * CAP + (CBP if with_bias else 0) + 63) // 64
+
+
+def build_reduce(nsplit, CB, CA, kind, seed=0):
+    """Partial filters [nsplit][9][CBP][CAP] and bias rows [nsplit][CBP] with NaN in the pad rows / columns.
+    kind "weights": split s = w_s x one pattern with entries in {-2, -1, 1, 2}, the w_s distinct integers 1..nsplit in a seeded order
+      (a dropped, doubled or swapped split changes EVERY entry; the sums stay below 2^24: exact);
+    kind "cancel": the first nsplit // 2 splits are integers of magnitude up to 2^23, the next nsplit // 2 their negatives (in a
+      seeded order of their own, so that a value and its negative seldom meet in one addition) plus grid values in -2..2, an odd
+      last split is a plain grid split: the sum is a small integer, exact in double in any order, and out of reach of an fp32
+      accumulation;
+    kind "randn"."""
+    CBP, CAP = reduce_pads(CB, CA)
+    rng = np.random.default_rng(33000 + seed + 7 * nsplit + 131 * CB + CA + len(kind))
+    shape = (nsplit, 9 * CBP * CAP + CBP)                 # filter part and bias row of a split side by side
+    if kind == "weights":
+        pat = rng.choice(np.array([-2.0, -1.0, 1.0, 2.0]), shape[1])
+        w = rng.permutation(nsplit) + 1.0
+        a = w[:, None] * pat[None]
+    elif kind == "cancel":
+        h = nsplit // 2
+        big = rng.integers(-2 ** 23, 2 ** 23 + 1, (h, shape[1])).astype(np.float64)
+        small = rng.integers(-2, 3, (nsplit - h, shape[1])).astype(np.float64)
+        a = np.concatenate([big, small])
+        a[h:2 * h] -= big[rng.permutation(h)]
+    else:
+        a = rng.standard_normal(shape)
+    a = a.astype(f32)
+    part, bias = a[:, :9 * CBP * CAP].reshape(nsplit, 9, CBP, CAP).copy(), a[:, 9 * CBP * CAP:].copy()
+    part[:, :, CB:, :], part[:, :, :, CA:], bias[:, CB:] = np.nan, np.nan, np.nan
+    return dict(nsplit=nsplit, CB=CB, CA=CA, CBP=CBP, CAP=CAP, kind=kind, part=part, bias=bias)
+
+
+def reduce_buffer(c, with_bias):
+    """The workspace as the reduction reads it: [nsplit][9][CBP][CAP], then (with the bias) [nsplit][CBP], then one more split of NaN."""
+    tail = np.full(9 * c["CBP"] * c["CAP"] + c["CBP"], np.nan, f32)
+    return np.concatenate([c["part"].reshape(-1)] + ([c["bias"].reshape(-1)] if with_bias else []) + [tail])
+
+
+def reduce_reference(c, keep=None):
+    """(dW, db) in float64; keep: boolean over the splits."""
+    k = slice(None) if keep is None else np.asarray(keep, bool)
+    return R.wgrad_reduce(c["part"][k], c["bias"][k], c["CB"], c["CA"])
+
+
+def reduce_fixed_order_fp32(x):
+    """x [nsplit][...] fp32 -> the sum in wgrad_reduce_block's order of additions, every addition rounded to fp32: group grp adds
+    the splits grp, grp + 16, ..., four at a time ((s, s + 32) and (s + 16, s + 48) on two accumulators) while s + 48 < nsplit, then
+    singly; the 16 group sums are added as ((0 + 1) + (2 + 3)) + ... in steps of four."""
+    ns = x.shape[0]
+    z = np.zeros(x.shape[1:], f32)
+    sh = []
+    for grp in range(16):
+        a0, a1, s = z.copy(), z.copy(), grp
+        while s + 48 < ns:
+            a0 = a0 + (x[s] + x[s + 32])
+            a1 = a1 + (x[s + 16] + x[s + 48])
+            s += 64
+        while s < ns:
+            a0 = a0 + x[s]
+            s += 16
+        sh.append(a0 + a1)
+    u = z.copy()
+    for g in range(0, 16, 4):
+        u = u + ((sh[g] + sh[g + 1]) + (sh[g + 2] + sh[g + 3]))
+    assert u.dtype == f32
+    return u
+
+
+# smallest share of the real entries (filter and bias together) that an fp32 accumulation in the kernel's order gets wrong on the
+# "cancel" case, per nsplit: half of what tests/test_small_ops.py measures (0 where two splits cancel inside one addition)
+REDUCE_FP32_MISS = {1: 0.0, 2: 0.0, 15: 0.04, 16: 0.08, 17: 0.09, 32: 0.16, 48: 0.27, 49: 0.24, 63: 0.32, 64: 0.32, 65: 0.31, 112: 0.41,
+                    113: 0.40, 129: 0.40, 200: 0.43}
+
+
+def check_reduce(c):
+    """The preconditions of the two exact kinds."""
+    CB, CA = c["CB"], c["CA"]
+    real, realb = c["part"][:, :, :CB, :CA].astype(np.float64), c["bias"][:, :CB].astype(np.float64)
+    assert not np.isnan(real).any() and not np.isnan(realb).any()
+    assert np.isnan(c["part"][:, :, CB:]).all() and np.isnan(c["part"][:, :, :, CA:]).all() and np.isnan(c["bias"][:, CB:]).all()
+    dw, db = reduce_reference(c)
+    assert np.all(dw == np.round(dw)) and np.all(db == np.round(db)) and max(np.abs(dw).max(), np.abs(db).max()) < 2.0 ** 24
+    if c["kind"] == "weights":
+        R.assert_exact(np.abs(real).sum(0), 1.0, "reduce weights")
+        assert_sensitive(lambda k: reduce_reference(c, k), c["nsplit"], 16, "wgrad_reduce %d splits" % c["nsplit"])
+        w = np.abs(real[:, 0, 0, 0]) / np.abs(real[:, 0, 0, 0]).min()
+        assert len(set(w.tolist())) == c["nsplit"], "the splits' weights must be distinct"
+        assert np.all(real != 0) and np.all(realb != 0)                 # so any split counted twice moves every entry as well
+    else:
+        assert max(np.abs(dw).max(), np.abs(db).max()) <= 2 * (c["nsplit"] - c["nsplit"] // 2)
+
+
+def reduce_fp32_miss(c):
+    """Share of the real entries on which the fixed-order fp32 sum differs from the float64 one."""
+    CB, CA = c["CB"], c["CA"]
+    dw, db = reduce_reference(c)
+    gw = reduce_fixed_order_fp32(c["part"][:, :, :CB, :CA])
+    gb = reduce_fixed_order_fp32(c["bias"][:, :CB])
+    wrong = int((gw.transpose(1, 2, 0).reshape(dw.shape) != dw).sum()) + int((gb != db).sum())
+    return wrong / float(dw.size + db.size)
+
+
+# ------------------------------------------------------------------------------------------ confusion counts
+CONF_CLASSES = (1, 2, 5, 8)
+CONF_ODD_LABELS = (-100, -1, None, 255, 2 ** 32 + 1, -2 ** 32 + 2)      # None = C
+
+
+def confusion_planes():
+    """(N, H, W): one workgroup per image; an odd plane; one pixel; a plane just past the kernel's workgroup cap (64 workgroups x
+    256 threads x 8 pixels = 131072 per image), where its grid-stride loop goes round once more than the launcher sized it for."""
+    big = (2, 257, 513)
+    assert big[1] * big[2] > 64 * 256 * 8
+    return [(3, 24, 40), (2, 37, 53), (2, 1, 1), big]
+
+
+def build_confusion(N, H, W, C, seed=0):
+    """uint8 predictions (some >= C) and int64 labels with about 5 % outside [0, C) -- 2^32 + 1 and -2^32 + 2 among them, which a
+    32-bit truncation would take for classes 1 and 2; the last pixel of the last image carries a (pred, label) pair found nowhere
+    else where C > 1."""
+    rng = np.random.default_rng(34000 + seed + N * H * W + C)
+    pred = rng.integers(0, C + 2, (N, H, W)).astype(np.uint8)
+    tgt = rng.integers(0, C, (N, H, W)).astype(np.int64)
+    odd = rng.random((N, H, W)) < 0.05
+    vals = np.array([C if x is None else x for x in CONF_ODD_LABELS], np.int64)
+    tgt[odd] = vals[rng.integers(0, len(vals), int(odd.sum()))]
+    if N * H * W >= len(vals):
+        tgt.reshape(-1)[:len(vals)] = vals                   # every odd label at least once
+    if C > 1 and H * W > 1:
+        tgt[-1][(pred[-1] == C - 1) & (tgt[-1] == 0)] = -1
+        pred[-1, -1, -1], tgt[-1, -1, -1] = C - 1, 0
+    return pred, tgt

@@ -1,6 +1,7 @@
 """Float64 numpy restatement of the operations around the 3x3 contractions of the training step -- load transforms, the three kinds
 of epilogue statistics (include/rcv.h), BatchNorm bookkeeping, the 1x1 classifier, weighted cross entropy, the Dice loss, 2x2
-max-pool, SGD -- and the integer-grid operand generators the exact GPU tests use.  Imports nothing from the library; pinned against
+max-pool, SGD, the Adam + L1 step with its running rounding bound, the filter-gradient reduction, the confusion counts -- and the
+integer-grid operand generators the exact GPU tests use.  Imports nothing from the library; pinned against
 torch float64 autograd by tests/test_small_ops.py.
 
 Tensors are NHWC ([..., C]) unless a name says NCHW.  Every reduction takes `keep`, a boolean vector over the pixels (leading axes
@@ -204,6 +205,92 @@ def sgd_step(p, g, buf, step, lr, momentum, wd, grad_scale=1.0, lr_elem=None):
     b = gr if step == 1 else F64(momentum) * buf + gr
     live = lre != 0
     return np.where(live, p - lre * b, p), np.where(live, b, buf)
+
+
+# ------------------------------------------------------------------------------------------ Adam + L1
+U32 = 2.0 ** -24        # unit roundoff of fp32, round to nearest: |fl(x) - x| <= U32 |x|
+
+
+def _w32(x):
+    """A hyper-parameter as the record carries it: rounded to fp32, widened."""
+    return F64(np.float32(x))
+
+
+def adam_l1_step(p, g, m, v, t, lr, b1, b2, eps, decay, grad_scale=1.0, lr_elem=None, prune=None, round_bc=True):
+    """One step of torch.optim.Adam (no weight decay, no amsgrad) on the gradient g * grad_scale + decay * sign(p) (the gradient of
+    decay * sum|p|, sign(+-0) = 0), float64 from the fp32 operands, hyper-parameters rounded to fp32 and widened:
+        gr = decay sign(p) + g gs  (0 where prune);  m' = b1 m + (1 - b1) gr;  v' = b2 v + ((1 - b2) gr) gr;
+        p' = p - (lre / bc1) (m' / (sqrt(v') / bc2_sqrt + eps)),  bc1 = 1 - b1^t,  bc2_sqrt = sqrt(1 - b2^t), both rounded to fp32
+    (round_bc=False leaves them unrounded: the comparison with torch.optim.Adam only).  lr_elem == 0: the element and its moments
+    are returned untouched.
+
+    -> (p', m', v'), (ep, em, ev): the values and a running first-order bound on the error of an fp32 evaluation in this order of
+    operations: each fp32 operation adds U32 |its result| (for a sum: of the rounded sum, the terms' own errors having been
+    carried), earlier errors go through each operation by its derivative, bc1 and bc2_sqrt carry one rounding each of their own
+    (a double pow may differ in the last place), 1 - b1 and 1 - b2 their actual fp32 error (0 for b >= 1/2), and the square root
+    passes ev on as sqrt(v' + ev) - sqrt(v') (no division by sqrt(v'): v' = 0 is not singular).  A contraction into an fma only
+    removes a rounding."""
+    p, g, m, v = _f(p), _f(g), _f(m), _f(v)
+    lr, b1, b2, eps, decay, gs = (_w32(x) for x in (lr, b1, b2, eps, decay, grad_scale))
+    bc1, bc2s = 1.0 - b1 ** F64(t), np.sqrt(1.0 - b2 ** F64(t))
+    if round_bc:
+        bc1, bc2s = _w32(bc1), _w32(bc2s)
+    o1, o2 = 1.0 - b1, 1.0 - b2
+    eo1, eo2 = abs(_w32(o1) - o1), abs(_w32(o2) - o2)
+    lre = np.full(p.shape, lr) if lr_elem is None else _f(lr_elem)
+    A = np.abs
+    a = g * gs
+    gr = decay * np.sign(p) + a                                      # fmaf(decay, sg, fl(g gs)): 2 roundings
+    egr = U32 * A(a) + U32 * A(gr)
+    if prune is not None:
+        pr = np.asarray(prune) != 0
+        gr, egr = np.where(pr, 0.0, gr), np.where(pr, 0.0, egr)
+    t1, t2 = b1 * m, o1 * gr
+    m1 = t1 + t2
+    em = U32 * A(t1) + (o1 * egr + eo1 * A(gr) + U32 * A(t2)) + U32 * A(m1)
+    s1 = o2 * gr
+    es1 = o2 * egr + eo2 * A(gr) + U32 * A(s1)
+    s2, t3 = s1 * gr, b2 * v
+    v1 = t3 + s2
+    ev = U32 * A(t3) + (A(gr) * es1 + A(s1) * egr + U32 * A(s2)) + U32 * A(v1)
+    sq = np.sqrt(v1)
+    esq = (np.sqrt(v1 + ev) - sq) + U32 * sq
+    q = sq / bc2s
+    eq = esq / bc2s + q * U32 + U32 * q                              # bc2_sqrt's own rounding, the quotient's
+    den = q + eps
+    eden = eq + U32 * den
+    step = lre / bc1
+    estep = A(step) * U32 + U32 * A(step)                            # bc1's own rounding, the quotient's
+    r = m1 / den
+    er = em / den + A(r) * eden / den + U32 * A(r)
+    w = step * r
+    ew = A(step) * er + A(r) * estep + U32 * A(w)
+    p1 = p - w
+    ep = ew + U32 * A(p1)
+    live = lre != 0
+    z = np.zeros_like(p)
+    return ((np.where(live, p1, p), np.where(live, m1, m), np.where(live, v1, v)),
+            (np.where(live, ep, z), np.where(live, em, z), np.where(live, ev, z)))
+
+
+# ------------------------------------------------------------------------------------------ filter-gradient reduction
+def wgrad_reduce(part, part_bias, CB, CA):
+    """part [nsplit][9][CBP][CAP], part_bias [nsplit][CBP] or None -> dW [CB][CA][3][3], db [CB] (None): float64 sums over the
+    splits; the pad rows / columns (cb >= CB, ca >= CA) are not looked at."""
+    s = _f(part)[:, :, :CB, :CA].sum(0)                              # [9][CB][CA]
+    dw = np.ascontiguousarray(s.transpose(1, 2, 0)).reshape(CB, CA, 3, 3)
+    return dw, (None if part_bias is None else _f(part_bias)[:, :CB].sum(0))
+
+
+# ------------------------------------------------------------------------------------------ confusion counts
+def confusion(pred, target, C):
+    """counts[n][pred][label] (int64) over the pixels with pred < C and 0 <= label < C, the label taken as the int64 it is."""
+    pred, target = np.asarray(pred).astype(np.int64), np.asarray(target).astype(np.int64)
+    N = pred.shape[0]
+    pn, tn = pred.reshape(N, -1), target.reshape(N, -1)
+    ok = (pn < C) & (tn >= 0) & (tn < C)
+    image = np.broadcast_to(np.arange(N)[:, None], pn.shape)
+    return np.bincount(((image * C + pn) * C + tn)[ok], minlength=N * C * C).reshape(N, C, C)     # one bin per (image, pred, label)
 
 
 # ------------------------------------------------------------------------------------------ the integer grid

@@ -11,8 +11,8 @@ grid cap (reducing kernels 4 workgroups per CU, streaming kernels 8), a multiple
 
 Kernel labels covered (rcv_op_kernel_label): bn_finalize, bn_bwd, bn_eval, pool_fwd, pool_bwd, pool_bwd_rows, bwd_stats, cls_fwd
 (cls_fwd_kernel<8, FUSED, CE>, cls_fwd16_kernel; beyond a streaming grid pass too), cls_bwd (cls_bwd_kernel<8, 1..8, FUSED, CE>: 24 instantiations, both store paths;
-<16, {1,5,8}, false, false>), ce_fwd, ce_bwd, dice_fwd, dice_bwd, sgd, adam_l1, combine, materialize, add_slice, nhwc_to_nchw,
-nchw_to_nhwc.
+<16, {1,5,8}, false, false>), ce_fwd, ce_bwd, dice_fwd, dice_bwd, sgd, adam_l1 (both instantiations), combine, materialize, add_slice,
+nhwc_to_nchw, nchw_to_nhwc, wgrad_reduce, wgrad_reduce_batch; RCV_OP_CONFUSION (no label of its own).
 
 BatchNorm bookkeeping: bound = (roundings + 1) * 2^-24 * sum|terms| against the restatement on the same fp32 rows.  The rows are
 accumulated in double (error <= n_part 2^-53 sum|rows|, covered by the +1 as long as the sums are not cancelled: asserted), so the
@@ -29,6 +29,26 @@ fp32 roundings on each output's path are
                shift = beta - rm * scale        6
                row 3 = fma(bias, scale, shift)  7
 SGD (one step from the device's own state): p 5 (g * grad_scale, fma, fma, lr * buf, difference), momentum buffer 3.
+Adam + L1 (one step from the uploaded state; R.adam_l1_step carries the bound alongside every intermediate, each rounding weighted by
+its OWN result and passed on through the later operations by their derivatives, so the count is per path, not one common factor):
+  gr = fmaf(decay, sign p, g * grad_scale)        2   product, fma (0 and exact where pruned)
+  m' = b1 m + (1 - b1) gr                         3 + gr's 2 = 5   two products, sum (1 - b exact for b >= 1/2)
+  v' = b2 v + ((1 - b2) gr) gr                    4 + gr's 2 twice over (gr enters as a square) = 6 distinct roundings
+  denom = sqrtf(v') / bc2_sqrt + eps              4   root (ev passed on as sqrt(v' + ev) - sqrt(v')), bc2_sqrt's own, quotient, sum
+  step = lr_elem / bc1                            2   bc1's own, quotient
+  p' = p - step * (m' / denom)                    3   quotient, product, difference
+  => p' 20 roundings in all (m' 5, v' 6, 9 of its own), dominated by the last one, 2^-24 |p'|.
+An fma contraction removes roundings only.  tests/test_small_ops.py: an fp32 emulation of this order stays inside (largest error / bound
+p 0.990, m 0.972, v 0.992 over the cases) and each of seven wrong kernels leaves TWICE the bound on its recorded share of the elements.
+
+Filter-gradient reduction: exact (==) on integer partials -- distinct weights per split; values of magnitude 2^23 that cancel across
+splits, which the kernel's order of additions done in fp32 gets wrong on 4 - 43 % of the entries (measured per nsplit on the CPU) --
+and for randn partials |got - ref| <= 2^-24 |ref| + nsplit 2^-53 sum|partials|: one fp32 rounding of a sum accumulated in double.
+
+Largest error / bound measured on the MI355X (printed by every test; reported, not used as bars): Adam + L1 p 0.993, m 0.817, v 0.897
+over the 13 cases x 3 record forms and the decay = 0 launch (the p bound is all but the final rounding of p, so a value just above a
+power of two comes close to it); second metrics launch 2.1e-16 relative against the float64 sum (bar 1e-12); filter-gradient
+reduction, randn partials, 0.998 (a correctly rounded fp32 of the double sum: the bound is that rounding).
 
 A label outside [0, C) in the Dice loss: the reference's torch.eye(C)[label] raises (or wraps for -C..-1); the kernels treat the pixel
 as belonging to no class (it adds to the cardinality through its probabilities only), which tests/test_small_ops.py pins."""
@@ -654,6 +674,297 @@ def test_adam_l1_unaligned_prune_mask_takes_the_scalar_path():
     pruned = mask.bool()
     assert torch.equal(outs[0][1].cpu()[pruned], (torch.tensor(0.9, dtype=torch.float32) * m0)[pruned])
     assert not torch.equal(outs[0][0].cpu()[~pruned], p0[~pruned])
+
+
+def _adam_op(c, t, p, g, m, v, lre=None, prune=None, decay=None, step_dev=None, metrics=None, loss_stats=None):
+    """One RCV_OP_ADAM_L1 record on device tensors; step_dev: an int32 tensor holding t (the record's own step is then 0)."""
+    ptr = lambda x: x.data_ptr() if x is not None else 0
+    return L.make_op(L.OP_ADAM_L1, 0, count=c["n"], aux0=0 if step_dev is not None else t, f0=c["lr"], f1=c["b1"], f2=c["b2"], f3=c["eps"],
+                     f4=c["decay"] if decay is None else decay, f5=c["gs"], p_in=ptr(p), p_in2=ptr(g), p_x0=ptr(m), p_x1=ptr(v), p_x2=ptr(lre),
+                     p_x5=ptr(prune), p_in_aux=ptr(step_dev), p_x3=ptr(metrics), p_x4=ptr(loss_stats))
+
+
+def _bits(t):
+    return t.detach().cpu().contiguous().view(torch.int32)
+
+
+def _inside(got, ref, bound, where, what):
+    g = _np(got)
+    err = np.abs(g - ref)[where]
+    b = bound[where]
+    ratio = float(np.where(err > 0, err / np.maximum(b, 1e-300), 0.0).max()) if err.size else 0.0
+    print("%s: max error / bound %.3f" % (what, ratio))
+    assert np.all(err <= b), "%s: %d of %d elements over the bound, largest error / bound %.3f" % (what, int((~(err <= b)).sum()), err.size, ratio)
+    return ratio
+
+
+@pytest.mark.parametrize("k", range(len(K.adam_cases(256))))
+def test_adam_l1_vs_float64(k):
+    """One step from the uploaded state, plain / with lr_elem / with lr_elem and the prune mask, against R.adam_l1_step inside its
+    running bound (p, m, v each); lr_elem == 0: p keeps its bits, the moments their sentinels; a pruned element's moments are exactly
+    fl(b1 m), fl(b2 v); with decay = 0 an element with g = m = v = 0 keeps its bits (-0 stays -0)."""
+    n, t, gs = K.adam_cases(_cus())[k]
+    c = K.build_adam(n, t, gs)
+    g_d, lre_d, pr_d = _dev(c["g"]), _dev(c["lr_elem"]), _dev(c["prune"], torch.uint8)
+    p0_bits = _bits(torch.from_numpy(c["p"]))
+    for form in K.ADAM_FORMS:
+        lre, pr = K.adam_form(c, form)
+        dead = (lre == 0) if lre is not None else np.zeros(n, bool)
+        live = ~dead
+        p = _dev(c["p"])
+        m, v = _dev(np.where(dead, np.float32(123.0), c["m"])), _dev(np.where(dead, np.float32(7.0), c["v"]))
+        op = _adam_op(c, t, p, g_d, m, v, lre_d if lre is not None else None, pr_d if pr is not None else None)
+        assert _label(op) == "adam_l1"
+        _run(op)
+        (rp, rm, rv), (ep, em, ev) = K.adam_reference(c, form)
+        what = "adam n=%d t=%d gs=%.3f %s " % (n, t, gs, form)
+        _inside(p, rp, ep, live, what + "p")
+        _inside(m, rm, em, live, what + "m")
+        _inside(v, rv, ev, live, what + "v")
+        if dead.any():
+            d = torch.from_numpy(dead)
+            assert torch.equal(_bits(p)[d], p0_bits[d]), what + "lr_elem == 0 must leave p's bits"
+            assert bool((m.cpu()[d] == 123.0).all()) and bool((v.cpu()[d] == 7.0).all()), what + "lr_elem == 0 must leave the moments"
+        if pr is not None:
+            pl = torch.from_numpy((pr != 0) & live)
+            assert torch.equal(_bits(m)[pl], _bits(torch.from_numpy(c["b1"] * c["m"]))[pl]), what + "pruned: m' = fl(b1 m)"
+            assert torch.equal(_bits(v)[pl], _bits(torch.from_numpy(c["b2"] * c["v"]))[pl]), what + "pruned: v' = fl(b2 v)"
+    # no decay: nothing moves an element whose gradient and moments are zero
+    p, m, v = _dev(c["p"]), _dev(c["m"]), _dev(c["v"])
+    _run(_adam_op(c, t, p, g_d, m, v, decay=0.0))
+    (rp, rm, rv), (ep, em, ev) = K.adam_reference(c, "plain", decay=0.0)
+    every = np.ones(n, bool)
+    _inside(p, rp, ep, every, "adam n=%d t=%d decay 0 p" % (n, t))
+    _inside(m, rm, em, every, "adam n=%d t=%d decay 0 m" % (n, t))
+    _inside(v, rv, ev, every, "adam n=%d t=%d decay 0 v" % (n, t))
+    z = torch.from_numpy((c["g"] == 0) & (c["m"] == 0) & (c["v"] == 0))
+    assert torch.equal(_bits(p)[z], p0_bits[z]) and not bool(_bits(m)[z].any()) and not bool(_bits(v)[z].any())
+    if n >= 1027:
+        assert bool((p0_bits[z] == -2 ** 31).any()) and bool(z.any()), "the case must hold a -0 with zero gradient and moments"
+
+
+@pytest.mark.parametrize("t", [1, 1000])
+def test_adam_l1_device_step_counter(t):
+    """The step of a replayed graph comes from an int32 on the device (p[RCV_P_IN_AUX]): the same bits as the record that carries t;
+    two such records of one op list with the counter advanced on the device between them = the records of t and t + 1."""
+    c = K.build_adam(100003, t, 0.125)
+    g_d, lre_d, pr_d = _dev(c["g"]), _dev(c["lr_elem"]), _dev(c["prune"], torch.uint8)
+    host = [_dev(c[k]) for k in "pmv"]
+    devc = [_dev(c[k]) for k in "pmv"]
+    counter = torch.tensor([t], dtype=torch.int32, device=DEV)
+    _run(_adam_op(c, t, *host[:1], g_d, *host[1:], lre_d, pr_d), _adam_op(c, t, *devc[:1], g_d, *devc[1:], lre_d, pr_d, step_dev=counter))
+    for a, b, name in zip(host, devc, "pmv"):
+        assert torch.equal(_bits(a), _bits(b)), "step %d from the device counter: %s differs" % (t, name)
+    assert not torch.equal(_bits(host[0]), _bits(torch.from_numpy(c["p"])))
+    # second step
+    _run(_adam_op(c, t + 1, *host[:1], g_d, *host[1:], lre_d, pr_d))
+    two = [_dev(c[k]) for k in "pmv"]
+    ops = L.OpList([_adam_op(c, t, *two[:1], g_d, *two[1:], lre_d, pr_d, step_dev=counter)] * 2)
+    stream = torch.cuda.current_stream(DEV).cuda_stream
+    ops.run_slice(_h(), stream, 0, 1)
+    counter.add_(1)
+    ops.run_slice(_h(), stream, 1, 2)
+    torch.cuda.synchronize()
+    assert int(counter.item()) == t + 1
+    for a, b, name in zip(host, two, "pmv"):
+        assert torch.equal(_bits(a), _bits(b)), "steps %d, %d from the device counter: %s differs" % (t, t + 1, name)
+    if t == 1:      # the two steps do differ in their bias corrections: a counter read as t twice is seen
+        stale = [_dev(c[k]) for k in "pmv"]
+        _run(_adam_op(c, t, *stale[:1], g_d, *stale[1:], lre_d, pr_d), _adam_op(c, t, *stale[:1], g_d, *stale[1:], lre_d, pr_d))
+        assert not torch.equal(_bits(stale[0]), _bits(host[0]))
+
+
+@pytest.mark.parametrize("size", ["5", "100003", "beyond a grid pass"])
+def test_adam_l1_metrics_exact(size):
+    """The metrics launch: p on the grid k / 8 (sum|p| exact in any order), a third of the elements unstepped, a quarter pruned;
+    metrics == [0.5 + decay sum|p|, decay sum|p|, 7, 1] over ALL n elements before the update, the ticket is left 0, p / m / v have
+    the bits of the launch without metrics; a second launch adds its row (p is off the grid by then: 1e-12 relative)."""
+    n = K.adam_big_n(_cus()) if size == "beyond a grid pass" else int(size)
+    c = K.adam_metrics_inputs(n)
+    c.update({k: np.float32(x) for k, x in K.ADAM_HYPER.items()})
+    c["gs"], c["decay"] = np.float32(1.0), np.float32(2.0 ** -10)
+    g_d, lre_d, pr_d = _dev(c["g"]), _dev(c["lr_elem"]), _dev(c["prune"], torch.uint8)
+    loss = _dev(np.array([0.5, np.nan, 7.0, np.nan], np.float32))
+    plain, met = [_dev(c[k]) for k in "pmv"], [_dev(c[k]) for k in "pmv"]
+    metrics = torch.zeros(4, dtype=torch.float64, device=DEV)
+    op = _adam_op(c, 3, *met[:1], g_d, *met[1:], lre_d, pr_d, metrics=metrics, loss_stats=loss)
+    nbytes = L.op_workspace(_h(), op)
+    rows = op.i[L.RCV_I_NPART]
+    assert nbytes == (rows + 1) * 8 and rows == min((n // 4 + 255) // 256 or 1, 2 * _cus())
+    ws = torch.full((rows + 1,), float("nan"), dtype=torch.float64, device=DEV)
+    ws[rows] = 0.0                                               # the ticket word (and its padding)
+    op.p[L.RCV_P_PART] = ws.data_ptr()
+    _run(_adam_op(c, 3, *plain[:1], g_d, *plain[1:], lre_d, pr_d), op)
+    reg = np.float64(c["decay"]) * np.abs(c["p"].astype(np.float64)).sum()
+    want = np.array([0.5 + reg, reg, 7.0, 1.0])
+    got = metrics.cpu().numpy()
+    assert np.array_equal(got, want), (got.tolist(), want.tolist())
+    assert not bool(torch.isnan(ws[:rows]).any()) and float(ws[:rows].sum()) * float(c["decay"]) == reg
+    assert int(ws[rows:].view(torch.int32)[0].item()) == 0, "the ticket must read 0 after the launch"
+    for a, b, name in zip(plain, met, "pmv"):
+        assert torch.equal(_bits(a), _bits(b)), "metrics launch: %s differs from the plain launch" % name
+    p1 = _np(met[0])
+    assert (np.abs(p1[c["lr_elem"] == 0]) == np.abs(c["p"][c["lr_elem"] == 0])).all() and (p1 != c["p"]).any()
+    _run(op)
+    reg2 = np.float64(c["decay"]) * np.abs(p1).sum()
+    want2 = want + np.array([0.5 + reg2, reg2, 7.0, 1.0])
+    got2 = metrics.cpu().numpy()
+    print("adam metrics n=%d second launch: relative difference %.2e" % (n, float(np.abs(got2 - want2).max() / np.abs(want2).max())))
+    assert np.all(np.abs(got2 - want2) <= 1e-12 * np.abs(want2)), (got2.tolist(), want2.tolist())
+    assert int(ws[rows:].view(torch.int32)[0].item()) == 0
+
+
+# ------------------------------------------------------------------------------------------ filter-gradient reductions
+GUARD = 777.0
+
+
+class _ReduceOut:
+    """NaN-prefilled dW [CB][CA][3][3] and db [n_db] with 16 guard floats before, between and after them."""
+
+    def __init__(self, CB, CA, n_db=None):
+        self.nw, self.nb = CB * CA * 9, CB if n_db is None else n_db
+        self.buf = torch.full((48 + self.nw + self.nb,), GUARD, device=DEV)
+        self.dw = self.buf[16:16 + self.nw]
+        self.db = self.buf[32 + self.nw:32 + self.nw + self.nb]
+        self.dw.fill_(float("nan"))
+        self.db.fill_(float("nan"))
+        self.shape = (CB, CA, 3, 3)
+
+    def guards_intact(self, db_written=True):
+        b = self.buf.cpu()
+        ok = bool((b[:16] == GUARD).all()) and bool((b[16 + self.nw:32 + self.nw] == GUARD).all()) and bool((b[-16:] == GUARD).all())
+        return ok and (db_written or bool(torch.isnan(b[32 + self.nw:32 + self.nw + self.nb]).all()))
+
+
+def _reduce_single(c, part_d, with_bias):
+    out = _ReduceOut(c["CB"], c["CA"])
+    op = L.make_op(L.OP_WGRAD_REDUCE, 0, cin=c["CA"], cout=c["CB"], nsplit=c["nsplit"], p_part=part_d.data_ptr(), p_out=out.dw.data_ptr(),
+                   p_bias=out.db.data_ptr() if with_bias else 0)
+    assert _label(op) == "wgrad_reduce"
+    _run(op)
+    return out
+
+
+@pytest.mark.parametrize("CB,CA", K.REDUCE_SHAPES + (K.REDUCE_WIDE[0],))
+def test_wgrad_reduce_every_split_regime(CB, CA):
+    """RCV_OP_WGRAD_REDUCE alone on hand-made partials [nsplit][9][CBP][CAP] (+ [nsplit][CBP]) with NaN in the pad rows / columns and
+    in a whole extra split behind the last: nsplit across every edge of the loop structure (<= 16, the 16-stride tail, the
+    four-loads-in-flight main loop from 49, its second round from 65 ... 113), with and without the bias row.  Exact on distinct
+    integer weights per split and on the cancelling integers only a double accumulation gets right; randn within one fp32 rounding
+    of the double sum."""
+    wide = (CB, CA) == K.REDUCE_WIDE[0]
+    worst = 0.0
+    for ns in (K.REDUCE_WIDE[1] if wide else K.REDUCE_NSPLIT):
+        for kind in ("weights", "cancel") + (("randn",) if ns in (49, 200) else ()):
+            c = K.build_reduce(ns, CB, CA, kind)
+            ref_dw, ref_db = K.reduce_reference(c)
+            for with_bias in ((True,) if wide else (True, False)):
+                part_d = _dev(K.reduce_buffer(c, with_bias))
+                out = _reduce_single(c, part_d, with_bias)
+                what = "wgrad_reduce (%d, %d) nsplit %d %s bias=%d " % (CB, CA, ns, kind, with_bias)
+                assert out.guards_intact(db_written=with_bias), what + "wrote outside its outputs"
+                got = [(out.dw.reshape(out.shape), ref_dw, c["part"][:, :, :CB, :CA].transpose(0, 2, 3, 1).reshape((ns,) + out.shape), "dW")]
+                if with_bias:
+                    got.append((out.db, ref_db, c["bias"][:, :CB], "db"))
+                for g, r, terms, name in got:
+                    if kind != "randn":
+                        _exact(g, r, what + name)
+                        continue
+                    assert not bool(torch.isnan(g).any()), what + name + ": an entry was not written (or took in a pad)"
+                    bound = U * np.abs(r) + ns * 2.0 ** -53 * np.abs(terms.astype(np.float64)).sum(0)
+                    err = np.abs(_np(g) - r)
+                    worst = max(worst, float((err / bound).max()))
+                    assert np.all(err <= bound), what + name + ": error / bound %.3f" % float((err / bound).max())
+    print("wgrad_reduce (%d, %d) randn: max error / bound %.3f" % (CB, CA, worst))
+
+
+def test_wgrad_reduce_batch_equals_the_single_records():
+    """One RCV_OP_WGRAD_REDUCE_BATCH whose job table is built here from the header's formula (rcv_reduce_job): reductions with and
+    without a bias row and two zero-fill jobs (one of two blocks); every output is bit for bit the single record's and equals the
+    float64 sums; a zero-filled vector is 0 over [0, CB) and nothing beyond; every guard is intact."""
+    import ctypes as C
+    specs = [("red", 16, 8, 49, True, "cancel"), ("zero", 300, 0, 0, True, None), ("red", 8, 3, 1, False, "weights"), ("red", 64, 32, 65, True, "cancel"),
+             ("zero", 1, 0, 0, True, None), ("red", 5, 16, 17, True, "weights")]
+    table = (L.RcvReduceJob * len(specs))()
+    keep, first = [], 0
+    for j, (what, CB, CA, ns, with_bias, kind) in enumerate(specs):
+        table[j].nsplit, table[j].CB, table[j].CA, table[j].first_block = ns, CB, CA, first
+        if what == "zero":
+            out = _ReduceOut(1, 1, n_db=CB)
+            table[j].db = out.db.data_ptr()
+            first += (CB + 255) // 256
+            keep.append((None, None, out))
+            continue
+        c = K.build_reduce(ns, CB, CA, kind, seed=j)
+        part_d = _dev(K.reduce_buffer(c, with_bias))
+        out = _ReduceOut(CB, CA)
+        table[j].part, table[j].dw, table[j].db = part_d.data_ptr(), out.dw.data_ptr(), out.db.data_ptr() if with_bias else None
+        CBP, CAP = (CB + 15) // 16 * 16, 4 if CA <= 4 else (CA + 15) // 16 * 16
+        first += (9 * CBP * CAP + (CBP if with_bias else 0) + 63) // 64
+        keep.append((c, part_d, out))
+    assert first == 37 + 2 + 9 + 289 + 1 + 37
+    table_d = torch.frombuffer(bytearray(bytes(table)), dtype=torch.uint8).to(DEV)
+    op = L.make_op(L.OP_WGRAD_REDUCE_BATCH, 0, count=len(specs), npart=first, p_in=table_d.data_ptr())
+    assert _label(op) == "wgrad_reduce_batch"
+    _run(op)
+    for (what, CB, CA, ns, with_bias, kind), (c, part_d, out) in zip(specs, keep):
+        name = "batch job %s (%d, %d) nsplit %d: " % (what, CB, CA, ns)
+        if what == "zero":
+            assert out.guards_intact() and bool(torch.isnan(out.dw).all()), name + "wrote outside [0, CB)"
+            assert torch.equal(out.db, torch.zeros(CB, device=DEV)), name + "not zero-filled"
+            continue
+        assert out.guards_intact(db_written=with_bias), name + "wrote outside its outputs"
+        single = _reduce_single(c, part_d, with_bias)
+        assert torch.equal(_bits(out.dw), _bits(single.dw)), name + "dW differs from the single record"
+        ref_dw, ref_db = K.reduce_reference(c)
+        _exact(out.dw.reshape(out.shape), ref_dw, name + "dW")
+        if with_bias:
+            assert torch.equal(_bits(out.db), _bits(single.db)), name + "db differs from the single record"
+            _exact(out.db, ref_db, name + "db")
+
+
+# ------------------------------------------------------------------------------------------ confusion counts
+def _confusion_op(pred_d, tgt_d, counts, C):
+    N, H, W = pred_d.shape
+    return L.make_op(L.OP_CONFUSION, 0, n=N, h=H, w=W, cout=C, p_in=pred_d.data_ptr(), p_in2=tgt_d.data_ptr(), p_out=counts.data_ptr())
+
+
+@pytest.mark.parametrize("C", K.CONF_CLASSES)
+def test_confusion_exact(C):
+    """RCV_OP_CONFUSION against numpy's bincount: uint8 predictions (some >= C), int64 labels with -100, -1, C, 255, 2^32 + 1 and
+    -2^32 + 2 among them (no class: the range test is made on the int64), one workgroup per image, odd planes, one pixel, and a plane
+    past the workgroup cap whose last pixel carries a pair of its own; the op accumulates."""
+    for N, H, W in K.confusion_planes():
+        pred, tgt = K.build_confusion(N, H, W, C)
+        ref = R.confusion(pred, tgt, C)
+        pred_d, tgt_d = _dev(pred, torch.uint8), _dev(tgt, torch.int64)
+        counts = torch.zeros(N, C, C, dtype=torch.int32, device=DEV)
+        op = _confusion_op(pred_d, tgt_d, counts, C)
+        _run(op)
+        what = "confusion %d classes %s: " % (C, (N, H, W))
+        got = counts.cpu().numpy().astype(np.int64)
+        assert np.array_equal(got, ref), what + "counts differ at %s: got %s, expected %s" % (
+            np.argwhere(got != ref)[:4].tolist(), got[got != ref][:4].tolist(), ref[got != ref][:4].tolist())
+        ok = (pred < C) & (tgt >= 0) & (tgt < C)
+        assert np.array_equal(got.sum((1, 2)), ok.reshape(N, -1).sum(1)), what + "the counts of an image must add up to its pixels in range"
+        _run(op)
+        assert np.array_equal(counts.cpu().numpy().astype(np.int64), 2 * ref), what + "a second run must add to the first"
+
+
+def test_confusion_more_images_than_a_grid_dimension():
+    """The image index is a grid dimension (at most 65535): more images fold onto it -- PatchMetrics counts one 1x1 image per patch."""
+    N, C = 65536 + 3, 4
+    pred, tgt = K.build_confusion(N, 1, 1, C)
+    ref = R.confusion(pred, tgt, C)
+    assert ref[65535:].sum() > 0 and ref.sum() < N
+    pred_d, tgt_d = _dev(pred, torch.uint8), _dev(tgt, torch.int64)
+    counts = torch.zeros(N, C, C, dtype=torch.int32, device=DEV)
+    _run(_confusion_op(pred_d, tgt_d, counts, C))
+    assert np.array_equal(counts.cpu().numpy().astype(np.int64), ref)
+    from robocupvision_amd.metrics import PatchMetrics
+    pm = PatchMetrics(C, DEV)
+    pm.update(pred_d.reshape(N), tgt_d.reshape(N))
+    assert np.array_equal(pm.conf.cpu().numpy(), ref.sum(0))
 
 
 # ------------------------------------------------------------------------------------------ pointwise ops

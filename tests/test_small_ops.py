@@ -1,6 +1,8 @@
 """No GPU: tests/small_ops_restatement.py (the float64 yardstick of tests/test_gpu_small_ops.py and of the epilogue-statistics tests
 of tests/test_gpu_kernels.py) against torch float64 autograd on ragged shapes, the integer-grid preconditions and the single-pixel
-sensitivity of every exact GPU case (small_ops_cases), and the plan-time refusal of RCV_OP_CONV1X1 (in the header, no kernel)."""
+sensitivity of every exact GPU case (small_ops_cases), the plan-time refusal of RCV_OP_CONV1X1 (in the header, no kernel); the Adam
++ L1 restatement against torch.optim.Adam in float64, its rounding bound against an fp32 emulation of the kernel (inside) and against
+seven wrong kernels (outside, each on a recorded share of the elements), the preconditions of the reduction and confusion cases."""
 import numpy as np
 import pytest
 import torch
@@ -288,3 +290,183 @@ def test_conv1x1_is_refused_when_planned():
     assert "(-1)" in str(ei.value) and "18" in str(ei.value), str(ei.value)
     with pytest.raises(L.RcvError):
         L.OpList([op]).labels(h)
+
+
+# ------------------------------------------------------------------------------------------ Adam + L1
+def _adam_case(case):
+    if case not in _adam_case.cache:
+        c = K.build_adam(*case)
+        _adam_case.cache[case] = (c, {form: K.adam_reference(c, form) for form in K.ADAM_FORMS})
+    return _adam_case.cache[case]
+
+
+_adam_case.cache = {}
+
+
+def test_adam_cases_cover_every_step_scale_and_size():
+    cases = K.adam_cases(CUS)
+    big = K.adam_big_n(CUS)
+    assert big == 529291 and big % 4 == 3 and big > 2 * CUS * 256 * 4
+    assert {c[0] for c in cases} == {1, 3, 4, 5, 255, 1027, 100003, big} and {c[1] for c in cases} == set(K.ADAM_T)
+    assert {c[2] for c in cases if c[0] == big} == set(K.ADAM_GS)
+    c = K.build_adam(big, 1000, 0.125)
+    z = (c["g"] == 0) & (c["m"] == 0) & (c["v"] == 0)
+    assert (z & (c["p"] == 0) & np.signbit(c["p"])).any() and (z & (c["p"] == 0) & ~np.signbit(c["p"])).any() and (z & (c["p"] != 0)).any()
+    assert set(np.unique(c["lr_elem"]).tolist()) == {0.0, float(c["lr"]), float(np.float32(10) * c["lr"])}
+    assert 0.2 < c["prune"].mean() < 0.3 and np.abs(c["g"][c["g"] != 0]).min() < 1e-9 and np.abs(c["g"]).max() > 0.5
+    quad = c["lr_elem"][:big // 4 * 4].reshape(-1, 4)
+    assert ((quad == 0).any(1) & (quad != 0).any(1)).any(), "a float4 must straddle a stepped and an unstepped stretch"
+
+
+def test_adam_restatement_vs_torch_adam():
+    """(a) R.adam_l1_step = torch.optim.Adam in float64 on the gradient g gs + decay sign(p), betas and eps the fp32-rounded values,
+    steps 1..3, to a few float64 ulps once bc1 / bc2_sqrt are left unrounded; a pruned element is one whose whole gradient is 0;
+    lr_elem == 0 leaves the element alone with a zero bound."""
+    rng = np.random.default_rng(77)
+    n = 2003
+    c = K.build_adam(n, 2, 1.0 / 3)
+    h = {k: float(c[k]) for k in ("lr", "b1", "b2", "eps", "decay", "gs")}
+    for pruned in (False, True):
+        ref = torch.nn.Parameter(_t(c["p"]).clone())
+        opt = torch.optim.Adam([ref], lr=h["lr"], betas=(h["b1"], h["b2"]), eps=h["eps"])
+        p, m, v = c["p"].astype(np.float64), np.zeros(n), np.zeros(n)
+        worst = 0.0
+        for step in (1, 2, 3):
+            g = (K._logu(rng, n, 1e-10, 1.0) * rng.choice([-1.0, 1.0], n)).astype(np.float32)
+            grad = _t(g) * h["gs"] + h["decay"] * torch.sign(ref.detach())
+            ref.grad = torch.where(torch.from_numpy(c["prune"] != 0), torch.zeros_like(grad), grad) if pruned else grad
+            p_prev, m_prev = p, m
+            opt.step()
+            (p, m, v), _ = R.adam_l1_step(p, g, m, v, step, c["lr"], c["b1"], c["b2"], c["eps"], c["decay"], c["gs"],
+                                          prune=c["prune"] if pruned else None, round_bc=False)
+            st = opt.state[ref]
+            # scales: the sums of |terms| (m' may cancel; what it loses goes into p' through step / denom)
+            sm = np.abs(m_prev) + np.abs(g.astype(np.float64) * h["gs"]) + h["decay"]
+            sp = np.abs(p_prev) + h["lr"] / (1 - h["b1"] ** step) * sm / (np.sqrt(v) / np.sqrt(1 - h["b2"] ** step) + h["eps"])
+            for got, want, scale in ((p, ref.detach().numpy(), sp), (m, st["exp_avg"].numpy(), sm), (v, st["exp_avg_sq"].numpy(), np.abs(v))):
+                err = np.abs(got - want)
+                worst = max(worst, float((err / np.maximum(scale, 1e-300)).max()))
+                assert np.all(err <= 1e-14 * scale), float((err / np.maximum(scale, 1e-300)).max())
+        print("adam restatement vs torch.optim.Adam (pruned=%d): largest relative difference %.2e" % (pruned, worst))
+    # rounding bc1 / bc2_sqrt to fp32 moves the step by at most 2^-24 relative each
+    a, _ = R.adam_l1_step(c["p"], c["g"], c["m"], c["v"], 2, c["lr"], c["b1"], c["b2"], c["eps"], c["decay"], c["gs"])
+    b, _ = R.adam_l1_step(c["p"], c["g"], c["m"], c["v"], 2, c["lr"], c["b1"], c["b2"], c["eps"], c["decay"], c["gs"], round_bc=False)
+    assert np.all(np.abs(a[0] - b[0]) <= 2.1 * 2.0 ** -24 * np.abs(b[0] - c["p"])) and np.array_equal(a[1], b[1]) and np.array_equal(a[2], b[2])
+    # lr_elem == 0
+    (p1, m1, v1), (ep, em, ev) = K.adam_reference(c, "lr_elem")
+    dead = c["lr_elem"] == 0
+    assert dead.any() and np.array_equal(p1[dead], c["p"][dead]) and np.array_equal(np.signbit(p1[dead]), np.signbit(c["p"][dead]))
+    assert np.array_equal(m1[dead], c["m"][dead]) and np.array_equal(v1[dead], c["v"][dead])
+    assert not ep[dead].any() and not em[dead].any() and not ev[dead].any() and (ep[~dead & (c["p"] != 0)] > 0).all()
+    # a pruned element: gr = 0 exactly, the moments only decay
+    (_, m2, v2), _ = K.adam_reference(c, "lr_elem+prune")
+    pr = (c["prune"] != 0) & ~dead
+    assert np.array_equal(m2[pr], np.float64(c["b1"]) * c["m"][pr]) and np.array_equal(v2[pr], np.float64(c["b2"]) * c["v"][pr])
+
+
+def test_adam_fp32_emulation_stays_inside_the_bound():
+    """(b) the kernel's expression order in fp32 numpy, uncontracted and with either contraction of a b + c d (and of p - step r),
+    stays inside the running bound on every case and record form.  The p bound is mostly the final rounding of p itself."""
+    worst = np.zeros(3)
+    for case in K.adam_cases(CUS):
+        c, refs = _adam_case(case)
+        for form in K.ADAM_FORMS:
+            ref, bound = refs[form]
+            for contract in (0, 1, 2):
+                got = K.adam_emulate(c, form, contract)
+                rat = K.adam_ratios(got, ref, bound)
+                for k, name in enumerate("pmv"):
+                    assert np.all(rat[k] <= 1.0), "%s %s contraction %d: %s leaves the bound (%.3f)" % (case, form, contract, name, rat[k].max())
+                worst = np.maximum(worst, [r.max() for r in rat])
+                if form != "plain":
+                    dead = c["lr_elem"] == 0
+                    assert all(np.array_equal(a[dead], c[k][dead]) for a, k in zip(got, "pmv"))
+    print("adam fp32 emulation: largest error / bound p %.3f m %.3f v %.3f" % tuple(worst))
+    assert worst.min() > 0.3, "a bound nothing comes near is no bound"
+
+
+@pytest.mark.parametrize("mutant", sorted(K.ADAM_MUTANTS))
+def test_adam_wrong_variants_leave_the_bound(mutant):
+    """(c) every wrong kernel of K.ADAM_MUTANTS puts its recorded share of the live elements outside TWICE the bound in at least one
+    case (whichever way the compiler contracts), so the GPU test would see it."""
+    form, best = "lr_elem+prune", 0.0
+    for case in K.adam_cases(CUS):
+        if case[0] < 1027:
+            continue
+        c, refs = _adam_case(case)
+        ref, bound = refs[form]
+        live = c["lr_elem"] != 0
+        share = 1.0
+        for contract in (0, 1, 2):
+            rat = K.adam_ratios(K.adam_emulate(c, form, contract, mutant), ref, bound)
+            out = ~(rat[0] <= 2.0) | ~(rat[1] <= 2.0) | ~(rat[2] <= 2.0)           # NaN and inf count as outside
+            share = min(share, float(out[live].mean()))
+        print("adam mutant %s, case %s: %.3f of the live elements outside twice the bound" % (mutant, case, share))
+        best = max(best, share)
+    assert best >= K.ADAM_MUTANTS[mutant], (mutant, best)
+
+
+# ------------------------------------------------------------------------------------------ filter-gradient reductions
+def test_wgrad_reduce_restatement_layout():
+    rng = np.random.default_rng(4)
+    ns, CB, CA = 3, 5, 3
+    CBP, CAP = K.reduce_pads(CB, CA)
+    assert (CBP, CAP) == (16, 4) and K.reduce_pads(16, 8) == (16, 16) and K.reduce_pads(64, 32) == (64, 32) and K.reduce_pads(8, 4) == (16, 4)
+    part, bias = rng.standard_normal((ns, 9, CBP, CAP)), rng.standard_normal((ns, CBP))
+    dw, db = R.wgrad_reduce(part, bias, CB, CA)
+    assert dw.shape == (CB, CA, 3, 3) and db.shape == (CB,)
+    for cb in range(CB):
+        assert db[cb] == bias[:, cb].sum()
+        for ca in range(CA):
+            for tap in range(9):
+                assert dw[cb, ca, tap // 3, tap % 3] == part[:, tap, cb, ca].sum()
+    assert R.wgrad_reduce(part, None, CB, CA)[1] is None
+    assert K.reduce_blocks(16, 8, True) == 37 and K.reduce_blocks(8, 3, False) == 9 and K.reduce_blocks(64, 32, True) == 289
+    c = K.build_reduce(2, CB, CA, "weights")
+    buf = K.reduce_buffer(c, True)
+    assert buf.size == 3 * (9 * CBP * CAP + CBP) and np.isnan(buf[2 * (9 * CBP * CAP + CBP):]).all()
+    assert np.array_equal(buf[2 * 9 * CBP * CAP:2 * 9 * CBP * CAP + 2 * CBP], c["bias"].reshape(-1), equal_nan=True)
+
+
+@pytest.mark.parametrize("CB,CA", K.REDUCE_SHAPES + (K.REDUCE_WIDE[0],))
+def test_wgrad_reduce_cases_are_exact_sensitive_and_out_of_fp32_reach(CB, CA):
+    """Both exact kinds: integer sums below 2^24; "weights": every split moves every entry; "cancel": the kernel's own order of
+    additions, done in fp32, misses at least the recorded share of the entries (so only a double accumulation passes)."""
+    for ns in (K.REDUCE_NSPLIT if (CB, CA) != K.REDUCE_WIDE[0] else K.REDUCE_WIDE[1]):
+        w = K.build_reduce(ns, CB, CA, "weights")
+        K.check_reduce(w)
+        dw, db = K.reduce_reference(w)
+        assert np.array_equal(K.reduce_fixed_order_fp32(w["part"][:, :, :CB, :CA]).transpose(1, 2, 0).reshape(dw.shape), dw)
+        assert np.array_equal(K.reduce_fixed_order_fp32(w["bias"][:, :CB]), db), "the emulated order must add every split once"
+        c = K.build_reduce(ns, CB, CA, "cancel")
+        K.check_reduce(c)
+        miss = K.reduce_fp32_miss(c)
+        print("wgrad_reduce (%d, %d) nsplit %d: an fp32 accumulation misses %.3f of the entries" % (CB, CA, ns, miss))
+        assert miss >= K.REDUCE_FP32_MISS[ns], (ns, miss)
+
+
+# ------------------------------------------------------------------------------------------ confusion counts
+@pytest.mark.parametrize("C", K.CONF_CLASSES)
+def test_confusion_restatement_and_cases(C):
+    for N, H, W in K.confusion_planes():
+        pred, tgt = K.build_confusion(N, H, W, C)
+        ref = R.confusion(pred, tgt, C)
+        slow = np.zeros((N, C, C), np.int64)
+        for n in range(min(N, 2)):
+            for p, t in zip(pred[n].reshape(-1).tolist()[:3000], tgt[n].reshape(-1).tolist()[:3000]):
+                if p < C and 0 <= t < C:
+                    slow[n, p, t] += 1
+        if H * W <= 3000:
+            assert np.array_equal(ref[:2], slow[:2])
+        ok = (pred < C) & (tgt >= 0) & (tgt < C)
+        assert np.array_equal(ref.sum((1, 2)), ok.reshape(N, -1).sum(1))
+        if N * H * W >= 6:
+            assert {int(x) for x in tgt.reshape(-1)[~ok.reshape(-1)]} >= {C if x is None else x for x in K.CONF_ODD_LABELS}
+            assert (pred >= C).any()
+            # a 32-bit truncation of the labels would count 2^32 + 1 as class 1 and -2^32 + 2 as class 2
+            if C > 1:
+                assert not np.array_equal(R.confusion(pred, tgt.astype(np.int32), C), ref)
+        if C > 1 and H * W > 1:
+            assert ref[-1, C - 1, 0] == 1 and pred[-1, -1, -1] == C - 1 and tgt[-1, -1, -1] == 0
+    one = R.confusion(np.array([[[0]], [[1]]], np.uint8), np.array([[[2 ** 32]], [[1]]], np.int64), 2)
+    assert one.tolist() == [[[0, 0], [0, 0]], [[0, 0], [0, 1]]]
