@@ -213,7 +213,7 @@ enum {
                              * = in[rint(y + flow[1])][rint(x + flow[0])] inside the plane, 0 outside; fp32 sums, rint = half to even.  i[N],
                              * i[H], i[W], i[INMODE] = element bytes (1 = uint8, 8 = int64); p[IN] = class map [N][H][W], p[IN2] = flow
                              * float[N][2][H][W], p[OUT] = class map [N][H][W] (not p[IN])                                              */
-  RCV_OP_OBJECT_PATCHES = 50 /* the boxes of an RCV_OP_OBJECTS result cut out of the full-resolution frames and brought to the patch
+  RCV_OP_OBJECT_PATCHES = 50,/* the boxes of an RCV_OP_OBJECTS result cut out of the full-resolution frames and brought to the patch
                              * classifiers' input (rcv_object_patches; csrc/patches.hip): Pillow's 8-bit BILINEAR resize of every box, then
                              * rgb2yuv + Normalize([.5,0,0],[.5,.5,.5]), one launch, one workgroup per slot.  i[N], i[H] / i[W] = Hs / Ws of the
                              * frames, i[HO] / i[WO] = H / W of the class map the boxes live in (1..Hs / 1..Ws), i[COUT] = C - 1 (classes with
@@ -224,6 +224,26 @@ enum {
                              * slot (zeros past the emitted count: nothing needs pre-zeroing).  No workspace.  Refused when planned: a count
                              * < 1, a patch side outside 1..64, margin < 0, a map larger than the frames, W Ws or H Hs past 32 bits,
                              * coefficient tables (2 + ceil(in / out) 2 + 1 int32 per output index and axis) beyond the LDS of a workgroup */
+  RCV_OP_RESIZE_U8 = 51,     /* the resize stage of RCV_OP_BATCH_PREP alone (rcv_resize_u8; csrc/batch_prep.hip): the bytes that record feeds its
+                             * normalisation lookup, and the labels gathered and NOT masked -- what a device-resident dataset keeps, since
+                             * everything random comes after them.  i[N] = B, i[H] / i[W] = source Hs / Ws, i[HO] / i[WO] = output H / W, i[CIN] /
+                             * i[COUT] = taps per output column / row of the frame tables, i[INMODE2] = label element bytes in (1 = uint8, 4 =
+                             * int32; 0 = no labels: p[IN2], p[X0], p[X3], p[X4] are not looked at), i[INMODE] = label element bytes out (1 =
+                             * uint8: the low byte of an int32 label, the 4 -> 1 narrowing for planes whose values are <= 255; 4 = int32);
+                             * p[IN] = frames uint8[B][Hs][Ws][3], p[IN2] = labels [B][Hs][Ws], p[X1] / p[X2] = frame tables of x / y, p[X3] /
+                             * p[X4] = label index tables of x / y (the four as RCV_OP_BATCH_PREP), p[OUT] = bytes uint8[B][H][W][3] (NHWC),
+                             * p[X0] = labels [B][H][W].  H == Hs and W == Ws: a plain copy (or narrowing / widening) of both.  Same tiles and
+                             * the same staged / through-the-cache choice as RCV_OP_BATCH_PREP.  No workspace.  Refused when planned: what
+                             * RCV_OP_BATCH_PREP refuses, and a label width out other than 1 or 4                                       */
+  RCV_OP_BATCH_PREP_IDX = 52 /* RCV_OP_BATCH_PREP whose image b is store[index[b]] (rcv_batch_prep_indexed): the slots of that record, and
+                             * i[COUNT] = N images in the store p[IN] = frames uint8[N][Hs][Ws][3] / p[IN2] = labels [N][Hs][Ws], p[IN_AUX] =
+                             * index [B] in DEVICE memory, i[INMODE] = its element bytes (4 = int32, 8 = int64), p[EPI_AUX] = int32 counter in
+                             * device memory.  i[N] = B = rows of the index, of p[IN_C], of p[OUT] and of p[X0].  Bit for bit the outputs of
+                             * RCV_OP_BATCH_PREP on the gathered images (the same arithmetic in the same order), in both kernel forms.  An
+                             * index outside [0, N) is tested before it forms an address: that image is written as zeros with targets 0 and
+                             * the counter is incremented once (an atomic add; the caller zeroes it and reads it when it likes) -- nothing
+                             * is read out of bounds, nothing synchronises.  Refused when planned: what RCV_OP_BATCH_PREP refuses (the pixel
+                             * limit counts the store), N < 1, an index element size other than 4 or 8, a null index or counter          */
 };
 
 /* i[RCV_I_AUX0] of RCV_OP_PRUNE: how the threshold of a tensor is chosen */
@@ -570,6 +590,27 @@ int rcv_batch_prep(rcv_handle* h, const uint8_t* frames, const void* labels, int
  * bit for bit what rcv_batch_prep(train = 0) writes for the same frames and tables.                                                */
 int rcv_frame_prep(rcv_handle* h, const uint8_t* frames, int B, int Hs, int Ws, int H, int W, const int32_t* frame_x, int kx,
                    const int32_t* frame_y, int ky, const float* norm, float* imgs, void* stream);
+
+/* RCV_OP_RESIZE_U8: the resize stage of rcv_batch_prep alone, for a dataset that is kept on the device.  Pillow's resize ends in a
+ * uint8 and everything random (flip, jitter) comes after it, so the bytes can be stored once: frames uint8[B][Hs][Ws][3] -> out
+ * uint8[B][H][W][3] (NHWC; the three values rcv_batch_prep looks up in `norm`), labels [B][Hs][Ws] (label_bytes 1 / 4) -> labels_out
+ * [B][H][W] of label_out_bytes 1 (uint8; an int32 label keeps its low byte: the caller has checked that every value is <= 255) or 4
+ * (int32), gathered through label_x / label_y and not masked.  labels == NULL: frames alone (label_bytes, label_out_bytes, label_x,
+ * label_y, labels_out are not looked at).  The tables are rcv_batch_prep's; H == Hs and W == Ws copies.  Exact (integers only).    */
+int rcv_resize_u8(rcv_handle* h, const uint8_t* frames, const void* labels /*may be NULL*/, int label_bytes, int B, int Hs, int Ws, int H,
+                  int W, const int32_t* frame_x, int kx, const int32_t* frame_y, int ky, const int32_t* label_x, const int32_t* label_y,
+                  uint8_t* out, void* labels_out, int label_out_bytes, void* stream);
+
+/* RCV_OP_BATCH_PREP_IDX: rcv_batch_prep whose image b is image index[b] of a store of N images (frames uint8[N][Hs][Ws][3], labels
+ * [N][Hs][Ws]); index is int32[B] (index_bytes 4) or int64[B] (8) in device memory, so an epoch's permutation is uploaded once and a
+ * batch is a slice of it.  params, imgs, targets have B rows; every other argument is rcv_batch_prep's.  imgs and targets are bit for
+ * bit those of rcv_batch_prep on the gathered images.  An index outside [0, N) reads nothing: its image is zeros, its targets 0, and
+ * *bad_count (int32, device memory, zeroed by the caller) is incremented once per such image.                                     */
+int rcv_batch_prep_indexed(rcv_handle* h, const uint8_t* frames, const void* labels, int label_bytes, int N, const void* index,
+                           int index_bytes, int B, int Hs, int Ws, int H, int W, const int32_t* frame_x, int kx, const int32_t* frame_y,
+                           int ky, const int32_t* label_x, const int32_t* label_y, const float* norm,
+                           const float* params /*NULL unless train*/, int train, int mask_flags, float* imgs, int64_t* targets,
+                           int32_t* bad_count, void* stream);
 
 /* RCV_OP_RGB_PREP: the RGB loader of trainer.py:75-123 (SSDataSet with Scale / HorizontalFlip / VerticalFlip / torchvision's PIL
  * ColorJitter / ToYUV / ToTensor / Normalize([.5,0,0],[.5,.5,.5]); the same chain feeds pruner.py, labelPropTrain.py, tester.py,

@@ -20,6 +20,10 @@ def __getattr__(name):
     if name in ("prepare_batch", "prepare_frames", "draw_jitter", "SSYUVDataset", "prepare_rgb_batch", "draw_color_jitter", "SSDataSet"):
         from . import data
         return getattr(data, name)
+    # ... and whole epochs from a dataset that stays on the device as resized bytes: resize_u8 / ResidentDataset / EpochLoader
+    if name in ("resize_u8", "draw_jitter_rows", "ResidentDataset", "EpochLoader"):
+        from . import data
+        return getattr(data, name)
     # class maps and colour masks on the device (detect.py): palette.py, infer.py
     if name in ("colorize", "Colorize", "labelcolormap"):
         from . import palette

@@ -33,6 +33,8 @@ OP_OBJECTS = 46             # boxes, areas and centres of the components of a cl
 OP_RGB_PREP = 47            # the RGB loader of trainer.py / pruner.py for a whole batch: PIL ColorJitter, rgb2yuv (rcv.h RCV_OP_RGB_PREP, csrc/rgb_prep.hip)
 OP_FARNEBACK, OP_REMAP_LABELS = 48, 49      # dense optical flow and the label remap through it (rcv.h RCV_OP_FARNEBACK / RCV_OP_REMAP_LABELS, csrc/flow.hip)
 OP_OBJECT_PATCHES = 50      # the boxes of OP_OBJECTS cut out of the frames -> 32x32 YUV patches (rcv.h RCV_OP_OBJECT_PATCHES, csrc/patches.hip)
+OP_RESIZE_U8 = 51           # OP_BATCH_PREP's resize stage alone: uint8 NHWC bytes and unmasked labels, what a resident dataset keeps (rcv.h RCV_OP_RESIZE_U8)
+OP_BATCH_PREP_IDX = 52      # OP_BATCH_PREP whose image b is store[index[b]], the index in device memory (rcv.h RCV_OP_BATCH_PREP_IDX)
 PRUNE_MAX_RATIO, PRUNE_STD_SEARCH, PRUNE_SMALLEST_K = range(3)      # i[AUX0] of OP_PRUNE: pruneModelNew / pruneModel / pruneModel2
 PRUNE_MAX_ITER = 4096
 PRUNE_ST_OK, PRUNE_ST_NO_END, PRUNE_ST_ALL_ZERO, PRUNE_ST_BAD_JOB = range(4)
@@ -77,7 +79,7 @@ EXPORTS = [
     "rcv_object_match", "rcv_labelprop_batch", "rcv_batch_prep", "rcv_frame_prep", "rcv_cls_label", "rcv_colorize",
     "rcv_bnn_stage_fwd", "rcv_bnn_stage_bwd", "rcv_bnn_head_fwd", "rcv_bnn_head_bwd",
     "rcv_sgd_step_pruned", "rcv_prune_check", "rcv_prune", "rcv_find_objects", "rcv_rgb_prep",
-    "rcv_farneback_flow", "rcv_update_labels", "rcv_object_patches",
+    "rcv_farneback_flow", "rcv_update_labels", "rcv_object_patches", "rcv_resize_u8", "rcv_batch_prep_indexed",
 ]
 
 
@@ -130,6 +132,10 @@ def load():
         lib.rcv_batch_prep.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p, C.c_int, C.c_void_p, C.c_int] + \
             [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.rcv_frame_prep.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 3
+        lib.rcv_resize_u8.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p, C.c_int, C.c_void_p, C.c_int] + \
+            [C.c_void_p] * 4 + [C.c_int, C.c_void_p]
+        lib.rcv_batch_prep_indexed.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p] + [C.c_int] * 6 + \
+            [C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_int] + [C.c_void_p] * 4
         lib.rcv_rgb_prep.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p, C.c_int, C.c_void_p, C.c_int] + \
             [C.c_void_p] * 3 + [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
         lib.rcv_cls_label.argtypes = [C.c_void_p] * 4 + [C.c_int] * 5 + [C.c_void_p] * 4

@@ -115,6 +115,8 @@ static int dispatch(const rcv_handle* h, const rcv_op* op, hipStream_t s, OpQuer
       return rcv_launch_lp_batch(h, op, s, q);
     case RCV_OP_BATCH_PREP:
     case RCV_OP_FRAME_PREP:
+    case RCV_OP_RESIZE_U8:
+    case RCV_OP_BATCH_PREP_IDX:
       return rcv_launch_batch_prep(h, op, s, q);
     case RCV_OP_RGB_PREP:
       return rcv_launch_rgb_prep(h, op, s, q);
@@ -480,6 +482,35 @@ int rcv_frame_prep(rcv_handle* h, const uint8_t* frames, int B, int Hs, int Ws, 
   op.i[RCV_I_N] = B; op.i[RCV_I_H] = Hs; op.i[RCV_I_W] = Ws; op.i[RCV_I_HO] = H; op.i[RCV_I_WO] = W; op.i[RCV_I_CIN] = kx; op.i[RCV_I_COUT] = ky;
   op.p[RCV_P_IN] = (void*)frames; op.p[RCV_P_OUT] = imgs; op.p[RCV_P_X1] = (void*)frame_x; op.p[RCV_P_X2] = (void*)frame_y;
   op.p[RCV_P_X5] = (void*)norm;
+  return rcv_run(h, &op, 1, stream);
+}
+
+int rcv_resize_u8(rcv_handle* h, const uint8_t* frames, const void* labels, int label_bytes, int B, int Hs, int Ws, int H, int W,
+                  const int32_t* frame_x, int kx, const int32_t* frame_y, int ky, const int32_t* label_x, const int32_t* label_y, uint8_t* out,
+                  void* labels_out, int label_out_bytes, void* stream) {
+  rcv_op op;
+  memset(&op, 0, sizeof(op));
+  op.kind = RCV_OP_RESIZE_U8;
+  op.i[RCV_I_N] = B; op.i[RCV_I_H] = Hs; op.i[RCV_I_W] = Ws; op.i[RCV_I_HO] = H; op.i[RCV_I_WO] = W; op.i[RCV_I_CIN] = kx; op.i[RCV_I_COUT] = ky;
+  op.i[RCV_I_INMODE2] = labels ? label_bytes : 0; op.i[RCV_I_INMODE] = labels ? label_out_bytes : 1;
+  op.p[RCV_P_IN] = (void*)frames; op.p[RCV_P_IN2] = (void*)labels; op.p[RCV_P_OUT] = out; op.p[RCV_P_X0] = labels_out;
+  op.p[RCV_P_X1] = (void*)frame_x; op.p[RCV_P_X2] = (void*)frame_y; op.p[RCV_P_X3] = (void*)label_x; op.p[RCV_P_X4] = (void*)label_y;
+  return rcv_run(h, &op, 1, stream);
+}
+
+int rcv_batch_prep_indexed(rcv_handle* h, const uint8_t* frames, const void* labels, int label_bytes, int N, const void* index, int index_bytes,
+                           int B, int Hs, int Ws, int H, int W, const int32_t* frame_x, int kx, const int32_t* frame_y, int ky,
+                           const int32_t* label_x, const int32_t* label_y, const float* norm, const float* params, int train, int mask_flags,
+                           float* imgs, int64_t* targets, int32_t* bad_count, void* stream) {
+  rcv_op op;
+  memset(&op, 0, sizeof(op));
+  op.kind = RCV_OP_BATCH_PREP_IDX;
+  op.i[RCV_I_N] = B; op.i[RCV_I_H] = Hs; op.i[RCV_I_W] = Ws; op.i[RCV_I_HO] = H; op.i[RCV_I_WO] = W; op.i[RCV_I_CIN] = kx; op.i[RCV_I_COUT] = ky;
+  op.i[RCV_I_INMODE2] = label_bytes; op.i[RCV_I_AUX0] = train; op.i[RCV_I_AUX1] = mask_flags;
+  op.i[RCV_I_COUNT] = N; op.i[RCV_I_INMODE] = index_bytes;
+  op.p[RCV_P_IN] = (void*)frames; op.p[RCV_P_IN2] = (void*)labels; op.p[RCV_P_OUT] = imgs; op.p[RCV_P_X0] = targets;
+  op.p[RCV_P_X1] = (void*)frame_x; op.p[RCV_P_X2] = (void*)frame_y; op.p[RCV_P_X3] = (void*)label_x; op.p[RCV_P_X4] = (void*)label_y;
+  op.p[RCV_P_X5] = (void*)norm; op.p[RCV_P_IN_C] = (void*)params; op.p[RCV_P_IN_AUX] = (void*)index; op.p[RCV_P_EPI_AUX] = bad_count;
   return rcv_run(h, &op, 1, stream);
 }
 

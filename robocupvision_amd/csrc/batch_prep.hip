@@ -16,6 +16,12 @@
 // when flipped).  STAGE: the source-row segments of the tile are first copied to LDS with 16-byte aligned loads, 8 rows at a time, and
 // the horizontal taps read LDS bytes; otherwise the taps read global bytes through the cache (DESIGN.md 4.5 has the measurement).
 // Every table entry is clamped where it is used: a wrong table gives wrong pixels, never an access outside the operands.
+//
+// Two more records run the same passes (the kernels are instantiated per form; nothing is copied):
+//   RCV_OP_RESIZE_U8 (rcv_resize_u8) stops after step 1: the three bytes go out as uint8 NHWC [B][H][W][3] and the label is gathered,
+//     not masked, and written as uint8 or int32 -- what a device-resident dataset keeps (everything random comes after the bytes);
+//   RCV_OP_BATCH_PREP_IDX (rcv_batch_prep_indexed) takes image b from store[index[b]]: the index is read from device memory and tested
+//     against [0, N) before it forms an address; an image whose index fails is written as zeros (targets 0) and counted.
 #include "rcv_internal.h"
 
 #define BP_TR 8
@@ -27,10 +33,15 @@
 #define BP_PREC 22
 #define BP_STAGE_MIN_TAPS 9                  /* taps per output column from which the source rows are staged in LDS */
 
+enum { BP_PREP = 0, BP_PREP_IDX = 1, BP_BYTES = 2 };          // the form a kernel is instantiated for
+
 struct BpArgs {
   const uint8_t* frames; const void* labels; float* imgs; int64_t* tgt;
   const int32_t* xtab; const int32_t* ytab; const int32_t* lx; const int32_t* ly; const float* norm; const float* params;
   int B, Hs, Ws, H, W, kx, ky, lab_bytes, train, mask, rows_cap, tiles_x, tiles_y;
+  int nsrc;                                 // images behind `frames` / `labels`: B, or the N of the store (BP_PREP_IDX)
+  const void* index; int idx_bytes; int* bad;          // BP_PREP_IDX: index [B] of 4 / 8 byte elements, counter of the refused ones
+  uint8_t* out8; void* lab_out; int lab_out_bytes;     // BP_BYTES: bytes [B][H][W][3], labels [B][H][W] of 1 / 4 byte elements (or null)
 };
 
 __device__ __forceinline__ int bp_clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
@@ -58,9 +69,41 @@ __device__ __forceinline__ BpJitter bp_jitter(const BpArgs& a, int b) {
   return j;
 }
 
-// steps 2-6 for one output pixel (x, y: coordinates before the mirror) of image b from its three resized bytes
+// BP_PREP_IDX: the store image of batch row b, or -1 where the index is outside [0, nsrc) (tested before it is used for anything)
+__device__ __forceinline__ int bp_source(const BpArgs& a, int b) {
+  const long long v = a.idx_bytes == 8 ? (long long)((const int64_t*)a.index)[b] : (long long)((const int32_t*)a.index)[b];
+  return v >= 0 && v < (long long)a.nsrc ? (int)v : -1;
+}
+
+// the label under output pixel (x, y) of source image src, through the NEAREST index tables
+__device__ __forceinline__ int bp_label(const BpArgs& a, int src, int y, int x) {
+  const int sy = bp_clampi(a.ly[y], 0, a.Hs - 1), sx = bp_clampi(a.lx[x], 0, a.Ws - 1);
+  const size_t li = ((size_t)src * a.Hs + sy) * a.Ws + sx;
+  return a.lab_bytes == 1 ? (int)((const uint8_t*)a.labels)[li] : ((const int32_t*)a.labels)[li];
+}
+
+// BP_BYTES: the three resized bytes and the gathered label of one output pixel, as they are
+__device__ __forceinline__ void bp_store_bytes(const BpArgs& a, int b, int y, int x, int c0, int c1, int c2) {
+  const size_t o = ((size_t)b * a.H + y) * a.W + x;
+  uint8_t* q = a.out8 + o * 3;
+  q[0] = (uint8_t)c0; q[1] = (uint8_t)c1; q[2] = (uint8_t)c2;
+  if (!a.lab_out) return;                  // frames without labels (uniform over the launch)
+  const int lv = bp_label(a, b, y, x);
+  if (a.lab_out_bytes == 1) ((uint8_t*)a.lab_out)[o] = (uint8_t)lv;
+  else ((int32_t*)a.lab_out)[o] = lv;
+}
+
+// BP_PREP_IDX with a refused index: output pixel (x, y) of batch row b is zeros, its target 0
+__device__ __forceinline__ void bp_zero(const BpArgs& a, int b, int y, int x) {
+  const size_t plane = (size_t)a.H * a.W, o = (size_t)y * a.W + x;
+  float* img = a.imgs + (size_t)b * 3 * plane + o;
+  img[0] = 0.f; img[plane] = 0.f; img[2 * plane] = 0.f;
+  a.tgt[(size_t)b * plane + o] = 0;
+}
+
+// steps 2-6 for one output pixel (x, y: coordinates before the mirror) of batch row b from the three resized bytes of image src
 template <typename LUT>
-__device__ __forceinline__ void bp_finish(const BpArgs& a, const BpJitter& j, LUT lut, int b, int y, int x, int c0, int c1, int c2) {
+__device__ __forceinline__ void bp_finish(const BpArgs& a, const BpJitter& j, LUT lut, int b, int src, int y, int x, int c0, int c1, int c2) {
   float v0 = lut[c0], v1 = lut[256 + c1], v2 = lut[512 + c2];
   const int xo = j.flip ? a.W - 1 - x : x;
   if (a.train) {
@@ -75,15 +118,12 @@ __device__ __forceinline__ void bp_finish(const BpArgs& a, const BpJitter& j, LU
   float* img = a.imgs + (size_t)b * 3 * plane + o;
   img[0] = v0; img[plane] = v1; img[2 * plane] = v2;
   if (!a.tgt) return;                      // RCV_OP_FRAME_PREP: frames without labels (uniform over the launch)
-  const int sy = bp_clampi(a.ly[y], 0, a.Hs - 1), sx = bp_clampi(a.lx[x], 0, a.Ws - 1);
-  const size_t li = ((size_t)b * a.Hs + sy) * a.Ws + sx;
-  const int lv = a.lab_bytes == 1 ? (int)((const uint8_t*)a.labels)[li] : ((const int32_t*)a.labels)[li];
-  a.tgt[(size_t)b * plane + o] = (int64_t)bp_mask(lv, a.mask);
+  a.tgt[(size_t)b * plane + o] = (int64_t)bp_mask(bp_label(a, src, y, x), a.mask);
 }
 
-template <bool STAGE>
+template <bool STAGE, int FORM>
 __global__ __launch_bounds__(256) void batch_prep_kernel(BpArgs a) {
-  __shared__ float s_lut[768];
+  __shared__ float s_lut[FORM == BP_BYTES ? 1 : 768];
   __shared__ int32_t s_xc[BP_TC * (2 + BP_MAXK)];
   __shared__ int32_t s_yc[BP_TR * (2 + BP_MAXK)];
   __shared__ uint8_t s_h[BP_ROWS_MAX * BP_TC * 3];
@@ -93,17 +133,29 @@ __global__ __launch_bounds__(256) void batch_prep_kernel(BpArgs a) {
   const int tx = bid % a.tiles_x, ty = (bid / a.tiles_x) % a.tiles_y, b = bid / (a.tiles_x * a.tiles_y);
   const int x0 = tx * BP_TC, y0 = ty * BP_TR;
   const int tw = min(BP_TC, a.W - x0), th = min(BP_TR, a.H - y0);
+  int src = b;
+  if (FORM == BP_PREP_IDX) {
+    src = bp_source(a, b);
+    if (src < 0) {                          // (the same for the whole workgroup, and in front of every barrier)
+      for (int idx = tid; idx < th * BP_TC; idx += 256)
+        if ((idx & (BP_TC - 1)) < tw) bp_zero(a, b, y0 + (idx >> 6), x0 + (idx & (BP_TC - 1)));
+      if (tx == 0 && ty == 0 && tid == 0) atomicAdd(a.bad, 1);
+      return;
+    }
+  }
   const int sx = 2 + a.kx, sy = 2 + a.ky;
-  for (int i = tid; i < 768; i += 256) s_lut[i] = a.norm[i];
+  if (FORM != BP_BYTES)
+    for (int i = tid; i < 768; i += 256) s_lut[i] = a.norm[i];
   for (int i = tid; i < tw * sx; i += 256) s_xc[i] = a.xtab[(size_t)x0 * sx + i];
   for (int i = tid; i < th * sy; i += 256) s_yc[i] = a.ytab[(size_t)y0 * sy + i];
   __syncthreads();
-  const BpJitter j = bp_jitter(a, b);
+  BpJitter j = {};
+  if (FORM != BP_BYTES) j = bp_jitter(a, b);
   // source rows under this tile's vertical taps
   const int ys0 = bp_clampi(s_yc[0], 0, a.Hs - 1);
   const int ys1 = bp_clampi(s_yc[(th - 1) * sy] + s_yc[(th - 1) * sy + 1], ys0 + 1, a.Hs);
   const int nrows = min(ys1 - ys0, a.rows_cap);
-  const uint8_t* fb = a.frames + (size_t)b * a.Hs * a.Ws * 3;
+  const uint8_t* fb = a.frames + (size_t)src * a.Hs * a.Ws * 3;
 
   // ---- horizontal pass: s_h[r][x][c] for the rows ys0 .. ys0 + nrows; this thread's column is fixed
   const int x = tid & (BP_TC - 1);
@@ -132,7 +184,7 @@ __global__ __launch_bounds__(256) void batch_prep_kernel(BpArgs a) {
     const int nvmax = (seg + 15 + 15) / 16;
     const int rel = bp_clampi(xf - xs0, 0, segpix - 1);
     const int xns = min(xn, segpix - rel);
-    const uintptr_t lo = (uintptr_t)a.frames, hi = lo + (size_t)a.B * a.Hs * a.Ws * 3;
+    const uintptr_t lo = (uintptr_t)a.frames, hi = lo + (size_t)a.nsrc * a.Hs * a.Ws * 3;
     for (int r0 = 0; r0 < nrows; r0 += BP_RC) {
       const int nr = min(BP_RC, nrows - r0);
       for (int i = tid; i < nr * nvmax; i += 256) {
@@ -184,22 +236,41 @@ __global__ __launch_bounds__(256) void batch_prep_kernel(BpArgs a) {
       const uint8_t* q = s_h + (bp_clampi(yf + k, 0, nrows - 1) * BP_TC + x) * 3;
       a0 += (int)q[0] * c; a1 += (int)q[1] * c; a2 += (int)q[2] * c;
     }
-    bp_finish(a, j, s_lut, b, y0 + yl, x0 + x, bp_clip8(a0), bp_clip8(a1), bp_clip8(a2));
+    if (FORM == BP_BYTES) bp_store_bytes(a, b, y0 + yl, x0 + x, bp_clip8(a0), bp_clip8(a1), bp_clip8(a2));
+    else bp_finish(a, j, s_lut, b, src, y0 + yl, x0 + x, bp_clip8(a0), bp_clip8(a1), bp_clip8(a2));
   }
 }
 
 // H == Hs and W == Ws: no resize (dataset.py:118-121); one thread per pixel, 2048 pixels of one image per workgroup
 #define BP_IDENT_PIX 2048
+template <int FORM>
 __global__ __launch_bounds__(256) void batch_prep_ident_kernel(BpArgs a, int blocks_per_image) {
   const int b = blockIdx.x / blocks_per_image, blk = blockIdx.x % blocks_per_image;
-  const BpJitter j = bp_jitter(a, b);
   const int npix = a.H * a.W;
-  const uint8_t* fb = a.frames + (size_t)b * npix * 3;
   const int end = min(npix, (blk + 1) * BP_IDENT_PIX);
+  int src = b;
+  if (FORM == BP_PREP_IDX) {
+    src = bp_source(a, b);
+    if (src < 0) {
+      for (int p = blk * BP_IDENT_PIX + threadIdx.x; p < end; p += 256) bp_zero(a, b, p / a.W, p % a.W);
+      if (blk == 0 && threadIdx.x == 0) atomicAdd(a.bad, 1);
+      return;
+    }
+  }
+  const BpJitter j = bp_jitter(a, b);
+  const uint8_t* fb = a.frames + (size_t)src * npix * 3;
   for (int p = blk * BP_IDENT_PIX + threadIdx.x; p < end; p += 256) {
     const int y = p / a.W, x = p - y * a.W;
     const uint8_t* q = fb + (size_t)p * 3;
-    bp_finish(a, j, a.norm, b, y, x, (int)q[0], (int)q[1], (int)q[2]);
+    bp_finish(a, j, a.norm, b, src, y, x, (int)q[0], (int)q[1], (int)q[2]);
+  }
+}
+
+// RCV_OP_RESIZE_U8 with H == Hs and W == Ws, labels whose width changes: out[i] = in[i] narrowed (4 -> 1, the low byte) or widened
+__global__ __launch_bounds__(256) void resize_u8_label_width_kernel(const void* in, void* out, int in_bytes, size_t n) {
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+    if (in_bytes == 4) ((uint8_t*)out)[i] = (uint8_t)((const int32_t*)in)[i];
+    else ((int32_t*)out)[i] = (int32_t)((const uint8_t*)in)[i];
   }
 }
 
@@ -212,50 +283,95 @@ static int bp_ksize(int in, int out) {
   return c * 2 + 1;
 }
 
+template <int FORM>
+static void bp_launch_tiles(bool stage, const BpArgs& a, hipStream_t s) {
+  void (*kern)(BpArgs) = batch_prep_kernel<false, FORM>;
+  if (stage) kern = batch_prep_kernel<true, FORM>;
+  hipLaunchKernelGGL(kern, dim3(a.B * a.tiles_x * a.tiles_y), dim3(256), 0, s, a);
+}
+
 // Every refusal that depends on the shape of the record, and the tables (a plan without them has nothing to read), sits in front of
 // the `query` return; the batch operands are checked at launch.
 int rcv_launch_batch_prep(const rcv_handle* h, const rcv_op* op, hipStream_t s, OpQuery* query) {
   const int B = op->i[RCV_I_N], Hs = op->i[RCV_I_H], Ws = op->i[RCV_I_W], H = op->i[RCV_I_HO], W = op->i[RCV_I_WO];
   // RCV_OP_FRAME_PREP (rcv_frame_prep): the validation form for frames alone -- no label, no label table, no target
   const bool frames_only = op->kind == RCV_OP_FRAME_PREP;
+  // RCV_OP_RESIZE_U8 (rcv_resize_u8): the resize alone, bytes out; RCV_OP_BATCH_PREP_IDX (rcv_batch_prep_indexed): images picked from a store
+  const bool bytes = op->kind == RCV_OP_RESIZE_U8, indexed = op->kind == RCV_OP_BATCH_PREP_IDX;
   const int kx = op->i[RCV_I_CIN], ky = op->i[RCV_I_COUT], lab_bytes = frames_only ? 1 : op->i[RCV_I_INMODE2];
-  const int train = frames_only ? 0 : op->i[RCV_I_AUX0], mask = frames_only ? 0 : op->i[RCV_I_AUX1];
+  const bool no_labels = frames_only || (bytes && lab_bytes == 0);
+  const int train = frames_only || bytes ? 0 : op->i[RCV_I_AUX0], mask = frames_only || bytes ? 0 : op->i[RCV_I_AUX1];
+  const int nsrc = indexed ? op->i[RCV_I_COUNT] : B;          // images behind p[IN] / p[IN2]
   if (query) {
     query->n_part = 0; query->n_split = 0; query->part_bytes = 0;
-    snprintf(query->label, sizeof(query->label), frames_only ? "frame_prep" : "batch_prep");
+    snprintf(query->label, sizeof(query->label), frames_only ? "frame_prep" : bytes ? "resize_u8" : indexed ? "batch_prep_idx" : "batch_prep");
   }
   RCV_CHECK_ARG(B >= 1 && H >= 1 && W >= 1 && Hs >= 1 && Ws >= 1, "batch prep: B %d, source %d x %d, output %d x %d: every size must be >= 1", B, Hs, Ws,
                 H, W);
+  RCV_CHECK_ARG(nsrc >= 1, "batch prep: a store of %d images (i[COUNT]): there must be at least 1", nsrc);
   RCV_CHECK_ARG((long long)Hs <= 8LL * H && (long long)Ws <= 8LL * W,
                 "batch prep: %d x %d -> %d x %d shrinks an axis by more than 8 (the kernel is built for at most %d taps)", Hs, Ws, H, W, BP_MAXK);
-  RCV_CHECK_ARG(lab_bytes == 1 || lab_bytes == 4, "batch prep: label element size %d unsupported (1 = uint8, 4 = int32)", lab_bytes);
+  RCV_CHECK_ARG(lab_bytes == 1 || lab_bytes == 4 || (bytes && lab_bytes == 0), "batch prep: label element size %d unsupported (1 = uint8, 4 = int32)",
+                lab_bytes);
+  if (bytes && !no_labels)
+    RCV_CHECK_ARG(op->i[RCV_I_INMODE] == 1 || op->i[RCV_I_INMODE] == 4,
+                  "resize u8: label element size out %d cannot hold the %d-byte labels (1 = uint8, also the narrowing of int32 planes whose "
+                  "values are <= 255; 4 = int32)", op->i[RCV_I_INMODE], lab_bytes);
+  if (indexed)
+    RCV_CHECK_ARG(op->i[RCV_I_INMODE] == 4 || op->i[RCV_I_INMODE] == 8, "batch prep: index element size %d unsupported (4 = int32, 8 = int64)",
+                  op->i[RCV_I_INMODE]);
   RCV_CHECK_ARG(kx == bp_ksize(Ws, W) && ky == bp_ksize(Hs, H), "batch prep: %d / %d taps per column / row given, %d -> %d and %d -> %d take %d / %d", kx,
                 ky, Ws, W, Hs, H, bp_ksize(Ws, W), bp_ksize(Hs, H));
   RCV_CHECK_ARG((train == 0 || train == 1) && mask >= 0 && mask <= 15, "batch prep: train %d / maskLabel flags %d out of range", train, mask);
   const int tiles_x = ceil_div(W, BP_TC), tiles_y = ceil_div(H, BP_TR);
-  RCV_CHECK_ARG((double)B * Hs * Ws < 2147483647.0 && (double)B * H * W < 2147483647.0 && (double)B * tiles_x * tiles_y < 2147483647.0,
-                "batch prep: %d images of %d x %d -> %d x %d: more than 2^31 pixels", B, Hs, Ws, H, W);
-  if (frames_only)
-    RCV_CHECK_ARG(op->p[RCV_P_X1] && op->p[RCV_P_X2] && op->p[RCV_P_X5], "frame prep: null table (frame taps of x / y, normalisation)");
+  RCV_CHECK_ARG((double)nsrc * Hs * Ws < 2147483647.0 && (double)B * H * W < 2147483647.0 && (double)B * tiles_x * tiles_y < 2147483647.0,
+                "batch prep: %d images of %d x %d -> %d x %d: more than 2^31 pixels", nsrc > B ? nsrc : B, Hs, Ws, H, W);
+  if (no_labels)
+    RCV_CHECK_ARG(op->p[RCV_P_X1] && op->p[RCV_P_X2] && (bytes || op->p[RCV_P_X5]),
+                  bytes ? "resize u8: null table (frame taps of x / y)" : "frame prep: null table (frame taps of x / y, normalisation)");
   else
-    RCV_CHECK_ARG(op->p[RCV_P_X1] && op->p[RCV_P_X2] && op->p[RCV_P_X3] && op->p[RCV_P_X4] && op->p[RCV_P_X5],
-                  "batch prep: null table (frame taps of x / y, label index of x / y, normalisation)");
+    RCV_CHECK_ARG(op->p[RCV_P_X1] && op->p[RCV_P_X2] && op->p[RCV_P_X3] && op->p[RCV_P_X4] && (bytes || op->p[RCV_P_X5]),
+                  bytes ? "resize u8: null table (frame taps of x / y, label index of x / y)"
+                        : "batch prep: null table (frame taps of x / y, label index of x / y, normalisation)");
+  // the index and its counter live for an epoch, as the tables do: a plan without them has nothing to gather by
+  if (indexed) RCV_CHECK_ARG(op->p[RCV_P_IN_AUX] && op->p[RCV_P_EPI_AUX], "batch prep: null index or null bad-index counter");
   if (query) return RCV_OK;
-  if (frames_only) RCV_CHECK_ARG(op->p[RCV_P_IN] && op->p[RCV_P_OUT], "frame prep: null operand");
-  else RCV_CHECK_ARG(op->p[RCV_P_IN] && op->p[RCV_P_IN2] && op->p[RCV_P_OUT] && op->p[RCV_P_X0], "batch prep: null operand");
+  if (no_labels) RCV_CHECK_ARG(op->p[RCV_P_IN] && op->p[RCV_P_OUT], bytes ? "resize u8: null operand" : "frame prep: null operand");
+  else RCV_CHECK_ARG(op->p[RCV_P_IN] && op->p[RCV_P_IN2] && op->p[RCV_P_OUT] && op->p[RCV_P_X0], bytes ? "resize u8: null operand" : "batch prep: null operand");
   RCV_CHECK_ARG(!train || op->p[RCV_P_IN_C], "batch prep: training mode needs the parameter rows float[B][8]");
   BpArgs a;
-  a.frames = (const uint8_t*)op->p[RCV_P_IN]; a.imgs = (float*)op->p[RCV_P_OUT];
-  a.labels = frames_only ? nullptr : op->p[RCV_P_IN2]; a.tgt = frames_only ? nullptr : (int64_t*)op->p[RCV_P_X0];
+  memset(&a, 0, sizeof(a));
+  a.frames = (const uint8_t*)op->p[RCV_P_IN];
+  a.labels = no_labels ? nullptr : op->p[RCV_P_IN2];
   a.xtab = (const int32_t*)op->p[RCV_P_X1]; a.ytab = (const int32_t*)op->p[RCV_P_X2];
-  a.lx = frames_only ? nullptr : (const int32_t*)op->p[RCV_P_X3]; a.ly = frames_only ? nullptr : (const int32_t*)op->p[RCV_P_X4];
-  a.norm = (const float*)op->p[RCV_P_X5]; a.params = frames_only ? nullptr : (const float*)op->p[RCV_P_IN_C];
-  a.B = B; a.Hs = Hs; a.Ws = Ws; a.H = H; a.W = W; a.kx = kx; a.ky = ky; a.lab_bytes = lab_bytes; a.train = train; a.mask = mask;
-  a.tiles_x = tiles_x; a.tiles_y = tiles_y;
+  a.lx = no_labels ? nullptr : (const int32_t*)op->p[RCV_P_X3]; a.ly = no_labels ? nullptr : (const int32_t*)op->p[RCV_P_X4];
+  if (bytes) {
+    a.out8 = (uint8_t*)op->p[RCV_P_OUT]; a.lab_out = no_labels ? nullptr : op->p[RCV_P_X0]; a.lab_out_bytes = op->i[RCV_I_INMODE];
+  } else {
+    a.imgs = (float*)op->p[RCV_P_OUT]; a.tgt = frames_only ? nullptr : (int64_t*)op->p[RCV_P_X0];
+    a.norm = (const float*)op->p[RCV_P_X5]; a.params = frames_only ? nullptr : (const float*)op->p[RCV_P_IN_C];
+  }
+  if (indexed) { a.index = op->p[RCV_P_IN_AUX]; a.idx_bytes = op->i[RCV_I_INMODE]; a.bad = (int*)op->p[RCV_P_EPI_AUX]; }
+  a.B = B; a.Hs = Hs; a.Ws = Ws; a.H = H; a.W = W; a.kx = kx; a.ky = ky; a.lab_bytes = no_labels ? 1 : lab_bytes; a.train = train; a.mask = mask;
+  a.tiles_x = tiles_x; a.tiles_y = tiles_y; a.nsrc = nsrc;
+  if (H == Hs && W == Ws && bytes) {          // nothing to resize: copies, and one launch where the label width changes
+    const size_t npix = (size_t)B * H * W;
+    if (a.out8 != a.frames) RCV_HIP(hipMemcpyAsync(a.out8, a.frames, npix * 3, hipMemcpyDeviceToDevice, s));
+    if (a.lab_out && a.lab_out_bytes == lab_bytes) {
+      if (a.lab_out != a.labels) RCV_HIP(hipMemcpyAsync(a.lab_out, a.labels, npix * lab_bytes, hipMemcpyDeviceToDevice, s));
+    } else if (a.lab_out) {
+      const size_t blocks = (npix + 255) / 256;
+      hipLaunchKernelGGL(resize_u8_label_width_kernel, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(256), 0, s, a.labels, a.lab_out, lab_bytes,
+                         npix);
+      RCV_HIP(hipGetLastError());
+    }
+    return RCV_OK;
+  }
   if (H == Hs && W == Ws) {
     const int bpi = ceil_div(H * W, BP_IDENT_PIX);
     RCV_CHECK_ARG((double)B * bpi < 2147483647.0, "batch prep: grid too large");
-    hipLaunchKernelGGL(batch_prep_ident_kernel, dim3(B * bpi), dim3(256), 0, s, a, bpi);
+    if (indexed) hipLaunchKernelGGL(batch_prep_ident_kernel<BP_PREP_IDX>, dim3(B * bpi), dim3(256), 0, s, a, bpi);
+    else hipLaunchKernelGGL(batch_prep_ident_kernel<BP_PREP>, dim3(B * bpi), dim3(256), 0, s, a, bpi);
     RCV_HIP(hipGetLastError());
     return RCV_OK;
   }
@@ -266,7 +382,9 @@ int rcv_launch_batch_prep(const rcv_handle* h, const rcv_op* op, hipStream_t s, 
   // staging pays where the row shrinks by more than about 3 (measured); RCV_BP_STAGE=0 / 1 overrides it in diagnostic builds
   bool stage = kx >= BP_STAGE_MIN_TAPS;
   if (const char* e = RCV_ENV("RCV_BP_STAGE")) stage = e[0] != '0';
-  hipLaunchKernelGGL(stage ? batch_prep_kernel<true> : batch_prep_kernel<false>, dim3(B * tiles_x * tiles_y), dim3(256), 0, s, a);
+  if (bytes) bp_launch_tiles<BP_BYTES>(stage, a, s);
+  else if (indexed) bp_launch_tiles<BP_PREP_IDX>(stage, a, s);
+  else bp_launch_tiles<BP_PREP>(stage, a, s);
   RCV_HIP(hipGetLastError());
   return RCV_OK;
 }

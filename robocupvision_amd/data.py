@@ -7,6 +7,24 @@ as ONE launch per batch (RCV_OP_BATCH_PREP, csrc/batch_prep.hip).
     imgs, targets = prepare_batch(frames, labels, (120, 160), params=draw_jitter(len(frames)))
     trainer.step(imgs, targets)
 
+That form uploads every frame at its decoded size for every batch, every epoch.  The way to run EPOCHS is the resident form: the
+dataset is decoded and resized ONCE (``resize_u8``, RCV_OP_RESIZE_U8: Pillow's resize ends in a uint8 and everything random comes after
+it), the resized bytes stay on the device, and a batch is one launch that picks its images from the store by index
+(``prepare_batch(..., index=)``, RCV_OP_BATCH_PREP_IDX) -- no upload, no host tensor work and no synchronisation per batch:
+
+    store = ResidentDataset(ds, img_size=(120, 160), device="cuda")     # decode (<= 16 threads) -> upload in chunks -> resize_u8, once
+    loader = EpochLoader(store, batch_size=64, train=True)              # one permutation + one draw_jitter_rows upload per epoch
+    for epoch in range(epochs):
+        for imgs, targets in loader:                                    # each: one prepare_batch(index=perm_dev[a:b], params=rows_dev[a:b])
+            trainer.step(imgs, targets)
+        store.check()                                                   # the one synchronisation: no index fell outside the store
+
+Pinned: the stored bytes (to Pillow, byte for byte: tests/test_resident.py, tests/test_gpu_resident.py) and the batch (bit for bit
+``prepare_batch`` of the full-size frames gathered by the same indices with the same rows).  The project's own definition: the epoch
+order (``torch.randperm(N, generator=)`` on the host) and the sharding (``perm[rank::world]``) -- the order of the reference's
+multi-worker ``DataLoader`` cannot be reproduced by any single process; row ``i`` of an epoch's draws belongs to the ``i``-th sample
+visited, the order a single-process reference loader draws in.
+
 The resize is Pillow's (8-bit BILINEAR frames, NEAREST mode-``I`` labels), restated as integer tables that are built here on the host
 and cached on the device per (Hs, Ws, H, W); the restatement was compared with ``Image.resize`` of Pillow 12.2.0 byte for byte
 (tests/test_batch_prep.py).  Random numbers and trigonometry stay on the host (``draw_jitter``): the kernel draws nothing.
@@ -44,7 +62,7 @@ import torch
 from . import _lib as L
 
 __all__ = ["prepare_batch", "prepare_frames", "draw_jitter", "SSYUVDataset", "bilinear_table", "nearest_table", "norm_table",
-           "prepare_rgb_batch", "draw_color_jitter", "SSDataSet"]
+           "prepare_rgb_batch", "draw_color_jitter", "SSDataSet", "resize_u8", "draw_jitter_rows", "ResidentDataset", "EpochLoader"]
 
 PRECISION_BITS = 22          # Pillow's 8-bit resampling: 32 - 8 - 2
 MEAN = {False: [0.36269532, 0.41144562, 0.282713], True: [0.34190056, 0.4833289, 0.48565758]}      # dataset.py:74 (key: finetune)
@@ -125,8 +143,11 @@ def _device_norm(finetune, dev):
     return t
 
 
+_bad_counters = {}    # device -> int32 [1] on the device: images whose index fell outside the store (prepare_batch(index=) without bad_index=)
+
+
 def prepare_batch(frames, labels, img_size=(120, 160), finetune=False, train=True, params=None, no_ball=False, no_robot=False,
-                  no_goal=False, no_line=False):
+                  no_goal=False, no_line=False, index=None, bad_index=None):
     """``frames`` uint8 [B,Hs,Ws,3] (decoded RGB) and ``labels`` uint8 or int32 [B,Hs,Ws], both on the HIP device -> ``(imgs, targets)``:
     float32 [B,3,H,W] and int64 [B,H,W], what ``Trainer.step`` / ``Trainer.evaluate`` take.  One launch.
 
@@ -134,6 +155,12 @@ def prepare_batch(frames, labels, img_size=(120, 160), finetune=False, train=Tru
     U/V matrix.  ``train=False`` is the validation loader: resize, normalise, maskLabel.  ``no_ball .. no_line`` are ``maskLabel``'s
     nb, nr, ng, nl.  Exact where the reference's arithmetic is (everything but U/V, which are within 2^-23 (|m0 U| + |m1 V|) of exact,
     as the reference's einsum is).
+
+    ``index`` (int32 or int64 [B], on the device): ``frames`` / ``labels`` are then a STORE of N images and image ``b`` of the batch is
+    ``store[index[b]]``; ``B = len(index)`` and ``params`` is [B,8] (RCV_OP_BATCH_PREP_IDX).  The result is bit for bit that of the call
+    without ``index`` on ``frames[index]``, ``labels[index]``.  An index outside [0, N) reads nothing: that image comes back as zeros
+    with targets 0, and ``bad_index`` (int32 [1] on the device; one per device is kept here if none is given) is incremented -- by the
+    kernel, with nothing synchronised; ``ResidentDataset.check`` reads it.  Without ``index`` the call is what it always was.
 
     Stated difference: when exactly one of ``H == Hs``, ``W == Ws`` holds the reference skips the resize altogether
     (dataset.py:118-121 joins the two comparisons with ``and``) and hands the network a frame of the wrong size; here that raises."""
@@ -156,6 +183,19 @@ def prepare_batch(frames, labels, img_size=(120, 160), finetune=False, train=Tru
     if not (frames.is_contiguous() and labels.is_contiguous()):
         raise ValueError("prepare_batch: frames and labels must be contiguous (no hidden copy of a batch)")
     dev = frames.device
+    N = B
+    if index is not None:
+        if not torch.is_tensor(index) or index.dtype not in (torch.int32, torch.int64) or index.dim() != 1 or index.shape[0] < 1:
+            raise TypeError("prepare_batch: index must be a non-empty int32 or int64 [B] tensor")
+        if index.device != dev or not index.is_contiguous():
+            raise ValueError("prepare_batch: index must be contiguous and on the device of the store (%s; got %s)" % (dev, index.device))
+        B = int(index.shape[0])
+        if bad_index is None:
+            bad_index = _bad_counters.get(str(dev))
+            if bad_index is None:
+                bad_index = _bad_counters[str(dev)] = torch.zeros(1, dtype=torch.int32, device=dev)
+        elif not torch.is_tensor(bad_index) or bad_index.dtype != torch.int32 or bad_index.numel() < 1 or bad_index.device != dev:
+            raise TypeError("prepare_batch: bad_index must be an int32 tensor on the device of the store")
     if train:
         if params is None:
             raise ValueError("prepare_batch: train=True needs params (draw_jitter(B))")
@@ -168,6 +208,13 @@ def prepare_batch(frames, labels, img_size=(120, 160), finetune=False, train=Tru
     targets = torch.empty(B, H, W, dtype=torch.int64, device=dev)
     mask = (1 if no_ball else 0) | (2 if no_robot else 0) | (4 if no_goal else 0) | (8 if no_line else 0)
     h = L.handle(dev.index if dev.index is not None else torch.cuda.current_device())
+    if index is not None:
+        L.check(L.load().rcv_batch_prep_indexed(h, frames.data_ptr(), labels.data_ptr(), labels.element_size(), N, index.data_ptr(),
+                                                index.element_size(), B, Hs, Ws, H, W, fx.data_ptr(), kx, fy.data_ptr(), ky, lx.data_ptr(),
+                                                ly.data_ptr(), norm.data_ptr(), params.data_ptr() if train else None, 1 if train else 0,
+                                                mask, imgs.data_ptr(), targets.data_ptr(), bad_index.data_ptr(),
+                                                torch.cuda.current_stream(dev).cuda_stream), "rcv_batch_prep_indexed")
+        return imgs, targets
     L.check(L.load().rcv_batch_prep(h, frames.data_ptr(), labels.data_ptr(), labels.element_size(), B, Hs, Ws, H, W, fx.data_ptr(), kx,
                                     fy.data_ptr(), ky, lx.data_ptr(), ly.data_ptr(), norm.data_ptr(),
                                     params.data_ptr() if train else None, 1 if train else 0, mask, imgs.data_ptr(), targets.data_ptr(),
@@ -205,6 +252,72 @@ def prepare_frames(frames, img_size=(120, 160), finetune=False):
     L.check(L.load().rcv_frame_prep(h, frames.data_ptr(), B, Hs, Ws, H, W, fx.data_ptr(), kx, fy.data_ptr(), ky, norm.data_ptr(),
                                     imgs.data_ptr(), torch.cuda.current_stream(dev).cuda_stream), "rcv_frame_prep")
     return imgs
+
+
+def resize_u8(frames, labels=None, img_size=(120, 160), label_dtype=torch.uint8):
+    """``frames`` uint8 [B,Hs,Ws,3] and ``labels`` uint8 or int32 [B,Hs,Ws] (or None), on the HIP device -> ``(bytes, labels_out)``:
+    uint8 [B,H,W,3] and ``label_dtype`` (uint8 or int32) [B,H,W] (None without labels).  The resize stage of ``prepare_batch`` alone, one
+    launch (RCV_OP_RESIZE_U8): ``bytes`` are what ``Image.fromarray(f).resize((W, H), BILINEAR)`` holds and ``labels_out`` what the
+    mode-``I`` label's ``resize((W, H), NEAREST)`` holds, byte for byte -- gathered, not masked.  ``prepare_batch`` of them at their own
+    size equals ``prepare_batch`` of the full-size frames bit for bit.  ``label_dtype=torch.uint8`` keeps the low byte of an int32
+    label: the caller has seen that every value is <= 255 (``ResidentDataset`` checks it on the host array).  ``H == Hs and W == Ws``
+    copies.  Same refusals as ``prepare_batch``."""
+    if not torch.is_tensor(frames) or (labels is not None and not torch.is_tensor(labels)):
+        raise TypeError("resize_u8: frames (and labels) must be tensors")
+    if frames.dtype != torch.uint8 or (labels is not None and labels.dtype not in (torch.uint8, torch.int32)):
+        raise TypeError("resize_u8: frames must be uint8 and labels uint8 or int32 (got %s, %s)"
+                        % (frames.dtype, None if labels is None else labels.dtype))
+    if label_dtype not in (torch.uint8, torch.int32):
+        raise TypeError("resize_u8: label_dtype must be torch.uint8 or torch.int32 (got %s)" % (label_dtype,))
+    if frames.dim() != 4 or frames.shape[3] != 3 or (labels is not None and labels.dim() != 3):
+        raise ValueError("resize_u8: frames must be [B,Hs,Ws,3] and labels [B,Hs,Ws] (got %s, %s)"
+                         % (tuple(frames.shape), None if labels is None else tuple(labels.shape)))
+    B, Hs, Ws, _ = frames.shape
+    H, W = int(img_size[0]), int(img_size[1])
+    if (labels is not None and tuple(labels.shape) != (B, Hs, Ws)) or B < 1 or Hs < 1 or Ws < 1 or H < 1 or W < 1:
+        raise ValueError("resize_u8: labels %s do not match frames %s (or an empty size)"
+                         % (None if labels is None else tuple(labels.shape), tuple(frames.shape)))
+    if (H == Hs) != (W == Ws):
+        raise ValueError("resize_u8: %d x %d -> %d x %d keeps exactly one axis: the reference skips the resize of such a frame altogether "
+                         "(dataset.py:118-121 tests `h != Hs and w != Ws`) and feeds the network the wrong size; resize the frames first"
+                         % (Hs, Ws, H, W))
+    if frames.device.type != "cuda" or (labels is not None and labels.device != frames.device):
+        raise L.RcvError("resize_u8 runs on the HIP device only (frames on %s, labels on %s)"
+                         % (frames.device, None if labels is None else labels.device))
+    if not (frames.is_contiguous() and (labels is None or labels.is_contiguous())):
+        raise ValueError("resize_u8: frames and labels must be contiguous (no hidden copy of a batch)")
+    dev = frames.device
+    fx, kx, fy, ky, lx, ly = _device_tables(Hs, Ws, H, W, dev)
+    out = torch.empty(B, H, W, 3, dtype=torch.uint8, device=dev)
+    lab_out = None if labels is None else torch.empty(B, H, W, dtype=label_dtype, device=dev)
+    h = L.handle(dev.index if dev.index is not None else torch.cuda.current_device())
+    L.check(L.load().rcv_resize_u8(h, frames.data_ptr(), None if labels is None else labels.data_ptr(),
+                                   0 if labels is None else labels.element_size(), B, Hs, Ws, H, W, fx.data_ptr(), kx, fy.data_ptr(), ky,
+                                   lx.data_ptr(), ly.data_ptr(), out.data_ptr(), None if lab_out is None else lab_out.data_ptr(),
+                                   0 if lab_out is None else lab_out.element_size(), torch.cuda.current_stream(dev).cuda_stream),
+            "rcv_resize_u8")
+    return out, lab_out
+
+
+def draw_jitter_rows(n, b=0.3, c=0.3, s=0.3, h=3.1415 / 6):
+    """The rows of ``draw_jitter(n)`` for a whole epoch in one call: bit for bit the same float32 [n,8] host tensor under the same
+    ``random`` / ``torch`` seeds, and both generators are left where ``draw_jitter(n)`` leaves them.  The draws are the same ones in
+    the same order on each generator (``torch.rand(n)`` is the ``n`` single draws of the CPU generator; the four ``random.uniform`` per
+    image); the rounding to float32 is one array conversion, not three tensor constructions per image.  cos / sin stay numpy's SCALAR
+    calls on the Python float, as in ``draw_jitter``: a vectorised call may take another code path of numpy and need not round alike."""
+    p = torch.rand(n) if n else torch.zeros(0)
+    u = random.uniform
+    d = np.array([(u(-b, b), u(1 - c, 1 + c), u(1 - s, 1 + s), u(-h, h)) for _ in range(n)], np.float64).reshape(n, 4)
+    hv = d[:, 3].tolist()
+    cos = np.array([np.cos(v) for v in hv], np.float64)
+    sin = np.array([np.sin(v) for v in hv], np.float64)
+    rows = np.zeros((n, 8), np.float32)
+    rows[:, 0] = (p > 0.5).numpy()
+    rows[:, 1], rows[:, 2] = d[:, 0], d[:, 1]
+    rows[:, 3] = rows[:, 6] = d[:, 2] * cos
+    rows[:, 4], rows[:, 5] = -sin, sin
+    rows[:, 7] = 0.0 if (s > 0 and h > 0) else 1.0
+    return torch.from_numpy(rows)
 
 
 def draw_jitter(B, b=0.3, c=0.3, s=0.3, h=3.1415 / 6):
@@ -443,3 +556,162 @@ class SSDataSet:
         with Image.open(osp.join(self.lab_dir, self.labels[index])) as im:
             label = np.asarray(im.convert("I"), dtype=np.int32)
         return np.ascontiguousarray(frame), np.ascontiguousarray(label)
+
+
+class ResidentDataset:
+    """A whole dataset as resized bytes on the device: ``frames`` uint8 [N,H,W,3] and ``labels`` [N,H,W], made once.
+
+    ``dataset[i]`` gives ``(uint8 [Hs,Ws,3], integer [Hs,Ws])`` arrays (``SSYUVDataset``; any sequence of such pairs).  Every item is
+    decoded once on the host (at most 16 threads), uploaded in chunks of ``chunk`` items and resized there with ``resize_u8``; a chunk is
+    cut where the source size changes, so mixed source sizes are allowed (a frame that keeps exactly one axis raises, as
+    ``prepare_batch`` does).  Labels are kept as uint8 when every decoded value is in 0..255 -- checked on the host array of every chunk
+    -- and as int32 otherwise.
+
+    Pinned: the stored bytes are Pillow's, byte for byte, so ``prepare_batch(store.frames, store.labels, img_size, index=...)`` is bit
+    for bit ``prepare_batch`` of the full-size frames gathered by the same indices.  ``bad_index`` (int32 [1] on the device) counts the
+    images a batch asked for outside [0, N); ``check()`` reads it."""
+
+    MAX_THREADS = 16
+
+    def __init__(self, dataset, img_size=(120, 160), device="cuda", chunk=64):
+        from concurrent.futures import ThreadPoolExecutor
+        self._start(img_size, device, chunk)
+        n = len(dataset)
+        with ThreadPoolExecutor(max_workers=max(1, min(self.MAX_THREADS, os.cpu_count() or 1))) as pool:
+            for a in range(0, n, self.chunk):
+                items = list(pool.map(dataset.__getitem__, range(a, min(n, a + self.chunk))))
+                k = 0
+                while k < len(items):          # runs of one source size
+                    e = k + 1
+                    while e < len(items) and np.shape(items[e][0]) == np.shape(items[k][0]):
+                        e += 1
+                    fr = np.stack([np.asarray(it[0], np.uint8) for it in items[k:e]])
+                    lb = np.stack([np.asarray(it[1]) for it in items[k:e]])
+                    small = lb.size == 0 or (int(lb.min()) >= 0 and int(lb.max()) <= 255)
+                    lb = lb.astype(np.uint8 if small else np.int32, copy=False)
+                    self._add(torch.from_numpy(fr), torch.from_numpy(lb), small)
+                    k = e
+        self._finish()
+
+    @classmethod
+    def from_tensors(cls, frames, labels, img_size=(120, 160), device=None, chunk=64):
+        """The same store from tensors already in memory: ``frames`` uint8 [N,Hs,Ws,3] and ``labels`` uint8 or int32 [N,Hs,Ws], on the
+        host or on the device (``device`` defaults to theirs if they are on one, else to "cuda")."""
+        if not (torch.is_tensor(frames) and torch.is_tensor(labels)) or frames.dim() != 4 or labels.dim() != 3 \
+                or frames.shape[:3] != labels.shape:
+            raise ValueError("ResidentDataset.from_tensors: frames must be a [N,Hs,Ws,3] tensor and labels [N,Hs,Ws]")
+        self = cls.__new__(cls)
+        self._start(img_size, device if device is not None else (frames.device if frames.device.type == "cuda" else "cuda"), chunk)
+        small = labels.dtype == torch.uint8 or labels.numel() == 0 or (int(labels.min()) >= 0 and int(labels.max()) <= 255)
+        for a in range(0, frames.shape[0], self.chunk):
+            self._add(frames[a:a + self.chunk], labels[a:a + self.chunk], small)
+        self._finish()
+        return self
+
+    def _start(self, img_size, device, chunk):
+        self.img_size = (int(img_size[0]), int(img_size[1]))
+        self.device = torch.device(device)
+        if self.device.type == "cuda" and self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.chunk = max(1, int(chunk))
+        self._parts = []
+
+    def _add(self, frames, labels, small):
+        f = frames.to(self.device).contiguous()
+        lab = labels.to(self.device).contiguous()
+        self._parts.append(resize_u8(f, lab, self.img_size, label_dtype=torch.uint8 if small else torch.int32))
+
+    def _finish(self):
+        if not self._parts:
+            raise ValueError("ResidentDataset: the dataset is empty")
+        wide = any(p[1].dtype == torch.int32 for p in self._parts)
+        self.frames = torch.cat([p[0] for p in self._parts]).contiguous()
+        self.labels = torch.cat([p[1].to(torch.int32) if wide else p[1] for p in self._parts]).contiguous()
+        self.bad_index = torch.zeros(1, dtype=torch.int32, device=self.device)
+        del self._parts
+
+    def __len__(self):
+        return int(self.frames.shape[0])
+
+    def check(self):
+        """Reads the bad-index counter (this synchronises: call it once an epoch, not once a batch) and raises if a batch asked for an
+        image outside the store; the counter is cleared so the next epoch starts clean."""
+        bad = int(self.bad_index.item())
+        if bad:
+            self.bad_index.zero_()
+            raise IndexError("ResidentDataset: %d images were asked for outside [0, %d): they came back as zeros with targets 0" % (bad, len(self)))
+
+
+class EpochLoader:
+    """One epoch of training (or validation) batches per ``iter()`` from a ``ResidentDataset``, with no host tensor work and no
+    synchronisation per batch: the epoch's permutation (``torch.randperm(N, generator=generator)`` on the host, or ``arange`` without
+    ``shuffle``) and, with ``train``, its ``draw_jitter_rows`` are uploaded once from pinned memory, and every ``next()`` is one
+    ``prepare_batch(store.frames, store.labels, index=perm_dev[a:b], params=rows_dev[a:b])``.
+
+    The project's own definition (the order of the reference's multi-worker ``DataLoader`` cannot be reproduced by any single process):
+    rank ``rank`` of ``world`` takes ``perm[rank::world]``, and row ``i`` of its draws belongs to the ``i``-th sample it visits -- the
+    order a single-process reference loader draws in.  Pinned: every batch, bit for bit, to ``prepare_batch`` of the full-size frames
+    gathered by the same indices with the same rows.  ``last_index`` / ``last_rows`` keep the host copies of the running epoch.
+    ``len()`` is ``DataLoader``'s: ``ceil(n / batch_size)``, ``floor`` with ``drop_last``, ``n`` = this rank's share.
+
+    An epoch's host work (for 4096 samples about 4 ms, nearly all of it the draws) is done when its first batch is asked for; after a
+    synchronisation at the end of the epoch before (``check()``, reading metrics) the device waits for it with nothing queued.
+    ``prefetch=True`` does that work for the NEXT epoch when an epoch has been iterated to its end, while the device still runs the
+    steps just enqueued: the same draws from the same generators in the same order, only earlier -- so one epoch's worth is drawn
+    after the last epoch and never used, and anything else that draws from ``random`` / ``torch`` / ``generator`` between two epochs
+    now draws after them.  Off by default for that reason."""
+
+    def __init__(self, resident, batch_size, train=True, shuffle=True, finetune=False, no_ball=False, no_robot=False, no_goal=False,
+                 no_line=False, jitter=(0.3, 0.3, 0.3, 3.1415 / 6), generator=None, drop_last=False, rank=0, world=1, prefetch=False):
+        if int(batch_size) < 1 or int(world) < 1 or not 0 <= int(rank) < int(world):
+            raise ValueError("EpochLoader: batch_size %r, rank %r of world %r" % (batch_size, rank, world))
+        self.resident = resident
+        self.batch_size = int(batch_size)
+        self.train, self.shuffle, self.finetune = bool(train), bool(shuffle), bool(finetune)
+        self.flags = dict(no_ball=no_ball, no_robot=no_robot, no_goal=no_goal, no_line=no_line)
+        self.jitter = tuple(jitter)
+        self.generator = generator
+        self.drop_last = bool(drop_last)
+        self.rank, self.world = int(rank), int(world)
+        self.prefetch = bool(prefetch)
+        self.last_index = self.last_rows = self._next = None
+
+    def _share_len(self, n):
+        return len(range(self.rank, n, self.world))
+
+    def __len__(self):
+        n = self._share_len(len(self.resident))
+        return n // self.batch_size if self.drop_last else -(-n // self.batch_size)
+
+    def share(self, epoch_perm):
+        """This rank's part of an epoch's permutation, in the order it is visited."""
+        return epoch_perm[self.rank::self.world]
+
+    def plan(self, epoch_perm):
+        """Host only: the ``(a, b)`` slices of ``share(epoch_perm)`` (and of the epoch's rows) that make the batches, in order."""
+        n, bs = self._share_len(len(epoch_perm)), self.batch_size
+        return [(a, min(n, a + bs)) for a in range(0, n, bs) if not self.drop_last or a + bs <= n]
+
+    def _draw_epoch(self):
+        """The host work of one epoch: permutation, share, draws, slices, and the two uploads from pinned memory."""
+        res = self.resident
+        n = len(res)
+        perm = torch.randperm(n, generator=self.generator) if self.shuffle else torch.arange(n)
+        index = self.share(perm).contiguous()
+        rows = draw_jitter_rows(int(index.shape[0]), *self.jitter) if self.train else None
+        slices = self.plan(perm)
+        index_dev = rows_dev = None
+        if slices:
+            index_dev = index.pin_memory().to(res.device, non_blocking=True)
+            rows_dev = rows.pin_memory().to(res.device, non_blocking=True) if self.train else None
+        return index, rows, slices, index_dev, rows_dev
+
+    def __iter__(self):
+        res = self.resident
+        epoch, self._next = self._next if self._next is not None else self._draw_epoch(), None
+        self.last_index, self.last_rows, slices, index_dev, rows_dev = epoch
+        for a, b in slices:
+            yield prepare_batch(res.frames, res.labels, res.img_size, finetune=self.finetune, train=self.train,
+                                params=rows_dev[a:b] if self.train else None, index=index_dev[a:b], bad_index=res.bad_index, **self.flags)
+        if self.prefetch:          # the consumer has enqueued its last step and asks for more: the device is busy, the host is free
+            self._next = self._draw_epoch()
