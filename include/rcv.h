@@ -235,7 +235,7 @@ enum {
                              * p[X0] = labels [B][H][W].  H == Hs and W == Ws: a plain copy (or narrowing / widening) of both.  Same tiles and
                              * the same staged / through-the-cache choice as RCV_OP_BATCH_PREP.  No workspace.  Refused when planned: what
                              * RCV_OP_BATCH_PREP refuses, and a label width out other than 1 or 4                                       */
-  RCV_OP_BATCH_PREP_IDX = 52 /* RCV_OP_BATCH_PREP whose image b is store[index[b]] (rcv_batch_prep_indexed): the slots of that record, and
+  RCV_OP_BATCH_PREP_IDX = 52,/* RCV_OP_BATCH_PREP whose image b is store[index[b]] (rcv_batch_prep_indexed): the slots of that record, and
                              * i[COUNT] = N images in the store p[IN] = frames uint8[N][Hs][Ws][3] / p[IN2] = labels [N][Hs][Ws], p[IN_AUX] =
                              * index [B] in DEVICE memory, i[INMODE] = its element bytes (4 = int32, 8 = int64), p[EPI_AUX] = int32 counter in
                              * device memory.  i[N] = B = rows of the index, of p[IN_C], of p[OUT] and of p[X0].  Bit for bit the outputs of
@@ -244,6 +244,28 @@ enum {
                              * the counter is incremented once (an atomic add; the caller zeroes it and reads it when it likes) -- nothing
                              * is read out of bounds, nothing synchronises.  Refused when planned: what RCV_OP_BATCH_PREP refuses (the pixel
                              * limit counts the store), N < 1, an index element size other than 4 or 8, a null index or counter          */
+  RCV_OP_RGB_PREP_IDX = 53,  /* RCV_OP_RGB_PREP whose image b is store[index[b]] (rcv_rgb_prep_indexed; csrc/rgb_prep.hip; the loader of
+                             * trainer.py:75-123 fed from a resident store): the slots of that record, and i[STRIDE] = N images in the store
+                             * (i[COUNT] stays that record's statistics switch) p[IN] = frames uint8[N][Hs][Ws][3] / p[IN2] = labels
+                             * [N][Hs][Ws], p[IN_AUX] = index [B] in DEVICE memory, i[INMODE] = its element bytes (4 = int32, 8 = int64),
+                             * p[EPI_AUX] = int32 counter in device memory.  i[N] = B = rows of the index, of p[IN_C], of p[OUT], of p[X0] and
+                             * of the partial sums (i[NPART] = B x workgroups per image, as RCV_OP_RGB_PREP).  Bit for bit the outputs of
+                             * RCV_OP_RGB_PREP on the gathered images, in both kernel forms and both launches.  An index outside [0, N) is
+                             * tested before it forms an address, in both launches: the statistics launch writes a 0 partial, the main
+                             * launch writes that image as zeros with targets 0 and increments the counter once (an atomic add) -- nothing
+                             * is read out of bounds, nothing synchronises.  Refused when planned: what RCV_OP_RGB_PREP refuses (the pixel
+                             * limit counts the store), N < 1, an index element size other than 4 or 8, a null index or counter          */
+  RCV_OP_LP_PAIR_PREP = 54   /* LabelProp's input straight from a resident store (rcv_lp_pair_prep; csrc/rgb_prep.hip): per pair the loader of
+                             * labelPropTrain.py:36-66 on both frames and the assembly of labelPropTrain.py:162-193, i.e. RCV_OP_LP_BATCH of
+                             * RCV_OP_RGB_PREP_IDX with ONE parameter row per pair, Y only.  i[N] = B pairs, i[H] / i[W] = size of the store's
+                             * images, i[HO] / i[WO] = the network's size (must equal i[H] / i[W]: only the no-resize form is built),
+                             * i[COUT] = classes (5), i[STRIDE] = N images in the store, i[INMODE2] = label element bytes (1 / 4), i[INMODE] =
+                             * element bytes of the pairs (4 / 8), i[AUX0] = train, i[COUNT] = statistics switch as RCV_OP_RGB_PREP; p[IN] =
+                             * frames uint8[N][H][W][3], p[IN2] = labels [N][H][W], p[IN_AUX] = pairs [B][2] in DEVICE memory (store indices
+                             * of frame a, frame b), p[EPI_AUX] = int32 counter, p[IN_C] = parameter rows float[B][12] (train only), p[OUT] =
+                             * inputs float[2B][H][W][8] (NHWC, 16-byte aligned), p[X0] = targets int64[2B][H][W], p[PART] =
+                             * uint32[i[NPART]], i[NPART] = 2B x workgroups per frame (0 unless train and i[COUNT]).  A pair with either
+                             * index outside [0, N): both samples zeros, targets 0, counted once                                       */
 };
 
 /* i[RCV_I_AUX0] of RCV_OP_PRUNE: how the threshold of a tensor is chosen */
@@ -638,6 +660,32 @@ int rcv_rgb_prep(rcv_handle* h, const uint8_t* frames, const void* labels /*may 
                  const int32_t* frame_x, int kx, const int32_t* frame_y, int ky, const int32_t* label_x, const int32_t* label_y,
                  const float* params /*NULL unless train*/, int train, int stats, int mask_flags, float* imgs, int64_t* targets,
                  void* workspace, size_t workspace_bytes, void* stream);
+
+/* RCV_OP_RGB_PREP_IDX: rcv_rgb_prep whose image b is image index[b] of a store of N images (trainer.py:75-123's loader, the store being
+ * what Scale leaves: its first transform ends in a uint8 and everything random comes after it).  index is int32[B] (index_bytes 4) or
+ * int64[B] (8) in device memory; params, imgs, targets and the partial sums have B rows; every other argument is rcv_rgb_prep's.  imgs
+ * and targets are bit for bit those of rcv_rgb_prep on the gathered images.  An index outside [0, N) reads nothing, in either launch:
+ * its image is zeros, its targets 0, and *bad_count (int32, device memory, zeroed by the caller) is incremented once per such image. */
+int rcv_rgb_prep_indexed(rcv_handle* h, const uint8_t* frames, const void* labels /*may be NULL*/, int label_bytes, int N, const void* index,
+                         int index_bytes, int B, int Hs, int Ws, int H, int W, const int32_t* frame_x, int kx, const int32_t* frame_y, int ky,
+                         const int32_t* label_x, const int32_t* label_y, const float* params /*NULL unless train*/, int train, int stats,
+                         int mask_flags, float* imgs, int64_t* targets, int32_t* bad_count, void* workspace, size_t workspace_bytes,
+                         void* stream);
+
+/* RCV_OP_LP_PAIR_PREP: LabelProp's input from a store of N frames at the network's size (frames uint8[N][H][W][3], labels [N][H][W] of
+ * label_bytes 1 or 4): the loader of labelPropTrain.py:36-66 for both frames of every pair and the assembly of labelPropTrain.py:162-193
+ * in one op.  pairs is int32 / int64 [B][2] in device memory (store indices of frame a and frame b), params float[B][12]: ONE
+ * rcv_rgb_prep row per pair.  Both frames and both label planes of pair p take steps 2-4 of rcv_rgb_prep with row p (the same mirrors
+ * for all four planes, the same colour operations on both frames, the contrast mean of EACH FRAME ON ITS OWN), no maskLabel; only Y is
+ * computed (step 3's fp64 arithmetic, rounded once to fp32).  Then rcv_labelprop_batch: inputs float[2B][H][W][8] (NHWC), sample 2p =
+ * {Ya, Yb, Ya - Yb, labelToPred(label_b)}, sample 2p + 1 = {Yb, Ya, Yb - Ya, labelToPred(label_a)}, one fp32 subtraction of the rounded
+ * values; a label outside [0, 5) gives -1 in all five class channels; targets int64[2B][H][W] = label_a, label_b.  Bit for bit
+ * rcv_labelprop_batch of rcv_rgb_prep of the gathered frames with every row repeated.  num_class must be 5; Hs x Ws must equal H x W
+ * (a store at another size is refused when planned).  A pair with either index outside [0, N): both samples zeros, targets 0,
+ * *bad_count incremented once.  With train and stats two launches (statistics over the 2B frames, then the main one), else one.   */
+int rcv_lp_pair_prep(rcv_handle* h, const uint8_t* frames, const void* labels, int label_bytes, int N, const void* pairs, int pair_bytes, int B,
+                     int Hs, int Ws, int H, int W, int num_class, const float* params /*NULL unless train*/, int train, int stats,
+                     float* inputs, int64_t* targets, int32_t* bad_count, void* workspace, size_t workspace_bytes, void* stream);
 
 /* RCV_OP_CLS_LABEL, source form 0 without the fused decoder input: labels uint8[N][H][W] = first arg-max over c of
  * (bias[c] + sum_k x[p][k] w[c][k]) (detect.py:131-132), colour uint8[N][H][W][3] = palette[label] (detect.py:133 Colorize) or NULL;

@@ -24,6 +24,10 @@ def __getattr__(name):
     if name in ("resize_u8", "draw_jitter_rows", "ResidentDataset", "EpochLoader"):
         from . import data
         return getattr(data, name)
+    # ... the RGB loader's epochs and LabelProp's frame pairs from the same store: RGBEpochLoader / LPDataSet / LPEpochLoader
+    if name in ("prepare_lp_pairs", "draw_color_jitter_rows", "RGBEpochLoader", "LPDataSet", "LPEpochLoader"):
+        from . import data
+        return getattr(data, name)
     # class maps and colour masks on the device (detect.py): palette.py, infer.py
     if name in ("colorize", "Colorize", "labelcolormap"):
         from . import palette

@@ -35,6 +35,8 @@ OP_FARNEBACK, OP_REMAP_LABELS = 48, 49      # dense optical flow and the label r
 OP_OBJECT_PATCHES = 50      # the boxes of OP_OBJECTS cut out of the frames -> 32x32 YUV patches (rcv.h RCV_OP_OBJECT_PATCHES, csrc/patches.hip)
 OP_RESIZE_U8 = 51           # OP_BATCH_PREP's resize stage alone: uint8 NHWC bytes and unmasked labels, what a resident dataset keeps (rcv.h RCV_OP_RESIZE_U8)
 OP_BATCH_PREP_IDX = 52      # OP_BATCH_PREP whose image b is store[index[b]], the index in device memory (rcv.h RCV_OP_BATCH_PREP_IDX)
+OP_RGB_PREP_IDX = 53        # OP_RGB_PREP whose image b is store[index[b]]: trainer.py:75-123's loader from a resident store (rcv.h RCV_OP_RGB_PREP_IDX)
+OP_LP_PAIR_PREP = 54        # both frames of a LabelProp pair from the store -> the 8-channel input of labelPropTrain.py:36-66, 162-193 (rcv.h RCV_OP_LP_PAIR_PREP)
 PRUNE_MAX_RATIO, PRUNE_STD_SEARCH, PRUNE_SMALLEST_K = range(3)      # i[AUX0] of OP_PRUNE: pruneModelNew / pruneModel / pruneModel2
 PRUNE_MAX_ITER = 4096
 PRUNE_ST_OK, PRUNE_ST_NO_END, PRUNE_ST_ALL_ZERO, PRUNE_ST_BAD_JOB = range(4)
@@ -80,6 +82,7 @@ EXPORTS = [
     "rcv_bnn_stage_fwd", "rcv_bnn_stage_bwd", "rcv_bnn_head_fwd", "rcv_bnn_head_bwd",
     "rcv_sgd_step_pruned", "rcv_prune_check", "rcv_prune", "rcv_find_objects", "rcv_rgb_prep",
     "rcv_farneback_flow", "rcv_update_labels", "rcv_object_patches", "rcv_resize_u8", "rcv_batch_prep_indexed",
+    "rcv_rgb_prep_indexed", "rcv_lp_pair_prep",
 ]
 
 
@@ -138,6 +141,10 @@ def load():
             [C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_int, C.c_int] + [C.c_void_p] * 4
         lib.rcv_rgb_prep.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p, C.c_int, C.c_void_p, C.c_int] + \
             [C.c_void_p] * 3 + [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+        lib.rcv_rgb_prep_indexed.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p] + [C.c_int] * 6 + \
+            [C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 3 + [C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 4 + [C.c_size_t, C.c_void_p]
+        lib.rcv_lp_pair_prep.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p] + [C.c_int] * 7 + \
+            [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4 + [C.c_size_t, C.c_void_p]
         lib.rcv_cls_label.argtypes = [C.c_void_p] * 4 + [C.c_int] * 5 + [C.c_void_p] * 4
         lib.rcv_colorize.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 3
         lib.rcv_sgd_step.argtypes = [C.c_void_p] * 5 + [C.c_int64, C.c_float, C.c_float, C.c_float, C.c_int, C.c_float, C.c_void_p]

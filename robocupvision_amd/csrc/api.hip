@@ -119,7 +119,10 @@ static int dispatch(const rcv_handle* h, const rcv_op* op, hipStream_t s, OpQuer
     case RCV_OP_BATCH_PREP_IDX:
       return rcv_launch_batch_prep(h, op, s, q);
     case RCV_OP_RGB_PREP:
+    case RCV_OP_RGB_PREP_IDX:
       return rcv_launch_rgb_prep(h, op, s, q);
+    case RCV_OP_LP_PAIR_PREP:
+      return rcv_launch_lp_pair_prep(h, op, s, q);
     case RCV_OP_CLS_LABEL:
       return rcv_launch_cls_label(h, op, s, q);
     case RCV_OP_BNN_STAGE_FWD:
@@ -530,6 +533,44 @@ int rcv_rgb_prep(rcv_handle* h, const uint8_t* frames, const void* labels, int l
   const int rc = rcv_op_workspace(h, &op, &need);
   if (rc) return rc;
   RCV_CHECK_ARG(workspace_bytes >= need, "rcv_rgb_prep: workspace of %zu bytes given, %zu needed (rcv_op_workspace)", workspace_bytes, need);
+  return rcv_run(h, &op, 1, stream);
+}
+
+int rcv_rgb_prep_indexed(rcv_handle* h, const uint8_t* frames, const void* labels, int label_bytes, int N, const void* index, int index_bytes,
+                         int B, int Hs, int Ws, int H, int W, const int32_t* frame_x, int kx, const int32_t* frame_y, int ky,
+                         const int32_t* label_x, const int32_t* label_y, const float* params, int train, int stats, int mask_flags,
+                         float* imgs, int64_t* targets, int32_t* bad_count, void* workspace, size_t workspace_bytes, void* stream) {
+  rcv_op op;
+  memset(&op, 0, sizeof(op));
+  op.kind = RCV_OP_RGB_PREP_IDX;
+  op.i[RCV_I_N] = B; op.i[RCV_I_H] = Hs; op.i[RCV_I_W] = Ws; op.i[RCV_I_HO] = H; op.i[RCV_I_WO] = W; op.i[RCV_I_CIN] = kx; op.i[RCV_I_COUT] = ky;
+  op.i[RCV_I_INMODE2] = labels ? label_bytes : 0; op.i[RCV_I_AUX0] = train; op.i[RCV_I_AUX1] = mask_flags; op.i[RCV_I_COUNT] = stats;
+  op.i[RCV_I_STRIDE] = N; op.i[RCV_I_INMODE] = index_bytes;
+  op.p[RCV_P_IN] = (void*)frames; op.p[RCV_P_IN2] = (void*)labels; op.p[RCV_P_OUT] = imgs; op.p[RCV_P_X0] = targets;
+  op.p[RCV_P_X1] = (void*)frame_x; op.p[RCV_P_X2] = (void*)frame_y; op.p[RCV_P_X3] = (void*)label_x; op.p[RCV_P_X4] = (void*)label_y;
+  op.p[RCV_P_IN_C] = (void*)params; op.p[RCV_P_PART] = workspace; op.p[RCV_P_IN_AUX] = (void*)index; op.p[RCV_P_EPI_AUX] = bad_count;
+  size_t need = 0;
+  const int rc = rcv_op_workspace(h, &op, &need);
+  if (rc) return rc;
+  RCV_CHECK_ARG(workspace_bytes >= need, "rcv_rgb_prep_indexed: workspace of %zu bytes given, %zu needed (rcv_op_workspace)", workspace_bytes,
+                need);
+  return rcv_run(h, &op, 1, stream);
+}
+
+int rcv_lp_pair_prep(rcv_handle* h, const uint8_t* frames, const void* labels, int label_bytes, int N, const void* pairs, int pair_bytes, int B,
+                     int Hs, int Ws, int H, int W, int num_class, const float* params, int train, int stats, float* inputs, int64_t* targets,
+                     int32_t* bad_count, void* workspace, size_t workspace_bytes, void* stream) {
+  rcv_op op;
+  memset(&op, 0, sizeof(op));
+  op.kind = RCV_OP_LP_PAIR_PREP;
+  op.i[RCV_I_N] = B; op.i[RCV_I_H] = Hs; op.i[RCV_I_W] = Ws; op.i[RCV_I_HO] = H; op.i[RCV_I_WO] = W; op.i[RCV_I_COUT] = num_class;
+  op.i[RCV_I_INMODE2] = label_bytes; op.i[RCV_I_AUX0] = train; op.i[RCV_I_COUNT] = stats; op.i[RCV_I_STRIDE] = N; op.i[RCV_I_INMODE] = pair_bytes;
+  op.p[RCV_P_IN] = (void*)frames; op.p[RCV_P_IN2] = (void*)labels; op.p[RCV_P_OUT] = inputs; op.p[RCV_P_X0] = targets;
+  op.p[RCV_P_IN_C] = (void*)params; op.p[RCV_P_PART] = workspace; op.p[RCV_P_IN_AUX] = (void*)pairs; op.p[RCV_P_EPI_AUX] = bad_count;
+  size_t need = 0;
+  const int rc = rcv_op_workspace(h, &op, &need);
+  if (rc) return rc;
+  RCV_CHECK_ARG(workspace_bytes >= need, "rcv_lp_pair_prep: workspace of %zu bytes given, %zu needed (rcv_op_workspace)", workspace_bytes, need);
   return rcv_run(h, &op, 1, stream);
 }
 

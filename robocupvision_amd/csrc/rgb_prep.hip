@@ -30,6 +30,12 @@
 // vertical pass reads it back; the plane stores are contiguous over the
 // lanes (reversed under a horizontal flip).  Every table entry is clamped where it is used.
 //
+// RCV_OP_RGB_PREP_IDX (rcv_rgb_prep_indexed) takes image b from store[index[b]]: the index is read from device memory and tested against
+// [0, N) before it forms an address, in both launches (a 0 partial; a zero image with zero targets, counted once).  The kernels are
+// instantiated with the index off for RCV_OP_RGB_PREP, as csrc/batch_prep.hip does.
+// RCV_OP_LP_PAIR_PREP (rcv_lp_pair_prep) is at the end of the file: both frames of a LabelProp pair through steps 2-5 with ONE row, Y only,
+// then the assembly of labelPropTrain.py:162-193, from a store that is already at the network's size.
+//
 // Roundings: this file is compiled with floating-point contraction off (the pragma below): every product that feeds a sum is rounded
 // on its own.  __fmul_rn and its kin would not do: the header defines them as the plain operators, which the compiler may fuse.
 #include "rcv_internal.h"
@@ -45,13 +51,19 @@
 #define RP_PREC 22
 #define RP_STAGE_MIN_TAPS 9              /* taps per output column from which the source rows are staged in LDS */
 #define RP_IDENT_PIX 2048                /* pixels of one image per workgroup where nothing is resized */
+#define RP_PAIR_PIX 512                  /* pixels of both frames of a pair per workgroup of lp_pair_prep_kernel */
 #define RP_NPAR 12                       /* floats of a parameter row */
 
 struct RpArgs {
   const uint8_t* frames; const void* labels; float* imgs; int64_t* tgt;
   const int32_t* xtab; const int32_t* ytab; const int32_t* lx; const int32_t* ly; const float* params; uint32_t* part;
   int B, Hs, Ws, H, W, kx, ky, lab_bytes, train, mask, rows_cap, tiles_x, tiles_y, stats, wpi;      // wpi: workgroups per image
+  // the indexed forms (behind everything the plain kernels read, whose argument offsets stay as they were)
+  int nsrc;                                 // images behind `frames` / `labels`: the N of the store
+  int idx_bytes; const void* index; int* bad;          // index [B] (pairs [B][2]) of 4 / 8 byte elements, counter of the refused ones
 };
+
+enum { RP_PLAIN = 0, RP_IDX = 1, RP_PAIR = 2 };          // the form a kernel is instantiated for
 
 __device__ __forceinline__ int rp_clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 __device__ __forceinline__ int rp_clip8(int acc) { return rp_clampi(acc >> RP_PREC, 0, 255); }
@@ -86,6 +98,20 @@ __device__ __forceinline__ RpRow rp_row(const RpArgs& a, int b) {
     for (int k = j.n_ops - 1; k >= 0; --k) if (((j.ops >> (4 * k)) & 15) == 1) j.cpos = k;
   }
   return j;
+}
+
+// RP_IDX / RP_PAIR: the store image of element e of the index, or -1 where it is outside [0, nsrc) (tested before it is used for anything)
+__device__ __forceinline__ int rp_source(const RpArgs& a, size_t e) {
+  const long long v = a.idx_bytes == 8 ? (long long)((const int64_t*)a.index)[e] : (long long)((const int32_t*)a.index)[e];
+  return v >= 0 && v < (long long)a.nsrc ? (int)v : -1;
+}
+
+// RP_IDX with a refused index: output pixel (x, y) of batch row b is zeros, its target 0
+__device__ __forceinline__ void rp_zero(const RpArgs& a, int b, int y, int x) {
+  const size_t plane = (size_t)a.H * a.W, o = (size_t)y * a.W + x;
+  float* img = a.imgs + (size_t)b * 3 * plane + o;
+  img[0] = 0.f; img[plane] = 0.f; img[2 * plane] = 0.f;
+  if (a.tgt) a.tgt[(size_t)b * plane + o] = 0;
 }
 
 __device__ __forceinline__ int rp_luma(int r, int g, int b) { return (19595 * r + 38470 * g + 7471 * b + 32768) >> 16; }
@@ -192,30 +218,39 @@ __device__ __forceinline__ int rp_mean(const RpArgs& a, const RpRow& j, int b, u
   return (int)((2ull * sum + n) / (2ull * n));
 }
 
-// steps 4 and 5 for one output pixel (x, y: coordinates before the mirrors) of image b from its bytes after step 3
-__device__ __forceinline__ void rp_finish(const RpArgs& a, const RpRow& j, const double* s_c, int b, int y, int x, int r, int g, int bl) {
-  const double cr = s_c[r], cg = s_c[g], cb = s_c[bl];
+// the Y of step 4 before Normalize, from c = byte / 255.0 of the three bytes
+__device__ __forceinline__ double rp_y(double cr, double cg, double cb) {
   const double y0 = cr * 0.299, y1 = cg * 0.587, y2 = cb * 0.114;
+  return (y0 + y1) + y2;
+}
+
+// Normalize([.5], [.5]) of Y, rounded once to fp32
+__device__ __forceinline__ float rp_ynorm(double yy) { return (float)((yy - 0.5) / 0.5); }
+
+// steps 4 and 5 for one output pixel (x, y: coordinates before the mirrors) of batch row b (image src of `labels`) from its bytes after step 3
+__device__ __forceinline__ void rp_finish(const RpArgs& a, const RpRow& j, const double* s_c, int b, int src, int y, int x, int r, int g, int bl) {
+  const double cr = s_c[r], cg = s_c[g], cb = s_c[bl];
+  const double yy = rp_y(cr, cg, cb);
   const double u0 = cr * -0.14714119, u1 = cg * -0.28886916, u2 = cb * 0.43601035;
   const double v0 = cr * 0.61497538, v1 = cg * -0.51496512, v2 = cb * -0.10001026;
-  const double yy = (y0 + y1) + y2, uu = (u0 + u1) + u2, vv = (v0 + v1) + v2;
+  const double uu = (u0 + u1) + u2, vv = (v0 + v1) + v2;
   const int xo = j.hflip ? a.W - 1 - x : x, yo = j.vflip ? a.H - 1 - y : y;
   const size_t plane = (size_t)a.H * a.W, o = (size_t)yo * a.W + xo;
   float* img = a.imgs + (size_t)b * 3 * plane + o;
-  img[0] = (float)((yy - 0.5) / 0.5); img[plane] = (float)(uu / 0.5); img[2 * plane] = (float)(vv / 0.5);
+  img[0] = rp_ynorm(yy); img[plane] = (float)(uu / 0.5); img[2 * plane] = (float)(vv / 0.5);
   if (!a.tgt) return;                      // the patch chain: no label plane (uniform over the launch)
   const int sy = rp_clampi(a.ly[y], 0, a.Hs - 1), sx = rp_clampi(a.lx[x], 0, a.Ws - 1);
-  const size_t li = ((size_t)b * a.Hs + sy) * a.Ws + sx;
+  const size_t li = ((size_t)src * a.Hs + sy) * a.Ws + sx;
   const int lv = a.lab_bytes == 1 ? (int)((const uint8_t*)a.labels)[li] : ((const int32_t*)a.labels)[li];
   a.tgt[(size_t)b * plane + o] = (int64_t)rp_mask(lv, a.mask);
 }
 
 struct RpTile { int x0, y0, tw, th, ys0, nrows; };
 
-// the tile's tables to LDS and the horizontal pass of the source rows under it: s_h[r][x][c].  STAGE (as csrc/batch_prep.hip, from 9
+// the tile's tables to LDS and the horizontal pass of the source rows of image b of `frames` under it: s_h[r][x][c].  STAGE (as csrc/batch_prep.hip, from 9
 // taps per column): the source-row segments of the tile are first copied to LDS with 16-byte aligned loads, RP_RC rows at a time, and
 // the taps read LDS bytes; otherwise the taps read global bytes through the cache.
-template <bool STAGE>
+template <bool STAGE, int FORM>
 __device__ __forceinline__ RpTile rp_horizontal(const RpArgs& a, int b, int tile, int32_t* s_xc, int32_t* s_yc, uint8_t* s_h, uint8_t* s_src) {
   const int tid = threadIdx.x;
   const int tx = tile % a.tiles_x, ty = tile / a.tiles_x;
@@ -256,7 +291,7 @@ __device__ __forceinline__ RpTile rp_horizontal(const RpArgs& a, int b, int tile
     const int nvmax = (seg + 15 + 15) / 16;
     const int rel = rp_clampi(xf - xs0, 0, segpix - 1);
     const int xns = min(xn, segpix - rel);
-    const uintptr_t lo = (uintptr_t)a.frames, hi = lo + (size_t)a.B * a.Hs * a.Ws * 3;
+    const uintptr_t lo = (uintptr_t)a.frames, hi = lo + (size_t)(FORM == RP_IDX ? a.nsrc : a.B) * a.Hs * a.Ws * 3;
     for (int r0 = 0; r0 < t.nrows; r0 += RP_RC) {
       const int nr = min(RP_RC, t.nrows - r0);
       for (int i = tid; i < nr * nvmax; i += 256) {
@@ -313,8 +348,8 @@ __device__ __forceinline__ void rp_vertical(const RpArgs& a, const RpTile& t, co
 }
 
 // STATS: the statistics launch (one partial sum of L per workgroup); otherwise the main launch.  STAGE: see rp_horizontal.
-// Grid: B * tiles_x * tiles_y.
-template <bool STATS, bool STAGE>
+// FORM: RP_PLAIN, or RP_IDX (image b is store[index[b]]).  Grid: B * tiles_x * tiles_y.
+template <bool STATS, bool STAGE, int FORM>
 __global__ __launch_bounds__(256) void rgb_prep_kernel(RpArgs a) {
   __shared__ double s_c[256];
   __shared__ unsigned long long s_red[256];
@@ -324,6 +359,22 @@ __global__ __launch_bounds__(256) void rgb_prep_kernel(RpArgs a) {
   __shared__ __align__(16) uint8_t s_src[STAGE ? RP_RC * RP_SEG : 16];
   const int tid = threadIdx.x;
   const int b = blockIdx.x / a.wpi, tile = blockIdx.x % a.wpi;
+  int src = b;
+  if (FORM == RP_IDX) {
+    src = rp_source(a, (size_t)b);
+    if (src < 0) {                               // (the same for the whole workgroup, and in front of every barrier)
+      if (STATS) {
+        if (tid == 0) a.part[blockIdx.x] = 0u;
+        return;
+      }
+      const int x0 = (tile % a.tiles_x) * RP_TC, y0 = (tile / a.tiles_x) * RP_TR;
+      const int tw = min(RP_TC, a.W - x0), th = min(RP_TR, a.H - y0);
+      for (int idx = tid; idx < th * RP_TC; idx += 256)
+        if ((idx & (RP_TC - 1)) < tw) rp_zero(a, b, y0 + (idx >> 6), x0 + (idx & (RP_TC - 1)));
+      if (tile == 0 && tid == 0) atomicAdd(a.bad, 1);
+      return;
+    }
+  }
   const RpRow j = rp_row(a, b);
   if (STATS && j.cpos < 0) {                     // no contrast in this image: nobody reads its partials
     if (tid == 0) a.part[blockIdx.x] = 0u;
@@ -334,7 +385,7 @@ __global__ __launch_bounds__(256) void rgb_prep_kernel(RpArgs a) {
     s_c[tid] = (double)tid / 255.0;
     m = rp_mean(a, j, b, s_red);
   }
-  const RpTile t = rp_horizontal<STAGE>(a, b, tile, s_xc, s_yc, s_h, s_src);
+  const RpTile t = rp_horizontal<STAGE, FORM>(a, src, tile, s_xc, s_yc, s_h, s_src);
   const int x = tid & (RP_TC - 1);
   unsigned long long lsum = 0;
   for (int idx = tid; idx < t.th * RP_TC; idx += 256) {
@@ -347,7 +398,7 @@ __global__ __launch_bounds__(256) void rgb_prep_kernel(RpArgs a) {
       lsum += (unsigned long long)rp_luma(r, g, bl);
     } else {
       rp_ops(j, j.n_ops, m, r, g, bl);
-      rp_finish(a, j, s_c, b, t.y0 + yl, t.x0 + x, r, g, bl);
+      rp_finish(a, j, s_c, b, src, t.y0 + yl, t.x0 + x, r, g, bl);
     }
   }
   if (STATS) {
@@ -356,14 +407,31 @@ __global__ __launch_bounds__(256) void rgb_prep_kernel(RpArgs a) {
   }
 }
 
-// H == Hs and W == Ws: no resize (transform.py:15-16); one thread per pixel, RP_IDENT_PIX pixels of one image per workgroup
-template <bool STATS>
+// H == Hs and W == Ws: no resize (transform.py:15-16); one thread per pixel, RP_IDENT_PIX pixels of one image per workgroup.
+// FORM: RP_PLAIN, RP_IDX, or (STATS only) RP_PAIR: the statistics launch of RCV_OP_LP_PAIR_PREP -- image b is frame b & 1 of pair b >> 1,
+// its row is the pair's, and a pair with either index outside the store leaves 0 partials for both its frames.
+template <bool STATS, int FORM>
 __global__ __launch_bounds__(256) void rgb_prep_ident_kernel(RpArgs a) {
   __shared__ double s_c[256];
   __shared__ unsigned long long s_red[256];
   const int tid = threadIdx.x;
   const int b = blockIdx.x / a.wpi, blk = blockIdx.x % a.wpi;
-  const RpRow j = rp_row(a, b);
+  int src = b;
+  if (FORM != RP_PLAIN) {
+    src = rp_source(a, (size_t)b);
+    const bool bad = src < 0 || (FORM == RP_PAIR && rp_source(a, (size_t)(b ^ 1)) < 0);
+    if (bad) {                                   // (the same for the whole workgroup, and in front of every barrier)
+      if (STATS) {
+        if (tid == 0) a.part[blockIdx.x] = 0u;
+        return;
+      }
+      const int start = blk * RP_IDENT_PIX, end = start + min(RP_IDENT_PIX, a.H * a.W - start);
+      for (int p = start + tid; p < end; p += 256) rp_zero(a, b, p / a.W, p % a.W);
+      if (blk == 0 && tid == 0) atomicAdd(a.bad, 1);
+      return;
+    }
+  }
+  const RpRow j = rp_row(a, FORM == RP_PAIR ? b >> 1 : b);
   if (STATS && j.cpos < 0) {
     if (tid == 0) a.part[blockIdx.x] = 0u;
     return;
@@ -375,7 +443,7 @@ __global__ __launch_bounds__(256) void rgb_prep_ident_kernel(RpArgs a) {
     __syncthreads();
   }
   const int npix = a.H * a.W;
-  const uint8_t* fb = a.frames + (size_t)b * npix * 3;
+  const uint8_t* fb = a.frames + (size_t)src * npix * 3;
   const int start = blk * RP_IDENT_PIX, end = start + min(RP_IDENT_PIX, npix - start);
   unsigned long long lsum = 0;
   for (int p = start + tid; p < end; p += 256) {
@@ -387,7 +455,7 @@ __global__ __launch_bounds__(256) void rgb_prep_ident_kernel(RpArgs a) {
     } else {
       const int y = p / a.W, x = p - y * a.W;
       rp_ops(j, j.n_ops, m, r, g, bl);
-      rp_finish(a, j, s_c, b, y, x, r, g, bl);
+      rp_finish(a, j, s_c, b, src, y, x, r, g, bl);
     }
   }
   if (STATS) {
@@ -412,12 +480,19 @@ int rcv_launch_rgb_prep(const rcv_handle* h, const rcv_op* op, hipStream_t s, Op
   const int kx = op->i[RCV_I_CIN], ky = op->i[RCV_I_COUT], lab_bytes = op->i[RCV_I_INMODE2];
   const int train = op->i[RCV_I_AUX0], mask = op->i[RCV_I_AUX1], stats = op->i[RCV_I_COUNT];
   const bool with_labels = lab_bytes != 0;
+  // RCV_OP_RGB_PREP_IDX (rcv_rgb_prep_indexed): images picked from a store of i[STRIDE] images
+  const bool indexed = op->kind == RCV_OP_RGB_PREP_IDX;
+  const int nsrc = indexed ? op->i[RCV_I_STRIDE] : B;          // images behind p[IN] / p[IN2]
   if (query) {
     query->n_part = 0; query->n_split = 0; query->part_bytes = 0;
-    snprintf(query->label, sizeof(query->label), "rgb_prep");
+    snprintf(query->label, sizeof(query->label), indexed ? "rgb_prep_idx" : "rgb_prep");
   }
   RCV_CHECK_ARG(B >= 1 && H >= 1 && W >= 1 && Hs >= 1 && Ws >= 1, "rgb prep: B %d, source %d x %d, output %d x %d: every size must be >= 1", B, Hs, Ws,
                 H, W);
+  RCV_CHECK_ARG(nsrc >= 1, "rgb prep: a store of %d images (i[STRIDE]): there must be at least 1", nsrc);
+  if (indexed)
+    RCV_CHECK_ARG(op->i[RCV_I_INMODE] == 4 || op->i[RCV_I_INMODE] == 8, "rgb prep: index element size %d unsupported (4 = int32, 8 = int64)",
+                  op->i[RCV_I_INMODE]);
   RCV_CHECK_ARG((long long)Hs <= 8LL * H && (long long)Ws <= 8LL * W,
                 "rgb prep: %d x %d -> %d x %d shrinks an axis by more than 8 (the kernel is built for at most %d taps)", Hs, Ws, H, W, RP_MAXK);
   RCV_CHECK_ARG(lab_bytes == 0 || lab_bytes == 1 || lab_bytes == 4,
@@ -427,13 +502,15 @@ int rcv_launch_rgb_prep(const rcv_handle* h, const rcv_op* op, hipStream_t s, Op
   RCV_CHECK_ARG((train == 0 || train == 1) && mask >= 0 && mask <= 15 && (stats == 0 || stats == 1),
                 "rgb prep: train %d / maskLabel flags %d / statistics %d out of range", train, mask, stats);
   const int tiles_x = ceil_div(W, RP_TC), tiles_y = ceil_div(H, RP_TR);
-  RCV_CHECK_ARG((double)B * Hs * Ws < 2147483647.0 && (double)B * H * W < 2147483647.0 && (double)B * tiles_x * tiles_y < 2147483647.0,
-                "rgb prep: %d images of %d x %d -> %d x %d: more than 2^31 pixels", B, Hs, Ws, H, W);
+  RCV_CHECK_ARG((double)nsrc * Hs * Ws < 2147483647.0 && (double)B * H * W < 2147483647.0 && (double)B * tiles_x * tiles_y < 2147483647.0,
+                "rgb prep: %d images of %d x %d -> %d x %d: more than 2^31 pixels", nsrc > B ? nsrc : B, Hs, Ws, H, W);
   if (with_labels)
     RCV_CHECK_ARG(op->p[RCV_P_X1] && op->p[RCV_P_X2] && op->p[RCV_P_X3] && op->p[RCV_P_X4],
                   "rgb prep: null table (frame taps of x / y, label index of x / y)");
   else
     RCV_CHECK_ARG(op->p[RCV_P_X1] && op->p[RCV_P_X2], "rgb prep: null table (frame taps of x / y)");
+  // the index and its counter live for an epoch, as the tables do: a plan without them has nothing to gather by
+  if (indexed) RCV_CHECK_ARG(op->p[RCV_P_IN_AUX] && op->p[RCV_P_EPI_AUX], "rgb prep: null index or null bad-index counter");
   const bool ident = H == Hs && W == Ws;
   const int wpi = ident ? ceil_div(H * W, RP_IDENT_PIX) : tiles_x * tiles_y;
   RCV_CHECK_ARG((double)B * wpi < 2147483647.0, "rgb prep: grid too large");
@@ -457,10 +534,15 @@ int rcv_launch_rgb_prep(const rcv_handle* h, const rcv_op* op, hipStream_t s, Op
   a.params = train ? (const float*)op->p[RCV_P_IN_C] : nullptr; a.part = two ? (uint32_t*)op->p[RCV_P_PART] : nullptr;
   a.B = B; a.Hs = Hs; a.Ws = Ws; a.H = H; a.W = W; a.kx = kx; a.ky = ky; a.lab_bytes = with_labels ? lab_bytes : 1; a.train = train; a.mask = mask;
   a.tiles_x = tiles_x; a.tiles_y = tiles_y; a.stats = two ? 1 : 0; a.wpi = wpi; a.rows_cap = 0;
+  a.nsrc = nsrc; a.idx_bytes = 0; a.index = nullptr; a.bad = nullptr;
+  if (indexed) { a.index = op->p[RCV_P_IN_AUX]; a.idx_bytes = op->i[RCV_I_INMODE]; a.bad = (int*)op->p[RCV_P_EPI_AUX]; }
   const dim3 grid(B * wpi), block(256);
   if (ident) {
-    if (two) hipLaunchKernelGGL(rgb_prep_ident_kernel<true>, grid, block, 0, s, a);
-    hipLaunchKernelGGL(rgb_prep_ident_kernel<false>, grid, block, 0, s, a);
+    void (*stat_ident)(RpArgs) = rgb_prep_ident_kernel<true, RP_PLAIN>;
+    void (*main_ident)(RpArgs) = rgb_prep_ident_kernel<false, RP_PLAIN>;
+    if (indexed) { stat_ident = rgb_prep_ident_kernel<true, RP_IDX>; main_ident = rgb_prep_ident_kernel<false, RP_IDX>; }
+    if (two) hipLaunchKernelGGL(stat_ident, grid, block, 0, s, a);
+    hipLaunchKernelGGL(main_ident, grid, block, 0, s, a);
     RCV_HIP(hipGetLastError());
     return RCV_OK;
   }
@@ -469,10 +551,130 @@ int rcv_launch_rgb_prep(const rcv_handle* h, const rcv_op* op, hipStream_t s, Op
   a.rows_cap = (int)span + ((double)(int)span < span ? 1 : 0) + 2;
   if (a.rows_cap > RP_ROWS_MAX) a.rows_cap = RP_ROWS_MAX;
   const bool stage = kx >= RP_STAGE_MIN_TAPS;
-  void (*const stat_kernel)(RpArgs) = stage ? rgb_prep_kernel<true, true> : rgb_prep_kernel<true, false>;
-  void (*const main_kernel)(RpArgs) = stage ? rgb_prep_kernel<false, true> : rgb_prep_kernel<false, false>;
+  void (*stat_kernel)(RpArgs) = stage ? rgb_prep_kernel<true, true, RP_PLAIN> : rgb_prep_kernel<true, false, RP_PLAIN>;
+  void (*main_kernel)(RpArgs) = stage ? rgb_prep_kernel<false, true, RP_PLAIN> : rgb_prep_kernel<false, false, RP_PLAIN>;
+  if (indexed) {
+    stat_kernel = stage ? rgb_prep_kernel<true, true, RP_IDX> : rgb_prep_kernel<true, false, RP_IDX>;
+    main_kernel = stage ? rgb_prep_kernel<false, true, RP_IDX> : rgb_prep_kernel<false, false, RP_IDX>;
+  }
   if (two) hipLaunchKernelGGL(stat_kernel, grid, block, 0, s, a);
   hipLaunchKernelGGL(main_kernel, grid, block, 0, s, a);
+  RCV_HIP(hipGetLastError());
+  return RCV_OK;
+}
+
+// ------------------------------------------------------------------------------------------
+// RCV_OP_LP_PAIR_PREP (rcv_lp_pair_prep): the store's bytes -> LabelProp's input.  Per pair p = (ia, ib) of store indices, with ONE
+// parameter row (labelPropTrain.py:36-66 for both frames, then labelPropTrain.py:162-193):
+//   both frames and both label planes through steps 2-5 above with row p -- the same mirrors for all four planes, the same colour
+//   operations on both frames, the contrast mean of EACH FRAME ON ITS OWN (ColorJitter is applied per image) -- Y only; then
+//   sample 2p = [Ya, Yb, Ya - Yb, labelToPred(label_b)], target label_a; sample 2p + 1 = [Yb, Ya, Yb - Ya, labelToPred(label_a)], target
+//   label_b, NHWC with 8 floats per pixel, as lp_batch_kernel of csrc/lp_tail.hip writes them.
+// The statistics launch is rgb_prep_ident_kernel<true, RP_PAIR> over the 2B frames (partials [2B][wpi]).  Here one workgroup handles the
+// same RP_PAIR_PIX pixels of both frames of a pair (fewer than the statistics launch takes: 8 pairs of 120 x 160 are 304 workgroups
+// instead of 80 on 256 compute units); a thread writes the two 32-byte pixels with four 16-byte stores.  Grid: B * bpp.
+__global__ __launch_bounds__(256) void lp_pair_prep_kernel(RpArgs a, int bpp) {
+  __shared__ double s_c[256];
+  __shared__ unsigned long long s_red[256];
+  const int tid = threadIdx.x;
+  const int pr = blockIdx.x / bpp, blk = blockIdx.x % bpp;
+  const int npix = a.H * a.W;
+  const int start = blk * RP_PAIR_PIX, end = start + min(RP_PAIR_PIX, npix - start);
+  const int sa = rp_source(a, (size_t)2 * pr), sb = rp_source(a, (size_t)2 * pr + 1);
+  float* out0 = a.imgs + (size_t)2 * pr * npix * 8;
+  float* out1 = out0 + (size_t)npix * 8;
+  int64_t* tgt0 = a.tgt + (size_t)2 * pr * npix;
+  int64_t* tgt1 = tgt0 + npix;
+  if (sa < 0 || sb < 0) {                        // (the same for the whole workgroup, and in front of every barrier)
+    const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int p = start + tid; p < end; p += 256) {
+      float4* o0 = (float4*)(out0 + (size_t)p * 8);
+      float4* o1 = (float4*)(out1 + (size_t)p * 8);
+      o0[0] = z; o0[1] = z; o1[0] = z; o1[1] = z;
+      tgt0[p] = 0; tgt1[p] = 0;
+    }
+    if (blk == 0 && tid == 0) atomicAdd(a.bad, 1);
+    return;
+  }
+  const RpRow j = rp_row(a, pr);
+  s_c[tid] = (double)tid / 255.0;
+  const int ma = rp_mean(a, j, 2 * pr, s_red);
+  const int mb = rp_mean(a, j, 2 * pr + 1, s_red);
+  __syncthreads();
+  const uint8_t* fa = a.frames + (size_t)sa * npix * 3;
+  const uint8_t* fb = a.frames + (size_t)sb * npix * 3;
+  for (int p = start + tid; p < end; p += 256) {
+    const uint8_t* qa = fa + (size_t)p * 3;
+    const uint8_t* qb = fb + (size_t)p * 3;
+    int ra = qa[0], ga = qa[1], ba = qa[2], rb = qb[0], gb = qb[1], bb = qb[2];
+    rp_ops(j, j.n_ops, ma, ra, ga, ba);
+    rp_ops(j, j.n_ops, mb, rb, gb, bb);
+    const float ya = rp_ynorm(rp_y(s_c[ra], s_c[ga], s_c[ba])), yb = rp_ynorm(rp_y(s_c[rb], s_c[gb], s_c[bb]));
+    const size_t la_i = (size_t)sa * npix + p, lb_i = (size_t)sb * npix + p;
+    const int la = a.lab_bytes == 1 ? (int)((const uint8_t*)a.labels)[la_i] : ((const int32_t*)a.labels)[la_i];
+    const int lb = a.lab_bytes == 1 ? (int)((const uint8_t*)a.labels)[lb_i] : ((const int32_t*)a.labels)[lb_i];
+    const int y = p / a.W, x = p - y * a.W;
+    const int xo = j.hflip ? a.W - 1 - x : x, yo = j.vflip ? a.H - 1 - y : y;
+    const size_t o = (size_t)yo * a.W + xo;
+    float pa[5], pb[5];
+#pragma unroll
+    for (int c = 0; c < 5; ++c) { pa[c] = la == c ? 1.f : -1.f; pb[c] = lb == c ? 1.f : -1.f; }
+    float4* o0 = (float4*)(out0 + o * 8);
+    float4* o1 = (float4*)(out1 + o * 8);
+    o0[0] = make_float4(ya, yb, ya - yb, pb[0]);
+    o0[1] = make_float4(pb[1], pb[2], pb[3], pb[4]);
+    o1[0] = make_float4(yb, ya, yb - ya, pa[0]);
+    o1[1] = make_float4(pa[1], pa[2], pa[3], pa[4]);
+    tgt0[o] = (int64_t)la;
+    tgt1[o] = (int64_t)lb;
+  }
+}
+
+int rcv_launch_lp_pair_prep(const rcv_handle* h, const rcv_op* op, hipStream_t s, OpQuery* query) {
+  const int B = op->i[RCV_I_N], Hs = op->i[RCV_I_H], Ws = op->i[RCV_I_W], H = op->i[RCV_I_HO], W = op->i[RCV_I_WO];
+  const int nClass = op->i[RCV_I_COUT], nsrc = op->i[RCV_I_STRIDE], lab_bytes = op->i[RCV_I_INMODE2], idx_bytes = op->i[RCV_I_INMODE];
+  const int train = op->i[RCV_I_AUX0], stats = op->i[RCV_I_COUNT];
+  if (query) {
+    query->n_part = 0; query->n_split = 0; query->part_bytes = 0;
+    snprintf(query->label, sizeof(query->label), "lp_pair_prep");
+  }
+  RCV_CHECK_ARG(nClass == 5, "lp pair prep: %d classes unsupported (the network's first conv reads 3 + 5 channels)", nClass);
+  RCV_CHECK_ARG(B >= 1 && H >= 1 && W >= 1 && Hs >= 1 && Ws >= 1, "lp pair prep: B %d, store %d x %d, output %d x %d: every size must be >= 1", B, Hs,
+                Ws, H, W);
+  RCV_CHECK_ARG(nsrc >= 1, "lp pair prep: a store of %d images (i[STRIDE]): there must be at least 1", nsrc);
+  RCV_CHECK_ARG(H == Hs && W == Ws,
+                "lp pair prep: a store of %d x %d frames for a network input of %d x %d: only the no-resize form is built; build the store at the "
+                "network's size (ResidentDataset(..., img_size=(%d, %d)))", Hs, Ws, H, W, H, W);
+  RCV_CHECK_ARG(lab_bytes == 1 || lab_bytes == 4, "lp pair prep: label element size %d unsupported (1 = uint8, 4 = int32)", lab_bytes);
+  RCV_CHECK_ARG(idx_bytes == 4 || idx_bytes == 8, "lp pair prep: index element size %d unsupported (4 = int32, 8 = int64)", idx_bytes);
+  RCV_CHECK_ARG((train == 0 || train == 1) && (stats == 0 || stats == 1), "lp pair prep: train %d / statistics %d out of range", train, stats);
+  RCV_CHECK_ARG((double)nsrc * H * W < 2147483647.0 && (double)B * 2.0 * H * W * 8.0 < 2147483647.0,
+                "lp pair prep: a store of %d images, %d pairs of %d x %d: more than 2^31 pixels (or output floats)", nsrc, B, H, W);
+  RCV_CHECK_ARG(op->p[RCV_P_IN_AUX] && op->p[RCV_P_EPI_AUX], "lp pair prep: null index or null bad-index counter");
+  const int wpi = ceil_div(H * W, RP_IDENT_PIX), bpp = ceil_div(H * W, RP_PAIR_PIX);
+  RCV_CHECK_ARG((double)B * 2.0 * wpi < 2147483647.0 && (double)B * bpp < 2147483647.0, "lp pair prep: grid too large");
+  const bool two = train && stats;
+  const int n_part = two ? 2 * B * wpi : 0;
+  if (query) {
+    query->n_part = n_part;
+    query->part_bytes = (size_t)n_part * sizeof(uint32_t);
+    return RCV_OK;
+  }
+  RCV_CHECK_ARG(op->p[RCV_P_IN] && op->p[RCV_P_IN2] && op->p[RCV_P_OUT] && op->p[RCV_P_X0], "lp pair prep: null operand");
+  RCV_CHECK_ARG(((uintptr_t)op->p[RCV_P_OUT] & 15) == 0, "lp pair prep: inputs must be 16-byte aligned");
+  RCV_CHECK_ARG(!train || op->p[RCV_P_IN_C], "lp pair prep: training mode needs the parameter rows float[B][%d]", RP_NPAR);
+  RCV_CHECK_ARG(!two || (op->p[RCV_P_PART] && ((uintptr_t)op->p[RCV_P_PART] & 3) == 0 && op->i[RCV_I_NPART] == n_part),
+                "lp pair prep: workspace missing, unaligned or of %d partial sums where %d are needed (rcv_op_workspace)", op->i[RCV_I_NPART], n_part);
+  RpArgs a;
+  memset(&a, 0, sizeof(a));
+  a.frames = (const uint8_t*)op->p[RCV_P_IN]; a.labels = op->p[RCV_P_IN2];
+  a.imgs = (float*)op->p[RCV_P_OUT]; a.tgt = (int64_t*)op->p[RCV_P_X0];
+  a.params = train ? (const float*)op->p[RCV_P_IN_C] : nullptr; a.part = two ? (uint32_t*)op->p[RCV_P_PART] : nullptr;
+  a.B = 2 * B; a.Hs = H; a.Ws = W; a.H = H; a.W = W; a.kx = 3; a.ky = 3; a.lab_bytes = lab_bytes; a.train = train;
+  a.stats = two ? 1 : 0; a.wpi = wpi;
+  a.nsrc = nsrc; a.index = op->p[RCV_P_IN_AUX]; a.idx_bytes = idx_bytes; a.bad = (int*)op->p[RCV_P_EPI_AUX];
+  if (two) hipLaunchKernelGGL((rgb_prep_ident_kernel<true, RP_PAIR>), dim3(2 * B * wpi), dim3(256), 0, s, a);
+  hipLaunchKernelGGL(lp_pair_prep_kernel, dim3(B * bpp), dim3(256), 0, s, a, bpp);
   RCV_HIP(hipGetLastError());
   return RCV_OK;
 }

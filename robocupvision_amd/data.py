@@ -47,7 +47,19 @@ What of it is pinned and what is the project's definition:
     to float32 (skimage's BLAS order and its byte-to-float form are not pinned; DESIGN 4.10 has the count of float32 outputs the
     other byte-to-float form changes).
 
-Not covered (it keeps raising): ``LPDataSet`` (cv2 ``cvtColor``)."""
+EPOCHS of that loader run from the same resident store, built at the SCALED size (``Scale`` is the first transform of every RGB list,
+trainer.py:75-104, labelPropTrain.py:36-66; it ends in a uint8 and both flips and ``ColorJitter`` come after it, so the store holds exactly
+the bytes the chain continues from): ``prepare_rgb_batch(..., index=)`` (RCV_OP_RGB_PREP_IDX) behind ``RGBEpochLoader``, and for LabelProp
+``prepare_lp_pairs`` (RCV_OP_LP_PAIR_PREP) behind ``LPEpochLoader`` -- both frames of a pair with ONE ``draw_color_jitter`` row, Y only,
+straight to the 8-channel input of labelPropTrain.py:162-193:
+
+    store = ResidentDataset(SSDataSet(root, "train"), img_size=(120, 160))
+    for imgs, targets in RGBEpochLoader(store, 32): ...                  # each: one prepare_rgb_batch(index=, params=)
+    lp = LPDataSet(root, train=True)                                    # the listing of dataset.py:191-228
+    store = ResidentDataset(lp.frames, img_size=(120, 160))
+    for inputs, targets in LPEpochLoader(store, lp.windows, 8): ...      # each: one prepare_lp_pairs
+
+Not covered (it keeps raising): ``LPDataSet.__getitem__`` (cv2 ``cvtColor``; labelPropTrain.py does not use it)."""
 from __future__ import annotations
 
 import math
@@ -62,7 +74,8 @@ import torch
 from . import _lib as L
 
 __all__ = ["prepare_batch", "prepare_frames", "draw_jitter", "SSYUVDataset", "bilinear_table", "nearest_table", "norm_table",
-           "prepare_rgb_batch", "draw_color_jitter", "SSDataSet", "resize_u8", "draw_jitter_rows", "ResidentDataset", "EpochLoader"]
+           "prepare_rgb_batch", "draw_color_jitter", "SSDataSet", "resize_u8", "draw_jitter_rows", "ResidentDataset", "EpochLoader", "prepare_lp_pairs", "draw_color_jitter_rows", "RGBEpochLoader",
+           "LPDataSet", "LPEpochLoader"]
 
 PRECISION_BITS = 22          # Pillow's 8-bit resampling: 32 - 8 - 2
 MEAN = {False: [0.36269532, 0.41144562, 0.282713], True: [0.34190056, 0.4833289, 0.48565758]}      # dataset.py:74 (key: finetune)
@@ -345,8 +358,53 @@ OP_BRIGHTNESS, OP_CONTRAST, OP_SATURATION, OP_HUE = 0, 1, 2, 3          # op cod
 _workspaces = {}          # (device, bytes) -> uint32 partial sums of the statistics launch (reused: every call overwrites what it reads)
 
 
+def _check_color_rows(rows, who):
+    """The host check of ``draw_color_jitter`` rows (numpy [n,12]): codes 0..3, each at most once.  Returns bool [n]: the row holds a
+    contrast among its operations."""
+    n, ops = rows[:, 2], rows[:, 3:7]
+    used = np.arange(4)[None, :] < n[:, None]
+    ok = (n == np.floor(n)) & (n >= 0) & (n <= 4) & (~used | ((ops == np.floor(ops)) & (ops >= 0) & (ops <= 3))).all(1)
+    for code in range(4):
+        ok &= (used & (ops == code)).sum(1) <= 1
+    if not ok.all():
+        b = int(np.argmin(ok))
+        raise ValueError("%s: row %d: n_ops %r with operations %r (codes 0..3, each at most once)"
+                         % (who, b, float(n[b]), [float(v) for v in ops[b]]))
+    return (used & (ops == OP_CONTRAST)).any(1)
+
+
+def _check_index(who, index, dim):
+    """The check ``prepare_batch`` makes of the form of ``index``; ``dim`` 1: [B], 2: pairs [B,2]."""
+    if not torch.is_tensor(index) or index.dtype not in (torch.int32, torch.int64) or index.dim() != dim or index.shape[0] < 1 \
+            or (dim == 2 and index.shape[1] != 2):
+        raise TypeError("%s: %s must be a non-empty int32 or int64 %s tensor" % ((who,) + (("index", "[B]") if dim == 1 else ("pairs", "[B,2]"))))
+
+
+def _index_args(who, index, bad_index, dev, dim):
+    """The checks ``prepare_batch`` makes of where ``index`` lives and of ``bad_index``.  Returns the counter."""
+    if index.device != dev or not index.is_contiguous():
+        raise ValueError("%s: %s must be contiguous and on the device of the store (%s; got %s)"
+                         % (who, "index" if dim == 1 else "pairs", dev, index.device))
+    if bad_index is None:
+        bad_index = _bad_counters.get(str(dev))
+        if bad_index is None:
+            bad_index = _bad_counters[str(dev)] = torch.zeros(1, dtype=torch.int32, device=dev)
+    elif not torch.is_tensor(bad_index) or bad_index.dtype != torch.int32 or bad_index.numel() < 1 or bad_index.device != dev:
+        raise TypeError("%s: bad_index must be an int32 tensor on the device of the store" % who)
+    return bad_index
+
+
+def _workspace(dev, need):
+    if not need:
+        return None
+    ws = _workspaces.get((str(dev), need))
+    if ws is None:
+        ws = _workspaces[(str(dev), need)] = torch.empty(need // 4, dtype=torch.int32, device=dev)
+    return ws
+
+
 def prepare_rgb_batch(frames, labels=None, scale=4, train=True, params=None, no_ball=False, no_robot=False, no_goal=False, no_line=False,
-                      img_size=None):
+                      img_size=None, index=None, bad_index=None, contrast=None):
     """``frames`` uint8 [B,Hs,Ws,3] (decoded RGB) and ``labels`` uint8 or int32 [B,Hs,Ws] or None, on the HIP device -> ``(imgs,
     targets)``: float32 YUV [B,3,H,W] and int64 [B,H,W] (None without labels: the patch chain of classTrainer.py / objDetEval.py).
     ``H = int(Hs / scale)``, ``W = int(Ws / scale)`` as transform.py:8-19 ``Scale``; ``scale == 1`` means no resize.  ``img_size=(H, W)``
@@ -357,7 +415,17 @@ def prepare_rgb_batch(frames, labels=None, scale=4, train=True, params=None, no_
     resize, YUV, normalise, maskLabel -- the same as training mode with no flip and ``n_ops = 0``.  Rows given on the host are checked
     (codes 0..3, each at most once) and the statistics launch is skipped when none of them holds a contrast; rows given on the device
     are taken as they are.  Every output element is exact to the contract of the module docstring.  Same refusals as
-    ``prepare_batch``."""
+    ``prepare_batch``.
+
+    ``index`` (int32 or int64 [B], on the device): ``frames`` / ``labels`` are then a STORE of N images and image ``b`` of the batch is
+    ``store[index[b]]``; ``B = len(index)`` and ``params`` is [B,12] (RCV_OP_RGB_PREP_IDX).  The result is bit for bit that of the call
+    without ``index`` on ``frames[index]``, ``labels[index]``.  An index outside [0, N) reads nothing in either launch: that image comes
+    back as zeros with targets 0 and ``bad_index`` (int32 [1] on the device; one per device is kept here if none is given) is
+    incremented by the kernel, with nothing synchronised.  Without ``index`` the call is what it always was.
+
+    ``contrast`` (None, or a bool for rows given on the DEVICE, which cannot be looked at without a synchronisation): the caller's word
+    on whether any of these rows holds a contrast -- ``RGBEpochLoader`` checked the epoch's rows once on the host and knows it per
+    slice.  False skips the statistics launch (a row that holds one anyway blends towards 0, rcv.h i[COUNT])."""
     if not torch.is_tensor(frames) or (labels is not None and not torch.is_tensor(labels)):
         raise TypeError("prepare_rgb_batch: frames (and labels) must be tensors")
     if frames.dtype != torch.uint8 or (labels is not None and labels.dtype not in (torch.uint8, torch.int32)):
@@ -367,6 +435,9 @@ def prepare_rgb_batch(frames, labels=None, scale=4, train=True, params=None, no_
         raise ValueError("prepare_rgb_batch: frames must be [B,Hs,Ws,3] and labels [B,Hs,Ws] (got %s, %s)"
                          % (tuple(frames.shape), None if labels is None else tuple(labels.shape)))
     B, Hs, Ws, _ = frames.shape
+    N = B
+    if index is not None:
+        _check_index("prepare_rgb_batch", index, 1)
     if not scale >= 1:
         raise ValueError("prepare_rgb_batch: scale %r must be >= 1" % (scale,))
     H, W = (Hs, Ws) if scale == 1 else (int(Hs / scale), int(Ws / scale))
@@ -377,6 +448,8 @@ def prepare_rgb_batch(frames, labels=None, scale=4, train=True, params=None, no_
                          % (None if labels is None else tuple(labels.shape), tuple(frames.shape)))
     if (H == Hs) != (W == Ws):
         raise ValueError("prepare_rgb_batch: %d x %d -> %d x %d keeps exactly one axis; resize the frames first" % (Hs, Ws, H, W))
+    if index is not None:
+        B = int(index.shape[0])
     stats = 0
     if train:
         if params is None:
@@ -385,23 +458,17 @@ def prepare_rgb_batch(frames, labels=None, scale=4, train=True, params=None, no_
             raise TypeError("prepare_rgb_batch: params must be a float32 [B,12] tensor (draw_color_jitter)")
         stats = 1
         if params.device.type == "cpu":
-            rows = params.numpy()
-            n, ops = rows[:, 2], rows[:, 3:7]
-            used = np.arange(4)[None, :] < n[:, None]
-            ok = (n == np.floor(n)) & (n >= 0) & (n <= 4) & (~used | ((ops == np.floor(ops)) & (ops >= 0) & (ops <= 3))).all(1)
-            for code in range(4):
-                ok &= (used & (ops == code)).sum(1) <= 1
-            if not ok.all():
-                b = int(np.argmin(ok))
-                raise ValueError("prepare_rgb_batch: row %d: n_ops %r with operations %r (codes 0..3, each at most once)"
-                                 % (b, float(n[b]), [float(v) for v in ops[b]]))
-            stats = int((used & (ops == OP_CONTRAST)).any())
+            stats = int(_check_color_rows(params.numpy(), "prepare_rgb_batch").any())
+        elif contrast is not None:
+            stats = 1 if contrast else 0
     if frames.device.type != "cuda" or (labels is not None and labels.device != frames.device):
         raise L.RcvError("prepare_rgb_batch runs on the HIP device only (frames on %s, labels on %s)"
                          % (frames.device, None if labels is None else labels.device))
     if not (frames.is_contiguous() and (labels is None or labels.is_contiguous())):
         raise ValueError("prepare_rgb_batch: frames and labels must be contiguous (no hidden copy of a batch)")
     dev = frames.device
+    if index is not None:
+        bad_index = _index_args("prepare_rgb_batch", index, bad_index, dev, 1)
     if train:
         params = params.to(dev).contiguous()
     fx, kx, fy, ky, lx, ly = _device_tables(Hs, Ws, H, W, dev)
@@ -410,14 +477,23 @@ def prepare_rgb_batch(frames, labels=None, scale=4, train=True, params=None, no_
     mask = (1 if no_ball else 0) | (2 if no_robot else 0) | (4 if no_goal else 0) | (8 if no_line else 0)
     h = L.handle(dev.index if dev.index is not None else torch.cuda.current_device())
     lab_bytes = 0 if labels is None else labels.element_size()
+    if index is not None:
+        op = L.make_op(L.OP_RGB_PREP_IDX, n=B, stride=N, inmode=index.element_size(), h=Hs, w=Ws, ho=H, wo=W, cin=kx, cout=ky, inmode2=lab_bytes,
+                       aux0=1 if train else 0, aux1=mask, count=stats, p_x1=fx.data_ptr(), p_x2=fy.data_ptr(), p_x3=lx.data_ptr(),
+                       p_x4=ly.data_ptr(), p_in_aux=index.data_ptr(), p_epi_aux=bad_index.data_ptr())
+        need = L.op_workspace(h, op)
+        ws = _workspace(dev, need)
+        L.check(L.load().rcv_rgb_prep_indexed(h, frames.data_ptr(), None if labels is None else labels.data_ptr(), lab_bytes, N, index.data_ptr(),
+                                              index.element_size(), B, Hs, Ws, H, W, fx.data_ptr(), kx, fy.data_ptr(), ky, lx.data_ptr(),
+                                              ly.data_ptr(), params.data_ptr() if train else None, 1 if train else 0, stats, mask,
+                                              imgs.data_ptr(), None if targets is None else targets.data_ptr(), bad_index.data_ptr(),
+                                              None if ws is None else ws.data_ptr(), need, torch.cuda.current_stream(dev).cuda_stream),
+                "rcv_rgb_prep_indexed")
+        return imgs, targets
     op = L.make_op(L.OP_RGB_PREP, n=B, h=Hs, w=Ws, ho=H, wo=W, cin=kx, cout=ky, inmode2=lab_bytes, aux0=1 if train else 0, aux1=mask,
                    count=stats, p_x1=fx.data_ptr(), p_x2=fy.data_ptr(), p_x3=lx.data_ptr(), p_x4=ly.data_ptr())
     need = L.op_workspace(h, op)
-    ws = None
-    if need:
-        ws = _workspaces.get((str(dev), need))
-        if ws is None:
-            ws = _workspaces[(str(dev), need)] = torch.empty(need // 4, dtype=torch.int32, device=dev)
+    ws = _workspace(dev, need)
     L.check(L.load().rcv_rgb_prep(h, frames.data_ptr(), None if labels is None else labels.data_ptr(), lab_bytes, B, Hs, Ws, H, W,
                                   fx.data_ptr(), kx, fy.data_ptr(), ky, lx.data_ptr(), ly.data_ptr(), params.data_ptr() if train else None,
                                   1 if train else 0, stats, mask, imgs.data_ptr(), None if targets is None else targets.data_ptr(),
@@ -458,6 +534,92 @@ def draw_color_jitter(B, brightness=0.5, contrast=0.5, saturation=0.4, hue=0.3, 
         rows[i, 7:10] = torch.FloatTensor(fac)
         rows[i, 10] = float(shift)
     return rows
+
+
+def draw_color_jitter_rows(n, brightness=0.5, contrast=0.5, saturation=0.4, hue=0.3, vflip=True, reseed=True):
+    """The rows of ``draw_color_jitter(n, ...)`` for a whole epoch in one call: bit for bit the same float32 [n,12] host tensor under the
+    same ``random`` / ``np.random`` seeds, and both generators are left where ``draw_color_jitter(n)`` leaves them.  The draws are the
+    same calls in the same order (nothing is vectorised: ``random.seed`` between two images makes every image's draws its own); the
+    rounding to float32 is one array conversion, not three tensor constructions per image."""
+    out = []
+    for _ in range(n):
+        if reseed:
+            random.seed(np.random.randint(2147483647))
+        hf = random.random() < 0.5
+        vf = (random.random() < 0.5) if vflip else False
+        ops, fac, shift = [], [1.0, 1.0, 1.0], 0
+        for code, strength in ((OP_BRIGHTNESS, brightness), (OP_CONTRAST, contrast), (OP_SATURATION, saturation)):
+            if strength > 0:
+                fac[code] = random.uniform(max(0, 1 - strength), 1 + strength)
+                ops.append(code)
+        if hue > 0:
+            shift = int(random.uniform(-hue, hue) * 255) & 255
+            ops.append(OP_HUE)
+        random.shuffle(ops)
+        out.append([float(hf), float(vf), float(len(ops))] + (ops + [-1] * 4)[:4] + fac + [float(shift), 0.0])
+    return torch.from_numpy(np.array(out, np.float64).reshape(n, 12).astype(np.float32))
+
+
+def prepare_lp_pairs(frames, labels, pairs, train=True, params=None, bad_index=None, contrast=None, num_class=5):
+    """LabelProp's input straight from a resident store, one op (RCV_OP_LP_PAIR_PREP): the per-pair work of the loader
+    (labelPropTrain.py:36-66) and of the batch assembly (labelPropTrain.py:162-193).
+
+    ``frames`` uint8 [N,H,W,3] and ``labels`` uint8 or int32 [N,H,W]: the store, already at the network's size (``ResidentDataset(...,
+    img_size=(H, W))``; another size is refused).  ``pairs`` int32 or int64 [B,2] on the device: the store indices of frame a and frame
+    b.  ``params`` float32 [B,12]: ONE ``draw_color_jitter`` row per pair (host rows are checked as ``prepare_rgb_batch`` checks them).
+    Returns ``(inputs, targets)``: ``inputs`` of logical shape [2B,8,H,W] whose memory is NHWC, what ``labelprop_batch`` returns and
+    ``LabelProp`` reads without a copy, and ``targets`` int64 [2B,H,W].
+
+    Bit for bit ``labelprop_batch(imgs.view(B,2,3,H,W), tgts.view(B,2,H,W))`` of ``imgs, tgts = prepare_rgb_batch(frames[pairs.flatten()],
+    labels[pairs.flatten()], img_size=(H, W), params=params.repeat_interleave(2, 0))``: both frames and both label planes of a pair are
+    mirrored alike, both frames get the same colour operations with the contrast mean of EACH FRAME ON ITS OWN, only Y is computed, a
+    label outside [0, 5) gives -1 in all five class channels, and there is no ``maskLabel``.  That one shared row per pair is the
+    project's own definition (the ``LPDataSet(root, split=, img_transform=, label_transform=)`` that labelPropTrain.py:79 calls is not in
+    the reference; ``Ya - Yb`` needs both frames mirrored alike, which is all the script fixes).  A pair with either index outside
+    [0, N) comes back as zeros (both samples, all 8 channels, targets 0) and is counted once in ``bad_index``.  ``contrast``: as
+    ``prepare_rgb_batch``."""
+    if num_class != 5:
+        raise ValueError("prepare_lp_pairs: num_class must be 5 (LabelProp's first conv reads 3 + 5 channels), got %r" % (num_class,))
+    if not (torch.is_tensor(frames) and torch.is_tensor(labels)):
+        raise TypeError("prepare_lp_pairs: frames and labels must be tensors")
+    if frames.dtype != torch.uint8 or labels.dtype not in (torch.uint8, torch.int32):
+        raise TypeError("prepare_lp_pairs: frames must be uint8 and labels uint8 or int32 (got %s, %s)" % (frames.dtype, labels.dtype))
+    if frames.dim() != 4 or frames.shape[3] != 3 or labels.dim() != 3 or tuple(labels.shape) != tuple(frames.shape[:3]) or frames.shape[0] < 1:
+        raise ValueError("prepare_lp_pairs: frames must be [N,H,W,3] and labels [N,H,W] (got %s, %s)" % (tuple(frames.shape), tuple(labels.shape)))
+    N, H, W, _ = frames.shape
+    _check_index("prepare_lp_pairs", pairs, 2)
+    B = int(pairs.shape[0])
+    stats = 0
+    if train:
+        if params is None:
+            raise ValueError("prepare_lp_pairs: train=True needs params (draw_color_jitter(B): one row per pair)")
+        if not torch.is_tensor(params) or params.dtype != torch.float32 or tuple(params.shape) != (B, 12):
+            raise TypeError("prepare_lp_pairs: params must be a float32 [B,12] tensor (draw_color_jitter: one row per pair)")
+        stats = 1
+        if params.device.type == "cpu":
+            stats = int(_check_color_rows(params.numpy(), "prepare_lp_pairs").any())
+        elif contrast is not None:
+            stats = 1 if contrast else 0
+    if frames.device.type != "cuda" or labels.device != frames.device:
+        raise L.RcvError("prepare_lp_pairs runs on the HIP device only (frames on %s, labels on %s)" % (frames.device, labels.device))
+    if not (frames.is_contiguous() and labels.is_contiguous()):
+        raise ValueError("prepare_lp_pairs: frames and labels must be contiguous (no hidden copy of a store)")
+    dev = frames.device
+    bad_index = _index_args("prepare_lp_pairs", pairs, bad_index, dev, 2)
+    if train:
+        params = params.to(dev).contiguous()
+    inputs = torch.empty(2 * B, H, W, 8, dtype=torch.float32, device=dev)
+    targets = torch.empty(2 * B, H, W, dtype=torch.int64, device=dev)
+    h = L.handle(dev.index if dev.index is not None else torch.cuda.current_device())
+    op = L.make_op(L.OP_LP_PAIR_PREP, n=B, stride=N, h=H, w=W, ho=H, wo=W, cout=num_class, inmode2=labels.element_size(),
+                   inmode=pairs.element_size(), aux0=1 if train else 0, count=stats, p_in_aux=pairs.data_ptr(), p_epi_aux=bad_index.data_ptr())
+    need = L.op_workspace(h, op)
+    ws = _workspace(dev, need)
+    L.check(L.load().rcv_lp_pair_prep(h, frames.data_ptr(), labels.data_ptr(), labels.element_size(), N, pairs.data_ptr(), pairs.element_size(),
+                                      B, H, W, H, W, num_class, params.data_ptr() if train else None, 1 if train else 0, stats,
+                                      inputs.data_ptr(), targets.data_ptr(), bad_index.data_ptr(), None if ws is None else ws.data_ptr(), need,
+                                      torch.cuda.current_stream(dev).cuda_stream), "rcv_lp_pair_prep")
+    return inputs.permute(0, 3, 1, 2), targets
 
 
 def _tryint(s):
@@ -715,3 +877,156 @@ class EpochLoader:
                                 params=rows_dev[a:b] if self.train else None, index=index_dev[a:b], bad_index=res.bad_index, **self.flags)
         if self.prefetch:          # the consumer has enqueued its last step and asks for more: the device is busy, the host is free
             self._next = self._draw_epoch()
+
+
+class RGBEpochLoader(EpochLoader):
+    """``EpochLoader`` for the RGB loader (trainer.py:75-123; pruner.py, classTrainer.py): one epoch of ``prepare_rgb_batch`` batches per
+    ``iter()`` from a ``ResidentDataset`` built at the SCALED size.  The bookkeeping is ``EpochLoader``'s, unchanged in meaning
+    (``randperm`` with ``generator`` on the host, ``perm[rank::world]``, row ``i`` belongs to the ``i``-th sample visited, ``last_index``
+    / ``last_rows``, ``plan``, ``share``, ``len``, ``prefetch``); the rows are ``draw_color_jitter_rows(n, *jitter, vflip=vflip)``, checked
+    ONCE on the host (codes 0..3, each at most once), and every ``next()`` is one ``prepare_rgb_batch(store.frames, store.labels,
+    img_size=store.img_size, index=perm_dev[a:b], params=rows_dev[a:b], bad_index=store.bad_index)`` that is told whether its slice
+    holds a contrast, so the statistics launch is skipped where it has nothing to do.  No host tensor work and no synchronisation per
+    batch.  Pinned: every batch, bit for bit, to ``prepare_rgb_batch`` of the full-size frames gathered by the same indices with the same
+    rows."""
+
+    def __init__(self, resident, batch_size, train=True, shuffle=True, jitter=(0.5, 0.5, 0.4, 0.3), vflip=True, no_ball=False, no_robot=False,
+                 no_goal=False, no_line=False, generator=None, drop_last=False, rank=0, world=1, prefetch=False):
+        EpochLoader.__init__(self, resident, batch_size, train=train, shuffle=shuffle, no_ball=no_ball, no_robot=no_robot, no_goal=no_goal,
+                             no_line=no_line, jitter=jitter, generator=generator, drop_last=drop_last, rank=rank, world=world,
+                             prefetch=prefetch)
+        self.vflip = bool(vflip)
+
+    def _count(self):
+        return len(self.resident)
+
+    def __len__(self):
+        n = self._share_len(self._count())
+        return n // self.batch_size if self.drop_last else -(-n // self.batch_size)
+
+    def _pick(self, share):
+        """What a sample of this rank's share is on the device: its store index."""
+        return share.contiguous()
+
+    def _draw_epoch(self):
+        """The host work of one epoch: permutation, share, draws and their check, slices with their contrast hints, the two uploads."""
+        dev = self.resident.device
+        n = self._count()
+        perm = torch.randperm(n, generator=self.generator) if self.shuffle else torch.arange(n)
+        index = self._pick(self.share(perm))
+        slices = self.plan(perm)
+        rows = hints = None
+        if self.train:
+            rows = draw_color_jitter_rows(int(index.shape[0]), *self.jitter, vflip=self.vflip)
+            has = _check_color_rows(rows.numpy(), type(self).__name__)
+            hints = [bool(has[a:b].any()) for a, b in slices]
+        index_dev = rows_dev = None
+        if slices:
+            index_dev = index.pin_memory().to(dev, non_blocking=True)
+            rows_dev = rows.pin_memory().to(dev, non_blocking=True) if self.train else None
+        return index, rows, slices, index_dev, rows_dev, hints
+
+    def _batch(self, index, rows, hint):
+        res = self.resident
+        return prepare_rgb_batch(res.frames, res.labels, img_size=res.img_size, train=self.train, params=rows, index=index,
+                                 bad_index=res.bad_index, contrast=hint, **self.flags)
+
+    def __iter__(self):
+        epoch, self._next = self._next if self._next is not None else self._draw_epoch(), None
+        self.last_index, self.last_rows, slices, index_dev, rows_dev, hints = epoch
+        for k, (a, b) in enumerate(slices):
+            yield self._batch(index_dev[a:b], rows_dev[a:b] if self.train else None, hints[k] if self.train else None)
+        if self.prefetch:
+            self._next = self._draw_epoch()
+
+
+class _LPFrames:
+    """The flat sequence of decoded ``(uint8 [Hs,Ws,3], int32 [Hs,Ws])`` items of an ``LPDataSet``: what ``ResidentDataset`` takes."""
+
+    def __init__(self, images, labels):
+        self.images, self.labels = images, labels
+
+    def __len__(self):
+        return len(self.images)
+
+    def __getitem__(self, index):
+        from PIL import Image
+        with Image.open(self.images[index]) as im:
+            frame = np.asarray(im.convert("RGB"), dtype=np.uint8)
+        with Image.open(self.labels[index]) as im:
+            label = np.asarray(im.convert("I"), dtype=np.int32)
+        return np.ascontiguousarray(frame), np.ascontiguousarray(label)
+
+
+class LPDataSet:
+    """The file listing of the reference's ``LPDataSet`` (dataset.py:191-228): ``<root>/LabelProp/{Real,Synthetic}/{train,val}/<dir>/
+    {images,labels}/*.png`` (``Real`` with ``finetune``), natural-key order within a directory, ``len()`` = sum over the directories of
+    ``len(dir) - len_seq + 1`` windows of ``len_seq`` consecutive frames.  Stated difference: the directories are visited in natural-key
+    order; the reference takes ``os.listdir`` order, which is not defined.
+
+    ``frames``: the flat sequence of all frames, directory after directory, as ``(uint8 [Hs,Ws,3], int32 [Hs,Ws])`` items that only
+    decode -- what ``ResidentDataset`` takes.  ``windows``: int64 [len(), len_seq], the flat indices of each window; no window crosses
+    a directory.  ``LPEpochLoader`` runs epochs from the two.  ``__getitem__`` (dataset.py:230-270: cv2-converted YUV) is not built."""
+
+    def __init__(self, root, train=True, finetune=True, len_seq=2):
+        if int(len_seq) < 1:
+            raise ValueError("LPDataSet: len_seq %r must be >= 1" % (len_seq,))
+        self.finetune, self.len_seq = bool(finetune), int(len_seq)
+        self.root = osp.join(root, "LabelProp")
+        self.split = "train" if train else "val"
+        data_dir = osp.join(self.root, "Real" if finetune else "Synthetic", self.split)
+        self.images, self.labels = [], []          # per directory, as the reference keeps them
+        dirs = sorted((d for d in os.listdir(data_dir) if osp.isdir(osp.join(data_dir, d))), key=_natural_key) if osp.isdir(data_dir) else []
+        flat_i, flat_l, win = [], [], []
+        for d in dirs:
+            img_dir, lab_dir = osp.join(data_dir, d, "images"), osp.join(data_dir, d, "labels")
+            imgs = [osp.join(img_dir, f) for f in SSYUVDataset._list(img_dir, ".png")]
+            labs = [osp.join(lab_dir, f) for f in SSYUVDataset._list(lab_dir, ".png")]
+            if len(imgs) != len(labs):
+                raise ValueError("LPDataSet: %s holds %d images and %d labels" % (osp.join(data_dir, d), len(imgs), len(labs)))
+            self.images.append(imgs)
+            self.labels.append(labs)
+            base = len(flat_i)
+            win += [[base + k + i for i in range(self.len_seq)] for k in range(len(imgs) - self.len_seq + 1)]
+            flat_i += imgs
+            flat_l += labs
+        self.frames = _LPFrames(flat_i, flat_l)
+        self.windows = torch.tensor(win, dtype=torch.int64).reshape(len(win), self.len_seq)
+
+    def __len__(self):
+        return int(self.windows.shape[0])
+
+    def __getitem__(self, index):
+        raise NotImplementedError("LPDataSet.__getitem__ (dataset.py:230-270) converts with cv2.cvtColor: OpenCV is not available to pin a "
+                                  "restatement against, and labelPropTrain.py does not use it; decode with .frames[i], run epochs with "
+                                  "ResidentDataset(.frames) + LPEpochLoader(store, .windows)")
+
+
+class LPEpochLoader(RGBEpochLoader):
+    """One epoch of LabelProp batches per ``iter()``: ``windows`` (int64 [n,2], ``LPDataSet.windows``: store indices of frame a and
+    frame b) are permuted -- the bookkeeping of ``EpochLoader`` over WINDOWS: ``randperm(n, generator=)``, ``perm[rank::world]``, row ``i``
+    of ``draw_color_jitter_rows`` belongs to the ``i``-th window visited -- the permuted [n,2] pairs and the rows are uploaded once, and
+    every ``next()`` is one ``prepare_lp_pairs(store.frames, store.labels, pairs_dev[a:b], params=rows_dev[a:b])`` of ``batch_size``
+    pairs, i.e. ``2 batch_size`` samples (labelPropTrain.py:91: batch 8).  ``last_index`` is the epoch's [n,2] pairs on the host.
+    Windows longer than 2 are refused: the network reads one pair."""
+
+    def __init__(self, resident, windows, batch_size=8, train=True, shuffle=True, jitter=(0.5, 0.5, 0.4, 0.3), vflip=True, generator=None,
+                 drop_last=False, rank=0, world=1, prefetch=False):
+        if not torch.is_tensor(windows) or windows.dtype not in (torch.int32, torch.int64) or windows.dim() != 2:
+            raise TypeError("LPEpochLoader: windows must be an int32 or int64 [n,2] tensor (LPDataSet.windows)")
+        if windows.shape[1] != 2:
+            raise ValueError("LPEpochLoader: windows of %d frames: only pairs are built (LPDataSet(len_seq=2)); LabelProp reads the two "
+                             "frames of one pair" % int(windows.shape[1]))
+        RGBEpochLoader.__init__(self, resident, batch_size, train=train, shuffle=shuffle, jitter=jitter, vflip=vflip, generator=generator,
+                                drop_last=drop_last, rank=rank, world=world, prefetch=prefetch)
+        self.windows = windows.cpu().contiguous()
+
+    def _count(self):
+        return int(self.windows.shape[0])
+
+    def _pick(self, share):
+        return self.windows[share].contiguous()
+
+    def _batch(self, index, rows, hint):
+        res = self.resident
+        return prepare_lp_pairs(res.frames, res.labels, index, train=self.train, params=rows, bad_index=res.bad_index, contrast=hint)
