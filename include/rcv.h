@@ -255,7 +255,7 @@ enum {
                              * launch writes that image as zeros with targets 0 and increments the counter once (an atomic add) -- nothing
                              * is read out of bounds, nothing synchronises.  Refused when planned: what RCV_OP_RGB_PREP refuses (the pixel
                              * limit counts the store), N < 1, an index element size other than 4 or 8, a null index or counter          */
-  RCV_OP_LP_PAIR_PREP = 54   /* LabelProp's input straight from a resident store (rcv_lp_pair_prep; csrc/rgb_prep.hip): per pair the loader of
+  RCV_OP_LP_PAIR_PREP = 54,  /* LabelProp's input straight from a resident store (rcv_lp_pair_prep; csrc/rgb_prep.hip): per pair the loader of
                              * labelPropTrain.py:36-66 on both frames and the assembly of labelPropTrain.py:162-193, i.e. RCV_OP_LP_BATCH of
                              * RCV_OP_RGB_PREP_IDX with ONE parameter row per pair, Y only.  i[N] = B pairs, i[H] / i[W] = size of the store's
                              * images, i[HO] / i[WO] = the network's size (must equal i[H] / i[W]: only the no-resize form is built),
@@ -266,6 +266,22 @@ enum {
                              * inputs float[2B][H][W][8] (NHWC, 16-byte aligned), p[X0] = targets int64[2B][H][W], p[PART] =
                              * uint32[i[NPART]], i[NPART] = 2B x workgroups per frame (0 unless train and i[COUNT]).  A pair with either
                              * index outside [0, N): both samples zeros, targets 0, counted once                                       */
+  RCV_OP_CONV5 = 55,         /* 5x5 gather convolution, stride 1, pad 2 (rcv_conv5x5; csrc/conv5.hip): the classifier convolution of
+                             * Classifier(kernelSize=5) / UltClassifier(size=5) (model.py:256-267, model.py:403-414) and, with the filter packed
+                             * flipped and transposed, its data gradient.  Slots, load transform, flags (RCV_F_BIAS / _RELU / _RESID) and
+                             * statistics rows exactly as RCV_OP_CONV; i[STRIDE] = i[DIL] = 1, i[HO] = i[H], i[WO] = i[W]; p[W] = the
+                             * [25][CIN][16] filter an RCV_OP_PACK5 record writes.  Channel pairs: CIN 8 / 16 -> COUT 8 (the class channels
+                             * padded to 8: at most 8 classes), CIN 8 -> COUT 8 / 16 (data gradient); i[INMODE] PLAIN / AFFINE / AFFINE_RELU.
+                             * Everything else is refused when planned.  One partial row per 256-pixel tile                            */
+  RCV_OP_WGRAD5 = 56,        /* its filter and bias gradient (rcv_wgrad5x5), split over pixels: slots as RCV_OP_WGRAD; p[IN] = the conv's input
+                             * (i[CIN] = 8 / 16 channels, i[INMODE] as above), p[IN2] = the output gradient NHWC with i[COUT] = 8 padded class
+                             * channels (i[INMODE2] = PLAIN), RCV_F_BIAS = also the bias gradient; p[PART] = float[i[NSPLIT]][25 * 8 * 16 + 8]
+                             * (i[NSPLIT] filled by rcv_op_workspace): per split the partial filter [25 taps][8][16] and the partial bias [8] */
+  RCV_OP_WGRAD5_REDUCE = 57, /* fixed-order sum (split 0, 1, ...) of RCV_OP_WGRAD5's partial rows -> p[OUT] = dW [COUT][CIN][5][5], p[BIAS] = db
+                             * [COUT] or NULL; i[CIN] = 8 / 16, i[COUT] = 1..8 classes, i[NSPLIT], p[PART]                              */
+  RCV_OP_PACK5 = 58          /* p[IN] = parameter [COUT][CIN][5][5] (i[CIN] = 8 / 16, i[COUT] = 1..8) -> p[OUT] = float[25][rows][16], zero
+                             * padded: forward rows = CIN, out[t][ci][co] = w[co][ci][t]; with RCV_F_FLIP the data gradient's filter, rows =
+                             * 8, out[t][co][ci] = w[co][ci][24 - t]                                                                    */
 };
 
 /* i[RCV_I_AUX0] of RCV_OP_PRUNE: how the threshold of a tensor is chosen */
@@ -472,6 +488,11 @@ int rcv_conv3x3(rcv_handle* h, const rcv_op* op, void* stream);
 int rcv_convT3x3s2(rcv_handle* h, const rcv_op* op, void* stream);
 /* filter gradients of both (aten::convolution_backward).                                        */
 int rcv_wgrad3x3(rcv_handle* h, const rcv_op* op, void* stream);
+/* nn.Conv2d(k=5, pad=2) of the classifiers built with kernelSize / size = 5 (model.py:256-267 Classifier, model.py:403-414
+ * UltClassifier; labelPropTrain.py:90-92 builds PB_FCN with kernelSize 5): forward and data gradient (RCV_OP_CONV5).          */
+int rcv_conv5x5(rcv_handle* h, const rcv_op* op, void* stream);
+/* its filter and bias gradient (RCV_OP_WGRAD5; aten::convolution_backward of model.py:256-267, model.py:403-414).           */
+int rcv_wgrad5x5(rcv_handle* h, const rcv_op* op, void* stream);
 
 /* nn.BatchNorm2d train-mode statistics -> normalisation constants (model.py:113,116,189,192).   *
  *   part [n_part][2][C] -> scale,shift (float[5][C] slot layout c0,c1), mean, istd, running.    */

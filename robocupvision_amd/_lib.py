@@ -37,6 +37,7 @@ OP_RESIZE_U8 = 51           # OP_BATCH_PREP's resize stage alone: uint8 NHWC byt
 OP_BATCH_PREP_IDX = 52      # OP_BATCH_PREP whose image b is store[index[b]], the index in device memory (rcv.h RCV_OP_BATCH_PREP_IDX)
 OP_RGB_PREP_IDX = 53        # OP_RGB_PREP whose image b is store[index[b]]: trainer.py:75-123's loader from a resident store (rcv.h RCV_OP_RGB_PREP_IDX)
 OP_LP_PAIR_PREP = 54        # both frames of a LabelProp pair from the store -> the 8-channel input of labelPropTrain.py:36-66, 162-193 (rcv.h RCV_OP_LP_PAIR_PREP)
+OP_CONV5, OP_WGRAD5, OP_WGRAD5_REDUCE, OP_PACK5 = 55, 56, 57, 58      # the 5x5 classifier convolution family (rcv.h RCV_OP_CONV5 ..., csrc/conv5.hip)
 PRUNE_MAX_RATIO, PRUNE_STD_SEARCH, PRUNE_SMALLEST_K = range(3)      # i[AUX0] of OP_PRUNE: pruneModelNew / pruneModel / pruneModel2
 PRUNE_MAX_ITER = 4096
 PRUNE_ST_OK, PRUNE_ST_NO_END, PRUNE_ST_ALL_ZERO, PRUNE_ST_BAD_JOB = range(4)
@@ -82,7 +83,7 @@ EXPORTS = [
     "rcv_bnn_stage_fwd", "rcv_bnn_stage_bwd", "rcv_bnn_head_fwd", "rcv_bnn_head_bwd",
     "rcv_sgd_step_pruned", "rcv_prune_check", "rcv_prune", "rcv_find_objects", "rcv_rgb_prep",
     "rcv_farneback_flow", "rcv_update_labels", "rcv_object_patches", "rcv_resize_u8", "rcv_batch_prep_indexed",
-    "rcv_rgb_prep_indexed", "rcv_lp_pair_prep",
+    "rcv_rgb_prep_indexed", "rcv_lp_pair_prep", "rcv_conv5x5", "rcv_wgrad5x5",
 ]
 
 
@@ -154,6 +155,9 @@ def load():
         for name in ("rcv_conv3x3", "rcv_convT3x3s2", "rcv_wgrad3x3", "rcv_bnn_stage_fwd", "rcv_bnn_stage_bwd", "rcv_bnn_head_fwd",
                      "rcv_bnn_head_bwd"):
             getattr(lib, name).argtypes = [C.c_void_p, C.POINTER(RcvOp), C.c_void_p]
+        for name in ("rcv_conv5x5", "rcv_wgrad5x5"):
+            if hasattr(lib, name):      # (RCV_LIBRARY may name the build of an older revision: scripts/plan_diff.sh, scripts/ab.sh)
+                getattr(lib, name).argtypes = [C.c_void_p, C.POINTER(RcvOp), C.c_void_p]
         _lib = lib
     return _lib
 

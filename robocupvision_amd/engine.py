@@ -256,6 +256,7 @@ class _Lowering:
 
         self.jobs: List[L.RcvPackJob] = []          # weight packing table (all layers, one launch per forward)
         self.pre: List[L.RcvOp] = []                # eval mode: running statistics -> constants, ahead of everything else
+        self.pack5: List[L.RcvOp] = []              # RCV_OP_PACK5 records of a 5x5 classifier (head of the forward list, behind `pre`)
         self.bn_finalize_flags = L.F_TRAINING if training else 0
         self.batch_at: Dict[int, int] = {}          # index of a folded reduction -> index of the launch that now carries it
         self._late: List[tuple] = []                # side-stream ops of the node being lowered, emitted behind its data-gradient op
@@ -506,13 +507,35 @@ class _Lowering:
             self.fwd.append(op)
             self.fwd.append(L.make_op(L.OP_NHWC_TO_NCHW, 0, n=self.N, h=src.H, w=src.W, cin=CLS3_PAD, cout=Cout, p_in=node.t["z"].data_ptr(),
                                  p_bias=_ptr(b), p_out=logits.data_ptr()))
+        elif tuple(w.shape[2:]) == (5, 5) and Cout <= CLS3_PAD:
+            # kernelSize / classSize = 5 (labelPropTrain.py:90-92): the 5x5 conv with the class channels padded to 8, then the 3x3 tail
+            self.fwd.append(self.cls5_conv(node, src, w))
+            self.fwd.append(L.make_op(L.OP_NHWC_TO_NCHW, 0, n=self.N, h=src.H, w=src.W, cin=CLS3_PAD, cout=Cout, p_in=node.t["z"].data_ptr(),
+                                 p_bias=_ptr(b), p_out=logits.data_ptr()))
         else:
-            raise L.RcvError("classifier kernels %s with %d classes are not built (1x1, or 3x3 with <= %d classes)"
+            raise L.RcvError("classifier kernels %s with %d classes are not built (1x1, or 3x3 / 5x5 with <= %d classes)"
                              % (tuple(w.shape[2:]), Cout, CLS3_PAD))
         node.out = Value("plain", logits, Cout, src.H, src.W, None, node)
         self.plan.logits = logits
         assert self.fwd[-1].p[L.RCV_P_OUT] == logits.data_ptr()
         self.plan.logits_slots = [(len(self.fwd) - 1, L.RCV_P_OUT)]
+
+    def add_pack5(self, w, flip: bool):
+        """The 25-tap filter of a 5x5 classifier (RCV_OP_PACK5): [25][Cin][16] for the forward, [25][8][16] flipped for the data gradient.
+        The records join the head of the forward list, next to the pack launch of the 3x3 filters."""
+        Cout, Cin = w.shape[0], w.shape[1]
+        dst = self.eng._zeros(self.plan, 25 * (CLS3_PAD if flip else Cin) * 16)
+        self.pack5.append(L.make_op(L.OP_PACK5, L.F_FLIP if flip else 0, cin=Cin, cout=Cout, p_in=w.data_ptr(), p_out=dst.data_ptr()))
+        return dst
+
+    def cls5_conv(self, node: _Node, src: Value, w) -> L.RcvOp:
+        """The conv record of a 5x5 classifier: load(src) -> z, NHWC with the class channels padded to CLS3_PAD."""
+        node.t["wp"] = self.add_pack5(w, False)
+        node.t["z"] = self.eng._alloc(self.plan, self.N, src.H, src.W, CLS3_PAD)
+        op = L.make_op(L.OP_CONV5, 0, n=self.N, h=src.H, w=src.W, cin=w.shape[1], cout=CLS3_PAD, ho=src.H, wo=src.W, stride=1, dil=1,
+                       inmode=src.load_mode, p_in_c=_ptr(src.consts), p_w=node.t["wp"].data_ptr(), p_out=node.t["z"].data_ptr())
+        op.p[L.RCV_P_IN] = self.bind_in(self.fwd, src, L.RCV_P_IN) or None
+        return op
 
     def fwd_cls_labels(self, node: _Node, src: Value, w, b):
         """The classifier node of an eval-labels plan: RCV_OP_CLS_LABEL in place of RCV_OP_CLS_FWD (1x1) resp. of RCV_OP_NHWC_TO_NCHW
@@ -537,8 +560,12 @@ class _Lowering:
             self.fwd.append(op)
             self.fwd.append(L.make_op(L.OP_CLS_LABEL, 0, cin=CLS3_PAD, inmode=L.CLS_LABEL_LOGITS, p_in=node.t["z"].data_ptr(), p_bias=_ptr(b),
                                       **dims))
+        elif tuple(w.shape[2:]) == (5, 5) and Cout <= CLS3_PAD:
+            self.fwd.append(self.cls5_conv(node, src, w))
+            self.fwd.append(L.make_op(L.OP_CLS_LABEL, 0, cin=CLS3_PAD, inmode=L.CLS_LABEL_LOGITS, p_in=node.t["z"].data_ptr(), p_bias=_ptr(b),
+                                      **dims))
         else:
-            raise L.RcvError("classifier kernels %s with %d classes are not built (1x1, or 3x3 with <= %d classes)"
+            raise L.RcvError("classifier kernels %s with %d classes are not built (1x1, or 3x3 / 5x5 with <= %d classes)"
                              % (tuple(w.shape[2:]), Cout, CLS3_PAD))
         node.out = Value("plain", None, Cout, src.H, src.W, None, node)
         self.plan.label_op = len(self.fwd) - 1
@@ -693,12 +720,29 @@ class _Lowering:
         src = self.ref(d["src"])
         w, b = d["weight"], d.get("bias")
         Cout, Cin = w.shape[0], w.shape[1]
-        if "z" in node.t:      # 3x3 classifier: NCHW dlogits -> padded NHWC, then the ordinary filter / data gradients
+        if "z" in node.t:      # 3x3 / 5x5 classifier: NCHW dlogits -> padded NHWC, then the ordinary filter / data gradients
+            five = tuple(w.shape[2:]) == (5, 5)
             if src.input_index is not None:
-                raise L.RcvError("the 3x3 classifier cannot read a graph input directly")
+                raise L.RcvError("the %s classifier cannot read a graph input directly" % ("5x5" if five else "3x3"))
             g8 = self.eng._alloc(self.plan, self.N, src.H, src.W, CLS3_PAD)
             self.plan.dlogits_slots.append((len(self.bwd), L.RCV_P_IN))
             self.bwd.append(L.make_op(L.OP_NCHW_TO_NHWC, 0, n=self.N, h=src.H, w=src.W, cin=Cout, cout=CLS3_PAD, p_out=g8.data_ptr()))
+            if five:       # the same three steps on the 25-tap records (csrc/conv5.hip)
+                wop = L.make_op(L.OP_WGRAD5, (L.F_BIAS if b is not None else 0), n=self.N, h=src.H, w=src.W, cin=Cin, ho=src.H, wo=src.W,
+                                cout=CLS3_PAD, stride=1, dil=1, inmode=src.load_mode, inmode2=L.LOAD_PLAIN,
+                                p_in=src.buf.data_ptr(), p_in_c=_ptr(src.consts), p_in2=g8.data_ptr())
+                self.eng._workspace(self.plan, wop)
+                self.bwd.append(wop)
+                self.bwd.append(L.make_op(L.OP_WGRAD5_REDUCE, 0, cin=Cin, cout=Cout, nsplit=wop.i[L.RCV_I_NSPLIT],
+                                     p_part=wop.p[L.RCV_P_PART], p_out=self.fl.grad_ptr(w),
+                                     p_bias=(self.fl.grad_ptr(b) if b is not None else 0)))
+                if src.needs_grad:
+                    node.t["wd"] = self.add_pack5(w, True)
+                    dop = L.make_op(L.OP_CONV5, 0, n=self.N, h=src.H, w=src.W, cin=CLS3_PAD, cout=Cin, ho=src.H, wo=src.W, stride=1, dil=1,
+                                    inmode=L.LOAD_PLAIN, p_in=g8.data_ptr(), p_w=node.t["wd"].data_ptr())
+                    self.grad_target(src, dop, src.H, src.W)
+                    self.bwd.append(dop)
+                return
             wop = L.make_op(L.OP_WGRAD, (L.F_BIAS if b is not None else 0), n=self.N, h=src.H, w=src.W, cin=Cin, ho=src.H, wo=src.W,
                             cout=CLS3_PAD, stride=1, dil=1, inmode=src.load_mode, inmode2=L.LOAD_PLAIN,
                             p_in=src.buf.data_ptr(), p_in_c=_ptr(src.consts), p_in2=g8.data_ptr())
@@ -967,7 +1011,7 @@ class _Lowering:
         plan.bwd_marks = marks if training else []
 
         # ---- head of the forward list: running statistics -> constants (eval), then the pack launch (whose jobs may scale by them) ----
-        head = list(self.pre)
+        head = list(self.pre) + self.pack5
         if self.jobs:        # (a graph without 3x3 filters -- a lone 1x1 classifier -- packs nothing)
             table = (L.RcvPackJob * len(self.jobs))(*self.jobs)
             host = torch.frombuffer(bytearray(bytes(table)), dtype=torch.uint8)
@@ -989,7 +1033,7 @@ class _Lowering:
         # second HIP stream inside rcv_run (measured -4 % step time: their latency-bound phases fill the other kernels' gaps)
         if SIDE_STREAM_WGRAD:
             for op in bwd:
-                if op.kind in (L.OP_WGRAD, L.OP_WGRAD_REDUCE, L.OP_WGRAD_REDUCE_BATCH, L.OP_MEMSET):
+                if op.kind in (L.OP_WGRAD, L.OP_WGRAD_REDUCE, L.OP_WGRAD_REDUCE_BATCH, L.OP_MEMSET, L.OP_WGRAD5, L.OP_WGRAD5_REDUCE):
                     op.flags |= L.F_SIDE_STREAM
         plan.fwd = L.OpList(fwd)
         plan.bwd = L.OpList(bwd)
@@ -1232,6 +1276,14 @@ class Engine:
         elif k == L.OP_WGRAD:
             flops = 2.0 * 9 * cin * cout * n * ho * wo
             nbytes = 4.0 * (px * cin * two(i[L.RCV_I_INMODE]) + n * ho * wo * cout * two(i[L.RCV_I_INMODE2]))
+        elif k == L.OP_CONV5:
+            flops = 2.0 * 25 * cin * cout * px
+            nbytes = 4.0 * px * (cin + cout * (1 + resid + bstats))
+        elif k == L.OP_WGRAD5:
+            flops = 2.0 * 25 * cin * cout * px
+            nbytes = 4.0 * px * (cin + cout)
+        elif k == L.OP_WGRAD5_REDUCE:
+            nbytes = 4.0 * i[L.RCV_I_NSPLIT] * (25 * 8 * 16 + 8) + 4.0 * 25 * cin * cout
         elif k == L.OP_WGRAD_REDUCE:
             nbytes = 4.0 * i[L.RCV_I_NSPLIT] * (9 * _round_up(cout, 16) * max(_round_up(cin, 4), 4)) + 4.0 * 9 * cin * cout
         elif k == L.OP_WGRAD_REDUCE_BATCH:

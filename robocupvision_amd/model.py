@@ -324,14 +324,20 @@ class LevelDown(nn.Module):
         return x
 
 
+POOLED_5X5 = ("the pooled patch-classification heads are built for a 1x1 classifier; a 5x5 classifier behind the pool is not built "
+              "(classTrainer.py uses kernel size 1)")
+
+
 class UltClassifier(nn.Module):
     """1x1 (or, for the v2 net, 3x3) classifier (model.py:403-414).  The pooled variant (AdaptiveAvgPool2d(1), Dropout2d, 1x1
     classifier: PB_FCN_2.classifier) is the patch-classification head of classTrainer.py, run as PB_FCN_2(classify=True)'s graph."""
 
     def __init__(self, inplanes, nClass, pool, dropout=0.5, size=1):
         super().__init__()
-        if size not in (1, 3):
-            raise NotImplementedError("classifier kernel sizes 1 and 3 are built (got %d)" % size)
+        if size not in (1, 3, 5):
+            raise NotImplementedError("classifier kernel sizes 1, 3 and 5 are built (got %d)" % size)
+        if pool and size == 5:
+            raise NotImplementedError(POOLED_5X5)
         self.pooled = bool(pool)
         self.layers = nn.Sequential()
         if pool:        # patch-classification head (PB_FCN_2.classifier): the containers hold the parameters and the dropout rate
@@ -927,6 +933,8 @@ class Classifier(nn.Module):
         """The pooled head as the graph's last node (model.py:262-265): MaxPool2d(poolSize) (floor), then the classifier."""
         if self.pool is None:
             raise L.RcvError("this Classifier has no pooled head")
+        if tuple(self.classifier.kernel_size) == (5, 5):
+            raise NotImplementedError(POOLED_5X5)
         k = self.pool.kernel_size
         return {"op": "pool_cls", "src": src, "pool": ("max", k if isinstance(k, int) else k[0]), "weight": self.classifier.weight,
                 "bias": self.classifier.bias, "dropout": 0.0}
