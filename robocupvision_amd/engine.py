@@ -274,11 +274,12 @@ class _Lowering:
             return 0
         return v.buf.data_ptr()
 
-    def add_pack(self, param, D0, D1, rows_from_d1, flip, merged=False, wino=0, scale: Optional[torch.Tensor] = None):
-        """wino: the layout rcv_op_filter_layout asked for (0 plain, 2 Winograd, 3 split-bf16: three bf16 per value, rows padded to 32)."""
+    def add_pack(self, param, D0, D1, rows_from_d1, flip, merged=False, wino=0, scale: Optional[torch.Tensor] = None, min_rows: int = 0):
+        """wino: the layout rcv_op_filter_layout asked for (0 plain, 2 Winograd, 3 split-bf16: three bf16 per value, rows padded to 32).
+        min_rows: the contraction channels of the record that reads the filter where they exceed the parameter's (zero rows between)."""
         wino = int(wino)
         merged = bool(merged) or wino == 4
-        rows = D1 if rows_from_d1 else D0
+        rows = max(D1 if rows_from_d1 else D0, min_rows)
         cols = D0 if rows_from_d1 else D1
         split = wino in (3, 4, 5)   # three bf16 per value, k = tap * rows + row in steps of 32 (zero beyond the last tap); 5: 16-row chunks, 5 steps each
         rp, cp = _round_up(rows, (16 if wino == 5 else (32 if rows > 32 else 8)) if split else 4), _round_up(cols * (4 if merged else 1), 16)
@@ -752,7 +753,8 @@ class _Lowering:
                                  p_part=wop.p[L.RCV_P_PART], p_out=self.fl.grad_ptr(w),
                                  p_bias=(self.fl.grad_ptr(b) if b is not None else 0)))
             if src.needs_grad:
-                node.t["wd"] = self.add_pack(w, Cout, Cin, False, True)
+                # (the record contracts over CLS3_PAD channels: the tap pitch of the filter is CLS3_PAD rows for every class count)
+                node.t["wd"] = self.add_pack(w, Cout, Cin, False, True, min_rows=CLS3_PAD)
                 dop = L.make_op(L.OP_CONV, 0, n=self.N, h=src.H, w=src.W, cin=CLS3_PAD, cout=Cin, ho=src.H, wo=src.W, stride=1, dil=1,
                                 inmode=L.LOAD_PLAIN, p_in=g8.data_ptr(), p_w=node.t["wd"].data_ptr())
                 self.grad_target(src, dop, src.H, src.W)

@@ -1,7 +1,9 @@
 """Shapes, load modes and record builders of the dilated and decoder-order cases of tests/test_gpu_kernels.py: the conv / transposed-conv
 / filter-gradient records that PB_FCN, PB_FCN_2 and LabelProp emit in training (engine.py bwd_conv / bwd_up; model.py ConvPoolSimple /
 ConvPool) and the ROBO-UNet / U-Net step does not -- dilation 2 on NHWC operands, the `bn_relu` order (gathered operand
-RCV_LOAD_AFFINE_RELU, gradient RCV_LOAD_GRAD_DEC) and the `relu` order (RCV_LOAD_PLAIN, RCV_LOAD_GRAD_ENC with the rows (1, 0, 0)).
+RCV_LOAD_AFFINE_RELU, gradient RCV_LOAD_GRAD_DEC) and the `relu` order (RCV_LOAD_PLAIN, RCV_LOAD_GRAD_ENC with the rows (1, 0, 0)) --
+and of the records behind the packer's flip and scale branches: stride-1 data gradients, the 3x3 classifier's data gradient, folded
+inference records.
 
 Records only, no tensors and no device: tests/test_lib_abi.py plans every one of them on the planning handle and pins the kernel
 labels they reach, so that a planner change which moves them onto another kernel shows there and not as a silent loss of coverage."""
@@ -56,6 +58,86 @@ def tconv_record(shape, mode_name, layout, **ptrs):
     N, H, W, Cin, Cout = shape
     return L.make_op(L.OP_TCONV, L.F_BIAS, n=N, h=H, w=W, cin=Cin, cout=Cout, ho=2 * H, wo=2 * W, stride=2, dil=1,
                      inmode=TCONV_RECORD_MODES[mode_name], aux0=layout, **ptrs)
+
+
+# ------------------------------------------------------------------------------------------ flipped and scaled filters
+# The records whose filter the packer flips (rcv_pack_job.flip = 1: the stride-1 data gradients of engine.py bwd_conv and of the 3x3
+# classifier) or scales per output channel (rcv_pack_job.scale: inference BatchNorm folding, engine.py fwd_conv / fwd_up).
+# Stride-1 data gradients: shapes read as the RECORD's channels (cin = the layer's Cout, cout = the layer's Cin)
+DGRAD_SHAPES = [sh for sh in DILATED_CONV_SHAPES + STRIDE1_CONV_SHAPES if sh[5] == 1] + \
+    [(3, 5, 7, 64, 64, 1, 1), (2, 37, 53, 128, 64, 1, 1), (2, 37, 53, 32, 16, 1, 1)]
+DGRAD_MODES = {"grad_dec": L.LOAD_GRAD_DEC, "grad_enc": L.LOAD_GRAD_ENC, "grad_enc_relu": L.LOAD_GRAD_ENC}     # (the last: rows (1, 0, 0))
+# (shape, layout) -> label as the planner answers for 256 CUs, under every load of DGRAD_MODES (dilation 2: DILATED_CONV_LABELS)
+DGRAD_LABELS = {
+    ((4, 30, 40, 64, 64, 1, 1), 0): "conv_dma<1,5,4,1,4>", ((4, 30, 40, 64, 64, 1, 1), 2): "conv_wino<64,80>",
+    ((4, 30, 40, 64, 64, 1, 1), 3): "conv_bf3<64,160>",
+    ((4, 30, 40, 32, 32, 1, 1), 0): "convs_mfma<2,3,32>", ((4, 30, 40, 32, 32, 1, 1), 3): "convn_bf3<32,2,3>",
+    ((2, 37, 53, 16, 16, 1, 1), 0): "convs_mfma<1,5,16>", ((2, 37, 53, 16, 16, 1, 1), 3): "convn_bf3<16,1,5>",
+    ((3, 5, 7, 64, 64, 1, 1), 0): "conv_dma<1,5,4,1,4>", ((3, 5, 7, 64, 64, 1, 1), 2): "conv_wino<64,80>",
+    ((3, 5, 7, 64, 64, 1, 1), 3): "conv_bf3<64,160>",
+    ((2, 37, 53, 128, 64, 1, 1), 0): "conv_dma<1,5,4,1,4>", ((2, 37, 53, 128, 64, 1, 1), 2): "conv_wino<64,80>",
+    ((2, 37, 53, 128, 64, 1, 1), 3): "conv_bf3<64,160>",
+    ((2, 37, 53, 32, 16, 1, 1), 0): "convs_mfma<1,3,32>", ((2, 37, 53, 32, 16, 1, 1), 3): "convn_bf3<32,1,5>",
+}
+DGRAD_LABELS.update({(sh, 0): lab for sh, lab in DILATED_CONV_LABELS.items()})
+
+
+def dgrad_record(shape, mode_name, layout, **ptrs):
+    N, H, W, Cin, Cout, s, d = shape
+    return L.make_op(L.OP_CONV, L.F_RESID, n=N, h=H, w=W, cin=Cin, cout=Cout, ho=H, wo=W, stride=1, dil=d, inmode=DGRAD_MODES[mode_name],
+                     stats=L.STATS_NONE, aux0=layout, **ptrs)
+
+
+# the 3x3 classifier's data gradient: the class gradient in 8 NHWC channels (zero beyond the classes) -> the classifier's input channels
+CLS_DGRAD_PLANES = [(2, 37, 53), (1, 9, 11)]
+CLS_DGRAD_CLASSES = [1, 3, 5, 8]
+CLS_DGRAD_COUT = [8, 16]
+CLS_DGRAD_LABELS = {((2, 37, 53), 8): "convs_mfma<1,5,8>", ((2, 37, 53), 16): "convs_mfma<1,5,8>",
+                    ((1, 9, 11), 8): "convs_mfma<1,3,8>", ((1, 9, 11), 16): "convs_mfma<1,3,8>"}
+
+
+def cls_dgrad_record(plane, cout, **ptrs):
+    N, H, W = plane
+    return L.make_op(L.OP_CONV, L.F_RESID, n=N, h=H, w=W, cin=8, cout=cout, ho=H, wo=W, stride=1, dil=1, inmode=L.LOAD_PLAIN, **ptrs)
+
+
+# folded inference records: relu(op(x, w * scale) + bias) (+ the skip tensor behind a transposed conv); one conv shape per family
+# (stride 1 wide and narrow, stride 2, dilation 2) and the image layer in the reference's own layout
+FOLDED_CONV_CASES = [((4, 30, 40, 64, 64, 1, 1), "plain"), ((2, 37, 53, 16, 16, 1, 1), "plain"), ((2, 30, 40, 32, 64, 2, 1), "plain"),
+                     ((2, 37, 53, 64, 128, 1, 2), "plain"), ((2, 48, 64, 3, 8, 1, 1), "nchw")]
+FOLDED_TCONV_SHAPES = [(2, 15, 20, 128, 64), (2, 24, 32, 32, 16), (2, 20, 28, 16, 16), (1, 5, 6, 128, 128)]
+# (shape, load, layout) / (shape, layout) -> label as the planner answers for 256 CUs
+FOLDED_CONV_LABELS = {
+    ((4, 30, 40, 64, 64, 1, 1), "plain", 0): "conv_dma<1,5,4,1,4>", ((4, 30, 40, 64, 64, 1, 1), "plain", 2): "conv_wino<64,80>",
+    ((4, 30, 40, 64, 64, 1, 1), "plain", 3): "conv_bf3<64,160>",
+    ((2, 37, 53, 16, 16, 1, 1), "plain", 0): "convs_mfma<1,5,16>", ((2, 37, 53, 16, 16, 1, 1), "plain", 3): "convn_bf3<16,1,5>",
+    ((2, 30, 40, 32, 64, 2, 1), "plain", 0): "conv_small<1>", ((2, 30, 40, 32, 64, 2, 1), "plain", 5): "conv2_bf3<64,160>",
+    ((2, 37, 53, 64, 128, 1, 2), "plain", 0): "conv_dma<1,5,4,1,4>", ((2, 48, 64, 3, 8, 1, 1), "nchw", 0): "conv_first<1>",
+}
+FOLDED_TCONV_LABELS = {
+    ((2, 15, 20, 128, 64), 0): "tconva_dma<1,5,4,1,4>", ((2, 24, 32, 32, 16), 1): "tconvms_mfma<4,3,32>",
+    ((2, 24, 32, 32, 16), 4): "tconvn_bf3<32,4,3>", ((2, 20, 28, 16, 16), 1): "tconvms_mfma<4,3,16>",
+    ((1, 5, 6, 128, 128), 0): "tconva_dma<1,5,4,1,4>",
+}
+
+
+def folded_conv_record(shape, load, layout, **ptrs):
+    N, H, W, Cin, Cout, s, d = shape
+    return L.make_op(L.OP_CONV, L.F_BIAS | L.F_RELU, n=N, h=H, w=W, cin=Cin, cout=Cout, ho=(H - 1) // s + 1, wo=(W - 1) // s + 1, stride=s,
+                     dil=d, inmode={"plain": L.LOAD_PLAIN, "nchw": L.LOAD_NCHW}[load], aux0=layout, **ptrs)
+
+
+def tconv_layouts(Cin, Cout, merged_max_cout):
+    """Filter layouts a transposed-conv record is run under (as test_transposed_conv_kernels_vs_fp64 enumerates them): 0 or 1 (merged
+    parity, up to engine.MERGED_TCONV_MAX_COUT output channels), and 4 where the split-bf16 narrow kernel is built."""
+    merged = 1 if Cout <= merged_max_cout else 0
+    return [merged] + ([4] if merged and (Cin, (4 * Cout + 15) // 16 * 16) in ((16, 32), (32, 64)) else [])
+
+
+def folded_tconv_record(shape, layout, **ptrs):
+    N, H, W, Cin, Cout = shape
+    return L.make_op(L.OP_TCONV, L.F_BIAS | L.F_RELU | L.F_RESID, n=N, h=H, w=W, cin=Cin, cout=Cout, ho=2 * H, wo=2 * W, stride=2, dil=1,
+                     inmode=L.LOAD_PLAIN, aux0=layout, **ptrs)
 
 
 # ------------------------------------------------------------------------------------------ the layer shapes of the networks

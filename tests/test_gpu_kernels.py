@@ -8,7 +8,11 @@ The records only PB_FCN, PB_FCN_2 and LabelProp emit in training -- dilation 2 o
 conv -> BatchNorm -> ReLU order (RCV_LOAD_AFFINE_RELU, RCV_LOAD_GRAD_DEC) and of relu(conv) without a BatchNorm (RCV_LOAD_PLAIN,
 RCV_LOAD_GRAD_ENC with the rows (1, 0, 0)), the fp32-instruction filter gradients under RCV_F_MFMA_FP32 with these loads -- are the
 cases of tests/conv_record_cases.py, at the same bars; measured <= 1.41e-6 (convolutions, dilation 2, 128 input channels), <= 3.3e-7
-(Winograd), <= 1.35e-7 (filter gradients), <= 6.1e-8 (bias gradients); per kernel label in the docstrings of the tests."""
+(Winograd), <= 1.35e-7 (filter gradients), <= 6.1e-8 (bias gradients); per kernel label in the docstrings of the tests.
+
+The records whose filter the packer flips (rcv_pack_job.flip: the stride-1 data gradients, the 3x3 classifier's data gradient) or scales
+per output channel (rcv_pack_job.scale: inference BatchNorm folding) run at the same bars, the folded ones also per channel against the
+unscaled record; measured <= 1.86e-6 (data gradients), <= 1.27e-6 (folded).  The packer's output itself: tests/test_gpu_pack.py."""
 import os
 import sys
 
@@ -474,6 +478,189 @@ def test_tiny_plane_conv_vs_fp64(N, H, W, Cin, Cout, s, d, mode_name, flags):
     torch.cuda.synchronize()
     err = float((out.double().cpu() - ref).abs().max() / ref.abs().max())
     assert err <= 3e-6, (label, err)
+
+
+# ------------------------------------------------------------------------------------------ flipped and scaled filters
+def _packed_filter(L, wd, D0, D1, rows_from_d1, flip, rp, cp, nfl, layout, scale=None):
+    """One RCV_OP_PACK record (a table of one job) for the parameter `wd` on the device; (record, buffers to keep alive)."""
+    wp = torch.zeros(nfl, device=DEV)
+    job = L.RcvPackJob()
+    job.src, job.dst, job.D0, job.D1 = wd.data_ptr(), wp.data_ptr(), D0, D1
+    job.rows_from_d1, job.flip, job.rows_pad, job.cols_pad, job.merged = rows_from_d1, flip, rp, cp, layout
+    job.scale = scale.data_ptr() if scale is not None else None
+    table = torch.frombuffer(bytearray(bytes((L.RcvPackJob * 1)(job))), dtype=torch.uint8).to(DEV)
+    return L.make_op(L.OP_PACK, 0, count=1, aux0=16 * rp * cp, p_in=table.data_ptr()), wp, table
+
+
+@pytest.mark.parametrize("shape", RC.DGRAD_SHAPES, ids=lambda s: "-".join(map(str, s)))
+@pytest.mark.parametrize("mode_name", list(RC.DGRAD_MODES))
+def test_stride1_data_gradient_records_vs_fp64(shape, mode_name):
+    """The stride-1 data gradient as engine.py bwd_conv emits it: an RCV_OP_CONV record over the layer's OUTPUT channels whose filter
+    is the layer's own parameter packed (D0 = cin, D1 = cout, rows_from_d1 = 0, flip = 1) -- the 180-degree-rotated filter, under every
+    layout the record can ask for (0, Winograd, split-bf16), at dilation 1 and 2.  Shapes are the record's channels.  Loads:
+    RCV_LOAD_GRAD_DEC and RCV_LOAD_GRAD_ENC with random constants, RCV_LOAD_GRAD_ENC with the rows (1, 0, 0); all with the residual.
+    Reference: torch.nn.grad.conv2d_input in float64 on the transformed fp32 operands, plus the residual.  Bars 3e-6 (2e-6 Winograd).
+    Measured (MI355X, largest over the three loads): dilation 1 conv_dma<1,5,4,1,4> 1.86e-6 (128 -> 64 channels, grad_dec),
+    conv_wino<64,80> 4.0e-7, conv_bf3<64,160> 1.07e-6, convs_mfma<2,3,32> 5.0e-7, <1,3,32> 6.1e-7, <1,5,16> 3.4e-7, convn_bf3<32,2,3>
+    4.5e-7, <32,1,5> 4.7e-7, <16,1,5> 2.7e-7; dilation 2 conv_dma<1,5,4,1,4> 1.32e-6, conv_mfma<1,5,2,2,8> 7.4e-7, convs_mfma<1,3,32>
+    4.8e-7, <1,5,16> 2.9e-7, <1,5,8> 2.7e-7, <2,3,32> 7.0e-8.  By load: grad_dec 1.86e-6, grad_enc 1.04e-6, grad_enc (1, 0, 0) 8.2e-7."""
+    from robocupvision_amd import _lib as L
+    h = L.handle(0)
+    N, H, W, Cin, Cout, s, d = shape
+    mode = RC.DGRAD_MODES[mode_name]
+    gen = torch.Generator().manual_seed(6000 + H * W + Cin + 7 * d)
+    g, ga, c = _rand(gen, N, H, W, Cin), _rand(gen, N, H, W, Cin), _rand(gen, 5, Cin, scale=0.5)
+    w, resid = _rand(gen, Cin, Cout, 3, 3, scale=0.1), _rand(gen, N, H, W, Cout)       # the layer's parameter: [its Cout][its Cin][3][3]
+    if mode_name == "grad_enc_relu":
+        c = _relu_grad_rows(Cin)
+    ref = torch.nn.grad.conv2d_input((N, Cout, H, W), w.double(), _load_fp64(mode, g, ga, c, L).permute(0, 3, 1, 2).contiguous(), stride=1,
+                                     padding=d, dilation=d).permute(0, 2, 3, 1) + resid.double()
+    gd, gad, cd, wd, rd = (v.to(DEV) for v in (g, ga, c, w, resid))
+    for layout in RC.conv_layouts(Cin, Cout, 1, d):
+        rp, cp, nfl = _pack_dims(Cin, Cout, layout)
+        pack, wp, table = _packed_filter(L, wd, Cin, Cout, 0, 1, rp, cp, nfl, layout)
+        out = torch.full((N, H, W, Cout), float("nan"), device=DEV)
+        conv = RC.dgrad_record(shape, mode_name, layout, p_in=gd.data_ptr(), p_in_aux=gad.data_ptr(), p_in_c=cd.data_ptr(), p_w=wp.data_ptr(),
+                               p_out=out.data_ptr(), p_resid=rd.data_ptr())
+        lst = L.OpList([pack, conv])
+        label = lst.labels(h)[1]
+        assert label.startswith("conv_wino") == (layout == 2) and ("_bf3" in label) == (layout == 3), label
+        assert not label.startswith("conv_small"), label
+        lst.run(h, torch.cuda.current_stream().cuda_stream)
+        torch.cuda.synchronize()
+        err = float((out.double().cpu() - ref).abs().max() / ref.abs().max())
+        print(".dgrad %s %s %s: max error %.3e" % (label, shape, mode_name, err))
+        assert err <= (2e-6 if layout == 2 else 3e-6), (label, err)
+
+
+@pytest.mark.parametrize("plane", RC.CLS_DGRAD_PLANES, ids=lambda s: "-".join(map(str, s)))
+@pytest.mark.parametrize("cout", RC.CLS_DGRAD_COUT)
+@pytest.mark.parametrize("n_class", RC.CLS_DGRAD_CLASSES)
+def test_classifier_data_gradient_record_vs_fp64(plane, cout, n_class):
+    """The 3x3 classifier's data gradient (engine.py bwd_cls): the class gradient in 8 NHWC channels, zero beyond the classes as
+    RCV_OP_NCHW_TO_NHWC leaves them, through the parameter [classes][cout][3][3] packed flipped with its 1..8 class rows padded to 8.
+    RCV_LOAD_PLAIN, with the residual; 3e-6 of the largest entry.
+    Measured (MI355X): convs_mfma<1,5,8> (37 x 53) 2.97e-7, convs_mfma<1,3,8> (9 x 11) 2.69e-7, both at 8 classes; 1.3e-7 at 1 class."""
+    from robocupvision_amd import _lib as L
+    h = L.handle(0)
+    N, H, W = plane
+    gen = torch.Generator().manual_seed(6500 + H * W + cout + n_class)
+    g = torch.zeros(N, H, W, 8)
+    g[..., :n_class] = _rand(gen, N, H, W, n_class)
+    w, resid = _rand(gen, n_class, cout, 3, 3, scale=0.2), _rand(gen, N, H, W, cout)
+    ref = torch.nn.grad.conv2d_input((N, cout, H, W), w.double(), g[..., :n_class].double().permute(0, 3, 1, 2).contiguous(), stride=1,
+                                     padding=1).permute(0, 2, 3, 1) + resid.double()
+    gd, wd, rd = g.to(DEV), w.to(DEV), resid.to(DEV)
+    rp, cp = 8, (cout + 15) // 16 * 16
+    pack, wp, table = _packed_filter(L, wd, n_class, cout, 0, 1, rp, cp, 9 * rp * cp, 0)
+    out = torch.full((N, H, W, cout), float("nan"), device=DEV)
+    conv = RC.cls_dgrad_record(plane, cout, p_in=gd.data_ptr(), p_w=wp.data_ptr(), p_out=out.data_ptr(), p_resid=rd.data_ptr())
+    lst = L.OpList([pack, conv])
+    label = lst.labels(h)[1]
+    lst.run(h, torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    err = float((out.double().cpu() - ref).abs().max() / ref.abs().max())
+    print(".cls dgrad %s %s -> %d, %d classes: max error %.3e" % (label, plane, cout, n_class, err))
+    assert err <= 3e-6, (label, err)
+
+
+def _folded_errors(out, pre, ref):
+    """(max error relative to the largest entry; largest per-channel error, each channel relative to ITS largest |pre-ReLU reference|)."""
+    dlt = (out.double().cpu() - ref).abs()
+    C = ref.shape[-1]
+    per_channel = dlt.reshape(-1, C).max(0)[0] / pre.abs().reshape(-1, C).max(0)[0]
+    return float(dlt.max() / ref.abs().max()), float(per_channel.max())
+
+
+def _signed_scale(gen, C):
+    """+-[0.25, 4] per output channel: the range over which an eval-mode BatchNorm's gamma / sqrt(var + eps) moves, both signs."""
+    return (0.25 + 3.75 * torch.rand(C, generator=gen)) * (torch.randint(0, 2, (C,), generator=gen) * 2 - 1).float()
+
+
+@pytest.mark.parametrize("case", RC.FOLDED_CONV_CASES, ids=lambda c: "-".join(map(str, c[0])) + "-" + c[1])
+def test_folded_inference_records_vs_fp64(case):
+    """Inference BatchNorm folding at record level (engine.EVAL_FOLD_BN, fwd_conv): RCV_F_BIAS | RCV_F_RELU on a filter packed with a
+    per-output-channel scale in +-[0.25, 4], under every filter layout of the shape; RCV_LOAD_PLAIN, and RCV_LOAD_NCHW on the image
+    layer.  Reference: float64 relu(conv(x, w * scale) + bias).  Two criteria: the bar of the unscaled records relative to the tensor's
+    largest entry (3e-6, 2e-6 Winograd), and per channel -- the error of channel c relative to the largest |pre-ReLU reference| of
+    channel c, so that a small-scale channel cannot hide behind a large one: the worst channel within 1.5 x the same quantity of the
+    unscaled record (scale = NULL, same kernel, layout and operands) + 2^-23.
+    Measured (MI355X), worst channel scaled / unscaled: conv_dma<1,5,4,1,4> 1.27e-6 / 1.17e-6 (dilation 2: 1.14e-6 / 1.15e-6),
+    conv_wino<64,80> 4.2e-7 / 4.6e-7, conv_bf3<64,160> 1.12e-6 / 1.09e-6, convs_mfma<1,5,16> 5.3e-7 / 4.9e-7, convn_bf3<16,1,5> 3.6e-7 /
+    4.6e-7, conv_small<1> (stride 2) 2.8e-7 / 2.1e-7, conv2_bf3<64,160> 5.9e-7 / 5.1e-7, conv_first<1> 2.2e-7 / 2.8e-7; relative to the
+    largest entry <= 1.19e-6 (conv_dma), 3.5e-7 (conv_wino)."""
+    from robocupvision_amd import _lib as L
+    h = L.handle(0)
+    shape, load = case
+    N, H, W, Cin, Cout, s, d = shape
+    gen = torch.Generator().manual_seed(7000 + H * W + Cin + 7 * d)
+    Ho, Wo = (H - 1) // s + 1, (W - 1) // s + 1
+    x = _rand(gen, N, Cin, H, W) if load == "nchw" else _rand(gen, N, H, W, Cin)
+    w, bias, scale = _rand(gen, Cout, Cin, 3, 3, scale=0.1), _rand(gen, Cout), _signed_scale(gen, Cout)
+    x64 = x.double() if load == "nchw" else x.double().permute(0, 3, 1, 2)
+    refs = {}
+    for name, w64 in (("scaled", w.double() * scale.double()[:, None, None, None]), ("unscaled", w.double())):
+        pre = (F.conv2d(x64, w64, stride=s, padding=d, dilation=d) + bias.double()[None, :, None, None]).permute(0, 2, 3, 1)
+        refs[name] = (pre, F.relu(pre))
+    xd, wd, bd, sd = (v.to(DEV) for v in (x, w, bias, scale))
+    for layout in RC.conv_layouts(Cin, Cout, s, d):
+        rp, cp, nfl = _pack_dims(Cin, Cout, layout)
+        res = {}
+        for name, sc in (("scaled", sd), ("unscaled", None)):
+            pack, wp, table = _packed_filter(L, wd, Cout, Cin, 1, 0, rp, cp, nfl, layout, scale=sc)
+            out = torch.full((N, Ho, Wo, Cout), float("nan"), device=DEV)
+            conv = RC.folded_conv_record(shape, load, layout, p_in=xd.data_ptr(), p_w=wp.data_ptr(), p_bias=bd.data_ptr(), p_out=out.data_ptr())
+            lst = L.OpList([pack, conv])
+            label = lst.labels(h)[1]
+            assert label.startswith("conv_wino") == (layout == 2) and ("_bf3" in label) == (layout in (3, 5)), label
+            lst.run(h, torch.cuda.current_stream().cuda_stream)
+            torch.cuda.synchronize()
+            res[name] = _folded_errors(out, *refs[name])
+        print(".folded %s %s %s: max error %.3e (unscaled %.3e); worst channel %.3e (unscaled %.3e)" %
+              (label, shape, load, res["scaled"][0], res["unscaled"][0], res["scaled"][1], res["unscaled"][1]))
+        assert res["scaled"][0] <= (2e-6 if layout == 2 else 3e-6), (label, res)
+        assert res["scaled"][1] <= 1.5 * res["unscaled"][1] + 2.0 ** -23, (label, res)
+
+
+@pytest.mark.parametrize("shape", RC.FOLDED_TCONV_SHAPES, ids=lambda s: "-".join(map(str, s)))
+def test_folded_inference_transposed_records_vs_fp64(shape):
+    """The folded decoder block (engine.py fwd_up): RCV_F_BIAS | RCV_F_RELU | RCV_F_RESID on a transposed-conv filter packed with a
+    per-output-channel scale -- relu(convT(x, w * scale) + bias) + skip in one launch -- in layout 0 or 1 (merged parity) and 4 (its
+    split-bf16 form) where test_transposed_conv_kernels_vs_fp64 enumerates it.  The two criteria of
+    test_folded_inference_records_vs_fp64, at the bar of the unscaled transposed records (3e-6).
+    Measured (MI355X), worst channel scaled / unscaled: tconva_dma<1,5,4,1,4> 8.7e-7 / 1.00e-6 (128 -> 128: 1.08e-6 / 1.70e-6),
+    tconvms_mfma<4,3,32> 3.7e-7 / 3.4e-7, <4,3,16> 2.9e-7 / 3.2e-7, tconvn_bf3<32,4,3> 3.0e-7 / 3.7e-7; relative to the largest entry
+    <= 8.0e-7."""
+    from robocupvision_amd import _lib as L
+    from robocupvision_amd.engine import MERGED_TCONV_MAX_COUT
+    h = L.handle(0)
+    N, H, W, Cin, Cout = shape
+    gen = torch.Generator().manual_seed(7500 + H * W + Cin)
+    x, w, bias = _rand(gen, N, H, W, Cin), _rand(gen, Cin, Cout, 3, 3, scale=0.1), _rand(gen, Cout)
+    resid, scale = _rand(gen, N, 2 * H, 2 * W, Cout), _signed_scale(gen, Cout)
+    refs = {}
+    for name, w64 in (("scaled", w.double() * scale.double()[None, :, None, None]), ("unscaled", w.double())):
+        pre = F.conv_transpose2d(x.double().permute(0, 3, 1, 2), w64, bias.double(), stride=2, padding=1, output_padding=1).permute(0, 2, 3, 1)
+        refs[name] = (pre, F.relu(pre) + resid.double())
+    xd, wd, bd, rd, sd = (v.to(DEV) for v in (x, w, bias, resid, scale))
+    for layout in RC.tconv_layouts(Cin, Cout, MERGED_TCONV_MAX_COUT):
+        rp, cp, nfl = _pack_dims(Cin, Cout, layout, merged=layout in (1, 4))
+        res = {}
+        for name, sc in (("scaled", sd), ("unscaled", None)):
+            pack, wp, table = _packed_filter(L, wd, Cin, Cout, 0, 0, rp, cp, nfl, layout, scale=sc)
+            out = torch.full((N, 2 * H, 2 * W, Cout), float("nan"), device=DEV)
+            tconv = RC.folded_tconv_record(shape, layout, p_in=xd.data_ptr(), p_w=wp.data_ptr(), p_bias=bd.data_ptr(), p_out=out.data_ptr(),
+                                           p_resid=rd.data_ptr())
+            lst = L.OpList([pack, tconv])
+            label = lst.labels(h)[1]
+            assert ("_bf3" in label) == (layout == 4), label
+            lst.run(h, torch.cuda.current_stream().cuda_stream)
+            torch.cuda.synchronize()
+            res[name] = _folded_errors(out, *refs[name])
+        print(".folded %s %s: max error %.3e (unscaled %.3e); worst channel %.3e (unscaled %.3e)" %
+              (label, shape, res["scaled"][0], res["unscaled"][0], res["scaled"][1], res["unscaled"][1]))
+        assert res["scaled"][0] <= 3e-6, (label, res)
+        assert res["scaled"][1] <= 1.5 * res["unscaled"][1] + 2.0 ** -23, (label, res)
 
 
 # ------------------------------------------------------------------------------------------ epilogue statistics

@@ -550,6 +550,30 @@ def test_ragged_shapes_vs_oracle(ctor, B, H, W):
         assert rel <= tol, "grad %s vs oracle: relative L2 error %.3e" % (n, rel)
 
 
+@pytest.mark.parametrize("n_class", [2, 3, 4])
+def test_3x3_classifier_with_few_classes_vs_oracle(n_class):
+    """The v2 net (3x3 classifier) with 2..4 classes: the classifier's data gradient contracts over 8 padded class channels, and its
+    flipped filter must have that tap pitch for every class count (with the parameter's own 4 rows every gradient upstream of the
+    classifier was O(1) wrong; the 5-class nets of the other tests pad to 8 either way).  Bars of test_ragged_shapes_vs_oracle."""
+    ctor = dict(noScale=False, v2=True, classSize=3, levels=1, bellySize=2, nClass=n_class)
+    weights = CE_W[:n_class]
+    torch.manual_seed(12345678)
+    model = M.ROBO_UNet(**ctor)
+    st = O.TrainState(model.state_dict(), O.NetConfig(**ctor), ce_weight=weights)
+    x, t = O.synthetic_batch(2, 40, 56, n_class=n_class, seed=13)
+    ref = O.train_step(st, x, t, do_step=False)
+    res = hip_step(model.to(DEV), x.to(DEV), t.to(DEV), do_step=False, weights=weights)
+    close(res["pred"], ref["pred"], "logits vs oracle, %d classes" % n_class)
+    assert abs(res["ce"] - ref["ce"]) <= 1e-3 * abs(ref["ce"])
+    for n in st.names:
+        if n.startswith("upPart") and n.endswith("conv.bias"):
+            continue
+        g, r = res["grads"][n].double().cpu(), st.sd[n].grad.double()
+        rel = float((g - r).norm() / (r.norm() + 1e-30))
+        tol = 2e-2 if (n.endswith("conv.bias") or n.endswith("bn.weight") or n.endswith("bn.bias")) else 5e-3
+        assert rel <= tol, "grad %s vs oracle: relative L2 error %.3e" % (n, rel)
+
+
 def test_single_value_batchnorm_raises_like_the_reference():
     """Train-mode BatchNorm over ONE value per channel: PyTorch (hence the reference) raises ValueError; so do we."""
     model = M.ROBO_UNet(noScale=True).to(DEV).train()

@@ -172,3 +172,54 @@ def test_planner_routes_the_dilated_and_decoder_order_records():
                                 tconv={"tconva_dma", "tconvms_mfma", "tconvn_bf3"},
                                 wgrad={"wgrad_mfma", "wgrad_bf3", "wgradn_bf3"},
                                 stats={"conv_dma", "conv_mfma", "convs_mfma"}), reached[256]
+
+
+def test_planner_routes_the_flipped_and_folded_filter_records():
+    """Planner pin (no GPU) of the records behind the packer's flip and scale branches (tests/conv_record_cases.py; run against float64
+    by tests/test_gpu_kernels.py): the stride-1 data gradients under every filter layout and gradient load, the 3x3 classifier's data
+    gradient, and the folded inference records.  Every record gets a plan and no workspace for 256 and for 64 CUs; at 256 CUs the label
+    is the one written in the case tables."""
+    import conv_record_cases as RC
+    from robocupvision_amd.engine import MERGED_TCONV_MAX_COUT
+
+    def plan(h, op):
+        assert L.op_workspace(h, op) == 0
+        label = L.OpList([op]).labels(h)[0]
+        assert "<" in label, label
+        return label
+
+    for cus in (256, 64):
+        h = L.planner_handle(cus)
+        pinned = cus == 256
+        seen = set()
+        for shape in RC.DGRAD_SHAPES:
+            N, H, W, Cin, Cout, s, d = shape
+            for layout in RC.conv_layouts(Cin, Cout, 1, d):
+                for mode_name in RC.DGRAD_MODES:
+                    label = plan(h, RC.dgrad_record(shape, mode_name, layout))
+                    assert label.startswith("conv_wino") == (layout == 2) and ("_bf3" in label) == (layout == 3), (shape, label)
+                    assert not label.startswith("conv_small"), (shape, label)
+                    assert not pinned or label == RC.DGRAD_LABELS[(shape, layout)], (shape, layout, mode_name, label)
+                seen.add((shape, layout))
+        assert seen == set(RC.DGRAD_LABELS)
+        for plane in RC.CLS_DGRAD_PLANES:
+            for cout in RC.CLS_DGRAD_COUT:
+                label = plan(h, RC.cls_dgrad_record(plane, cout))
+                assert not pinned or label == RC.CLS_DGRAD_LABELS[(plane, cout)], (plane, cout, label)
+        seen = set()
+        for shape, load in RC.FOLDED_CONV_CASES:
+            N, H, W, Cin, Cout, s, d = shape
+            for layout in RC.conv_layouts(Cin, Cout, s, d):
+                label = plan(h, RC.folded_conv_record(shape, load, layout))
+                assert label.startswith("conv_wino") == (layout == 2) and ("_bf3" in label) == (layout in (3, 5)), (shape, label)
+                assert not pinned or label == RC.FOLDED_CONV_LABELS[(shape, load, layout)], (shape, load, layout, label)
+                seen.add((shape, load, layout))
+        assert seen == set(RC.FOLDED_CONV_LABELS)
+        seen = set()
+        for shape in RC.FOLDED_TCONV_SHAPES:
+            for layout in RC.tconv_layouts(shape[3], shape[4], MERGED_TCONV_MAX_COUT):
+                label = plan(h, RC.folded_tconv_record(shape, layout))
+                assert ("_bf3" in label) == (layout == 4), (shape, label)
+                assert not pinned or label == RC.FOLDED_TCONV_LABELS[(shape, layout)], (shape, layout, label)
+                seen.add((shape, layout))
+        assert seen == set(RC.FOLDED_TCONV_LABELS)

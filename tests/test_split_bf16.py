@@ -14,21 +14,9 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
 
-
-def _bf16_rne(x: np.ndarray) -> np.ndarray:
-    """float32 -> nearest bfloat16 (ties to even), returned as float32 (what v_cvt_pk_bf16_f32 does for finite inputs)."""
-    u = x.astype(np.float32).view(np.uint32).astype(np.uint64)
-    u = (u + 0x7FFF + ((u >> 16) & 1)) & 0xFFFF0000
-    return u.astype(np.uint32).view(np.float32)
-
-
-def _split3(x):
-    h = _bf16_rne(x)
-    r1 = (x - h).astype(np.float32)
-    m = _bf16_rne(r1)
-    r2 = (r1 - m).astype(np.float32)
-    return h, m, _bf16_rne(r2), r1, r2
+from pack_restatement import _bf16_rne, _split3      # noqa: E402  (the packer's restatement owns the rounding)
 
 
 def test_three_bf16_values_hold_an_fp32_value_exactly():
