@@ -1,6 +1,7 @@
 // Shared declarations of the convolution kernel families (dispatch: conv_dispatch.hip).
 #pragma once
 #include "load_xform.h"
+#include "bn_sums.h"
 
 enum { KIND_GATHER = 0, KIND_TPHASE = 1, KIND_TMERGED = 2, KIND_TALL = 3 };   // TALL: all four output parities of a transposed conv in one workgroup
 

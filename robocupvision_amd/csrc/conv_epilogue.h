@@ -1,13 +1,36 @@
-// The epilogue shared by the convolution kernels whose lanes end with four consecutive output channels of one pixel (conv_mfma.hip,
-// conv_bf3.hip).
+// The epilogue of the convolution kernels whose lanes end with four consecutive output channels of one pixel.  conv_mfma.hip,
+// conv_bf3.hip and conv5.hip use all of it; convn_bf3.hip has its own form for tiles inside the plane (n3_epi_tile) and takes this one
+// for ragged tiles and for the statistics row; conv_wino.hip, whose lanes meet their pixels after an exchange through LDS, takes
+// epi_consts.  The statistics arithmetic (bn_sums_*, bn_reduce16) is in bn_sums.h, for these and for convs_mfma.hip, which includes
+// nothing of this file: its epilogue is specialised at compile time and reads its constants from LDS.
 #pragma once
 #include "conv_common.h"
+
+// The lane's constants for the four output channels from `co`: bias (a.bias) and rows 0 / 1 / 2 of a.epi_c, each zero where the launch
+// does not use it or the lane has no channels (!co_ok).
+__device__ __forceinline__ void epi_consts(const ConvArgs& a, int co, bool co_ok, float4& bias, float4& e0, float4& e1, float4& mu) {
+  bias = make_float4(0.f, 0.f, 0.f, 0.f);
+  e0 = bias; e1 = bias; mu = bias;
+  if (co_ok) {
+    if (a.flags & RCV_F_BIAS) bias = ld4(a.bias + co);
+    if (a.stats == RCV_STATS_BWD_DEC) { e0 = ld4(a.epi_c + co); e1 = ld4(a.epi_c + a.Cout + co); }
+    if (a.stats == RCV_STATS_BWD_DEC || a.stats == RCV_STATS_BWD_ENC) mu = ld4(a.epi_c + 2 * a.Cout + co);
+  }
+}
 
 // Epilogue shared by the conv kernels: bias / ReLU / skip-gradient add, 16-byte NHWC stores, and the per-tile
 // BatchNorm partial sums (forward or backward), reduced in a fixed order through `red` ([WAVES_N][2][COT]).
 // Two parts, so that a persistent kernel can keep the statistics of all its tiles in registers and reduce them once:
 //   conv_epilogue_tile : bias / ReLU / residual, stores, and the lane's share of the BatchNorm sums ADDED to s1 / s2;
 //   conv_epilogue_stats: the fixed-order reduction of s1 / s2 over the workgroup and the partial row `row` of a.part.
+// acc + bias, and the ReLU where the launch asks for it.  (Operands by value, here as in bn_sums.h: by reference the same lines
+// compile to differently scheduled code.)
+__device__ __forceinline__ float4 epi_bias_relu(const ConvArgs& a, f32x4 acc, float4 bias) {
+  float4 v = make_float4(acc[0] + bias.x, acc[1] + bias.y, acc[2] + bias.z, acc[3] + bias.w);
+  if (a.flags & RCV_F_RELU) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
+  return v;
+}
+
 template <int WM, int WN, int WAVES_M, int WAVES_N, int KIND, int EB = (WM == 1 ? WN : 0)>
 __device__ __forceinline__ void conv_epilogue_tile(const ConvArgs& a, const TileInfo& ti, f32x4 (&acc)[WM][WN], float (&s1)[WM][4], float (&s2)[WM][4], int tid) {
   const int lane = tid & 63, wave = tid >> 6;
@@ -19,13 +42,8 @@ __device__ __forceinline__ void conv_epilogue_tile(const ConvArgs& a, const Tile
       int co = cov, py = ti.py, pxx = ti.px;
       if (KIND == KIND_TMERGED) { const int ph = cov / a.Cout; co = cov - ph * a.Cout; py = ph >> 1; pxx = ph & 1; }
       const bool co_ok = cov < a.CoutV;
-      float4 bias = make_float4(0.f, 0.f, 0.f, 0.f);
-      float4 e0 = bias, e1 = bias, mu = bias;
-      if (co_ok) {
-        if (a.flags & RCV_F_BIAS) bias = ld4(a.bias + co);
-        if (a.stats == RCV_STATS_BWD_DEC) { e0 = ld4(a.epi_c + co); e1 = ld4(a.epi_c + a.Cout + co); }
-        if (a.stats == RCV_STATS_BWD_DEC || a.stats == RCV_STATS_BWD_ENC) mu = ld4(a.epi_c + 2 * a.Cout + co);
-      }
+      float4 bias, e0, e1, mu;
+      epi_consts(a, co, co_ok, bias, e0, e1, mu);
       // The residual / BN-backward operands of all WN pixel blocks are requested in one batch, branch-free (a lane without an output
       // element reads element 0 and discards it): with each load inside its own `if (ok)` the compiler waits for it on the spot,
       // 2 * WN serialized HBM round trips per channel block in the data-gradient kernels.
@@ -47,29 +65,12 @@ __device__ __forceinline__ void conv_epilogue_tile(const ConvArgs& a, const Tile
           }
           if (!ok) continue;
           const size_t off = ((size_t)(ti.n * a.Ho + oy) * a.Wo + ox) * a.Cout + co;
-          float4 v = make_float4(acc[m][b][0] + bias.x, acc[m][b][1] + bias.y, acc[m][b][2] + bias.z, acc[m][b][3] + bias.w);
-          if (a.flags & RCV_F_RELU) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
+          float4 v = epi_bias_relu(a, acc[m][b], bias);
           if (a.flags & RCV_F_RESID) { const float4 rr = ld4(a.resid + off); v.x += rr.x; v.y += rr.y; v.z += rr.z; v.w += rr.w; }
           *reinterpret_cast<float4*>(a.out + off) = v;
-          if (a.stats == RCV_STATS_FWD) {
-            s1[m][0] += v.x; s1[m][1] += v.y; s1[m][2] += v.z; s1[m][3] += v.w;
-            s2[m][0] = fmaf(v.x, v.x, s2[m][0]); s2[m][1] = fmaf(v.y, v.y, s2[m][1]);
-            s2[m][2] = fmaf(v.z, v.z, s2[m][2]); s2[m][3] = fmaf(v.w, v.w, s2[m][3]);
-          } else if (a.stats == RCV_STATS_BWD_ENC) {
-            const float4 e = ld4(a.epi_aux + off);
-            s1[m][0] += v.x; s1[m][1] += v.y; s1[m][2] += v.z; s1[m][3] += v.w;
-            s2[m][0] = fmaf(v.x, e.x - mu.x, s2[m][0]); s2[m][1] = fmaf(v.y, e.y - mu.y, s2[m][1]);
-            s2[m][2] = fmaf(v.z, e.z - mu.z, s2[m][2]); s2[m][3] = fmaf(v.w, e.w - mu.w, s2[m][3]);
-          } else if (a.stats == RCV_STATS_BWD_DEC) {
-            const float4 e = ld4(a.epi_aux + off);
-            const float gx = fmaf(e.x, e0.x, e1.x) > 0.f ? v.x : 0.f;
-            const float gy = fmaf(e.y, e0.y, e1.y) > 0.f ? v.y : 0.f;
-            const float gz = fmaf(e.z, e0.z, e1.z) > 0.f ? v.z : 0.f;
-            const float gw = fmaf(e.w, e0.w, e1.w) > 0.f ? v.w : 0.f;
-            s1[m][0] += gx; s1[m][1] += gy; s1[m][2] += gz; s1[m][3] += gw;
-            s2[m][0] = fmaf(gx, e.x - mu.x, s2[m][0]); s2[m][1] = fmaf(gy, e.y - mu.y, s2[m][1]);
-            s2[m][2] = fmaf(gz, e.z - mu.z, s2[m][2]); s2[m][3] = fmaf(gw, e.w - mu.w, s2[m][3]);
-          }
+          if (a.stats == RCV_STATS_FWD) bn_sums_fwd(s1[m], s2[m], v);
+          else if (a.stats == RCV_STATS_BWD_ENC) bn_sums_bwd_enc(s1[m], s2[m], v, ld4(a.epi_aux + off), mu);
+          else if (a.stats == RCV_STATS_BWD_DEC) bn_sums_bwd_dec(s1[m], s2[m], v, ld4(a.epi_aux + off), e0, e1, mu);
         }
       } else {
         const bool bwd_stats = a.stats == RCV_STATS_BWD_ENC || a.stats == RCV_STATS_BWD_DEC;
@@ -111,29 +112,12 @@ __device__ __forceinline__ void conv_epilogue_tile(const ConvArgs& a, const Tile
             if (b >= WN) continue;
             if (!okb[i]) continue;
             const size_t off = offb[i];
-            float4 v = make_float4(acc[m][b][0] + bias.x, acc[m][b][1] + bias.y, acc[m][b][2] + bias.z, acc[m][b][3] + bias.w);
-            if (a.flags & RCV_F_RELU) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
+            float4 v = epi_bias_relu(a, acc[m][b], bias);
             if (a.flags & RCV_F_RESID) { const float4 rr = rrb[i]; v.x += rr.x; v.y += rr.y; v.z += rr.z; v.w += rr.w; }
             *reinterpret_cast<float4*>(a.out + off) = v;
-            if (a.stats == RCV_STATS_FWD) {
-              s1[m][0] += v.x; s1[m][1] += v.y; s1[m][2] += v.z; s1[m][3] += v.w;
-              s2[m][0] = fmaf(v.x, v.x, s2[m][0]); s2[m][1] = fmaf(v.y, v.y, s2[m][1]);
-              s2[m][2] = fmaf(v.z, v.z, s2[m][2]); s2[m][3] = fmaf(v.w, v.w, s2[m][3]);
-            } else if (a.stats == RCV_STATS_BWD_ENC) {
-              const float4 e = eb[i];
-              s1[m][0] += v.x; s1[m][1] += v.y; s1[m][2] += v.z; s1[m][3] += v.w;
-              s2[m][0] = fmaf(v.x, e.x - mu.x, s2[m][0]); s2[m][1] = fmaf(v.y, e.y - mu.y, s2[m][1]);
-              s2[m][2] = fmaf(v.z, e.z - mu.z, s2[m][2]); s2[m][3] = fmaf(v.w, e.w - mu.w, s2[m][3]);
-            } else if (a.stats == RCV_STATS_BWD_DEC) {
-              const float4 e = eb[i];
-              const float gx = fmaf(e.x, e0.x, e1.x) > 0.f ? v.x : 0.f;
-              const float gy = fmaf(e.y, e0.y, e1.y) > 0.f ? v.y : 0.f;
-              const float gz = fmaf(e.z, e0.z, e1.z) > 0.f ? v.z : 0.f;
-              const float gw = fmaf(e.w, e0.w, e1.w) > 0.f ? v.w : 0.f;
-              s1[m][0] += gx; s1[m][1] += gy; s1[m][2] += gz; s1[m][3] += gw;
-              s2[m][0] = fmaf(gx, e.x - mu.x, s2[m][0]); s2[m][1] = fmaf(gy, e.y - mu.y, s2[m][1]);
-              s2[m][2] = fmaf(gz, e.z - mu.z, s2[m][2]); s2[m][3] = fmaf(gw, e.w - mu.w, s2[m][3]);
-            }
+            if (a.stats == RCV_STATS_FWD) bn_sums_fwd(s1[m], s2[m], v);
+            else if (a.stats == RCV_STATS_BWD_ENC) bn_sums_bwd_enc(s1[m], s2[m], v, eb[i], mu);
+            else if (a.stats == RCV_STATS_BWD_DEC) bn_sums_bwd_dec(s1[m], s2[m], v, eb[i], e0, e1, mu);
           }
         }
       }
@@ -149,15 +133,7 @@ __device__ __forceinline__ void conv_epilogue_stats(const ConvArgs& a, size_t ro
   const int l15 = lane & 15, l4 = lane >> 4;
     {
       // wave: sum over the 16 pixel lanes (xor 1,2,4,8 stays inside a 16-lane group); fixed order
-#pragma unroll
-      for (int m = 0; m < WM; ++m)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          float u = s1[m][r], v = s2[m][r];
-#pragma unroll
-          for (int sh = 1; sh < 16; sh <<= 1) { u += __shfl_xor(u, sh); v += __shfl_xor(v, sh); }
-          s1[m][r] = u; s2[m][r] = v;
-        }
+      bn_reduce16<4 * WM>(s1[0], s2[0]);
       if (l15 == 0) {
 #pragma unroll
         for (int m = 0; m < WM; ++m)

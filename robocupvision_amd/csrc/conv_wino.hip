@@ -18,7 +18,7 @@
 // After the K loop the 16 M_xi of a (channel, tile) live in 8 different waves: they meet through LDS, one 16-tile block at a time,
 // where the output transform, bias / ReLU / skip gradient, the NHWC stores and the BatchNorm partial sums are applied.
 #include <type_traits>
-#include "conv_common.h"
+#include "conv_epilogue.h"
 
 typedef __attribute__((address_space(3))) void* wino_lds_ptr;
 typedef const __attribute__((address_space(1))) void* wino_glb_ptr;
@@ -239,12 +239,8 @@ __global__ __launch_bounds__(W_NT) void conv_wino_kernel(const ConvArgs a) {
   const int e_tile = tid & 15, e_quad = (tid >> 4) & 15, e_i = tid >> 8;      // reader: (tile, 4 channels, output row)
   const int co = co0 + 4 * e_quad;
   const bool co_ok = co < a.Cout;
-  float4 bias = make_float4(0.f, 0.f, 0.f, 0.f), mu = bias, e0 = bias, e1 = bias;
-  if (co_ok) {
-    if (a.flags & RCV_F_BIAS) bias = ld4(a.bias + co);
-    if (a.stats == RCV_STATS_BWD_DEC) { e0 = ld4(a.epi_c + co); e1 = ld4(a.epi_c + a.Cout + co); }
-    if (a.stats == RCV_STATS_BWD_DEC || a.stats == RCV_STATS_BWD_ENC) mu = ld4(a.epi_c + 2 * a.Cout + co);
-  }
+  float4 bias, e0, e1, mu;
+  epi_consts(a, co, co_ok, bias, e0, e1, mu);
   float s1[4] = {0.f, 0.f, 0.f, 0.f}, s2[4] = {0.f, 0.f, 0.f, 0.f};
   const bool bwd_stats = a.stats == RCV_STATS_BWD_ENC || a.stats == RCV_STATS_BWD_DEC;
 #pragma unroll
@@ -303,27 +299,14 @@ __global__ __launch_bounds__(W_NT) void conv_wino_kernel(const ConvArgs a) {
       if (a.flags & RCV_F_RELU) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
       if (a.flags & RCV_F_RESID) { v.x += rr[jx].x; v.y += rr[jx].y; v.z += rr[jx].z; v.w += rr[jx].w; }
       *reinterpret_cast<float4*>(a.out + offp[jx]) = v;
-      const float4 e = ee[jx];
-      if (a.stats == RCV_STATS_FWD) {
-        s1[0] += v.x; s1[1] += v.y; s1[2] += v.z; s1[3] += v.w;
-        s2[0] = fmaf(v.x, v.x, s2[0]); s2[1] = fmaf(v.y, v.y, s2[1]); s2[2] = fmaf(v.z, v.z, s2[2]); s2[3] = fmaf(v.w, v.w, s2[3]);
-      } else if (a.stats == RCV_STATS_BWD_ENC) {
-        s1[0] += v.x; s1[1] += v.y; s1[2] += v.z; s1[3] += v.w;
-        s2[0] = fmaf(v.x, e.x - mu.x, s2[0]); s2[1] = fmaf(v.y, e.y - mu.y, s2[1]);
-        s2[2] = fmaf(v.z, e.z - mu.z, s2[2]); s2[3] = fmaf(v.w, e.w - mu.w, s2[3]);
-      } else if (a.stats == RCV_STATS_BWD_DEC) {
-        const float gx = fmaf(e.x, e0.x, e1.x) > 0.f ? v.x : 0.f;
-        const float gy = fmaf(e.y, e0.y, e1.y) > 0.f ? v.y : 0.f;
-        const float gz = fmaf(e.z, e0.z, e1.z) > 0.f ? v.z : 0.f;
-        const float gw = fmaf(e.w, e0.w, e1.w) > 0.f ? v.w : 0.f;
-        s1[0] += gx; s1[1] += gy; s1[2] += gz; s1[3] += gw;
-        s2[0] = fmaf(gx, e.x - mu.x, s2[0]); s2[1] = fmaf(gy, e.y - mu.y, s2[1]);
-        s2[2] = fmaf(gz, e.z - mu.z, s2[2]); s2[3] = fmaf(gw, e.w - mu.w, s2[3]);
-      }
+      if (a.stats == RCV_STATS_FWD) bn_sums_fwd(s1, s2, v);
+      else if (a.stats == RCV_STATS_BWD_ENC) bn_sums_bwd_enc(s1, s2, v, ee[jx], mu);
+      else if (a.stats == RCV_STATS_BWD_DEC) bn_sums_bwd_dec(s1, s2, v, ee[jx], e0, e1, mu);
     }
   }
   if (a.stats != RCV_STATS_NONE) {
     // the 16 tile lanes of a (channel quad, output row) group: xor 1,2,4,8 stays inside the 16-lane group; then the two output rows
+    // (bn_reduce16 of bn_sums.h written out: called from this kernel, in every form tried, it reorders 3154 lines of the assembly)
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       float u = s1[r], v = s2[r];

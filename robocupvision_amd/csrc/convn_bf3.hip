@@ -68,38 +68,17 @@ __device__ __forceinline__ void n3_epi_tile(const N3Epi<WM, WN>& E, const ConvAr
       for (int b = 0; b < WN; ++b) ee[b] = ld4(eaux + (E.off[m][b] < 0 ? 0 : E.off[m][b]));
     }
     // (per tile from L1: kept in registers across tiles they cost 16 registers per channel block and the 64-virtual-channel variants spilled)
-    float4 bias = make_float4(0.f, 0.f, 0.f, 0.f), e0 = bias, e1 = bias, mu = bias;
-    if (E.co[m] >= 0) {
-      if (a.flags & RCV_F_BIAS) bias = ld4(a.bias + E.co[m]);
-      if (a.stats == RCV_STATS_BWD_DEC) { e0 = ld4(a.epi_c + E.co[m]); e1 = ld4(a.epi_c + a.Cout + E.co[m]); }
-      if (bwd_stats) mu = ld4(a.epi_c + 2 * a.Cout + E.co[m]);
-    }
+    float4 bias, e0, e1, mu;
+    epi_consts(a, E.co[m], E.co[m] >= 0, bias, e0, e1, mu);
 #pragma unroll
     for (int b = 0; b < WN; ++b) {
       if (E.off[m][b] < 0) continue;
-      float4 v = make_float4(acc[m][b][0] + bias.x, acc[m][b][1] + bias.y, acc[m][b][2] + bias.z, acc[m][b][3] + bias.w);
-      if (a.flags & RCV_F_RELU) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
+      float4 v = epi_bias_relu(a, acc[m][b], bias);
       if (a.flags & RCV_F_RESID) { v.x += rr[b].x; v.y += rr[b].y; v.z += rr[b].z; v.w += rr[b].w; }
       *reinterpret_cast<float4*>(out + E.off[m][b]) = v;
-      if (a.stats == RCV_STATS_FWD) {
-        s1[m][0] += v.x; s1[m][1] += v.y; s1[m][2] += v.z; s1[m][3] += v.w;
-        s2[m][0] = fmaf(v.x, v.x, s2[m][0]); s2[m][1] = fmaf(v.y, v.y, s2[m][1]);
-        s2[m][2] = fmaf(v.z, v.z, s2[m][2]); s2[m][3] = fmaf(v.w, v.w, s2[m][3]);
-      } else if (a.stats == RCV_STATS_BWD_ENC) {
-        const float4 e = ee[b];
-        s1[m][0] += v.x; s1[m][1] += v.y; s1[m][2] += v.z; s1[m][3] += v.w;
-        s2[m][0] = fmaf(v.x, e.x - mu.x, s2[m][0]); s2[m][1] = fmaf(v.y, e.y - mu.y, s2[m][1]);
-        s2[m][2] = fmaf(v.z, e.z - mu.z, s2[m][2]); s2[m][3] = fmaf(v.w, e.w - mu.w, s2[m][3]);
-      } else if (a.stats == RCV_STATS_BWD_DEC) {
-        const float4 e = ee[b];
-        const float gx = fmaf(e.x, e0.x, e1.x) > 0.f ? v.x : 0.f;
-        const float gy = fmaf(e.y, e0.y, e1.y) > 0.f ? v.y : 0.f;
-        const float gz = fmaf(e.z, e0.z, e1.z) > 0.f ? v.z : 0.f;
-        const float gw = fmaf(e.w, e0.w, e1.w) > 0.f ? v.w : 0.f;
-        s1[m][0] += gx; s1[m][1] += gy; s1[m][2] += gz; s1[m][3] += gw;
-        s2[m][0] = fmaf(gx, e.x - mu.x, s2[m][0]); s2[m][1] = fmaf(gy, e.y - mu.y, s2[m][1]);
-        s2[m][2] = fmaf(gz, e.z - mu.z, s2[m][2]); s2[m][3] = fmaf(gw, e.w - mu.w, s2[m][3]);
-      }
+      if (a.stats == RCV_STATS_FWD) bn_sums_fwd(s1[m], s2[m], v);
+      else if (a.stats == RCV_STATS_BWD_ENC) bn_sums_bwd_enc(s1[m], s2[m], v, ee[b], mu);
+      else if (a.stats == RCV_STATS_BWD_DEC) bn_sums_bwd_dec(s1[m], s2[m], v, ee[b], e0, e1, mu);
     }
   }
 }

@@ -433,23 +433,9 @@ __global__ __launch_bounds__(256, 2) void convs_mfma_kernel(const ConvArgs a) {
             st4b(a.out, omt + ob[b], v);
             float4 e = make_float4(0.f, 0.f, 0.f, 0.f);
             if (NEED_E) e = EARLY ? ee_early[EARLY ? m : 0][b] : ee[bb];
-            if (STATS == RCV_STATS_FWD) {
-              s1[m][0] += v.x; s1[m][1] += v.y; s1[m][2] += v.z; s1[m][3] += v.w;
-              s2[m][0] = fmaf(v.x, v.x, s2[m][0]); s2[m][1] = fmaf(v.y, v.y, s2[m][1]);
-              s2[m][2] = fmaf(v.z, v.z, s2[m][2]); s2[m][3] = fmaf(v.w, v.w, s2[m][3]);
-            } else if (STATS == RCV_STATS_BWD_ENC) {
-              s1[m][0] += v.x; s1[m][1] += v.y; s1[m][2] += v.z; s1[m][3] += v.w;
-              s2[m][0] = fmaf(v.x, e.x - mu.x, s2[m][0]); s2[m][1] = fmaf(v.y, e.y - mu.y, s2[m][1]);
-              s2[m][2] = fmaf(v.z, e.z - mu.z, s2[m][2]); s2[m][3] = fmaf(v.w, e.w - mu.w, s2[m][3]);
-            } else if (STATS == RCV_STATS_BWD_DEC) {
-              const float gx = fmaf(e.x, e0.x, e1.x) > 0.f ? v.x : 0.f;
-              const float gy = fmaf(e.y, e0.y, e1.y) > 0.f ? v.y : 0.f;
-              const float gz = fmaf(e.z, e0.z, e1.z) > 0.f ? v.z : 0.f;
-              const float gw = fmaf(e.w, e0.w, e1.w) > 0.f ? v.w : 0.f;
-              s1[m][0] += gx; s1[m][1] += gy; s1[m][2] += gz; s1[m][3] += gw;
-              s2[m][0] = fmaf(gx, e.x - mu.x, s2[m][0]); s2[m][1] = fmaf(gy, e.y - mu.y, s2[m][1]);
-              s2[m][2] = fmaf(gz, e.z - mu.z, s2[m][2]); s2[m][3] = fmaf(gw, e.w - mu.w, s2[m][3]);
-            }
+            if (STATS == RCV_STATS_FWD) bn_sums_fwd(s1[m], s2[m], v);
+            else if (STATS == RCV_STATS_BWD_ENC) bn_sums_bwd_enc(s1[m], s2[m], v, e, mu);
+            else if (STATS == RCV_STATS_BWD_DEC) bn_sums_bwd_dec(s1[m], s2[m], v, e, e0, e1, mu);
           }
         }
       };
@@ -481,15 +467,7 @@ __global__ __launch_bounds__(256, 2) void convs_mfma_kernel(const ConvArgs a) {
 
   // ---- one statistics row per workgroup
   if (a.stats != RCV_STATS_NONE) {
-#pragma unroll
-    for (int m = 0; m < WM; ++m)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        float u = s1[m][r], v = s2[m][r];
-#pragma unroll
-        for (int sh = 1; sh < 16; sh <<= 1) { u += __shfl_xor(u, sh); v += __shfl_xor(v, sh); }
-        s1[m][r] = u; s2[m][r] = v;
-      }
+    bn_reduce16<4 * WM>(s1[0], s2[0]);
     __syncthreads();
     if (l15 == 0) {
 #pragma unroll

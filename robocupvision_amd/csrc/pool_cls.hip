@@ -9,6 +9,7 @@
 // in index order) and pool_cls_scatter_kernel (a grid-stride stream over the source plane, one work item per (pixel, channel quad):
 // one 16-byte store of the gradient; r read where the arg-max or the statistics need it).  Fixed summation orders, no float atomics.
 #include "rcv_internal.h"
+#include "bn_sums.h"
 
 #define POOL_CLS_MAX_OUT 8
 #define POOL_CLS_MAX_C 512
@@ -192,13 +193,8 @@ __global__ __launch_bounds__(256) void pool_cls_scatter_kernel(const float* __re
     pc_st4(dy + e * 4, v);
     if (stats != RCV_STATS_NONE) {
       const float4 xr = pc_ld4(r + e * 4);
-      if (stats == RCV_STATS_BWD_DEC) {
-        v.x = fmaf(xr.x, c0.x, c1.x) > 0.f ? v.x : 0.f; v.y = fmaf(xr.y, c0.y, c1.y) > 0.f ? v.y : 0.f;
-        v.z = fmaf(xr.z, c0.z, c1.z) > 0.f ? v.z : 0.f; v.w = fmaf(xr.w, c0.w, c1.w) > 0.f ? v.w : 0.f;
-      }
-      a1.x += v.x; a1.y += v.y; a1.z += v.z; a1.w += v.w;
-      a2.x = fmaf(v.x, xr.x - mu.x, a2.x); a2.y = fmaf(v.y, xr.y - mu.y, a2.y);
-      a2.z = fmaf(v.z, xr.z - mu.z, a2.z); a2.w = fmaf(v.w, xr.w - mu.w, a2.w);
+      if (stats == RCV_STATS_BWD_DEC) v = bn_relu_mask(v, xr, c0, c1);
+      bn_sums_bwd_enc(a1, a2, v, xr, mu);
     }
   }
   if (stats != RCV_STATS_NONE) {

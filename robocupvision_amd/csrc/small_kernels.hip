@@ -4,6 +4,7 @@
 // shuffles + fixed-order LDS trees for the reductions (no float atomics).
 #include "rcv_internal.h"
 #include "cls_common.h"
+#include "bn_sums.h"
 #include <type_traits>
 
 __device__ __forceinline__ float wave_sum(float v) {
@@ -976,9 +977,7 @@ __global__ void pool_bwd_kernel(const float* __restrict__ dp, const float* __res
       float4 v = make_float4(ix == j ? g.x : 0.f, iy == j ? g.y : 0.f, iz == j ? g.z : 0.f, iw == j ? g.w : 0.f);
       if (resid) { const float4 rr = sld4(resid + off); v.x += rr.x; v.y += rr.y; v.z += rr.z; v.w += rr.w; }
       sst4(dy + off, v);
-      a1.x += v.x; a1.y += v.y; a1.z += v.z; a1.w += v.w;
-      a2.x = fmaf(v.x, rv[j].x - mu.x, a2.x); a2.y = fmaf(v.y, rv[j].y - mu.y, a2.y);
-      a2.z = fmaf(v.z, rv[j].z - mu.z, a2.z); a2.w = fmaf(v.w, rv[j].w - mu.w, a2.w);
+      bn_sums_bwd_enc(a1, a2, v, rv[j], mu);
     }
   }
   if (stats != RCV_STATS_NONE) {
@@ -1256,13 +1255,8 @@ __global__ void bwd_stats_kernel(const float* __restrict__ g, const float* __res
     float4 v = sld4(g + (e / C4) * Csrc + coff + (e % C4) * 4);
     sst4(out + e * 4, v);
     const float4 x = sld4(ev + e * 4);
-    if (stats == RCV_STATS_BWD_DEC) {
-      v.x = fmaf(x.x, c0.x, c1.x) > 0.f ? v.x : 0.f; v.y = fmaf(x.y, c0.y, c1.y) > 0.f ? v.y : 0.f;
-      v.z = fmaf(x.z, c0.z, c1.z) > 0.f ? v.z : 0.f; v.w = fmaf(x.w, c0.w, c1.w) > 0.f ? v.w : 0.f;
-    }
-    a1.x += v.x; a1.y += v.y; a1.z += v.z; a1.w += v.w;
-    a2.x = fmaf(v.x, x.x - mu.x, a2.x); a2.y = fmaf(v.y, x.y - mu.y, a2.y);
-    a2.z = fmaf(v.z, x.z - mu.z, a2.z); a2.w = fmaf(v.w, x.w - mu.w, a2.w);
+    if (stats == RCV_STATS_BWD_DEC) v = bn_relu_mask(v, x, c0, c1);
+    bn_sums_bwd_enc(a1, a2, v, x, mu);
   }
   sh4[threadIdx.x] = a1;
   sh4[blockDim.x + threadIdx.x] = a2;
