@@ -340,6 +340,13 @@ enum {
                                       wide layers form their fp32 products on the bf16 matrix pipe from operands split EXACTLY into three
                                       bf16 values (six partial products per multiply-add, fp32 accumulate; error <= the fp32 chain's against
                                       fp64, csrc/wgrad_bf3.hip): same results to fp32 rounding, 2-2.5 x the matrix rate.  Part of the plan key. */
+#define RCV_F_STREAM_OUT (1u << 18) /* CONV / TCONV / COMBINE: store the output tensor with streaming (nontemporal) stores whatever its size.  Without
+                                      the flag the library decides from the tensor's size (rcv_set_stream_min_mb, default 128 MiB; 0 = never):
+                                      a tensor that large is gone from the caches before its consumer asks for it.  Honoured by the narrow
+                                      families (convs_mfma, convn_bf3), the first layer and combine / concat; the others ignore it.  Results
+                                      are bit for bit the same either way.  Not part of the plan key. */
+#define RCV_F_STREAM_PW  (1u << 19) /* COMBINE (WGRAD, CONV: accepted, not honoured by a kernel yet): read the pointwise operands -- read once per
+                                      element, no halo -- with streaming loads whatever their size; without the flag by size, as above */
 #define RCV_F_CONCAT    256u  /* COMBINE: out[..,0:C] = relu(t*s+h), out[..,C:2C] = f(r)  (v2 skip concat, model.py:507) */
 /* bits 20..22: profiling ablations of diagnostic builds (skip staging / skip the contraction); the shipped kernels of the wide
  * layers ignore them */
@@ -422,6 +429,14 @@ int rcv_run_timed(rcv_handle* h, const rcv_op* ops, int n, void* stream, float* 
  * RCV_OP_TCONV records in the merged form (i[RCV_I_AUX0] = 1) answer 4 where the split-bf16 narrow kernel is the faster one;
  * `force` != 0 answers 2 for every shape the Winograd kernel can run. */
 int rcv_op_filter_layout(const rcv_handle* h, const rcv_op* op, int force);
+
+/* The streaming hints the library applies to `op`: RCV_F_STREAM_OUT | RCV_F_STREAM_PW bits (>= 0), decided from the record's own
+ * N*H*W*C against the handle's threshold, or forced by the record's flags; negative RCV_E_* for a record the planner refuses. */
+int rcv_op_stream_hints(const rcv_handle* h, const rcv_op* op);
+/* The handle's threshold in MiB (may be fractional; default 128): a tensor at least this large is accessed with streaming hints where
+ * a kernel touches it exactly once.  0 switches every hint off.  The binding passes the RCV_STREAM_MIN_MB environment value here once,
+ * when it creates the handle; the library itself reads no environment. */
+int rcv_set_stream_min_mb(rcv_handle* h, double mb);
 
 /* Label of the kernel (template instantiation / tiling) the library launches for `op`, e.g.
  * "conv_mfma<2,5,4,1,8>" -- written NUL-terminated into buf[0..size). */

@@ -50,6 +50,7 @@ F_FUSED_UP = 512
 F_FUSED_CE = 1024
 F_SIDE_STREAM = 1 << 16
 F_MFMA_FP32 = 1 << 17      # contract on the fp32 matrix instructions only (rcv.h RCV_F_MFMA_FP32)
+F_STREAM_OUT, F_STREAM_PW = 1 << 18, 1 << 19      # force the streaming hints of a record whatever its size (rcv.h RCV_F_STREAM_OUT / _PW)
 
 
 class RcvOp(C.Structure):
@@ -83,7 +84,7 @@ EXPORTS = [
     "rcv_bnn_stage_fwd", "rcv_bnn_stage_bwd", "rcv_bnn_head_fwd", "rcv_bnn_head_bwd",
     "rcv_sgd_step_pruned", "rcv_prune_check", "rcv_prune", "rcv_find_objects", "rcv_rgb_prep",
     "rcv_farneback_flow", "rcv_update_labels", "rcv_object_patches", "rcv_resize_u8", "rcv_batch_prep_indexed",
-    "rcv_rgb_prep_indexed", "rcv_lp_pair_prep", "rcv_conv5x5", "rcv_wgrad5x5",
+    "rcv_rgb_prep_indexed", "rcv_lp_pair_prep", "rcv_conv5x5", "rcv_wgrad5x5", "rcv_op_stream_hints", "rcv_set_stream_min_mb",
 ]
 
 
@@ -158,8 +159,20 @@ def load():
         for name in ("rcv_conv5x5", "rcv_wgrad5x5"):
             if hasattr(lib, name):      # (RCV_LIBRARY may name the build of an older revision: scripts/plan_diff.sh, scripts/ab.sh)
                 getattr(lib, name).argtypes = [C.c_void_p, C.POINTER(RcvOp), C.c_void_p]
+        if hasattr(lib, "rcv_set_stream_min_mb"):      # (RCV_LIBRARY may name an older build)
+            lib.rcv_set_stream_min_mb.argtypes = [C.c_void_p, C.c_double]
+            lib.rcv_op_stream_hints.argtypes = [C.c_void_p, C.POINTER(RcvOp)]
         _lib = lib
     return _lib
+
+
+def _apply_stream_min(h):
+    """RCV_STREAM_MIN_MB (MiB; 0 = every streaming hint off, unset = the library's 128 MiB), read once per handle, here: the library
+    reads no environment itself."""
+    ev = os.environ.get("RCV_STREAM_MIN_MB")
+    if ev is not None and hasattr(load(), "rcv_set_stream_min_mb"):
+        check(load().rcv_set_stream_min_mb(h, float(ev)), "rcv_set_stream_min_mb")
+    return h
 
 
 def check(rc: int, what: str = ""):
@@ -175,7 +188,7 @@ def handle(device_index: int):
     if h is None:
         out = C.c_void_p()
         check(lib.rcv_create(device_index, C.byref(out)), "rcv_create")
-        h = out
+        h = _apply_stream_min(out)
         _handles[device_index] = h
     return h
 
@@ -188,7 +201,7 @@ def planner_handle(num_cus: int = 256):
     if h is None:
         out = C.c_void_p()
         check(lib.rcv_create_planner(num_cus, C.byref(out)), "rcv_create_planner")
-        h = out
+        h = _apply_stream_min(out)
         _handles[("planner", num_cus)] = h
     return h
 
@@ -221,6 +234,14 @@ def make_op(kind: int, flags: int = 0, **kw) -> RcvOp:
 def op_filter_layout(h, op: RcvOp, force: bool = False) -> int:
     """0: plain [9][Cin][Cout] filter; 2: the library wants the Winograd-transformed filter for this conv record."""
     return int(load().rcv_op_filter_layout(h, C.byref(op), 1 if force else 0))
+
+
+def op_stream_hints(h, op: RcvOp) -> int:
+    """F_STREAM_OUT | F_STREAM_PW bits the library applies to the record (by size against the handle's threshold, or forced)."""
+    rc = int(load().rcv_op_stream_hints(h, C.byref(op)))
+    if rc < 0:
+        check(rc, "rcv_op_stream_hints")
+    return rc
 
 
 def op_workspace(h, op: RcvOp) -> int:

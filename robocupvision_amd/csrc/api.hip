@@ -56,6 +56,7 @@ int rcv_create(int device, rcv_handle** out) {
   h->num_cus = prop.multiProcessorCount;
   h->max_lds = 160 * 1024;
   h->plans = new rcv_plan_cache;
+  h->stream_min_bytes = rcv_stream_min_bytes(RCV_STREAM_MIN_MB_DEFAULT);
   h->side_stream = nullptr;
   h->ev_join = nullptr;
   h->ev_next = 0;
@@ -72,6 +73,7 @@ int rcv_create_planner(int num_cus, rcv_handle** out) {
   h->num_cus = num_cus;
   h->max_lds = 160 * 1024;
   h->plans = new rcv_plan_cache;
+  h->stream_min_bytes = rcv_stream_min_bytes(RCV_STREAM_MIN_MB_DEFAULT);
   h->side_stream = nullptr;
   h->ev_join = nullptr;
   h->ev_next = 0;
@@ -227,6 +229,21 @@ static int run_ops(rcv_handle* h, const rcv_op* ops, int n, void* stream, bool j
 extern "C" {
 
 int rcv_op_filter_layout(const rcv_handle* h, const rcv_op* op, int force) { return h && op ? rcv_filter_layout(h, op, force) : 0; }
+
+int rcv_set_stream_min_mb(rcv_handle* h, double mb) {
+  RCV_CHECK_ARG(h && mb >= 0.0, "rcv_set_stream_min_mb: NULL handle or negative threshold");
+  h->stream_min_bytes = rcv_stream_min_bytes(mb);
+  return RCV_OK;
+}
+
+int rcv_op_stream_hints(const rcv_handle* h, const rcv_op* op) {
+  RCV_CHECK_ARG(h && op, "rcv_op_stream_hints: bad arguments");
+  OpQuery q;
+  memset(&q, 0, sizeof(q));
+  const int rc = dispatch(h, op, nullptr, &q);      // refuses what a launch would refuse
+  if (rc) return rc;
+  return (int)rcv_stream_hints(h, op);
+}
 
 int rcv_op_kernel_label(const rcv_handle* h, const rcv_op* op, char* buf, int size) {
   RCV_CHECK_ARG(h && op && buf && size > 0, "rcv_op_kernel_label: bad arguments");

@@ -1,17 +1,7 @@
 // Loads shared by the classifier kernels (small_kernels.hip: logits; cls_label.hip: class maps): the 16-byte accessors and the
 // formation of the 1x1 classifier's input, so that every kernel that forms logits rounds them the same way.
 #pragma once
-#include "rcv_internal.h"
-
-__device__ __forceinline__ float4 sld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ void sst4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
-// streaming (nontemporal) accesses for tensors a kernel touches exactly once and nobody reads soon after: measured on this part
-// (scripts/micro/stream_bw.hip) a 2-reads-1-write stream gains 4-5 % and a read-only one 8 % over plain accesses
-typedef float sv4f __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ float4 sld4_nt(const float* p) {
-  const sv4f v = __builtin_nontemporal_load(reinterpret_cast<const sv4f*>(p));
-  return make_float4(v[0], v[1], v[2], v[3]);
-}
+#include "stream_hint.h"      // sld4 / sst4 and their streaming forms
 
 #define CLS_MAX_OUT 8
 // FUSED: the classifier input up = relu(t*c0+c1) + f(r) (decoder block output + skip, model.py:509) is formed here from the

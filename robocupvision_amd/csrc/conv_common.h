@@ -2,6 +2,7 @@
 #pragma once
 #include "load_xform.h"
 #include "bn_sums.h"
+#include "stream_hint.h"
 
 enum { KIND_GATHER = 0, KIND_TPHASE = 1, KIND_TMERGED = 2, KIND_TALL = 3 };   // TALL: all four output parities of a transposed conv in one workgroup
 
@@ -28,6 +29,8 @@ struct ConvArgs {
   int xk;                      // conv_dma_kernel: channels per staged input chunk (8 or 16)
   FastDiv fdWt, fdIW;
   FastDiv fdTX, fdTY;          // tiles_x, tiles_y (narrow kernel: tile decode on the scalar unit)
+  int nt_out, nt_pw;           // streaming hints (stream_hint.h).  nt_out: the final store of `out` (convs_mfma, convn_bf3, conv_first pick their
+                               // STREAM instantiation by it); nt_pw: the epilogue operands resid / epi_aux -- carried, no conv family honours it yet
 #ifdef RCV_STAMPS
   unsigned long long* stamps;  // diagnostic build: per wave [12] cycle sums (conv_dma_kernel)
 #endif

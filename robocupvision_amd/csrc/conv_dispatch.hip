@@ -71,6 +71,8 @@ int rcv_launch_conv(const rcv_handle* h, const rcv_op* op, hipStream_t s, OpQuer
   a.wl_floats = pl.wl_floats; a.xl_floats = pl.xl_floats; a.xk = pl.xk;
   a.xpitch = conv_xpitch(pl.xpitch_ck, pl.kind == KIND_GATHER ? a.stride : 1);
   a.fdWt = make_fastdiv(pl.Wt); a.fdIW = make_fastdiv(pl.IW); a.fdTX = make_fastdiv(pl.tiles_x); a.fdTY = make_fastdiv(pl.tiles_y);
+  const uint32_t hints = rcv_stream_hints(h, op);
+  a.nt_out = (hints & RCV_F_STREAM_OUT) ? 1 : 0; a.nt_pw = (hints & RCV_F_STREAM_PW) ? 1 : 0;
 #ifdef RCV_STAMPS
   a.stamps = (unsigned long long*)op->p[RCV_P_X5];
 #endif

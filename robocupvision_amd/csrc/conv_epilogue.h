@@ -31,7 +31,9 @@ __device__ __forceinline__ float4 epi_bias_relu(const ConvArgs& a, f32x4 acc, fl
   return v;
 }
 
-template <int WM, int WN, int WAVES_M, int WAVES_N, int KIND, int EB = (WM == 1 ? WN : 0)>
+// STREAM: the output tensor is stream-once (stream_hint.h): its stores are nontemporal.  A template parameter, so that a kernel without the
+// hint is instruction for instruction what it was; the partial rows are re-read at once and are always plain stores.
+template <int WM, int WN, int WAVES_M, int WAVES_N, int KIND, int EB = (WM == 1 ? WN : 0), bool STREAM = false>
 __device__ __forceinline__ void conv_epilogue_tile(const ConvArgs& a, const TileInfo& ti, f32x4 (&acc)[WM][WN], float (&s1)[WM][4], float (&s2)[WM][4], int tid) {
   const int lane = tid & 63, wave = tid >> 6;
   const int wave_m = wave / WAVES_N, wave_n = wave % WAVES_N;
@@ -67,7 +69,7 @@ __device__ __forceinline__ void conv_epilogue_tile(const ConvArgs& a, const Tile
           const size_t off = ((size_t)(ti.n * a.Ho + oy) * a.Wo + ox) * a.Cout + co;
           float4 v = epi_bias_relu(a, acc[m][b], bias);
           if (a.flags & RCV_F_RESID) { const float4 rr = ld4(a.resid + off); v.x += rr.x; v.y += rr.y; v.z += rr.z; v.w += rr.w; }
-          *reinterpret_cast<float4*>(a.out + off) = v;
+          if constexpr (STREAM) sst4_nt(a.out + off, v); else *reinterpret_cast<float4*>(a.out + off) = v;
           if (a.stats == RCV_STATS_FWD) bn_sums_fwd(s1[m], s2[m], v);
           else if (a.stats == RCV_STATS_BWD_ENC) bn_sums_bwd_enc(s1[m], s2[m], v, ld4(a.epi_aux + off), mu);
           else if (a.stats == RCV_STATS_BWD_DEC) bn_sums_bwd_dec(s1[m], s2[m], v, ld4(a.epi_aux + off), e0, e1, mu);
@@ -114,7 +116,7 @@ __device__ __forceinline__ void conv_epilogue_tile(const ConvArgs& a, const Tile
             const size_t off = offb[i];
             float4 v = epi_bias_relu(a, acc[m][b], bias);
             if (a.flags & RCV_F_RESID) { const float4 rr = rrb[i]; v.x += rr.x; v.y += rr.y; v.z += rr.z; v.w += rr.w; }
-            *reinterpret_cast<float4*>(a.out + off) = v;
+            if constexpr (STREAM) sst4_nt(a.out + off, v); else *reinterpret_cast<float4*>(a.out + off) = v;
             if (a.stats == RCV_STATS_FWD) bn_sums_fwd(s1[m], s2[m], v);
             else if (a.stats == RCV_STATS_BWD_ENC) bn_sums_bwd_enc(s1[m], s2[m], v, eb[i], mu);
             else if (a.stats == RCV_STATS_BWD_DEC) bn_sums_bwd_dec(s1[m], s2[m], v, eb[i], e0, e1, mu);
@@ -171,14 +173,14 @@ __device__ __forceinline__ void conv_epilogue_stats(const ConvArgs& a, size_t ro
   }
 }
 
-template <int WM, int WN, int WAVES_M, int WAVES_N, int KIND, int EB = (WM == 1 ? WN : 0)>
+template <int WM, int WN, int WAVES_M, int WAVES_N, int KIND, int EB = (WM == 1 ? WN : 0), bool STREAM = false>
 __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, const TileInfo& ti, f32x4 (&acc)[WM][WN], float* red, int tid) {
   float s1[WM][4], s2[WM][4];
 #pragma unroll
   for (int m = 0; m < WM; ++m)
 #pragma unroll
     for (int r = 0; r < 4; ++r) { s1[m][r] = 0.f; s2[m][r] = 0.f; }
-  conv_epilogue_tile<WM, WN, WAVES_M, WAVES_N, KIND, EB>(a, ti, acc, s1, s2, tid);
+  conv_epilogue_tile<WM, WN, WAVES_M, WAVES_N, KIND, EB, STREAM>(a, ti, acc, s1, s2, tid);
   if (a.stats != RCV_STATS_NONE) {
     const size_t row = (size_t)(KIND == KIND_TPHASE ? (ti.py * 2 + ti.px) * a.n_pix_tiles : 0) + ti.pt;
     conv_epilogue_stats<WM, WAVES_M, WAVES_N, KIND>(a, row, ti.co0, s1, s2, red, tid);

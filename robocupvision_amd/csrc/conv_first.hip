@@ -19,7 +19,9 @@ __device__ __forceinline__ float cf_wave_sum(float v) {
   return v;
 }
 
-template <int DIL>
+// STREAM: nontemporal output stores (ConvArgs::nt_out: the output is stream-once, stream_hint.h); a template parameter: the plain
+// instantiation is instruction for instruction the kernel without the hint
+template <int DIL, bool STREAM = false>
 __global__ __launch_bounds__(256) void conv_first_kernel(const ConvArgs a, int tiles_x, int tiles_y, int total_tiles) {
   constexpr int TY = 16, TX = 64, NT = 256;
   constexpr int IH = TY + 2 * DIL, IWV = TX + 2 * DIL;       // staged rows / valid columns
@@ -179,7 +181,10 @@ __global__ __launch_bounds__(256) void conv_first_kernel(const ConvArgs a, int t
           const int r = f >> 7, fq = f & 127, blk = fq >> 3;
           const float4 v = st[r * 128 + 8 * blk + (((fq & 7) + blk) & 7)];
           const int oy = y0 + wv * 4 + pass * 2 + r, ox = x0 + (fq >> 1);
-          if (oy < a.H && ox < a.W) *reinterpret_cast<float4*>(a.out + ((size_t)(n * a.H + oy) * a.W + x0) * 8 + fq * 4) = v;
+          if (oy < a.H && ox < a.W) {
+            float* o = a.out + ((size_t)(n * a.H + oy) * a.W + x0) * 8 + fq * 4;
+            if constexpr (STREAM) sst4_nt(o, v); else *reinterpret_cast<float4*>(o) = v;
+          }
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // reads done before the window is rewritten
       }
@@ -228,7 +233,9 @@ static int conv_first_plan(const rcv_handle* h, const rcv_op* op, int kind, Conv
 static void conv_first_label(const ConvPlan& pl, const rcv_op* op, char* buf, size_t n) { snprintf(buf, n, "conv_first<%d>", op->i[RCV_I_DIL]); }
 
 static int conv_first_launch(const ConvPlan& pl, const ConvArgs& a, hipStream_t s) {
-  if (a.dil == 1) hipLaunchKernelGGL(conv_first_kernel<1>, dim3(pl.grid), dim3(256), 0, s, a, pl.tiles_x, pl.tiles_y, pl.total_tiles);
+  if (a.dil == 1 && a.nt_out) hipLaunchKernelGGL((conv_first_kernel<1, true>), dim3(pl.grid), dim3(256), 0, s, a, pl.tiles_x, pl.tiles_y, pl.total_tiles);
+  else if (a.dil == 1) hipLaunchKernelGGL(conv_first_kernel<1>, dim3(pl.grid), dim3(256), 0, s, a, pl.tiles_x, pl.tiles_y, pl.total_tiles);
+  else if (a.nt_out) hipLaunchKernelGGL((conv_first_kernel<2, true>), dim3(pl.grid), dim3(256), 0, s, a, pl.tiles_x, pl.tiles_y, pl.total_tiles);
   else hipLaunchKernelGGL(conv_first_kernel<2>, dim3(pl.grid), dim3(256), 0, s, a, pl.tiles_x, pl.tiles_y, pl.total_tiles);
   RCV_HIP(hipGetLastError());
   return RCV_OK;

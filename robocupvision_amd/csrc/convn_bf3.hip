@@ -50,7 +50,7 @@ __device__ __forceinline__ void n3_epi_setup(N3Epi<WM, WN>& E, const ConvArgs& a
     }
   }
 }
-template <int WM, int WN>
+template <int WM, int WN, bool STREAM>
 __device__ __forceinline__ void n3_epi_tile(const N3Epi<WM, WN>& E, const ConvArgs& a, size_t base, f32x4 (&acc)[WM][WN], float (&s1)[WM][4], float (&s2)[WM][4]) {
   float* __restrict__ out = a.out + base;
   const float* __restrict__ resid = a.resid + base;
@@ -75,7 +75,7 @@ __device__ __forceinline__ void n3_epi_tile(const N3Epi<WM, WN>& E, const ConvAr
       if (E.off[m][b] < 0) continue;
       float4 v = epi_bias_relu(a, acc[m][b], bias);
       if (a.flags & RCV_F_RESID) { v.x += rr[b].x; v.y += rr[b].y; v.z += rr[b].z; v.w += rr[b].w; }
-      *reinterpret_cast<float4*>(out + E.off[m][b]) = v;
+      if constexpr (STREAM) sst4_nt(out + E.off[m][b], v); else *reinterpret_cast<float4*>(out + E.off[m][b]) = v;
       if (a.stats == RCV_STATS_FWD) bn_sums_fwd(s1[m], s2[m], v);
       else if (a.stats == RCV_STATS_BWD_ENC) bn_sums_bwd_enc(s1[m], s2[m], v, ee[b], mu);
       else if (a.stats == RCV_STATS_BWD_DEC) bn_sums_bwd_dec(s1[m], s2[m], v, ee[b], e0, e1, mu);
@@ -83,7 +83,9 @@ __device__ __forceinline__ void n3_epi_tile(const N3Epi<WM, WN>& E, const ConvAr
   }
 }
 
-template <int CIN, int WM, int WN, int KIND, bool TWO>
+// STREAM: nontemporal output stores (ConvArgs::nt_out: the output is stream-once, stream_hint.h); a template parameter: the plain
+// instantiation is instruction for instruction the kernel without the hint
+template <int CIN, int WM, int WN, int KIND, bool TWO, bool STREAM = false>
 __global__ __launch_bounds__(512) void convn_bf3_kernel(const ConvArgs a) {
   constexpr int TAPS = KIND == KIND_GATHER ? 9 : 4;
   constexpr int NKS = (TAPS * CIN + 31) / 32;
@@ -206,11 +208,11 @@ __global__ __launch_bounds__(512) void convn_bf3_kernel(const ConvArgs a) {
       if constexpr (FAST_EPI) {
         if (ti.y0 + a.R <= lim_h && ti.x0 + a.Wt <= lim_w) {       // (uniform) the tile lies inside the plane: offsets precomputed
           const int ym = KIND == KIND_TMERGED ? 2 : 1;
-          n3_epi_tile<WM, WN>(E, a, ((size_t)(ti.n * a.Ho + ym * ti.y0) * a.Wo + ym * ti.x0) * a.Cout, acc, s1, s2);
+          n3_epi_tile<WM, WN, STREAM>(E, a, ((size_t)(ti.n * a.Ho + ym * ti.y0) * a.Wo + ym * ti.x0) * a.Cout, acc, s1, s2);
           fast = true;
         }
       }
-      if (!fast) conv_epilogue_tile<WM, WN, 1, 4, KIND, WN>(a, ti, acc, s1, s2, tid);
+      if (!fast) conv_epilogue_tile<WM, WN, 1, 4, KIND, WN, STREAM>(a, ti, acc, s1, s2, tid);
     }
     __syncthreads();
   }
@@ -321,6 +323,10 @@ static int convn_bf3_plan(const rcv_handle* h, const rcv_op* op, int kind, ConvP
 
 template <int CIN, int WM, int KIND>
 static int n3_launch_wn(const ConvPlan& pl, const ConvArgs& a, bool two, hipStream_t s) {
+  if (a.nt_out) {
+    if (pl.WN == 5) return two ? conv_launch_with_lds<convn_bf3_kernel<CIN, WM, 5, KIND, true, true>>(pl, a, s) : conv_launch_with_lds<convn_bf3_kernel<CIN, WM, 5, KIND, false, true>>(pl, a, s);
+    return two ? conv_launch_with_lds<convn_bf3_kernel<CIN, WM, 3, KIND, true, true>>(pl, a, s) : conv_launch_with_lds<convn_bf3_kernel<CIN, WM, 3, KIND, false, true>>(pl, a, s);
+  }
   if (pl.WN == 5) return two ? conv_launch_with_lds<convn_bf3_kernel<CIN, WM, 5, KIND, true>>(pl, a, s) : conv_launch_with_lds<convn_bf3_kernel<CIN, WM, 5, KIND, false>>(pl, a, s);
   return two ? conv_launch_with_lds<convn_bf3_kernel<CIN, WM, 3, KIND, true>>(pl, a, s) : conv_launch_with_lds<convn_bf3_kernel<CIN, WM, 3, KIND, false>>(pl, a, s);
 }

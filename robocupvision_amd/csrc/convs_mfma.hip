@@ -29,6 +29,10 @@ __device__ __forceinline__ float4 ld4b(const float* base, uint32_t byte_off) {
 __device__ __forceinline__ void st4b(float* base, uint32_t byte_off, float4 v) {
   *reinterpret_cast<float4*>(reinterpret_cast<char*>(base) + byte_off) = v;
 }
+// the streaming form, for the instantiations whose output is stream-once (stream_hint.h)
+__device__ __forceinline__ void st4b_nt(float* base, uint32_t byte_off, float4 v) {
+  sst4_nt(reinterpret_cast<float*>(reinterpret_cast<char*>(base) + byte_off), v);
+}
 
 typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
 
@@ -96,7 +100,9 @@ __device__ __forceinline__ void narrow_write_x(const ConvArgs& a, float* xl, con
   }
 }
 
-template <int WM, int WN, int CK, int KIND, int XMAX, bool TWO>
+// STREAM: nontemporal output stores (the launch's output tensor is stream-once, ConvArgs::nt_out); a template parameter: the plain
+// instantiation is instruction for instruction the kernel without the hint
+template <int WM, int WN, int CK, int KIND, int XMAX, bool TWO, bool STREAM = false>
 __global__ __launch_bounds__(256, 2) void convs_mfma_kernel(const ConvArgs a) {
   constexpr int NT = 256, WAVES = 4;
   constexpr int COT = WM * 16;
@@ -430,7 +436,7 @@ __global__ __launch_bounds__(256, 2) void convs_mfma_kernel(const ConvArgs a) {
               v.z = __builtin_amdgcn_fmed3f(v.z, 0.f, inf); v.w = __builtin_amdgcn_fmed3f(v.w, 0.f, inf);
             }
             if (RESID) { v.x += rr[bb].x; v.y += rr[bb].y; v.z += rr[bb].z; v.w += rr[bb].w; }
-            st4b(a.out, omt + ob[b], v);
+            if constexpr (STREAM) st4b_nt(a.out, omt + ob[b], v); else st4b(a.out, omt + ob[b], v);
             float4 e = make_float4(0.f, 0.f, 0.f, 0.f);
             if (NEED_E) e = EARLY ? ee_early[EARLY ? m : 0][b] : ee[bb];
             if (STATS == RCV_STATS_FWD) bn_sums_fwd(s1[m], s2[m], v);
@@ -597,9 +603,9 @@ static int convs_plan(const rcv_handle* h, const rcv_op* op, int kind, ConvPlan*
   return RCV_OK;
 }
 
-template <int WM, int WN, int CK, int KIND, bool TWO>
+template <int WM, int WN, int CK, int KIND, bool TWO, bool STREAM>
 static int convs_launch_inst(const ConvPlan& pl, const ConvArgs& a, hipStream_t s) {
-  auto kern = convs_mfma_kernel<WM, WN, CK, KIND, kNarrowXMAX, TWO>;
+  auto kern = convs_mfma_kernel<WM, WN, CK, KIND, kNarrowXMAX, TWO, STREAM>;
   static size_t configured[RCV_MAX_DEVICES];
   RCV_ENSURE_LDS(kern, pl.lds, pl.dev, configured);
   hipLaunchKernelGGL(kern, dim3(pl.grid), dim3(256), pl.lds, s, a);
@@ -609,7 +615,8 @@ static int convs_launch_inst(const ConvPlan& pl, const ConvArgs& a, hipStream_t 
 
 template <int WM, int WN, int CK, int KIND>
 static int convs_launch_two(const ConvPlan& pl, const ConvArgs& a, bool two, hipStream_t s) {
-  return two ? convs_launch_inst<WM, WN, CK, KIND, true>(pl, a, s) : convs_launch_inst<WM, WN, CK, KIND, false>(pl, a, s);
+  if (a.nt_out) return two ? convs_launch_inst<WM, WN, CK, KIND, true, true>(pl, a, s) : convs_launch_inst<WM, WN, CK, KIND, false, true>(pl, a, s);
+  return two ? convs_launch_inst<WM, WN, CK, KIND, true, false>(pl, a, s) : convs_launch_inst<WM, WN, CK, KIND, false, false>(pl, a, s);
 }
 
 template <int WM, int KIND>

@@ -32,6 +32,7 @@ struct rcv_handle {
   int num_cus;
   int max_lds;   // bytes of LDS one workgroup may use
   rcv_plan_cache* plans;
+  size_t stream_min_bytes;   // streaming-hint threshold (rcv_stream_once); 0: every hint off.  Set once, when the handle is created
   // RCV_F_SIDE_STREAM: ops off the critical path (filter gradients) run on this stream, forked from / joined to the caller's
   // stream with events inside rcv_run; created on first use
   hipStream_t side_stream;
@@ -83,6 +84,48 @@ __device__ __forceinline__ int xcd_remap(int b, int n) {
   return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + i;
 }
 #endif
+
+// ---- streaming hints, host half (device half and the reasoning: stream_hint.h) ----
+// Default threshold.  The Infinity Cache holds 256 MiB, and a line survives only while everything touched between two uses fits in it.
+// The kernel that writes a tensor of 128 MiB reads at least as many bytes again, and so does its consumer before it comes back to a
+// given line: 128 MiB + the producer's and the consumer's other traffic exceeds 256 MiB, so nothing of such a tensor is still cached
+// when it is asked for, and caching it only evicts what is re-read (halos, filters, partial rows).
+#define RCV_STREAM_MIN_MB_DEFAULT 128.0
+// MiB (may be fractional) -> the handle's threshold in bytes: 0 switches every hint off (the A/B lever); anything positive is at least
+// one byte.  The library itself reads no environment (tests/test_lib_abi.py): the binding hands RCV_STREAM_MIN_MB over ONCE per handle,
+// when it creates it (rcv_set_stream_min_mb; _lib.py).
+static inline size_t rcv_stream_min_bytes(double mb) {
+  if (!(mb > 0.0)) return 0;
+  const double b = mb * 1048576.0;
+  return b < 1.0 ? (size_t)1 : (b > 1e18 ? (size_t)1e18 : (size_t)b);
+}
+// true when a tensor of `bytes` is too large to be found in cache by whoever touches it next
+static inline bool rcv_stream_once(const rcv_handle* h, size_t bytes) { return h->stream_min_bytes != 0 && bytes >= h->stream_min_bytes; }
+// The hints of one record (RCV_F_STREAM_OUT | RCV_F_STREAM_PW), from its own N*H*W*C: the output tensor of a conv / transposed conv /
+// combine record, the pointwise operand of a filter-gradient record.  The record's own flag bits force a hint whatever the size.
+// Kinds without hinted kernels answer 0.  Whether a family honours a hint is the family's business (DESIGN 4.1 has the table).
+static inline uint32_t rcv_stream_hints(const rcv_handle* h, const rcv_op* op) {
+  uint32_t f = op->flags & (RCV_F_STREAM_OUT | RCV_F_STREAM_PW);
+  const size_t n = (size_t)(op->i[RCV_I_N] > 0 ? op->i[RCV_I_N] : 0);
+  const size_t c_out = (size_t)(op->i[RCV_I_COUT] > 0 ? op->i[RCV_I_COUT] : 0);
+  switch (op->kind) {
+    case RCV_OP_CONV:
+    case RCV_OP_TCONV:
+      if (rcv_stream_once(h, n * op->i[RCV_I_HO] * op->i[RCV_I_WO] * c_out * sizeof(float))) f |= RCV_F_STREAM_OUT;
+      break;
+    case RCV_OP_COMBINE:      // out: [N][H][W][C], twice the channels with RCV_F_CONCAT; the two inputs have the size of a plain output
+      if (rcv_stream_once(h, n * op->i[RCV_I_H] * op->i[RCV_I_W] * c_out * sizeof(float) * ((op->flags & RCV_F_CONCAT) ? 2 : 1))) f |= RCV_F_STREAM_OUT;
+      if (rcv_stream_once(h, n * op->i[RCV_I_H] * op->i[RCV_I_W] * c_out * sizeof(float))) f |= RCV_F_STREAM_PW;
+      break;
+    case RCV_OP_WGRAD:        // pointwise operand: [N][Hp][Wp][CB]
+      if (rcv_stream_once(h, n * op->i[RCV_I_HO] * op->i[RCV_I_WO] * c_out * sizeof(float))) f |= RCV_F_STREAM_PW;
+      break;
+    default:
+      f = 0;
+      break;
+  }
+  return f;
+}
 
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 static inline int round_up(int a, int b) { return ceil_div(a, b) * b; }

@@ -210,46 +210,48 @@ __global__ void bn_bwd_kernel(const float* __restrict__ part, int n_part, int C,
 // ------------------------------------------------------------------------------------------
 // RCV_OP_COMBINE: up = relu(t*c0+c1) + f(r)   f = affine / affine+relu / identity  (model.py:509)
 // ------------------------------------------------------------------------------------------
+// nt_out / nt_pw (uniform): streaming store of `out` / streaming loads of t and r where the tensors are too large to stay cached
+// (stream_hint.h); the per-channel constants are re-read by every thread and stay plain
 template <int MODE2>
 __global__ void combine_kernel(const float* __restrict__ t, const float* __restrict__ tc, const float* __restrict__ r,
-                               const float* __restrict__ rc, float* __restrict__ out, size_t n4, int C) {
+                               const float* __restrict__ rc, float* __restrict__ out, size_t n4, int C, int nt_out, int nt_pw) {
   const int C4 = C / 4;
   for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < n4; e += (size_t)gridDim.x * blockDim.x) {
     const int ch = (int)(e % C4) * 4;
-    const float4 a = sld4(t + e * 4), s = sld4(tc + ch), h = sld4(tc + C + ch);
+    const float4 a = sld4_hint(t + e * 4, nt_pw), s = sld4(tc + ch), h = sld4(tc + C + ch);
     float4 v;
     v.x = fmaxf(fmaf(a.x, s.x, h.x), 0.f); v.y = fmaxf(fmaf(a.y, s.y, h.y), 0.f);
     v.z = fmaxf(fmaf(a.z, s.z, h.z), 0.f); v.w = fmaxf(fmaf(a.w, s.w, h.w), 0.f);
-    float4 b = sld4(r + e * 4);
+    float4 b = sld4_hint(r + e * 4, nt_pw);
     if (MODE2 != RCV_LOAD_PLAIN) {
       const float4 s2 = sld4(rc + ch), h2 = sld4(rc + C + ch);
       b.x = fmaf(b.x, s2.x, h2.x); b.y = fmaf(b.y, s2.y, h2.y); b.z = fmaf(b.z, s2.z, h2.z); b.w = fmaf(b.w, s2.w, h2.w);
       if (MODE2 == RCV_LOAD_AFFINE_RELU) { b.x = fmaxf(b.x, 0.f); b.y = fmaxf(b.y, 0.f); b.z = fmaxf(b.z, 0.f); b.w = fmaxf(b.w, 0.f); }
     }
     v.x += b.x; v.y += b.y; v.z += b.z; v.w += b.w;
-    sst4(out + e * 4, v);
+    sst4_hint(out + e * 4, v, nt_out);
   }
 }
 
 // RCV_F_CONCAT: up[.., 0:C] = relu(t*c0+c1), up[.., C:2C] = f(r)   (torch.cat([layer(up), skip], 1), model.py:507)
 __global__ void concat_kernel(const float* __restrict__ t, const float* __restrict__ tc, const float* __restrict__ r,
-                              const float* __restrict__ rc, float* __restrict__ out, size_t n4, int C, int mode2) {
+                              const float* __restrict__ rc, float* __restrict__ out, size_t n4, int C, int mode2, int nt_out, int nt_pw) {
   const int C4 = C / 4;
   for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < n4; e += (size_t)gridDim.x * blockDim.x) {
     const int ch = (int)(e % C4) * 4;
     const size_t pix = e / C4;
-    const float4 a = sld4(t + e * 4), s = sld4(tc + ch), h = sld4(tc + C + ch);
+    const float4 a = sld4_hint(t + e * 4, nt_pw), s = sld4(tc + ch), h = sld4(tc + C + ch);
     float4 v;
     v.x = fmaxf(fmaf(a.x, s.x, h.x), 0.f); v.y = fmaxf(fmaf(a.y, s.y, h.y), 0.f);
     v.z = fmaxf(fmaf(a.z, s.z, h.z), 0.f); v.w = fmaxf(fmaf(a.w, s.w, h.w), 0.f);
-    float4 b = sld4(r + e * 4);
+    float4 b = sld4_hint(r + e * 4, nt_pw);
     if (mode2 != RCV_LOAD_PLAIN) {
       const float4 s2 = sld4(rc + ch), h2 = sld4(rc + C + ch);
       b.x = fmaf(b.x, s2.x, h2.x); b.y = fmaf(b.y, s2.y, h2.y); b.z = fmaf(b.z, s2.z, h2.z); b.w = fmaf(b.w, s2.w, h2.w);
       if (mode2 == RCV_LOAD_AFFINE_RELU) { b.x = fmaxf(b.x, 0.f); b.y = fmaxf(b.y, 0.f); b.z = fmaxf(b.z, 0.f); b.w = fmaxf(b.w, 0.f); }
     }
-    sst4(out + pix * 2 * C + ch, v);
-    sst4(out + pix * 2 * C + C + ch, b);
+    sst4_hint(out + pix * 2 * C + ch, v, nt_out);
+    sst4_hint(out + pix * 2 * C + C + ch, b, nt_out);
   }
 }
 
@@ -1399,10 +1401,12 @@ int rcv_launch_small(const rcv_handle* h, const rcv_op* op, hipStream_t s, OpQue
       const float* t = (const float*)op->p[RCV_P_IN]; const float* tc = (const float*)op->p[RCV_P_IN_C];
       const float* r = (const float*)op->p[RCV_P_IN2]; const float* rc = (const float*)op->p[RCV_P_IN2_C];
       float* out = (float*)op->p[RCV_P_OUT];
-      if (op->flags & RCV_F_CONCAT) hipLaunchKernelGGL(concat_kernel, dim3(g), dim3(256), 0, s, t, tc, r, rc, out, n4, Cout, m2);
-      else if (m2 == RCV_LOAD_PLAIN) hipLaunchKernelGGL(combine_kernel<RCV_LOAD_PLAIN>, dim3(g), dim3(256), 0, s, t, tc, r, rc, out, n4, Cout);
-      else if (m2 == RCV_LOAD_AFFINE) hipLaunchKernelGGL(combine_kernel<RCV_LOAD_AFFINE>, dim3(g), dim3(256), 0, s, t, tc, r, rc, out, n4, Cout);
-      else hipLaunchKernelGGL(combine_kernel<RCV_LOAD_AFFINE_RELU>, dim3(g), dim3(256), 0, s, t, tc, r, rc, out, n4, Cout);
+      const uint32_t hints = rcv_stream_hints(h, op);
+      const int nt_out = (hints & RCV_F_STREAM_OUT) ? 1 : 0, nt_pw = (hints & RCV_F_STREAM_PW) ? 1 : 0;
+      if (op->flags & RCV_F_CONCAT) hipLaunchKernelGGL(concat_kernel, dim3(g), dim3(256), 0, s, t, tc, r, rc, out, n4, Cout, m2, nt_out, nt_pw);
+      else if (m2 == RCV_LOAD_PLAIN) hipLaunchKernelGGL(combine_kernel<RCV_LOAD_PLAIN>, dim3(g), dim3(256), 0, s, t, tc, r, rc, out, n4, Cout, nt_out, nt_pw);
+      else if (m2 == RCV_LOAD_AFFINE) hipLaunchKernelGGL(combine_kernel<RCV_LOAD_AFFINE>, dim3(g), dim3(256), 0, s, t, tc, r, rc, out, n4, Cout, nt_out, nt_pw);
+      else hipLaunchKernelGGL(combine_kernel<RCV_LOAD_AFFINE_RELU>, dim3(g), dim3(256), 0, s, t, tc, r, rc, out, n4, Cout, nt_out, nt_pw);
       break;
     }
     case RCV_OP_CLS_FWD: {
