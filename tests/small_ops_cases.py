@@ -257,9 +257,41 @@ CONV_RANDN_CASES = [("conv", (4, 15, 20, 64, 64, 1), 0, "conv_dma"), ("conv", (4
                     ("tconv", (2, 24, 32, 32, 16), 4, "tconvn_bf3")]
 
 
-def build_conv_stats(shape, transposed=False, nchw=False, seed=0, randn=False):
-    """Operands shared by the four statistics variants of one shape: x (LOAD_AFFINE constants c, or the NCHW image), sparse filter,
-    bias, residual, e and its (c0, c1, mean)."""
+STATS_FAMILIES = dict(conv=CONV_STATS_SHAPES, tconv=TCONV_STATS_SHAPES, image=IMAGE_STATS_SHAPES, tiny=TINY_STATS_SHAPES,
+                      dilated=DILATED_STATS_SHAPES)
+
+# One shape per persistent kernel family on which a workgroup loops over three tiles or more, the last round ragged (conv_first: two
+# rounds): the sums carried in registers across the tiles of a workgroup.  (family of build_conv_stats, shape, filter layout,
+# (label, workgroups, tiles) as the planner answers for 256 CUs -- pinned by tests/test_plan_census.py)
+MULTI_ROUND_STATS_CASES = [
+    ("conv", (65, 64, 80, 8, 8, 1), 0, ("convs_mfma<1,5,8>", 347, 1040)),
+    ("conv", (13, 96, 128, 8, 8, 1), 3, ("convn_bf3<8,1,5>", 256, 520)),
+    ("tconv", (65, 64, 80, 16, 8), 1, ("tconvms_mfma<2,5,16>", 347, 1040)),
+    ("tconv", (9, 96, 128, 32, 16), 4, ("tconvn_bf3<32,4,3>", 256, 576)),
+    ("image", (73, 100, 140, 3, 8, 1, 1), 0, ("conv_first<1>", 1024, 1533)),
+]
+# the randn case beside them (532 tiles over 256 workgroups): appended to CONV_RANDN_CASES
+MULTI_ROUND_RANDN_CASE = ("conv", (19, 64, 80, 32, 32, 1), 3, "convn_bf3")
+MULTI_ROUND_RANDN_PIN = ("convn_bf3<32,2,3>", 256, 532)
+CONV_RANDN_CASES = CONV_RANDN_CASES + [MULTI_ROUND_RANDN_CASE]
+
+
+def multi_round_stats_variants(case):
+    """conv_first takes no residual and no backward statistics (the other variants of an image shape run on convs_mfma)."""
+    if case[3][0].startswith("conv_first"):
+        return [(R.STATS_FWD, 3), (R.STATS_FWD, 0)]
+    return STATS_VARIANTS
+
+
+def randn_variants(prefix):
+    """(statistics kind, flags) of a randn case on the kernel family `prefix`."""
+    if prefix == "conv_first":          # the first-layer kernel takes no residual and no backward statistics
+        return [(R.STATS_FWD, 3), (R.STATS_FWD, 0)]
+    return [(R.STATS_FWD, 3), (R.STATS_BWD_ENC, 4), (R.STATS_BWD_DEC, 4)]
+
+
+def conv_stats_dims(shape, transposed=False, nchw=False):
+    """The dimensions of a statistics case, without its operands."""
     if transposed:
         N, H, W, Cin, Cout = shape
         s, d, Ho, Wo = 2, 1, 2 * H, 2 * W
@@ -267,8 +299,15 @@ def build_conv_stats(shape, transposed=False, nchw=False, seed=0, randn=False):
         N, H, W, Cin, Cout, s = shape[:6]
         d = shape[6] if len(shape) > 6 else 1
         Ho, Wo = (H - 1) // s + 1, (W - 1) // s + 1
+    return dict(shape=shape, transposed=transposed, nchw=nchw, N=N, H=H, W=W, Cin=Cin, Cout=Cout, s=s, d=d, Ho=Ho, Wo=Wo)
+
+
+def build_conv_stats(shape, transposed=False, nchw=False, seed=0, randn=False):
+    """Operands shared by the four statistics variants of one shape: x (LOAD_AFFINE constants c, or the NCHW image), sparse filter,
+    bias, residual, e and its (c0, c1, mean)."""
+    c = conv_stats_dims(shape, transposed, nchw)
+    N, H, W, Cin, Cout, s, d, Ho, Wo = (c[k] for k in ("N", "H", "W", "Cin", "Cout", "s", "d", "Ho", "Wo"))
     rng = np.random.default_rng(11000 + seed + H * W + Cin + 3 * Cout)
-    c = dict(shape=shape, transposed=transposed, nchw=nchw, N=N, H=H, W=W, Cin=Cin, Cout=Cout, s=s, d=d, Ho=Ho, Wo=Wo)
     c["x"] = R.grid(rng, (N, Cin, H, W) if nchw else (N, H, W, Cin), 2)
     c["c"] = R.grid_consts(rng, Cin)
     c["w"] = R.sparse_filter(rng, Cout, Cin, transposed=transposed)
@@ -345,6 +384,36 @@ def check_conv_stats(c):
             assert_sensitive(lambda k: (R.stats(kind, v, c["e"], c["ec"], k),), c["npix"], 0, "conv statistics kind %d" % kind)
     z = R._f(c["e"]) * R._f(c["ec"])[0] + R._f(c["ec"])[1]
     assert (z == 0).any() and (z < 0).any()
+
+
+def multi_round_row_pixels(case):
+    """Upper bound of the output pixels behind ONE partial row of a multi-round case: the tile rounds of a workgroup x the pixel slots
+    of its tile (convs_mfma<WM,WN,CK> / convn_bf3<CK,WM,WN>: 64 WN, four output pixels per slot in the merged transposed forms;
+    conv_first: 16 x 64).  From the case's pin, i.e. for 256 CUs: on fewer CUs a workgroup runs more rounds and the bound of
+    check_multi_round_stats would have to be taken again (on more CUs it only gets easier)."""
+    label, grid, tiles = case[3]
+    name, args = label.rstrip(">").split("<")
+    args = [int(a) for a in args.split(",")]
+    slots = 16 * 64 if name == "conv_first" else 64 * (args[2] if name.endswith("n_bf3") else args[1]) * (4 if name.startswith("tconv") else 1)
+    return -(-tiles // grid) * slots
+
+
+def check_multi_round_stats(c, case):
+    """The preconditions of an exact case whose plane is too large for one fp32 sum: every PARTIAL ROW is exact -- every term an
+    integer, the largest |term| x the pixels behind a row below 2^24 -- and the rows are added in float64; every variant stays
+    sensitive to the last and to the middle pixel; the RCV_STATS_BWD_DEC mask meets pixels at and below zero (check_conv_stats)."""
+    npx = multi_round_row_pixels(case)
+    z = R._f(c["e"]) * R._f(c["ec"])[0] + R._f(c["ec"])[1]
+    assert (z == 0).any() and (z < 0).any() and (z > 0).any()
+    for kind, flags in multi_round_stats_variants(case):
+        v, ref, sabs = conv_stats_reference(c, kind, flags)
+        assert np.all(v == np.round(v)) and np.all(sabs == np.round(sabs)) and float(sabs.max()) < 2.0 ** 53
+        dev = np.abs(R._f(c["e"]) - R._f(c["ec"])[2])
+        assert np.all(dev == np.round(dev))
+        worst = max(float((v * v).max()), float((np.abs(v) * dev).max()), float(np.abs(v).max()))
+        assert worst * npx < 2.0 ** 24, "largest term %.0f x %d pixels per partial row reaches 2^24" % (worst, npx)
+        if flags & 4 or not c["transposed"]:
+            assert_sensitive(lambda k: (R.stats(kind, v, c["e"], c["ec"], k),), c["npix"], 0, "conv statistics kind %d" % kind)
 
 
 # ------------------------------------------------------------------------------------------ Adam + L1

@@ -26,6 +26,7 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 import conv_record_cases as RC      # noqa: E402  (tests/conv_record_cases.py: the dilated and decoder-order records)
+import small_ops_cases as K         # noqa: E402  (tests/small_ops_cases.py: the operands of the epilogue-statistics cases)
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
@@ -60,18 +61,15 @@ def _pack_dims(rows, cols, layout, merged=False):
     return rp, cp, (3 * ksteps * cp * 16 if split else taps * rp * cp)
 
 
-CONV_SHAPES = [(4, 15, 20, 64, 64, 1), (4, 15, 20, 128, 64, 1), (2, 30, 40, 128, 128, 1), (4, 30, 40, 64, 32, 1), (4, 15, 20, 64, 128, 1),
-               (4, 30, 40, 32, 64, 2), (4, 30, 40, 32, 32, 1), (4, 60, 80, 16, 16, 1), (3, 5, 7, 64, 64, 1), (2, 37, 53, 32, 64, 1),
-               (2, 120, 160, 8, 16, 2), (5, 9, 11, 128, 128, 1), (1, 60, 80, 64, 128, 2), (2, 48, 64, 16, 32, 2),
-               (32, 30, 40, 128, 128, 1), (16, 60, 80, 64, 64, 1)]      # (the planes of the 640 x 480 step: the 320-pixel tile of conv_bf3 = its 32x32x16 form)
+CONV_SHAPES = RC.CONV_SHAPES      # (the tables and record builders of the plain cases: tests/conv_record_cases.py)
 
 
 @pytest.mark.parametrize("N,H,W,Cin,Cout,s", CONV_SHAPES)
-@pytest.mark.parametrize("mode_name", ["grad_enc", "affine"])
+@pytest.mark.parametrize("mode_name", list(RC.CONV_KERNEL_MODES))
 def test_conv_kernels_vs_fp64(N, H, W, Cin, Cout, s, mode_name):
     from robocupvision_amd import _lib as L
     h = L.handle(0)
-    mode = {"grad_enc": L.LOAD_GRAD_ENC, "affine": L.LOAD_AFFINE}[mode_name]
+    mode = RC.CONV_KERNEL_MODES[mode_name]
     gen = torch.Generator().manual_seed(1000 + H * W + Cin)
     Ho, Wo = (H - 1) // s + 1, (W - 1) // s + 1
     x, xa, c = _rand(gen, N, H, W, Cin), _rand(gen, N, H, W, Cin), _rand(gen, 5, Cin, scale=0.5)
@@ -80,10 +78,8 @@ def test_conv_kernels_vs_fp64(N, H, W, Cin, Cout, s, mode_name):
     xd, xad, cd, wd, rd = (v.to(DEV) for v in (x, xa, c, w, resid))
     # filter layouts (rcv_op_filter_layout): 0 plain, 2 Winograd, 3 split-bf16 (conv_bf3.hip: fp32 products as six bf16 MFMA products)
     # 3 on the wide stride-1 layers: conv_bf3.hip; on the 8 / 16 / 32 -> <= 32 channel layers (stride 1 | 2): convn_bf3.hip
-    winos = [0] + ([2] if (s == 1 and Cin % 16 == 0 and Cin >= 32 and Cout >= 64) else []) + \
-            ([3] if (s == 1 and Cin % 32 == 0 and Cin >= 64 and Cout >= 64) or (Cin in (8, 16, 32) and Cout <= 32) else []) + \
-            ([5] if (s == 2 and Cin % 16 == 0 and Cin >= 32 and Cout >= 64) else [])       # stride-2 wide: conv2_bf3_kernel
-    for wino in winos:
+    # (5: the stride-2 wide layers, conv2_bf3_kernel)
+    for wino in RC.conv_layouts(Cin, Cout, s, 1):
         rp, cp, nfl = _pack_dims(Cin, Cout, wino)
         wp = torch.zeros(nfl, device=DEV)
         job = L.RcvPackJob()
@@ -92,9 +88,8 @@ def test_conv_kernels_vs_fp64(N, H, W, Cin, Cout, s, mode_name):
         table = torch.frombuffer(bytearray(bytes((L.RcvPackJob * 1)(job))), dtype=torch.uint8).to(DEV)
         out = torch.full((N, Ho, Wo, Cout), float("nan"), device=DEV)
         pack = L.make_op(L.OP_PACK, 0, count=1, aux0=16 * rp * cp, p_in=table.data_ptr())
-        conv = L.make_op(L.OP_CONV, L.F_RESID, n=N, h=H, w=W, cin=Cin, cout=Cout, ho=Ho, wo=Wo, stride=s, dil=1, inmode=mode,
-                         aux0=wino, p_in=xd.data_ptr(), p_in_aux=xad.data_ptr(), p_in_c=cd.data_ptr(), p_w=wp.data_ptr(),
-                         p_out=out.data_ptr(), p_resid=rd.data_ptr())
+        conv = RC.conv_kernel_record((N, H, W, Cin, Cout, s), mode_name, wino, p_in=xd.data_ptr(), p_in_aux=xad.data_ptr(),
+                                     p_in_c=cd.data_ptr(), p_w=wp.data_ptr(), p_out=out.data_ptr(), p_resid=rd.data_ptr())
         lst = L.OpList([pack, conv])
         label = lst.labels(h)[1]
         assert label.startswith("conv_wino") == (wino == 2) and ("_bf3" in label) == (wino in (3, 5)), label
@@ -177,8 +172,7 @@ def test_dilated_and_decoder_order_conv_records_vs_fp64(shape, mode_name):
             close(part.double().cpu().sum(0), ref_rows, "%s %s %s partial rows" % (label, shape, mode_name), rtol=1e-4, floor=1.0)
 
 
-@pytest.mark.parametrize("N,H,W,Cin,Cout,s,d", [(2, 48, 64, 3, 8, 1, 1), (2, 120, 160, 3, 16, 1, 1), (3, 37, 53, 4, 16, 1, 1), (2, 48, 64, 3, 16, 2, 1),
-                                               (2, 40, 56, 3, 8, 1, 2), (1, 33, 47, 3, 16, 2, 1), (2, 24, 40, 2, 32, 1, 2)])
+@pytest.mark.parametrize("N,H,W,Cin,Cout,s,d", RC.NCHW_CONV_SHAPES)
 def test_conv_nchw_image_input_vs_fp64(N, H, W, Cin, Cout, s, d):
     """RCV_LOAD_NCHW: the graph input in the reference's own layout (the 3-channel image) read by the first conv without an NHWC copy --
     on the first-layer kernel (8 output channels, stride 1) and on the narrow-layer kernel (the other shapes)."""
@@ -197,8 +191,7 @@ def test_conv_nchw_image_input_vs_fp64(N, H, W, Cin, Cout, s, d):
     table = torch.frombuffer(bytearray(bytes((L.RcvPackJob * 1)(job))), dtype=torch.uint8).to(DEV)
     out = torch.full((N, Ho, Wo, Cout), float("nan"), device=DEV)
     pack = L.make_op(L.OP_PACK, 0, count=1, aux0=9 * rp * cp, p_in=table.data_ptr())
-    conv = L.make_op(L.OP_CONV, L.F_BIAS | L.F_RELU, n=N, h=H, w=W, cin=Cin, cout=Cout, ho=Ho, wo=Wo, stride=s, dil=d, inmode=L.LOAD_NCHW,
-                     p_in=xd.data_ptr(), p_w=wp.data_ptr(), p_bias=bd.data_ptr(), p_out=out.data_ptr())
+    conv = RC.nchw_conv_record((N, H, W, Cin, Cout, s, d), p_in=xd.data_ptr(), p_w=wp.data_ptr(), p_bias=bd.data_ptr(), p_out=out.data_ptr())
     lst = L.OpList([pack, conv])
     label = lst.labels(h)[1]
     lst.run(h, torch.cuda.current_stream().cuda_stream)
@@ -207,20 +200,11 @@ def test_conv_nchw_image_input_vs_fp64(N, H, W, Cin, Cout, s, d):
     assert err <= 3e-6, (label, err)
 
 
-WGRAD_SHAPES = [(4, 15, 20, 64, 64, 1), (4, 30, 40, 32, 64, 2), (4, 15, 20, 64, 128, 1), (4, 15, 20, 128, 128, 1), (4, 30, 40, 32, 32, 1),
-                (4, 60, 80, 16, 16, 1), (4, 120, 160, 8, 16, 2), (2, 15, 20, 64, 64, 1), (4, 16, 20, 64, 64, 1), (4, 15, 24, 64, 64, 1),
-                (3, 5, 7, 64, 64, 1), (4, 10, 14, 128, 64, 1), (64, 15, 20, 64, 64, 1), (1, 30, 40, 64, 64, 1), (4, 7, 10, 128, 128, 1),
-                (2, 37, 53, 16, 32, 1), (2, 48, 64, 8, 8, 1), (3, 33, 47, 32, 16, 1), (2, 60, 80, 32, 64, 2), (2, 120, 160, 16, 32, 2),
-                (3, 14, 18, 64, 128, 2), (1, 96, 128, 8, 16, 2),
-                # planes with at least one 8 x 16 tile per CU: the narrow layers' split-bf16 kernel (wgradn_bf3.hip), every channel-tile shape
-                (8, 64, 128, 16, 16, 1), (8, 64, 128, 32, 32, 1), (8, 128, 128, 16, 16, 2), (8, 128, 128, 16, 32, 2), (6, 60, 100, 32, 16, 1),
-                (5, 72, 112, 16, 32, 1), (8, 128, 128, 32, 32, 2), (6, 62, 100, 16, 24, 1), (8, 128, 128, 32, 16, 2),
-                # eight gathered channels, stride 2: the pixel-pair view of wgradn_bf3
-                (8, 128, 128, 8, 16, 2), (8, 128, 128, 8, 32, 2), (6, 126, 140, 8, 16, 2), (7, 100, 132, 8, 24, 2)]
+WGRAD_SHAPES = RC.WGRAD_SHAPES
 
 
 @pytest.mark.parametrize("N,H,W,Cin,Cout,s", WGRAD_SHAPES)
-@pytest.mark.parametrize("modes", [False, True, "dec"])
+@pytest.mark.parametrize("modes", RC.WGRAD_KERNEL_MODES)
 def test_filter_gradient_kernels_vs_fp64(N, H, W, Cin, Cout, s, modes):
     from robocupvision_amd import _lib as L
     h = L.handle(0)
@@ -239,18 +223,15 @@ def test_filter_gradient_kernels_vs_fp64(N, H, W, Cin, Cout, s, modes):
         Gad, gcd = Ga.to(DEV), gc.to(DEV)
         pc = torch.rand(5, Cout, generator=gen) + 0.5
         pcd = pc.to(DEV)
-        op = L.make_op(L.OP_WGRAD, 0, n=N, h=H, w=W, cin=Cin, ho=Ho, wo=Wo, cout=Cout, stride=2, dil=1, inmode=L.LOAD_GRAD_DEC,
-                       inmode2=L.LOAD_AFFINE, p_in=Gd.data_ptr(), p_in_aux=Gad.data_ptr(), p_in_c=gcd.data_ptr(), p_in2=Pd.data_ptr(),
-                       p_in2_c=pcd.data_ptr())
+        op = RC.wgrad_kernel_record((N, H, W, Cin, Cout, s), modes, p_in=Gd.data_ptr(), p_in_aux=Gad.data_ptr(), p_in_c=gcd.data_ptr(),
+                                    p_in2=Pd.data_ptr(), p_in2_c=pcd.data_ptr())
         x64, gy64 = _load_fp64(L.LOAD_GRAD_DEC, G, Ga, gc, L), _load_fp64(L.LOAD_AFFINE, P, P, pc, L)
     elif modes:      # gathered operand: BatchNorm apply of the producer; pointwise operand: BatchNorm + ReLU backward of (g, r)
-        op = L.make_op(L.OP_WGRAD, L.F_BIAS, n=N, h=H, w=W, cin=Cin, ho=Ho, wo=Wo, cout=Cout, stride=s, dil=1, inmode=L.LOAD_AFFINE,
-                       inmode2=L.LOAD_GRAD_ENC, p_in=Gd.data_ptr(), p_in_c=gcd.data_ptr(), p_in2=Pd.data_ptr(), p_in2_aux=Pad.data_ptr(),
-                       p_in2_c=pcd.data_ptr())
+        op = RC.wgrad_kernel_record((N, H, W, Cin, Cout, s), modes, p_in=Gd.data_ptr(), p_in_c=gcd.data_ptr(), p_in2=Pd.data_ptr(),
+                                    p_in2_aux=Pad.data_ptr(), p_in2_c=pcd.data_ptr())
         x64, gy64 = _load_fp64(L.LOAD_AFFINE, G, G, gc, L), _load_fp64(L.LOAD_GRAD_ENC, P, Pa, pc, L)
     else:
-        op = L.make_op(L.OP_WGRAD, L.F_BIAS, n=N, h=H, w=W, cin=Cin, ho=Ho, wo=Wo, cout=Cout, stride=s, dil=1, inmode=L.LOAD_PLAIN,
-                       inmode2=L.LOAD_PLAIN, p_in=Gd.data_ptr(), p_in2=Pd.data_ptr())
+        op = RC.wgrad_kernel_record((N, H, W, Cin, Cout, s), modes, p_in=Gd.data_ptr(), p_in2=Pd.data_ptr())
         x64, gy64 = G.double(), P.double()
     nb = L.op_workspace(h, op)
     part = torch.zeros(max(nb // 4, 4), device=DEV)
@@ -324,8 +305,7 @@ def test_dilated_and_decoder_order_filter_gradients_vs_fp64(shape, pair):
         assert e <= 5e-7 and eb <= 5e-7, (label, e, eb)
 
 
-@pytest.mark.parametrize("N,H,W,Cin,Cout,s,d", [(2, 48, 64, 3, 8, 1, 1), (2, 40, 56, 3, 8, 1, 2), (2, 48, 64, 3, 16, 1, 1), (2, 37, 53, 4, 16, 1, 1),
-                                               (2, 48, 64, 3, 32, 1, 1), (2, 48, 64, 4, 8, 1, 1), (1, 96, 128, 3, 16, 2, 1), (3, 24, 40, 2, 8, 1, 1)])
+@pytest.mark.parametrize("N,H,W,Cin,Cout,s,d", RC.NCHW_WGRAD_SHAPES)
 @pytest.mark.parametrize("two", [False, True])
 def test_filter_gradient_nchw_image_vs_fp64(N, H, W, Cin, Cout, s, d, two):
     """Filter gradient of a first layer: the gathered operand is the NCHW image itself (RCV_LOAD_NCHW, <= 4 channels) -- the vector-ALU
@@ -341,8 +321,8 @@ def test_filter_gradient_nchw_image_vs_fp64(N, H, W, Cin, Cout, s, d, two):
     dw = torch.full((Cout, Cin, 3, 3), float("nan"), device=DEV)
     db = torch.full((Cout,), float("nan"), device=DEV)
     mode2 = L.LOAD_GRAD_ENC if two else L.LOAD_PLAIN
-    op = L.make_op(L.OP_WGRAD, L.F_BIAS, n=N, h=H, w=W, cin=Cin, ho=Ho, wo=Wo, cout=Cout, stride=s, dil=d, inmode=L.LOAD_NCHW, inmode2=mode2,
-                   p_in=Gd.data_ptr(), p_in2=Pd.data_ptr(), p_in2_aux=Pad.data_ptr(), p_in2_c=pcd.data_ptr())
+    op = RC.nchw_wgrad_record((N, H, W, Cin, Cout, s, d), two, p_in=Gd.data_ptr(), p_in2=Pd.data_ptr(), p_in2_aux=Pad.data_ptr(),
+                              p_in2_c=pcd.data_ptr())
     gy64 = _load_fp64(mode2, P, Pa, pc, L)
     nb = L.op_workspace(h, op)
     part = torch.zeros(max(nb // 4, 4), device=DEV)
@@ -359,8 +339,7 @@ def test_filter_gradient_nchw_image_vs_fp64(N, H, W, Cin, Cout, s, d, two):
     assert e <= 5e-7 and eb <= 5e-7, (lst.labels(h)[0], e, eb)
 
 
-TCONV_SHAPES = [(2, 15, 20, 128, 64), (2, 30, 40, 64, 32), (2, 60, 80, 32, 16), (2, 120, 160, 16, 8), (3, 7, 9, 128, 64), (1, 33, 21, 64, 32),
-                (2, 24, 32, 32, 16), (4, 8, 10, 64, 64), (2, 20, 28, 16, 16), (1, 5, 6, 128, 128)]
+TCONV_SHAPES = RC.TCONV_SHAPES
 
 
 @pytest.mark.parametrize("N,H,W,Cin,Cout", TCONV_SHAPES)
@@ -375,7 +354,7 @@ def test_transposed_conv_kernels_vs_fp64(N, H, W, Cin, Cout, mode_name):
     from robocupvision_amd import _lib as L
     from robocupvision_amd.engine import MERGED_TCONV_MAX_COUT
     h = L.handle(0)
-    mode = dict(RC.TCONV_RECORD_MODES, grad_enc=L.LOAD_GRAD_ENC, affine=L.LOAD_AFFINE)[mode_name]
+    mode = RC.TCONV_KERNEL_MODES[mode_name]
     gen = torch.Generator().manual_seed(3000 + H * W + Cin)
     x, xa, c = _rand(gen, N, H, W, Cin), _rand(gen, N, H, W, Cin), _rand(gen, 5, Cin, scale=0.5)
     w, bias = _rand(gen, Cin, Cout, 3, 3, scale=0.1), _rand(gen, Cout)
@@ -384,8 +363,7 @@ def test_transposed_conv_kernels_vs_fp64(N, H, W, Cin, Cout, mode_name):
     xd, xad, cd, wd, bd = (v.to(DEV) for v in (x, xa, c, w, bias))
     merged = 1 if Cout <= MERGED_TCONV_MAX_COUT else 0
     # merged layout as it is (fp32 kernels) and, where the split-bf16 narrow kernel is built, split into bf16 (layout 4: tconvn_bf3)
-    layouts = [merged] + ([4] if merged and (Cin, (4 * Cout + 15) // 16 * 16) in ((16, 32), (32, 64)) else [])
-    for layout in layouts:
+    for layout in RC.tconv_layouts(Cin, Cout, MERGED_TCONV_MAX_COUT):
         rp, cp, nfl = _pack_dims(Cin, Cout, layout, merged=bool(merged))
         wp = torch.zeros(nfl, device=DEV)
         job = L.RcvPackJob()
@@ -394,9 +372,8 @@ def test_transposed_conv_kernels_vs_fp64(N, H, W, Cin, Cout, mode_name):
         table = torch.frombuffer(bytearray(bytes((L.RcvPackJob * 1)(job))), dtype=torch.uint8).to(DEV)
         out = torch.full((N, 2 * H, 2 * W, Cout), float("nan"), device=DEV)
         pack = L.make_op(L.OP_PACK, 0, count=1, aux0=9 * rp * cp, p_in=table.data_ptr())
-        tconv = L.make_op(L.OP_TCONV, L.F_BIAS, n=N, h=H, w=W, cin=Cin, cout=Cout, ho=2 * H, wo=2 * W, stride=2, dil=1, inmode=mode, aux0=layout,
-                          p_in=xd.data_ptr(), p_in_aux=xad.data_ptr(), p_in_c=cd.data_ptr(), p_w=wp.data_ptr(), p_bias=bd.data_ptr(),
-                          p_out=out.data_ptr())
+        tconv = RC.tconv_record((N, H, W, Cin, Cout), mode_name, layout, p_in=xd.data_ptr(), p_in_aux=xad.data_ptr(), p_in_c=cd.data_ptr(),
+                                p_w=wp.data_ptr(), p_bias=bd.data_ptr(), p_out=out.data_ptr())
         lst = L.OpList([pack, tconv])
         label = lst.labels(h)[1]
         assert ("_bf3" in label) == (layout == 4), label
@@ -436,9 +413,8 @@ def test_maxpool_backward_first_maximum_exact(N, H, W, C, affine):
     assert torch.equal(out.cpu(), ref)
 
 
-@pytest.mark.parametrize("N,H,W,Cin,Cout,s,d", [(2, 15, 20, 32, 64, 1, 2), (2, 15, 20, 64, 64, 1, 2), (2, 15, 20, 64, 32, 1, 2), (1, 7, 9, 128, 64, 1, 1),
-                                               (3, 9, 11, 16, 48, 2, 1), (1, 30, 40, 64, 128, 1, 1), (2, 5, 3, 20, 36, 1, 2)])
-@pytest.mark.parametrize("mode_name,flags", [("affine_relu", 0), ("affine", 3), ("plain", 1)])
+@pytest.mark.parametrize("N,H,W,Cin,Cout,s,d", RC.TINY_CONV_SHAPES)
+@pytest.mark.parametrize("mode_name,flags", RC.TINY_CONV_MODES)
 def test_tiny_plane_conv_vs_fp64(N, H, W, Cin, Cout, s, d, mode_name, flags):
     """conv_small.hip (inference on planes of a few hundred pixels: LabelProp's dilated convs for one frame pair, model.py:546-548): one
     MFMA block per workgroup, K split over its four waves, operands straight from global memory.  Zero padding applies AFTER the load
@@ -468,9 +444,8 @@ def test_tiny_plane_conv_vs_fp64(N, H, W, Cin, Cout, s, d, mode_name, flags):
     table = torch.frombuffer(bytearray(bytes((L.RcvPackJob * 1)(job))), dtype=torch.uint8).to(DEV)
     out = torch.full((N, Ho, Wo, Cout), float("nan"), device=DEV)
     pack = L.make_op(L.OP_PACK, 0, count=1, aux0=9 * rp * cp, p_in=table.data_ptr())
-    conv = L.make_op(L.OP_CONV, (L.F_BIAS if use_bias else 0) | (L.F_RELU if use_relu else 0), n=N, h=H, w=W, cin=Cin, cout=Cout, ho=Ho, wo=Wo,
-                     stride=s, dil=d, inmode=mode, p_in=xd.data_ptr(), p_in_c=cd.data_ptr(), p_w=wp.data_ptr(), p_bias=bd.data_ptr(),
-                     p_out=out.data_ptr())
+    conv = RC.tiny_conv_record((N, H, W, Cin, Cout, s, d), mode_name, flags, p_in=xd.data_ptr(), p_in_c=cd.data_ptr(), p_w=wp.data_ptr(),
+                               p_bias=bd.data_ptr(), p_out=out.data_ptr())
     lst = L.OpList([pack, conv])
     label = lst.labels(h)[1]
     assert label.startswith("conv_small"), label
@@ -562,6 +537,85 @@ def test_classifier_data_gradient_record_vs_fp64(plane, cout, n_class):
     err = float((out.double().cpu() - ref).abs().max() / ref.abs().max())
     print(".cls dgrad %s %s -> %d, %d classes: max error %.3e" % (label, plane, cout, n_class, err))
     assert err <= 3e-6, (label, err)
+
+
+MULTI_ROUND_PARAMS = [(case, mode_name) for case in RC.MULTI_ROUND_CASES for mode_name in RC.multi_round_modes(case)]
+
+
+@pytest.mark.parametrize("case,mode_name", MULTI_ROUND_PARAMS,
+                         ids=["%s-%s-layout%d-%s" % (c[0], "x".join(map(str, c[1])), c[2], m) for c, m in MULTI_ROUND_PARAMS])
+def test_multi_round_records_vs_fp64(case, mode_name):
+    """The persistent kernels beyond their first tile round (tests/conv_record_cases.py MULTI_ROUND_CASES): on 256 CUs every workgroup
+    of convs_mfma / tconvms_mfma, convn_bf3 / tconvn_bf3 loops over three tiles or more and the last round is ragged (conv_first:
+    two rounds) -- the prefetch of the next tile while this one is contracted, the parity of convn_bf3's two staging buffers, the tile
+    index of the later rounds, workgroups without a tile in the last round, and the BatchNorm sums carried across the tiles of a
+    workgroup.  The condition is re-asserted on the device's own handle: should it no longer hold, the test fails.
+    Forward: RCV_LOAD_AFFINE_RELU with the bias and RCV_STATS_FWD (the first layer: RCV_LOAD_NCHW); gradients: RCV_LOAD_GRAD_DEC and
+    RCV_LOAD_GRAD_ENC with the residual.  Each record runs plain and with RCV_F_STREAM_OUT forced (the streaming store is a template
+    instantiation of its own in these families): outputs and partial rows NaN-prefilled, torch.equal between the two runs, and per
+    element against float64 at the bars of the tests above -- 3e-6 of the largest entry, the float64 sum of the partial rows within
+    close(rtol=1e-4, floor=1.0).
+    Measured (MI355X, largest over the three modes; plain and streaming runs bit-identical): convs_mfma<1,5,8> 2.6e-7, <1,5,16> 3.5e-7,
+    <2,3,32> 5.1e-7, <2,2,16> 4.4e-7, <1,3,8> 2.4e-7; convn_bf3<8,1,5> 2.5e-7, <16,1,5> 3.4e-7, <32,2,3> 5.0e-7, <16,2,3> 2.7e-7;
+    tconvms_mfma<2,5,16> 2.0e-7, <4,3,32> 3.7e-7; tconvn_bf3<16,2,5> 1.5e-7, <32,4,3> 3.4e-7; conv_first<1> 2.6e-7.  43 cases (14 shapes x 3 loads, the first layer's one), at most
+    0.9 s each; the largest tensor is the 48 MB output of the 32 -> 16 transposed conv at 37 x 64 x 80 (tconvms_mfma<4,3,32> needs
+    1036 tiles of 192 input pixels for three rounds)."""
+    import plan_census as PC
+    from robocupvision_amd import _lib as L
+    from test_gpu_blocks import close
+    h = L.handle(0)
+    what, shape, layout, pinned = case
+    N, H, W, Cin, Cout, Ho, Wo, s = RC.multi_round_dims(case)
+    mode, flags, stats = RC.MULTI_ROUND_MODES[mode_name]
+    gen = torch.Generator().manual_seed(8000 + H * W + Cin + 3 * layout)
+    x = _rand(gen, N, Cin, H, W) if what == "first" else _rand(gen, N, H, W, Cin)
+    xa, c = _rand(gen, *x.shape), _rand(gen, 5, Cin, scale=0.5)
+    w = _rand(gen, Cin, Cout, 3, 3, scale=0.1) if what == "tconv" else _rand(gen, Cout, Cin, 3, 3, scale=0.1 if Cin > 4 else 0.2)
+    resid, bias = _rand(gen, N, Ho, Wo, Cout), _rand(gen, Cout)
+    x64 = x.double() if what == "first" else _load_fp64(mode, x, xa, c, L).permute(0, 3, 1, 2)
+    if what == "tconv":
+        ref = F.conv_transpose2d(x64, w.double(), stride=2, padding=1, output_padding=1).permute(0, 2, 3, 1)
+    else:
+        ref = F.conv2d(x64, w.double(), stride=s, padding=1).permute(0, 2, 3, 1)
+    ref = ref + (resid.double() if flags & L.F_RESID else bias.double())
+    ref_rows = torch.stack([ref.sum((0, 1, 2)), (ref * ref).sum((0, 1, 2))])
+    xd, xad, cd, wd, rd, bd = (v.to(DEV) for v in (x, xa, c, w, resid, bias))
+    if what == "tconv":
+        rp, cp, nfl = _pack_dims(Cin, Cout, layout, merged=True)
+        pack, wp, table = _packed_filter(L, wd, Cin, Cout, 0, 0, rp, cp, nfl, layout)
+    elif what == "first":
+        rp, cp = (Cin + 3) // 4 * 4, (Cout + 15) // 16 * 16
+        pack, wp, table = _packed_filter(L, wd, Cout, Cin, 1, 0, rp, cp, 9 * rp * cp, 0)
+    else:
+        rp, cp, nfl = _pack_dims(Cin, Cout, layout)
+        pack, wp, table = _packed_filter(L, wd, Cout, Cin, 1, 0, rp, cp, nfl, layout)
+    L.OpList([pack]).run(h, torch.cuda.current_stream().cuda_stream)
+    got = []
+    for stream in (False, True):
+        out = torch.full((N, Ho, Wo, Cout), float("nan"), device=DEV)
+        op = RC.multi_round_record(case, mode_name, stream, p_in=xd.data_ptr(), p_in_aux=xad.data_ptr(), p_in_c=cd.data_ptr(),
+                                   p_w=wp.data_ptr(), p_out=out.data_ptr(), p_resid=rd.data_ptr(), p_bias=bd.data_ptr())
+        assert L.op_stream_hints(h, op) == (L.F_STREAM_OUT if stream else 0)
+        grid, tiles = PC.assert_multi_round(op, h, L.load().rcv_num_cus(h), pinned)
+        part = None
+        if stats != L.STATS_NONE:
+            nbytes = L.op_workspace(h, op)
+            assert op.i[L.RCV_I_NPART] == grid and nbytes == grid * 2 * Cout * 4
+            part = torch.full((grid, 2, Cout), float("nan"), device=DEV)
+            op.p[L.RCV_P_PART] = part.data_ptr()
+        lst = L.OpList([op])
+        label = lst.labels(h)[0]
+        lst.run(h, torch.cuda.current_stream().cuda_stream)
+        torch.cuda.synchronize()
+        err = float((out.double().cpu() - ref).abs().max() / ref.abs().max())
+        print(".%s %s %s%s: %d tiles over %d workgroups, max error %.3e" % (label, shape, mode_name, " streaming" if stream else "", tiles, grid, err))
+        assert err <= 3e-6, (label, stream, err)        # (NaN, an unwritten element, fails here as well)
+        if part is not None:
+            assert not torch.isnan(part).any(), (label, "a workgroup left its partial row unwritten")
+            close(part.double().cpu().sum(0), ref_rows, "%s %s %s partial rows" % (label, shape, mode_name), rtol=1e-4, floor=1.0)
+        got.append((out, part))
+    assert torch.equal(got[0][0], got[1][0]), (label, "the streaming store changes the output")
+    assert got[0][1] is None or torch.equal(got[0][1], got[1][1]), (label, "the streaming store changes the partial rows")
 
 
 def _folded_errors(out, pre, ref):
@@ -669,7 +723,7 @@ def _conv_layouts(Cin, Cout, s):
     return RC.conv_layouts(Cin, Cout, s, 1)
 
 
-def _stats_case_on_device(c, layout, merged, labels, variants=None, randn=False):
+def _stats_case_on_device(c, layout, merged, labels, variants=None, randn=False, multi_round=None):
     """Packs the filter of a small_ops_cases conv case in `layout` and runs the record once per statistics variant: the stored
     tensor and the float64 sum of ALL partial rows (NaN-prefilled: an unwritten row shows) must equal the float64 answer exactly --
     or, for random operands (randn), meet the accuracy bar of the tests above resp. close(rtol=1e-4, floor=1.0)."""
@@ -693,10 +747,12 @@ def _stats_case_on_device(c, layout, merged, labels, variants=None, randn=False)
     pack = L.make_op(L.OP_PACK, 0, count=1, aux0=16 * rp * cp, p_in=table.data_ptr())
     for kind, flags in (variants or K.STATS_VARIANTS):
         out = torch.full((N, Ho, Wo, Cout), float("nan"), device=DEV)
-        op = L.make_op(L.OP_TCONV if tr else L.OP_CONV, flags, n=N, h=H, w=W, cin=Cin, cout=Cout, ho=Ho, wo=Wo, stride=c["s"], dil=c["d"],
-                       inmode=L.LOAD_NCHW if c["nchw"] else L.LOAD_AFFINE, aux0=layout, stats=kind, p_in=dv["x"].data_ptr(),
-                       p_in_c=dv["c"].data_ptr(), p_w=wp.data_ptr(), p_bias=dv["bias"].data_ptr(), p_resid=dv["res"].data_ptr(),
-                       p_epi_aux=dv["e"].data_ptr(), p_epi_c=dv["ec"].data_ptr(), p_out=out.data_ptr())
+        op = RC.stats_record(c, layout, kind, flags, p_in=dv["x"].data_ptr(), p_in_c=dv["c"].data_ptr(), p_w=wp.data_ptr(),
+                             p_bias=dv["bias"].data_ptr(), p_resid=dv["res"].data_ptr(), p_epi_aux=dv["e"].data_ptr(),
+                             p_epi_c=dv["ec"].data_ptr(), p_out=out.data_ptr())
+        if multi_round is not None:       # the guard of a multi-round case: still three rounds, the last ragged, on THIS device
+            import plan_census as PC
+            PC.assert_multi_round(op, h, L.load().rcv_num_cus(h), multi_round)
         nbytes = L.op_workspace(h, op)
         n_part = op.i[L.RCV_I_NPART]
         assert n_part > 0 and nbytes == n_part * 2 * Cout * 4
@@ -746,19 +802,10 @@ def test_epilogue_statistics_exact(family):
     import small_ops_cases as K
     from robocupvision_amd.engine import MERGED_TCONV_MAX_COUT
     labels = set()
-    shapes = dict(conv=K.CONV_STATS_SHAPES, tconv=K.TCONV_STATS_SHAPES, image=K.IMAGE_STATS_SHAPES, tiny=K.TINY_STATS_SHAPES,
-                  dilated=K.DILATED_STATS_SHAPES)[family]
-    for shape in shapes:
+    for shape in K.STATS_FAMILIES[family]:
         c = K.build_conv_stats(shape, transposed=family == "tconv", nchw=family == "image")
-        if family == "conv":
-            for layout in _conv_layouts(c["Cin"], c["Cout"], c["s"]):
-                _stats_case_on_device(c, layout, False, labels)
-        elif family == "tconv":
-            merged = 1 if c["Cout"] <= MERGED_TCONV_MAX_COUT else 0
-            for layout in [merged] + ([4] if merged and (c["Cin"], (4 * c["Cout"] + 15) // 16 * 16) in ((16, 32), (32, 64)) else []):
-                _stats_case_on_device(c, layout, merged, labels)
-        else:
-            _stats_case_on_device(c, 0, False, labels)
+        for layout, merged in RC.stats_layouts(family, c, MERGED_TCONV_MAX_COUT):
+            _stats_case_on_device(c, layout, merged, labels)
     print(".epilogue statistics %s: labels %s" % (family, sorted(labels)))
     expected = dict(conv={"conv_dma", "conv_mfma", "conv_wino", "conv_bf3", "conv2_bf3", "convs_mfma", "convn_bf3"},
                     tconv={"tconva_dma", "tconvms_mfma", "tconvn_bf3"}, image={"conv_first", "convs_mfma"}, tiny={"conv_dma", "conv_mfma"},
@@ -766,19 +813,31 @@ def test_epilogue_statistics_exact(family):
     assert labels == expected, (family, sorted(labels))
 
 
-@pytest.mark.parametrize("ci", range(11))
+@pytest.mark.parametrize("ci", range(12))
 def test_epilogue_statistics_randn(ci):
     """Random operands (dense filters), one case per kernel family, every statistics kind: the stored tensor at the bar of the accuracy
     tests above, the float64 sum of the partial rows within close(rtol=1e-4, floor=1.0) of the float64 restatement -- so that the exact
-    cases do not hide a rounding-order regression of the partial sums."""
+    cases do not hide a rounding-order regression of the partial sums.  The last case is a multi-round one (convn_bf3, 532 tiles over
+    256 workgroups): sums carried across the tiles of a workgroup."""
     import small_ops_cases as K
-    import small_ops_restatement as R
-    assert len(K.CONV_RANDN_CASES) == 11
+    assert len(K.CONV_RANDN_CASES) == 12
     family, shape, layout, prefix = K.CONV_RANDN_CASES[ci]
     c = K.build_conv_stats(shape, transposed=family == "tconv", nchw=family == "image", randn=True)
-    variants = [(R.STATS_FWD, 3), (R.STATS_BWD_ENC, 4), (R.STATS_BWD_DEC, 4)]
-    if prefix == "conv_first":          # the first-layer kernel takes no residual and no backward statistics
-        variants = [(R.STATS_FWD, 3), (R.STATS_FWD, 0)]
     labels = set()
-    _stats_case_on_device(c, layout, family == "tconv" and layout in (1, 4), labels, variants=variants, randn=True)
+    _stats_case_on_device(c, layout, family == "tconv" and layout in (1, 4), labels, variants=K.randn_variants(prefix), randn=True,
+                          multi_round=K.MULTI_ROUND_RANDN_PIN if K.CONV_RANDN_CASES[ci] == K.MULTI_ROUND_RANDN_CASE else None)
     assert labels == {prefix}, labels
+
+
+@pytest.mark.parametrize("k", range(len(K.MULTI_ROUND_STATS_CASES)))
+def test_epilogue_statistics_exact_beyond_the_first_tile_round(k):
+    """test_epilogue_statistics_exact on one plane per persistent kernel family (convs_mfma, convn_bf3, tconvms_mfma, tconvn_bf3,
+    conv_first) on which a workgroup loops over three tiles or more, the last round ragged (conv_first: two rounds): s1 / s2 stay in
+    registers across all tiles of a workgroup, which writes ONE partial row.  Every partial row is exact in fp32
+    (tests/test_small_ops.py asserts the bound row by row); the rows are added in float64 and must equal the exact integers."""
+    import small_ops_cases as K
+    case = K.MULTI_ROUND_STATS_CASES[k]
+    c = K.build_conv_stats(case[1], transposed=case[0] == "tconv", nchw=case[0] == "image")
+    labels = set()
+    _stats_case_on_device(c, case[2], case[0] == "tconv", labels, variants=K.multi_round_stats_variants(case), multi_round=case[3])
+    assert labels == {case[3][0].split("<")[0]}, labels

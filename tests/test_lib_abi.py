@@ -124,7 +124,7 @@ def test_planner_routes_the_dilated_and_decoder_order_records():
     reached = {}
     for cus in (256, 64):
         h = L.planner_handle(cus)
-        conv, tconv, wgrad, stats = set(), set(), set(), set()
+        conv, tconv, wgrad, stats, census = set(), set(), set(), set(), set()
         # 1. conv records: every shape x load mode x filter layout
         for shape in RC.CONV_RECORD_SHAPES:
             N, H, W, Cin, Cout, s, d = shape
@@ -134,6 +134,9 @@ def test_planner_routes_the_dilated_and_decoder_order_records():
                     assert label.startswith("conv_wino") == (layout == 2) and ("_bf3" in label) == (layout in (3, 5)), (shape, label)
                     if cus == 256 and shape in RC.DILATED_CONV_LABELS:
                         assert label == RC.DILATED_CONV_LABELS[shape], (shape, mode_name, label)
+                    if cus == 256 and (shape, layout) in RC.CENSUS_CONV_LABELS:      # the tilings only whole networks reached
+                        assert label == RC.CENSUS_CONV_LABELS[(shape, layout)], (shape, layout, mode_name, label)
+                        census.add((shape, layout))
                     conv.add(label.split("<")[0])
         for shape in TCONV_SHAPES:
             merged = 1 if shape[4] <= MERGED_TCONV_MAX_COUT else 0
@@ -141,7 +144,11 @@ def test_planner_routes_the_dilated_and_decoder_order_records():
                 for mode_name in RC.TCONV_RECORD_MODES:
                     label = plan(h, RC.tconv_record(shape, mode_name, layout))
                     assert ("_bf3" in label) == (layout == 4), (shape, label)
+                    if cus == 256 and (shape, layout) in RC.CENSUS_TCONV_LABELS:
+                        assert label == RC.CENSUS_TCONV_LABELS[(shape, layout)], (shape, layout, mode_name, label)
+                        census.add((shape, layout))
                     tconv.add(label.split("<")[0])
+        assert cus != 256 or census == set(RC.CENSUS_CONV_LABELS) | set(RC.CENSUS_TCONV_LABELS)
         # 2. filter-gradient records: the dilated ones, and dilation 1 as routed and under RCV_F_MFMA_FP32
         dilated = set()
         for pair in RC.WGRAD_RECORD_PAIRS:
@@ -169,7 +176,7 @@ def test_planner_routes_the_dilated_and_decoder_order_records():
                 stats.add(plan(h, op, True).split("<")[0])
         reached[cus] = dict(conv=conv, tconv=tconv, wgrad=wgrad, stats=stats)
     assert reached[256] == dict(conv={"conv_dma", "conv_mfma", "convs_mfma", "conv_wino", "conv_bf3", "conv2_bf3", "convn_bf3"},
-                                tconv={"tconva_dma", "tconvms_mfma", "tconvn_bf3"},
+                                tconv={"tconva_dma", "tconvms_mfma", "tconvn_bf3", "tconv_dma", "tconvm_dma"},
                                 wgrad={"wgrad_mfma", "wgrad_bf3", "wgradn_bf3"},
                                 stats={"conv_dma", "conv_mfma", "convs_mfma"}), reached[256]
 

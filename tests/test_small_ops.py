@@ -280,6 +280,13 @@ def test_conv_statistics_cases_are_exact(family):
         K.check_conv_stats(K.build_conv_stats(shape, transposed=family == "tconv", nchw=family == "image"))
 
 
+@pytest.mark.parametrize("k", range(len(K.MULTI_ROUND_STATS_CASES)))
+def test_multi_round_statistics_cases_are_exact_row_by_row(k):
+    """The multi-round planes are too large for check_conv_stats' bound on the whole sum; each partial row stays exact."""
+    case = K.MULTI_ROUND_STATS_CASES[k]
+    K.check_multi_round_stats(K.build_conv_stats(case[1], transposed=case[0] == "tconv", nchw=case[0] == "image"), case)
+
+
 def test_conv1x1_is_refused_when_planned():
     """RCV_OP_CONV1X1 is in the header and has no kernel: rcv_op_workspace refuses it with a message; nothing is launched."""
     from robocupvision_amd import _lib as L
