@@ -279,9 +279,23 @@ enum {
                              * (i[NSPLIT] filled by rcv_op_workspace): per split the partial filter [25 taps][8][16] and the partial bias [8] */
   RCV_OP_WGRAD5_REDUCE = 57, /* fixed-order sum (split 0, 1, ...) of RCV_OP_WGRAD5's partial rows -> p[OUT] = dW [COUT][CIN][5][5], p[BIAS] = db
                              * [COUT] or NULL; i[CIN] = 8 / 16, i[COUT] = 1..8 classes, i[NSPLIT], p[PART]                              */
-  RCV_OP_PACK5 = 58          /* p[IN] = parameter [COUT][CIN][5][5] (i[CIN] = 8 / 16, i[COUT] = 1..8) -> p[OUT] = float[25][rows][16], zero
+  RCV_OP_PACK5 = 58,         /* p[IN] = parameter [COUT][CIN][5][5] (i[CIN] = 8 / 16, i[COUT] = 1..8) -> p[OUT] = float[25][rows][16], zero
                              * padded: forward rows = CIN, out[t][ci][co] = w[co][ci][t]; with RCV_F_FLIP the data gradient's filter, rows =
                              * 8, out[t][co][ci] = w[co][ci][24 - t]                                                                    */
+  RCV_OP_LP_INPUT = 59       /* LabelProp's input from a PREDICTION of the previous frame (rcv_lp_input; csrc/lp_input.hip; makeLPImages.py:94-102,
+                             * validLabelProp.py:116-135, the commented prior of labelPropTrain.py:179): per pixel of sample s,
+                             * [Ycur, Yprev, Ycur - Yprev, prior_0 .. prior_4].  i[N] = B samples, i[H], i[W], i[CIN] = channels per frame (only
+                             * channel 0 is read), i[COUT] = classes (5), i[INMODE] = the prior's form: 1 = class map uint8[B][H][W], 8 = class
+                             * map int64[B][H][W] (labelToPred; a value outside [0, 5), decided on all 64 bits, gives -1 in all five channels
+                             * and is never used as an index), 4 = logits float[B][5][H][W] (2 * softmax - 1: m = max z, e_c = expf(z_c - m),
+                             * S = (((e_0 + e_1) + e_2) + e_3) + e_4, 2 * (e_c / S) - 1, IEEE division).  i[AUX0] = pairing: 0 = stream form,
+                             * p[IN] = current frames float[B][C][H][W], p[IN2] = previous frames float[B][i[AUX1]][H][W] (i[AUX1] = 0: C
+                             * channels), sample s reads frame s of both and prior[s]; 1 = pair form, p[IN] = float[B/2][2][C][H][W] seen as
+                             * B frames (B even, p[IN2] not read, i[AUX1] = 0 or C), sample s reads frames s, s ^ 1 and prior[s ^ 1]
+                             * (labelPropTrain.py:181-182; the targets of that script are the label tensor itself: none are written).
+                             * p[X0] = the prior, p[OUT] = inputs float[B][H][W][8] (NHWC, 16-byte aligned), p[X1] = Ycur as a dense plane
+                             * float[B][H][W] or NULL.  Refused when planned: classes != 5, another prior form or pairing, odd B in the
+                             * pair form, B / C / H / W < 1, an operand of 2^31 elements or more                                        */
 };
 
 /* i[RCV_I_AUX0] of RCV_OP_PRUNE: how the threshold of a tensor is chosen */
@@ -624,6 +638,17 @@ int rcv_update_labels(rcv_handle* h, const void* labels, int elem_bytes, const f
  * [0, 5) gives -1 in all five class channels (it is never used as an index).  Exact: copies, +-1 and one fp32 subtraction.        */
 int rcv_labelprop_batch(rcv_handle* h, const float* images, const int64_t* labels, int B, int C, int H, int W, int num_class,
                         float* inputs, int64_t* targets, void* stream);
+
+/* RCV_OP_LP_INPUT: LabelProp's input for B samples from a prediction of the previous frame, one launch; inputs float[B][H][W][8]
+ * (NHWC) = [Ycur, Yprev, Ycur - Yprev, prior], Y = channel 0.  It replaces the loop body of makeLPImages.py:98-100 and the assembly of
+ * validLabelProp.py:116-130 run on a class map the network wrote (RCV_OP_CLS_LABEL's uint8 map: prior_bytes 1; int64: 8), and builds the
+ * prior the reference leaves commented, `F.softmax(modelSeg(img))*2 - 1.0` (labelPropTrain.py:179,250, validLabelProp.py:118), from fp32
+ * NCHW logits float[B][5][H][W] (prior_bytes 4) with the arithmetic stated at RCV_OP_LP_INPUT.  pair = 0: cur float[B][C][H][W], prev
+ * float[B][prev_C][H][W] (prev_C = 0: C), prior[s] belongs to sample s.  pair = 1: cur is float[B/2][2][C][H][W] seen as B frames, prev
+ * is not read, sample s takes frames s and s ^ 1 and prior[s ^ 1] (labelPropTrain.py:181-182).  plane: float[B][H][W] = Ycur, or NULL.
+ * Hard priors are exact (copies, +-1, one fp32 subtraction); num_class must be 5.                                                  */
+int rcv_lp_input(rcv_handle* h, const float* cur, const float* prev /*NULL when pair*/, int prev_C, const void* prior, int prior_bytes, int pair,
+                 int B, int C, int H, int W, int num_class, float* inputs, float* plane /*may be NULL*/, void* stream);
 
 /* The per-image work of the reference's loader (SSYUVDataset.__getitem__, dataset.py:107-133; ColorJitter, dataset.py:19-39) and the
  * training loop's maskLabel (transform.py:26-49, train.py:43-46) for a whole batch in one launch: frames uint8[B][Hs][Ws][3] (decoded

@@ -12,6 +12,10 @@ def __getattr__(name):
     if name == "labelprop_batch":
         from .model import labelprop_batch
         return labelprop_batch
+    # ... and robocupvision_amd.labelprop_next(cur, prev, prior): the same input from a prediction of the previous frame
+    if name == "labelprop_next":
+        from .model import labelprop_next
+        return labelprop_next
     # robocupvision_amd.data / prepare_batch / draw_jitter / SSYUVDataset: batches prepared on the device (data.py)
     if name == "data":
         import importlib
@@ -33,7 +37,7 @@ def __getattr__(name):
         from . import palette
         return getattr(palette, name)
     # ... and the objects of a class map (test.py:43-67, DBConvert.py:47-102): find_objects
-    if name in ("Segmenter", "find_objects", "Objects", "DBCONVERT"):
+    if name in ("Segmenter", "find_objects", "Objects", "DBCONVERT", "LabelPropagator"):
         from . import infer
         return getattr(infer, name)
     # ... and the patches of those objects, cut out of the full-resolution frames for the patch classifiers: patches.py

@@ -38,6 +38,8 @@ OP_BATCH_PREP_IDX = 52      # OP_BATCH_PREP whose image b is store[index[b]], th
 OP_RGB_PREP_IDX = 53        # OP_RGB_PREP whose image b is store[index[b]]: trainer.py:75-123's loader from a resident store (rcv.h RCV_OP_RGB_PREP_IDX)
 OP_LP_PAIR_PREP = 54        # both frames of a LabelProp pair from the store -> the 8-channel input of labelPropTrain.py:36-66, 162-193 (rcv.h RCV_OP_LP_PAIR_PREP)
 OP_CONV5, OP_WGRAD5, OP_WGRAD5_REDUCE, OP_PACK5 = 55, 56, 57, 58      # the 5x5 classifier convolution family (rcv.h RCV_OP_CONV5 ..., csrc/conv5.hip)
+OP_LP_INPUT = 59            # LabelProp's input from a prediction of the previous frame: class map or logits as the prior (rcv.h RCV_OP_LP_INPUT, csrc/lp_input.hip)
+LP_PRIOR_U8, LP_PRIOR_LOGITS, LP_PRIOR_I64 = 1, 4, 8      # i[INMODE] of OP_LP_INPUT: the prior's form
 PRUNE_MAX_RATIO, PRUNE_STD_SEARCH, PRUNE_SMALLEST_K = range(3)      # i[AUX0] of OP_PRUNE: pruneModelNew / pruneModel / pruneModel2
 PRUNE_MAX_ITER = 4096
 PRUNE_ST_OK, PRUNE_ST_NO_END, PRUNE_ST_ALL_ZERO, PRUNE_ST_BAD_JOB = range(4)
@@ -85,6 +87,7 @@ EXPORTS = [
     "rcv_sgd_step_pruned", "rcv_prune_check", "rcv_prune", "rcv_find_objects", "rcv_rgb_prep",
     "rcv_farneback_flow", "rcv_update_labels", "rcv_object_patches", "rcv_resize_u8", "rcv_batch_prep_indexed",
     "rcv_rgb_prep_indexed", "rcv_lp_pair_prep", "rcv_conv5x5", "rcv_wgrad5x5", "rcv_op_stream_hints", "rcv_set_stream_min_mb",
+    "rcv_lp_input",
 ]
 
 
@@ -134,6 +137,8 @@ def load():
         lib.rcv_update_labels.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         lib.rcv_labelprop_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                             C.c_void_p, C.c_void_p]
+        if hasattr(lib, "rcv_lp_input"):      # (RCV_LIBRARY may name an older build)
+            lib.rcv_lp_input.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p] + [C.c_int] * 7 + [C.c_void_p] * 3
         lib.rcv_batch_prep.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p, C.c_int, C.c_void_p, C.c_int] + \
             [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.rcv_frame_prep.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 3

@@ -120,6 +120,8 @@ static int dispatch(const rcv_handle* h, const rcv_op* op, hipStream_t s, OpQuer
       return rcv_launch_lp_tail(h, op, s, q);
     case RCV_OP_LP_BATCH:
       return rcv_launch_lp_batch(h, op, s, q);
+    case RCV_OP_LP_INPUT:
+      return rcv_launch_lp_input(h, op, s, q);
     case RCV_OP_BATCH_PREP:
     case RCV_OP_FRAME_PREP:
     case RCV_OP_RESIZE_U8:
@@ -491,6 +493,17 @@ int rcv_labelprop_batch(rcv_handle* h, const float* images, const int64_t* label
   op.kind = RCV_OP_LP_BATCH;
   op.i[RCV_I_N] = B; op.i[RCV_I_H] = H; op.i[RCV_I_W] = W; op.i[RCV_I_CIN] = C; op.i[RCV_I_COUT] = num_class;
   op.p[RCV_P_IN] = (void*)images; op.p[RCV_P_IN2] = (void*)labels; op.p[RCV_P_OUT] = inputs; op.p[RCV_P_X0] = targets;
+  return rcv_run(h, &op, 1, stream);
+}
+
+int rcv_lp_input(rcv_handle* h, const float* cur, const float* prev, int prev_C, const void* prior, int prior_bytes, int pair, int B, int C,
+                 int H, int W, int num_class, float* inputs, float* plane, void* stream) {
+  rcv_op op;
+  memset(&op, 0, sizeof(op));
+  op.kind = RCV_OP_LP_INPUT;
+  op.i[RCV_I_N] = B; op.i[RCV_I_H] = H; op.i[RCV_I_W] = W; op.i[RCV_I_CIN] = C; op.i[RCV_I_COUT] = num_class;
+  op.i[RCV_I_INMODE] = prior_bytes; op.i[RCV_I_AUX0] = pair; op.i[RCV_I_AUX1] = prev_C;
+  op.p[RCV_P_IN] = (void*)cur; op.p[RCV_P_IN2] = (void*)prev; op.p[RCV_P_X0] = (void*)prior; op.p[RCV_P_OUT] = inputs; op.p[RCV_P_X1] = plane;
   return rcv_run(h, &op, 1, stream);
 }
 

@@ -201,6 +201,7 @@ int rcv_launch_pool_cls(const rcv_handle* h, const rcv_op* op, hipStream_t s, Op
 int rcv_launch_objdet(const rcv_handle* h, const rcv_op* op, hipStream_t s, OpQuery* query);
 int rcv_launch_lp_batch(const rcv_handle* h, const rcv_op* op, hipStream_t s, OpQuery* query);
 int rcv_launch_lp_tail(const rcv_handle* h, const rcv_op* op, hipStream_t s, OpQuery* query);
+int rcv_launch_lp_input(const rcv_handle* h, const rcv_op* op, hipStream_t s, OpQuery* query);
 int rcv_launch_batch_prep(const rcv_handle* h, const rcv_op* op, hipStream_t s, OpQuery* query);
 int rcv_launch_rgb_prep(const rcv_handle* h, const rcv_op* op, hipStream_t s, OpQuery* query);
 int rcv_launch_lp_pair_prep(const rcv_handle* h, const rcv_op* op, hipStream_t s, OpQuery* query);

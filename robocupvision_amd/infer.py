@@ -16,7 +16,13 @@ the box centre; DBConvert.py:47-102: the per-class area rules of the detection d
 and the boxes go on to the patch classifiers without leaving the device (``patches.py``: ``object_patches``, ``classify_objects``):
 
     seg = Segmenter(model, objects=DBCONVERT, patches={}, classifier=BNNMC().to(dev))
-    labels, colour, objs, cut, classes = seg(frames)     # cut.images float32 [P,3,32,32]; classes uint8 [B,C-1,M], 255 = no object"""
+    labels, colour, objs, cut, classes = seg(frames)     # cut.images float32 [P,3,32,32]; classes uint8 [B,C-1,M], 255 = no object
+
+A video stream need not run the segmenter on every frame: ``LabelPropagator`` (makeLPImages.py:94-102, validLabelProp.py:116-135) runs it
+on key frames and ``LabelProp`` in between, fed with what was said about the frame before (``model.labelprop_next``, RCV_OP_LP_INPUT):
+
+    prop = LabelPropagator(seg_model, lp_model, key_every=30)      # soft=True: the previous logits, not the class map, are the prior
+    labels = prop(imgs)                                  # imgs: a prepared float32 [B,C,H,W] batch, channel 0 = Y"""
 from __future__ import annotations
 
 import ctypes
@@ -29,7 +35,7 @@ from .data import prepare_frames
 from .palette import device_palette
 from .patches import check_keywords, classify_patches, object_patches
 
-__all__ = ["Segmenter", "find_objects", "Objects", "ObjectsRecord", "DBCONVERT"]
+__all__ = ["Segmenter", "LabelPropagator", "find_objects", "Objects", "ObjectsRecord", "DBCONVERT"]
 
 
 class _Rules(dict):
@@ -240,3 +246,96 @@ class Segmenter:
         if self._classifier is None:
             return labels, colour, objs, cut
         return labels, colour, objs, cut, classify_patches(cut, self._classifier)
+
+
+class LabelPropagator:
+    """Labels for a stream of frames: the segmenter on key frames, ``LabelProp`` on the frames between them, fed with what was said
+    about the frame before -- the loop of makeLPImages.py:94-102 and the network branch of validLabelProp.py:116-135 on predictions.
+
+        p = LabelPropagator(seg_model, lp_model, key_every=30)      # both models are put in eval mode here
+        labels = p(imgs)                                             # imgs float32 [B,C,H,W], channel 0 = Y; labels uint8 [B,H,W]
+        labels, colour = p(imgs, colour=True)                        # colour uint8 [B,H,W,3] = palette[labels]
+        p.reset()                                                    # the next call is a key frame again
+
+    ``imgs`` is a prepared batch (``prepare_rgb_batch(frames, train=False)``, ``prepare_frames``, ...): the driver does not choose the
+    loader.  Call number n since construction or ``reset()`` is a key frame when n == 0 or ``key_every > 0 and n % key_every == 0``.
+
+    ``soft=False``: a key frame is ``seg_model.predict(imgs)``; a propagated frame is ``lp_model.predict(labelprop_next(imgs, plane,
+    labels_prev))``, the uint8 class map of the frame before as the prior.  ``soft=True``: the prior is ``2 * softmax - 1`` of the
+    LOGITS of the frame before (``seg_model(imgs)`` on a key frame, ``lp_model(labelprop_next(imgs, plane, logits_prev))`` otherwise) and
+    the labels are their first arg-max, ``torch.max(logits, 1)[1]``.  State -- the Y plane ``labelprop_next(keep_plane=True)`` kept
+    and the previous labels or logits -- stays on the device; nothing synchronises.  A batch of another shape or on another device
+    without ``reset()`` is refused: the state belongs to the stream it came from."""
+
+    def __init__(self, seg_model, lp_model, key_every=0, soft=False, palette=None):
+        for name, m in (("seg_model", seg_model), ("lp_model", lp_model)):
+            if not hasattr(m, "predict"):
+                raise TypeError("LabelPropagator: %s must be one of this package's networks (it has no predict)" % name)
+        if getattr(seg_model, "classify", False):
+            raise L.RcvError("LabelPropagator: seg_model is in classify mode (one class per patch, not a class map)")
+        if isinstance(key_every, bool) or not isinstance(key_every, int) or key_every < 0:
+            raise ValueError("LabelPropagator: key_every must be an integer >= 0 (0 = only the first frame is a key frame), got %r" % (key_every,))
+        self.seg_model, self.lp_model = seg_model.eval(), lp_model.eval()
+        self.key_every, self.soft = key_every, bool(soft)
+        self._palette = palette
+        self._device_palettes = {}          # device -> the palette padded to uint8 [8,3], uploaded once
+        if palette is not None:
+            device_palette(palette, "cpu")          # a wrong palette is refused at construction
+        self.reset()
+
+    def reset(self):
+        """Forget the stream: the next call is a key frame."""
+        self._n, self._key, self._plane, self._prior = 0, None, None, None
+
+    @property
+    def prior(self):
+        """What the last call said about its frames and the next call reads as its prior: the uint8 class map, with ``soft`` the
+        logits; None before the first call and after ``reset()``."""
+        return self._prior
+
+    @property
+    def plane(self):
+        """The Y plane float32 [B,H,W] kept of the last call's frames (the next call's previous frame), or None."""
+        return self._plane
+
+    def _pal(self, dev):
+        pal = self._device_palettes.get(dev)
+        if pal is None:
+            pal = self._device_palettes[dev] = device_palette(self._palette, dev)
+        return pal
+
+    def __call__(self, imgs, colour=False):
+        from .model import labelprop_next
+        from .palette import colorize
+        if not torch.is_tensor(imgs) or imgs.dtype != torch.float32 or imgs.dim() != 4:
+            raise TypeError("LabelPropagator: imgs must be a float32 [B,C,H,W] tensor (a prepared batch, channel 0 = Y)")
+        if imgs.device.type != "cuda":
+            raise L.RcvError("LabelPropagator runs on the HIP device only (imgs on %s); there is no CPU path" % imgs.device)
+        key = (tuple(imgs.shape), imgs.device)
+        if self._key is not None and key != self._key:
+            raise L.RcvError("LabelPropagator: this batch is %s on %s, the stream so far %s on %s; call reset() before another stream"
+                             % (key[0], key[1], self._key[0], self._key[1]))
+        key_frame = self._n == 0 or (self.key_every > 0 and self._n % self.key_every == 0)
+        pal = self._pal(imgs.device) if colour else None
+        col = None
+        with torch.no_grad():
+            if key_frame:
+                plane = imgs[:, 0].clone(memory_format=torch.contiguous_format)      # (the caller's buffer is not held on to)
+                x = imgs
+                model = self.seg_model
+            else:
+                x, plane = labelprop_next(imgs, self._plane, self._prior, keep_plane=True)
+                model = self.lp_model
+            if self.soft:
+                prior = model(x)
+                labels = torch.max(prior, 1)[1].to(torch.uint8)
+                if colour:
+                    col = colorize(labels, pal)
+            elif colour:
+                labels, col = model.predict(x, colour=True, palette=pal)
+                prior = labels
+            else:
+                prior = labels = model.predict(x)
+        self._key, self._plane, self._prior = key, plane, prior
+        self._n += 1
+        return (labels, col) if colour else labels

@@ -24,7 +24,7 @@ from .engine import Engine
 from .bnn import BNNL, BNNMC      # the reference's model.py:569-619 (kernels: csrc/bnn.hip)
 
 __all__ = ["ROBO_UNet", "CrossEntropyLoss2d", "DiceLoss", "PB_FCN", "PB_FCN_2", "LabelProp", "Conv", "Pool", "LevelDown",
-           "labelprop_batch", "upSampleTransposeConv", "UltClassifier", "ConvPoolSimple", "ConvPool", "DownSampler", "Classifier", "pruneModelNew",
+           "labelprop_batch", "labelprop_next", "upSampleTransposeConv", "UltClassifier", "ConvPoolSimple", "ConvPool", "DownSampler", "Classifier", "pruneModelNew",
            "count_zero_weights", "getParamSize", "BNNL", "BNNMC", "pruneModel", "pruneModel2"]
 
 
@@ -658,7 +658,61 @@ class LabelProp(_EngineOwner, nn.Module):
         return _run_engine(self._get_engine(), self.training, self._engine_inputs(x))
 
 
-def labelprop_batch(images, labels, num_class=5):
+def _lp_input(cur, prev, prev_c, prior, pair, B, C, H, W, keep_plane, what):
+    """One RCV_OP_LP_INPUT launch on the current stream (operands checked and contiguous): the NHWC inputs, logically [B,8,H,W], and
+    the kept Y plane or None."""
+    dev = cur.device
+    h = L.handle(dev.index if dev.index is not None else torch.cuda.current_device())
+    inputs = torch.empty(B, H, W, 8, dtype=torch.float32, device=dev)
+    plane = torch.empty(B, H, W, dtype=torch.float32, device=dev) if keep_plane else None
+    mode = {torch.uint8: L.LP_PRIOR_U8, torch.int64: L.LP_PRIOR_I64, torch.float32: L.LP_PRIOR_LOGITS}[prior.dtype]
+    L.check(L.load().rcv_lp_input(h, cur.data_ptr(), prev.data_ptr() if prev is not None else None, prev_c, prior.data_ptr(), mode,
+                                  1 if pair else 0, B, C, H, W, 5, inputs.data_ptr(), plane.data_ptr() if keep_plane else None,
+                                  torch.cuda.current_stream(dev).cuda_stream), what)
+    return inputs.permute(0, 3, 1, 2), plane
+
+
+def _frame_planes(t, name, what):
+    """(B, C, H, W) of a float32 frame tensor [B,C,H,W] or plane tensor [B,H,W] (C = 1)."""
+    if not torch.is_tensor(t):
+        raise TypeError("%s: %s must be a tensor" % (what, name))
+    if t.dtype != torch.float32:
+        raise TypeError("%s: %s must be float32 (got %s)" % (what, name, t.dtype))
+    if t.dim() not in (3, 4) or min(t.shape) < 1:
+        raise ValueError("%s: %s must be [B,C,H,W] or a [B,H,W] plane (got %s)" % (what, name, tuple(t.shape)))
+    return (t.shape[0], 1, t.shape[1], t.shape[2]) if t.dim() == 3 else tuple(t.shape)
+
+
+def labelprop_next(cur, prev, prior, keep_plane=False):
+    """LabelProp's input for the frames ``cur`` from a PREDICTION of the frames before them, one launch (RCV_OP_LP_INPUT): the loop body of
+    makeLPImages.py:98-100 and the network branch of validLabelProp.py:116-130 on what a network said, not on ground truth.
+
+    ``cur`` and ``prev`` float32 [B,C,H,W] (only channel 0, Y, is read) or [B,H,W] planes; ``prior`` is what was predicted for ``prev``:
+    a class map uint8 or int64 [B,H,W] (``predict``'s output) -> labelToPred (transform.py:172-183), +1 at the class and -1 elsewhere,
+    a value outside [0, 5) giving -1 in all five channels; or float32 logits [B,5,H,W] (``model(x)`` in eval mode) -> the prior the
+    reference leaves commented at labelPropTrain.py:179, ``softmax * 2 - 1`` with m = max z, e = expf(z - m), S = (((e0 + e1) + e2) + e3)
+    + e4, 2 * (e / S) - 1.  Returns ``inputs`` of logical shape [B,8,H,W] whose MEMORY is NHWC (``LabelProp`` reads it without a copy, in
+    training mode too) = [Ycur, Yprev, Ycur - Yprev, prior]; with ``keep_plane=True`` ``(inputs, plane)``, ``plane`` a fresh float32
+    [B,H,W] copy of Ycur written by the same launch (the next call's ``prev``)."""
+    what = "labelprop_next"
+    B, C, H, W = _frame_planes(cur, "cur", what)
+    Bp, Cp, Hp, Wp = _frame_planes(prev, "prev", what)
+    if not torch.is_tensor(prior):
+        raise TypeError("%s: prior must be a tensor" % what)
+    if prior.dtype not in (torch.uint8, torch.int64, torch.float32):
+        raise TypeError("%s: prior must be a uint8 / int64 class map or float32 logits (got %s)" % (what, prior.dtype))
+    if (Bp, Hp, Wp) != (B, H, W):
+        raise ValueError("%s: prev %s does not match cur %s" % (what, tuple(prev.shape), tuple(cur.shape)))
+    want = (B, 5, H, W) if prior.dtype == torch.float32 else (B, H, W)
+    if tuple(prior.shape) != want:
+        raise ValueError("%s: a %s prior must be %s for these frames (got %s)" % (what, prior.dtype, list(want), tuple(prior.shape)))
+    if cur.device.type != "cuda" or prev.device != cur.device or prior.device != cur.device:
+        raise L.RcvError("%s runs on the HIP device only (cur on %s, prev on %s, prior on %s)" % (what, cur.device, prev.device, prior.device))
+    inputs, plane = _lp_input(cur.contiguous(), prev.contiguous(), Cp, prior.contiguous(), False, B, C, H, W, bool(keep_plane), "rcv_lp_input")
+    return (inputs, plane) if keep_plane else inputs
+
+
+def labelprop_batch(images, labels, num_class=5, prior_logits=None):
     """The batch assembly of labelPropTrain.py:162-193 in one launch (RCV_OP_LP_BATCH).
 
     ``images`` float32 [B,2,C,H,W] (frame pairs; only channel 0 of each frame is read, as the script does) and ``labels`` int64
@@ -666,7 +720,14 @@ def labelprop_batch(images, labels, num_class=5):
     copy), ``targets`` int64 [2B,H,W].  ``inputs[2b] = [Ya, Yb, Ya - Yb, labelToPred(label_b)]``, ``targets[2b] = label_a``, and the
     swapped sample at ``2b + 1``; labelToPred (transform.py:172-183) is -1 everywhere and +1 at the label's class.  A label outside
     [0, 5) cannot be refused without a host synchronisation (torch's ``scatter_`` would raise): such a pixel gets -1 in all five class
-    channels and the label is never used as an index.  Exact: copies, +-1 and one fp32 subtraction."""
+    channels and the label is never used as an index.  Exact: copies, +-1 and one fp32 subtraction.
+
+    ``prior_logits`` float32 [B,2,5,H,W] (e.g. ``modelSeg(images.view(2B,3,H,W)).view(B,2,5,H,W)``): the class channels are the soft
+    prior the script leaves commented at labelPropTrain.py:179, ``softmax(prior_logits) * 2 - 1`` of the OTHER frame of the pair, in
+    place of ``labelToPred(labels)`` (the pair form of RCV_OP_LP_INPUT, arithmetic as ``labelprop_next``); ``targets`` is then
+    ``labels.view(2B,H,W)``, a view without a copy.  Without the keyword nothing changes."""
+    if prior_logits is not None:
+        return _labelprop_batch_soft(images, labels, num_class, prior_logits)
     if num_class != 5:
         raise ValueError("labelprop_batch: num_class must be 5 (LabelProp's first conv reads 3 + 5 channels), got %r" % (num_class,))
     if not (torch.is_tensor(images) and torch.is_tensor(labels)):
@@ -689,6 +750,30 @@ def labelprop_batch(images, labels, num_class=5):
     L.check(L.load().rcv_labelprop_batch(h, images.data_ptr(), labels.data_ptr(), B, Cc, H, W, num_class, inputs.data_ptr(),
                                          targets.data_ptr(), torch.cuda.current_stream(dev).cuda_stream), "rcv_labelprop_batch")
     return inputs.permute(0, 3, 1, 2), targets
+
+
+def _labelprop_batch_soft(images, labels, num_class, prior_logits):
+    """``labelprop_batch(images, labels, prior_logits=...)``: the same argument checks, then the pair form of RCV_OP_LP_INPUT."""
+    if num_class != 5:
+        raise ValueError("labelprop_batch: num_class must be 5 (LabelProp's first conv reads 3 + 5 channels), got %r" % (num_class,))
+    if not (torch.is_tensor(images) and torch.is_tensor(labels) and torch.is_tensor(prior_logits)):
+        raise TypeError("labelprop_batch: images, labels and prior_logits must be tensors")
+    if images.dtype != torch.float32 or labels.dtype != torch.int64 or prior_logits.dtype != torch.float32:
+        raise TypeError("labelprop_batch: images and prior_logits must be float32 and labels int64 (got %s, %s, %s)"
+                        % (images.dtype, prior_logits.dtype, labels.dtype))
+    if images.dim() != 5 or images.shape[1] != 2 or images.shape[2] < 1 or labels.dim() != 4:
+        raise ValueError("labelprop_batch: images must be [B,2,C,H,W] and labels [B,2,H,W] (got %s, %s)"
+                         % (tuple(images.shape), tuple(labels.shape)))
+    B, _, Cc, H, W = images.shape
+    if tuple(labels.shape) != (B, 2, H, W) or B < 1 or H < 1 or W < 1:
+        raise ValueError("labelprop_batch: labels %s do not match images %s" % (tuple(labels.shape), tuple(images.shape)))
+    if tuple(prior_logits.shape) != (B, 2, 5, H, W):
+        raise ValueError("labelprop_batch: prior_logits must be %s for these images (got %s)" % ([B, 2, 5, H, W], tuple(prior_logits.shape)))
+    if images.device.type != "cuda" or labels.device != images.device or prior_logits.device != images.device:
+        raise L.RcvError("labelprop_batch runs on the HIP device only (images on %s, labels on %s, prior_logits on %s)"
+                         % (images.device, labels.device, prior_logits.device))
+    inputs, _ = _lp_input(images.contiguous(), None, 0, prior_logits.contiguous(), True, 2 * B, Cc, H, W, False, "rcv_lp_input")
+    return inputs, labels.contiguous().view(2 * B, H, W)
 
 
 # ------------------------------------------------------------------------------------------
