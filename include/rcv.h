@@ -282,7 +282,7 @@ enum {
   RCV_OP_PACK5 = 58,         /* p[IN] = parameter [COUT][CIN][5][5] (i[CIN] = 8 / 16, i[COUT] = 1..8) -> p[OUT] = float[25][rows][16], zero
                              * padded: forward rows = CIN, out[t][ci][co] = w[co][ci][t]; with RCV_F_FLIP the data gradient's filter, rows =
                              * 8, out[t][co][ci] = w[co][ci][24 - t]                                                                    */
-  RCV_OP_LP_INPUT = 59       /* LabelProp's input from a PREDICTION of the previous frame (rcv_lp_input; csrc/lp_input.hip; makeLPImages.py:94-102,
+  RCV_OP_LP_INPUT = 59,      /* LabelProp's input from a PREDICTION of the previous frame (rcv_lp_input; csrc/lp_input.hip; makeLPImages.py:94-102,
                              * validLabelProp.py:116-135, the commented prior of labelPropTrain.py:179): per pixel of sample s,
                              * [Ycur, Yprev, Ycur - Yprev, prior_0 .. prior_4].  i[N] = B samples, i[H], i[W], i[CIN] = channels per frame (only
                              * channel 0 is read), i[COUT] = classes (5), i[INMODE] = the prior's form: 1 = class map uint8[B][H][W], 8 = class
@@ -296,6 +296,29 @@ enum {
                              * p[X0] = the prior, p[OUT] = inputs float[B][H][W][8] (NHWC, 16-byte aligned), p[X1] = Ycur as a dense plane
                              * float[B][H][W] or NULL.  Refused when planned: classes != 5, another prior form or pairing, odd B in the
                              * pair form, B / C / H / W < 1, an operand of 2^31 elements or more                                        */
+  RCV_OP_CLS_VALID = 60,     /* the validation form of the classifier tails (rcv_cls_valid; csrc/cls_valid.hip; valid() of train.py:97-178:
+                             * `criterion(model(imgs), targets)`, `torch.max(pred, 1)` and the mask loops of train.py:136-153): the class, the
+                             * loss terms and the confusion bin of every pixel from its logits in registers; no logits are stored.  Slots and
+                             * source forms as RCV_OP_CLS_LABEL: i[N], i[H], i[W], i[CIN], i[COUT] = 1..8 classes, i[INMODE] 0 = features
+                             * (p[IN], p[W], p[BIAS] or NULL, CIN 8 / 16; with RCV_F_FUSED_UP p[IN_C], p[X3], p[X4], i[AUX0], i[AUX1]),
+                             * 1 = NHWC logits of i[CIN] floats per pixel plus p[BIAS], 2 = p[IN] is a uint8 class map: only the counts are
+                             * produced, no loss (p[PART] NULL and i[NPART] 0, refused otherwise).  p[IN2] = targets int64[N][H][W]; p[X0] =
+                             * class weights float[COUT] or NULL (no colour image is produced here); p[PART] = float[i[NPART]][3] partial rows
+                             * (rcv_op_workspace) of sum w*nll, sum w, #correct, the columns of RCV_OP_CE_FWD; p[X2] = int32[N][COUT][COUT]
+                             * counts[image][pred][label], ACCUMULATED as RCV_OP_CONFUSION accumulates; p[OUT] = class map uint8[N][H][W] or
+                             * NULL (forms 0 and 1).  The class is the first maximum (a NaN never wins), bit for bit RCV_OP_CLS_LABEL's.  A
+                             * target outside [0, COUT), decided on the int64 value, has weight 0 and counts in no bin.  For 8-channel
+                             * features and for logits the rows are bit for bit those RCV_OP_CE_FWD forms from the logits RCV_OP_CLS_FWD /
+                             * RCV_OP_NHWC_TO_NCHW write (same grid, pixel -> thread mapping and summation order); with 16 channels four
+                             * lanes share a pixel and the rows are sums over other pixel sets (the loss agrees to rounding)          */
+  RCV_OP_VALID_FOLD = 61     /* folds one batch into the running validation state and clears the counts it read (rcv_valid_fold; one
+                             * workgroup).  p[IN] = counts int32[N][C][C] of RCV_OP_CLS_VALID (zero afterwards); the batch loss: p[IN2] =
+                             * partial rows with i[NPART] > 0, summed in RCV_OP_CE_FWD's finalising order to the fp32 loss, OR p[X0] = a
+                             * device float with i[NPART] = 0 (exactly one of the two, checked when planned); i[N], i[H], i[W], i[COUT] = C;
+                             * p[OUT] = state double[76]: [0] += (double)loss (train.py:131 `losstotal += loss.item()`), [1] += 1 (batches),
+                             * [2] += N (images), [3] += N*H*W (pixels), [4 + c] = iou_sum[c]: one thread per class adds, image by image in
+                             * index order, inter / union with inter = n[c][c], union = sum_l n[c][l] + sum_p n[p][c] - inter, 1.0 where
+                             * union is 0 (train.py:148-153); [12 + 8 * pred + label] += sum over the images of n[pred][label]        */
 };
 
 /* i[RCV_I_AUX0] of RCV_OP_PRUNE: how the threshold of a tensor is chosen */
@@ -757,6 +780,17 @@ int rcv_cls_label(rcv_handle* h, const float* x, const float* w, const float* bi
  * where the class is outside [0, 8); elem_bytes 1 = uint8, 8 = int64.                                                              */
 int rcv_colorize(rcv_handle* h, const void* classmap, int elem_bytes, int N, int H, int W, uint8_t* colour, const uint8_t* palette,
                  void* stream);
+
+/* RCV_OP_CLS_VALID, source form 0 without the fused decoder input: per pixel the first arg-max of (bias[c] + sum_k x[p][k] w[c][k]), the
+ * weighted cross-entropy terms against targets int64[N][H][W] (class_weights float[COUT] or NULL) as partial rows float[*n_rows][3] in
+ * `workspace` (rcv_op_workspace bytes of the record), counts int32[N][COUT][COUT] += [image][pred][label], labels uint8[N][H][W] or NULL. */
+int rcv_cls_valid(rcv_handle* h, const float* x, const float* w, const float* bias /*may be NULL*/, int N, int H, int W, int CIN, int COUT,
+                  const int64_t* targets, const float* class_weights /*may be NULL*/, int32_t* counts, uint8_t* labels /*may be NULL*/,
+                  void* workspace, size_t workspace_bytes, int* n_rows /*may be NULL*/, void* stream);
+/* RCV_OP_VALID_FOLD: state double[76] += this batch (slots at the kind); the loss from `rows` (n_rows > 0, loss NULL) or from the device
+ * float `loss` (n_rows = 0, rows NULL); counts are zero afterwards.                                                                   */
+int rcv_valid_fold(rcv_handle* h, int32_t* counts, const float* rows, int n_rows, const float* loss, int N, int H, int W, int num_class,
+                   double* state, void* stream);
 
 /* The BNN-L / BNN-M-C patch classifiers (model.py:569-619; objDetEval.py:89-119, classVal.py).  Each call runs ONE record of the kind
  * named (RCV_OP_BNN_STAGE_FWD / _BWD: conv -> Dropout2d -> MaxPool2d(k, 2) -> ReLU of model.py:590-592,615-618 and its

@@ -39,6 +39,8 @@ OP_RGB_PREP_IDX = 53        # OP_RGB_PREP whose image b is store[index[b]]: trai
 OP_LP_PAIR_PREP = 54        # both frames of a LabelProp pair from the store -> the 8-channel input of labelPropTrain.py:36-66, 162-193 (rcv.h RCV_OP_LP_PAIR_PREP)
 OP_CONV5, OP_WGRAD5, OP_WGRAD5_REDUCE, OP_PACK5 = 55, 56, 57, 58      # the 5x5 classifier convolution family (rcv.h RCV_OP_CONV5 ..., csrc/conv5.hip)
 OP_LP_INPUT = 59            # LabelProp's input from a prediction of the previous frame: class map or logits as the prior (rcv.h RCV_OP_LP_INPUT, csrc/lp_input.hip)
+OP_CLS_VALID, OP_VALID_FOLD = 60, 61      # the validation tail: loss rows, class map and per-image confusion counts from the logits in registers; its fold into the running state (rcv.h, csrc/cls_valid.hip)
+VALID_STATE = 76            # doubles of the state OP_VALID_FOLD keeps: loss sum, batches, images, pixels, iou_sum[8], conf[8][8]
 LP_PRIOR_U8, LP_PRIOR_LOGITS, LP_PRIOR_I64 = 1, 4, 8      # i[INMODE] of OP_LP_INPUT: the prior's form
 PRUNE_MAX_RATIO, PRUNE_STD_SEARCH, PRUNE_SMALLEST_K = range(3)      # i[AUX0] of OP_PRUNE: pruneModelNew / pruneModel / pruneModel2
 PRUNE_MAX_ITER = 4096
@@ -87,7 +89,7 @@ EXPORTS = [
     "rcv_sgd_step_pruned", "rcv_prune_check", "rcv_prune", "rcv_find_objects", "rcv_rgb_prep",
     "rcv_farneback_flow", "rcv_update_labels", "rcv_object_patches", "rcv_resize_u8", "rcv_batch_prep_indexed",
     "rcv_rgb_prep_indexed", "rcv_lp_pair_prep", "rcv_conv5x5", "rcv_wgrad5x5", "rcv_op_stream_hints", "rcv_set_stream_min_mb",
-    "rcv_lp_input",
+    "rcv_lp_input", "rcv_cls_valid", "rcv_valid_fold",
 ]
 
 
@@ -153,6 +155,9 @@ def load():
         lib.rcv_lp_pair_prep.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p] + [C.c_int] * 7 + \
             [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4 + [C.c_size_t, C.c_void_p]
         lib.rcv_cls_label.argtypes = [C.c_void_p] * 4 + [C.c_int] * 5 + [C.c_void_p] * 4
+        if hasattr(lib, "rcv_cls_valid"):      # (RCV_LIBRARY may name an older build)
+            lib.rcv_cls_valid.argtypes = [C.c_void_p] * 4 + [C.c_int] * 5 + [C.c_void_p] * 5 + [C.c_size_t, C.POINTER(C.c_int), C.c_void_p]
+            lib.rcv_valid_fold.argtypes = [C.c_void_p] * 3 + [C.c_int, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 2
         lib.rcv_colorize.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 3
         lib.rcv_sgd_step.argtypes = [C.c_void_p] * 5 + [C.c_int64, C.c_float, C.c_float, C.c_float, C.c_int, C.c_float, C.c_void_p]
         lib.rcv_sgd_step_pruned.argtypes = [C.c_void_p] * 6 + [C.c_int64, C.c_float, C.c_float, C.c_float, C.c_int, C.c_float, C.c_void_p]

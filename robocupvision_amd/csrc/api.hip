@@ -134,6 +134,10 @@ static int dispatch(const rcv_handle* h, const rcv_op* op, hipStream_t s, OpQuer
       return rcv_launch_lp_pair_prep(h, op, s, q);
     case RCV_OP_CLS_LABEL:
       return rcv_launch_cls_label(h, op, s, q);
+    case RCV_OP_CLS_VALID:
+      return rcv_launch_cls_valid(h, op, s, q);
+    case RCV_OP_VALID_FOLD:
+      return rcv_launch_valid_fold(h, op, s, q);
     case RCV_OP_BNN_STAGE_FWD:
     case RCV_OP_BNN_STAGE_BWD:
     case RCV_OP_BNN_HEAD_FWD:
@@ -637,6 +641,33 @@ int rcv_colorize(rcv_handle* h, const void* classmap, int elem_bytes, int N, int
   op.i[RCV_I_N] = N; op.i[RCV_I_H] = H; op.i[RCV_I_W] = W; op.i[RCV_I_CIN] = 1; op.i[RCV_I_COUT] = 8; op.i[RCV_I_INMODE] = 2;
   op.i[RCV_I_INMODE2] = elem_bytes;
   op.p[RCV_P_IN] = (void*)classmap; op.p[RCV_P_X0] = colour; op.p[RCV_P_X1] = (void*)palette;
+  return rcv_run(h, &op, 1, stream);
+}
+
+int rcv_cls_valid(rcv_handle* h, const float* x, const float* w, const float* bias, int N, int H, int W, int CIN, int COUT, const int64_t* targets,
+                  const float* class_weights, int32_t* counts, uint8_t* labels, void* workspace, size_t workspace_bytes, int* n_rows,
+                  void* stream) {
+  rcv_op op;
+  memset(&op, 0, sizeof(op));
+  op.kind = RCV_OP_CLS_VALID;
+  op.i[RCV_I_N] = N; op.i[RCV_I_H] = H; op.i[RCV_I_W] = W; op.i[RCV_I_CIN] = CIN; op.i[RCV_I_COUT] = COUT; op.i[RCV_I_INMODE] = 0;
+  op.p[RCV_P_IN] = (void*)x; op.p[RCV_P_W] = (void*)w; op.p[RCV_P_BIAS] = (void*)bias; op.p[RCV_P_IN2] = (void*)targets;
+  op.p[RCV_P_X0] = (void*)class_weights; op.p[RCV_P_X2] = counts; op.p[RCV_P_OUT] = labels; op.p[RCV_P_PART] = workspace;
+  size_t need = 0;
+  const int rc = rcv_op_workspace(h, &op, &need);
+  if (rc) return rc;
+  RCV_CHECK_ARG(workspace_bytes >= need, "rcv_cls_valid: workspace of %zu bytes given, %zu needed (rcv_op_workspace)", workspace_bytes, need);
+  if (n_rows) *n_rows = op.i[RCV_I_NPART];
+  return rcv_run(h, &op, 1, stream);
+}
+
+int rcv_valid_fold(rcv_handle* h, int32_t* counts, const float* rows, int n_rows, const float* loss, int N, int H, int W, int num_class,
+                   double* state, void* stream) {
+  rcv_op op;
+  memset(&op, 0, sizeof(op));
+  op.kind = RCV_OP_VALID_FOLD;
+  op.i[RCV_I_N] = N; op.i[RCV_I_H] = H; op.i[RCV_I_W] = W; op.i[RCV_I_COUT] = num_class; op.i[RCV_I_NPART] = n_rows;
+  op.p[RCV_P_IN] = counts; op.p[RCV_P_IN2] = (void*)rows; op.p[RCV_P_X0] = (void*)loss; op.p[RCV_P_OUT] = state;
   return rcv_run(h, &op, 1, stream);
 }
 

@@ -4,15 +4,11 @@
 // shuffles + fixed-order LDS trees for the reductions (no float atomics).
 #include "rcv_internal.h"
 #include "cls_common.h"
+#include "ce_common.h"      // wave_sum_d, the per-pixel pieces of the cross entropy, ce_store_row, ce_finalize_body, reduce_grid
 #include "bn_sums.h"
 #include <type_traits>
 
 __device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int sh = 32; sh >= 1; sh >>= 1) v += __shfl_xor(v, sh);
-  return v;
-}
-__device__ __forceinline__ double wave_sum_d(double v) {
 #pragma unroll
   for (int sh = 32; sh >= 1; sh >>= 1) v += __shfl_xor(v, sh);
   return v;
@@ -258,58 +254,10 @@ __global__ void concat_kernel(const float* __restrict__ t, const float* __restri
 // ------------------------------------------------------------------------------------------
 // 1x1 classifier (model.py:411): NHWC [.,CIN] -> NCHW logits [N][COUT][H][W]
 // ------------------------------------------------------------------------------------------
-#define CE_MAX_C 8
+// (CE_MAX_C and the per-pixel pieces of the weighted cross entropy -- ce_label_weight, ce_first_max, ce_target_logit, ce_pixel_sums,
+// ce_store_row -- are in ce_common.h, shared with the validation tails of cls_valid.hip)
 // (CLS_MAX_OUT and the loads that form the classifier's input -- ClsRaw, cls_load_raw, cls_form_up, cls_load_up -- are in cls_common.h,
 // shared with the class-map kernels of cls_label.hip)
-
-// The per-pixel pieces of the weighted cross entropy that cls_fwd_kernel<CE>, the training-step kernel (cls_bwd_kernel<..., ClsStepArgs>) and the
-// normaliser pre-pass (ce_norm_kernel) share, so that each of them rounds as the others do.
-// weight of a pixel's label: a label outside [0, C) (e.g. -100) is ignored, like NLLLoss's ignore_index
-__device__ __forceinline__ float ce_label_weight(int tg, int C, const float* __restrict__ cw) {
-  return (unsigned)tg < (unsigned)C ? (cw ? cw[tg] : 1.f) : 0.f;
-}
-// first maximum in class order (torch.max): strict '>', a NaN never wins
-template <int NC>
-__device__ __forceinline__ float ce_first_max(const float (&lg)[NC], int C, int& am) {
-  float mx = -INFINITY;
-  am = 0;
-#pragma unroll
-  for (int c = 0; c < NC; ++c) if (c < C && lg[c] > mx) { mx = lg[c]; am = c; }
-  return mx;
-}
-// the logit of the pixel's label (a label outside [0, C) has none: 0, and its weight is 0 too)
-template <int NC>
-__device__ __forceinline__ float ce_target_logit(const float (&lg)[NC], int C, int tg) {
-  float vt = 0.f;
-#pragma unroll
-  for (int c = 0; c < NC; ++c) if (c == tg && c < C) vt = lg[c];
-  return vt;
-}
-// one pixel's share of the three sums, from the maximum of its logits, the label's logit and se = sum_c exp(lg[c] - mx)
-// (OK: double in cls_fwd_kernel; the step kernel counts in an int, exact as well and a register less)
-template <class OK>
-__device__ __forceinline__ void ce_pixel_sums(float mx, float vt, float se, int am, int tg, int C, const float* __restrict__ cw,
-                                              double& a_nll, double& a_w, OK& a_ok) {
-  const float wt = ce_label_weight(tg, C, cw);
-  const float nll = (mx - vt) + logf(se);
-  a_nll += (double)(wt * nll);
-  a_w += (double)wt;
-  a_ok += (am == tg) ? OK(1) : OK(0);
-}
-// a workgroup's partial row: wave shuffles, then the waves through LDS in index order, rounded to float once.  w_row: the row's
-// sum of weights where ce_norm_kernel has formed it already (the same sum in the same order), in place of a_w
-__device__ __forceinline__ void ce_store_row(double a_nll, double a_w, double a_ok, float* __restrict__ row, const float* __restrict__ w_row = nullptr) {
-  __shared__ double sh[3][4];
-  a_nll = wave_sum_d(a_nll); a_w = wave_sum_d(a_w); a_ok = wave_sum_d(a_ok);
-  const int wv = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) { sh[0][wv] = a_nll; sh[1][wv] = a_w; sh[2][wv] = a_ok; }
-  __syncthreads();
-  if (threadIdx.x < 3) {
-    double t = 0.0;
-    for (int i = 0; i < (int)(blockDim.x >> 6); ++i) t += sh[threadIdx.x][i];
-    row[threadIdx.x] = (w_row && threadIdx.x == 1) ? w_row[0] : (float)t;
-  }
-}
 
 // CE: the weighted cross-entropy partial sums, the arg-max mask and the pixel-accuracy count of RCV_OP_CE_FWD are taken from the
 // logits while they are still in registers (same pixel -> thread assignment and summation order as ce_fwd_kernel: bit-identical loss).
@@ -698,25 +646,7 @@ __global__ void ce_fwd_kernel(const float* __restrict__ logits, const int64_t* _
   }
 }
 
-__device__ __forceinline__ void ce_finalize_body(const float* __restrict__ part, int n_part, float* __restrict__ loss_out) {
-  __shared__ double sh[3][4];
-  double s[3] = {0.0, 0.0, 0.0};
-  for (int i = threadIdx.x; i < n_part; i += blockDim.x) {
-    s[0] += (double)part[(size_t)i * 3 + 0]; s[1] += (double)part[(size_t)i * 3 + 1]; s[2] += (double)part[(size_t)i * 3 + 2];
-  }
-  const int wv = threadIdx.x >> 6;
-  for (int j = 0; j < 3; ++j) { s[j] = wave_sum_d(s[j]); if ((threadIdx.x & 63) == 0) sh[j][wv] = s[j]; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double t[3] = {0.0, 0.0, 0.0};
-    for (int j = 0; j < 3; ++j) for (int i = 0; i < (int)(blockDim.x >> 6); ++i) t[j] += sh[j][i];
-    loss_out[0] = (float)(t[0] / t[1]);
-    loss_out[1] = (float)t[1];
-    loss_out[2] = (float)t[2];
-    loss_out[3] = (float)t[0];
-  }
-}
-
+// (ce_finalize_body: ce_common.h)
 __global__ void ce_finalize_kernel(const float* __restrict__ part, int n_part, float* __restrict__ loss_out) {
   ce_finalize_body(part, n_part, loss_out);
 }
@@ -1287,15 +1217,6 @@ static inline int stream_grid(const rcv_handle* h, size_t work_items, int block)
 static inline int adam_grid(const rcv_handle* h, size_t n) {
   size_t g = (n / 4 + 255) / 256;
   const size_t cap = (size_t)h->num_cus * 2;
-  if (g > cap) g = cap;
-  if (g < 1) g = 1;
-  return (int)g;
-}
-
-// number of workgroups used by the reducing stream kernels (deterministic function of the shape)
-static inline int reduce_grid(const rcv_handle* h, size_t work_items, int block) {
-  size_t g = (work_items + block - 1) / block;
-  const size_t cap = (size_t)h->num_cus * 4;
   if (g > cap) g = cap;
   if (g < 1) g = 1;
   return (int)g;

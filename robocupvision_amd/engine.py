@@ -4,7 +4,9 @@ A network is described once as a small graph (conv / pool / up / cls nodes, buil
 the module tree).  For every (input shape, train|eval) the engine lowers that graph to two cached
 arrays of `rcv_op` records -- one forward, one backward -- whose operands are persistent HBM
 buffers owned by the engine.  (A third variant per shape, eval-labels, is the eval plan whose
-classifier tail writes a uint8 class map and a colour image instead of logits: `Engine.predict`.)  Running a pass is then ONE call into librcv.so (rcv_run), which
+classifier tail writes a uint8 class map and a colour image instead of logits: `Engine.predict`; a
+fourth, eval-valid, ends in the validation tail -- loss rows, class map and confusion counts, folded into a
+running state: `Engine.validate`.)  Running a pass is then ONE call into librcv.so (rcv_run), which
 enqueues every kernel of the pass on the current HIP stream: no per-layer Python, no allocation,
 no host synchronisation, graph-capturable.
 
@@ -194,6 +196,7 @@ class Plan:
         self.logits_slots: List[tuple] = []   # (fwd op index, slot) of the records that write the logits (inference: a fresh tensor per call)
         self.label_op: Optional[int] = None   # eval-labels plan: fwd index of the RCV_OP_CLS_LABEL record (its outputs are fresh tensors per call)
         self.label_shape: Optional[tuple] = None   # ... and the (N, H, W) of its class map
+        self.valid_classes: Optional[int] = None   # eval-valid plan: classes of the RCV_OP_CLS_VALID record at label_op (RCV_OP_VALID_FOLD follows it)
         self.input_grads: List[Optional[torch.Tensor]] = []
         self.n_head = 0                      # leading ops of fwd that depend on the parameters only (filter repack, eval-mode BN constants)
         self.head_key = None                 # parameter-state key the head was last run for (eval plans)
@@ -222,7 +225,8 @@ class _Lowering:
         self.eng = eng
         self.training = training
         # eval-labels plan (Engine.predict): the eval plan up to the classifier node, whose tail is RCV_OP_CLS_LABEL -- a uint8 class map
-        # (+ colour image) instead of logits; no logits buffer exists
+        # (+ colour image) instead of logits; no logits buffer exists.  labels == "valid": the eval-valid plan (Engine.validate), the same
+        # plan with RCV_OP_CLS_VALID + RCV_OP_VALID_FOLD as its tail
         self.labels = labels
         if labels and training:
             raise L.RcvError("an eval-labels plan is an inference plan")
@@ -540,16 +544,19 @@ class _Lowering:
 
     def fwd_cls_labels(self, node: _Node, src: Value, w, b):
         """The classifier node of an eval-labels plan: RCV_OP_CLS_LABEL in place of RCV_OP_CLS_FWD (1x1) resp. of RCV_OP_NHWC_TO_NCHW
-        behind the padded conv (3x3).  Its outputs (p[OUT] class map, p[X0] colour, p[X1] palette) are set per call by Engine.predict."""
+        behind the padded conv (3x3).  Its outputs (p[OUT] class map, p[X0] colour, p[X1] palette) are set per call by Engine.predict.
+        In an eval-valid plan the record is RCV_OP_CLS_VALID (same slots and source forms) with its partial rows, followed by
+        RCV_OP_VALID_FOLD; targets, class weights, counts, class map and state are set per call by Engine.validate."""
         Cout, Cin = w.shape[0], w.shape[1]
+        tail_kind = L.OP_CLS_VALID if self.labels == "valid" else L.OP_CLS_LABEL
         dims = dict(n=self.N, h=src.H, w=src.W, cout=Cout)
         if tuple(w.shape[2:]) == (1, 1) and src.kind == "fused_up":
             tt, skip = src.fused
-            self.fwd.append(L.make_op(L.OP_CLS_LABEL, L.F_FUSED_UP, cin=Cin, inmode=L.CLS_LABEL_FEATURES, aux0=skip.load_mode,
+            self.fwd.append(L.make_op(tail_kind, L.F_FUSED_UP, cin=Cin, inmode=L.CLS_LABEL_FEATURES, aux0=skip.load_mode,
                                  aux1=getattr(src, "fused_rch", 0), p_in=tt.data_ptr(), p_in_c=src.consts.data_ptr(),
                                  p_x3=skip.buf.data_ptr(), p_x4=_ptr(skip.consts), p_w=w.data_ptr(), p_bias=_ptr(b), **dims))
         elif tuple(w.shape[2:]) == (1, 1):
-            op = L.make_op(L.OP_CLS_LABEL, 0, cin=Cin, inmode=L.CLS_LABEL_FEATURES, p_w=w.data_ptr(), p_bias=_ptr(b), **dims)
+            op = L.make_op(tail_kind, 0, cin=Cin, inmode=L.CLS_LABEL_FEATURES, p_w=w.data_ptr(), p_bias=_ptr(b), **dims)
             op.p[L.RCV_P_IN] = self.bind_in(self.fwd, src, L.RCV_P_IN) or None
             self.fwd.append(op)
         elif tuple(w.shape[2:]) == (3, 3) and Cout <= CLS3_PAD:
@@ -559,11 +566,11 @@ class _Lowering:
                            inmode=src.load_mode, p_w=node.t["wp"].data_ptr(), p_out=node.t["z"].data_ptr())
             op.p[L.RCV_P_IN] = self.bind_in(self.fwd, src, L.RCV_P_IN) or None
             self.fwd.append(op)
-            self.fwd.append(L.make_op(L.OP_CLS_LABEL, 0, cin=CLS3_PAD, inmode=L.CLS_LABEL_LOGITS, p_in=node.t["z"].data_ptr(), p_bias=_ptr(b),
+            self.fwd.append(L.make_op(tail_kind, 0, cin=CLS3_PAD, inmode=L.CLS_LABEL_LOGITS, p_in=node.t["z"].data_ptr(), p_bias=_ptr(b),
                                       **dims))
         elif tuple(w.shape[2:]) == (5, 5) and Cout <= CLS3_PAD:
             self.fwd.append(self.cls5_conv(node, src, w))
-            self.fwd.append(L.make_op(L.OP_CLS_LABEL, 0, cin=CLS3_PAD, inmode=L.CLS_LABEL_LOGITS, p_in=node.t["z"].data_ptr(), p_bias=_ptr(b),
+            self.fwd.append(L.make_op(tail_kind, 0, cin=CLS3_PAD, inmode=L.CLS_LABEL_LOGITS, p_in=node.t["z"].data_ptr(), p_bias=_ptr(b),
                                       **dims))
         else:
             raise L.RcvError("classifier kernels %s with %d classes are not built (1x1, or 3x3 / 5x5 with <= %d classes)"
@@ -571,6 +578,11 @@ class _Lowering:
         node.out = Value("plain", None, Cout, src.H, src.W, None, node)
         self.plan.label_op = len(self.fwd) - 1
         self.plan.label_shape = (self.N, src.H, src.W)
+        if self.labels == "valid":
+            tail = self.fwd[-1]
+            rows = self.eng._workspace(self.plan, tail)
+            self.fwd.append(L.make_op(L.OP_VALID_FOLD, 0, npart=tail.i[L.RCV_I_NPART], p_in2=rows.data_ptr(), **dims))
+            self.plan.valid_classes = Cout
 
     def fwd_add_slice(self, node: _Node):
         d = node.d
@@ -1129,9 +1141,11 @@ class Engine:
 
     def _plan_for(self, inputs: Sequence[torch.Tensor], training: bool, labels: bool = False) -> Plan:
         self._ensure_device(inputs[0].device)
-        # three plan variants per input shape: training, eval (logits) and eval-labels (class map, Engine.predict); one cache, one budget
-        # (the key's second item stays a truth value -- True: training -- for every reader of `plans`; the labels variant is None)
-        key = (tuple(tuple(t.shape) for t in inputs), None if labels else training)
+        # four plan variants per input shape: training, eval (logits), eval-labels (class map, Engine.predict) and eval-valid (loss rows,
+        # class map and counts, Engine.validate); one cache, one budget
+        # (the key's second item stays a truth value -- True: training -- for every reader of `plans`; the labels variant is None, the
+        # valid variant "")
+        key = (tuple(tuple(t.shape) for t in inputs), ("" if labels == "valid" else None) if labels else training)
         plan = self.plans.get(key)
         if plan is None:
             plan = self._build([tuple(t.shape) for t in inputs], training, labels)
@@ -1231,6 +1245,43 @@ class Engine:
         finally:          # (the records are copied at enqueue: the cached list keeps no pointer into a caller's tensor)
             op.p[L.RCV_P_OUT] = op.p[L.RCV_P_X0] = op.p[L.RCV_P_X1] = None
         return (labels, col) if colour else labels
+
+    def validate(self, inputs: Sequence[torch.Tensor], targets: torch.Tensor, weight: Optional[torch.Tensor], state, labels: bool = False):
+        """Runs the eval-valid plan: the network up to the classifier, whose tail (RCV_OP_CLS_VALID) forms the weighted cross entropy
+        against ``targets`` (int64 [N,H,W]; ``weight``: float32 [C] on the device or None), the class of every pixel and the per-image
+        (pred, label) counts without storing logits, and RCV_OP_VALID_FOLD, which folds the batch into ``state`` (a
+        ``metrics.ValidationState``: its 76 doubles and its counts buffer).  Returns the class map as a fresh uint8 [N,H,W] tensor with
+        ``labels``, else None.  Nothing synchronises; leaves no forward in flight."""
+        for t in inputs:
+            if t.dtype != torch.float32 or not t.is_contiguous():
+                raise L.RcvError("engine inputs must be contiguous float32 tensors")
+        plan = self._plan_for(inputs, False, labels="valid")
+        C = plan.valid_classes
+        if getattr(state, "C", None) != C or state.buf.device != self.device:
+            raise L.RcvError("validate: the state counts %s classes on %s; this network has %d on %s"
+                             % (getattr(state, "C", None), state.buf.device, C, self.device))
+        if targets.dtype != torch.int64 or not targets.is_contiguous() or tuple(targets.shape) != plan.label_shape or targets.device != self.device:
+            raise L.RcvError("validate: targets must be a contiguous int64 %s tensor on %s (got %s %s on %s)"
+                             % (list(plan.label_shape), self.device, targets.dtype, list(targets.shape), targets.device))
+        if weight is not None and (weight.dtype != torch.float32 or weight.numel() != C or not weight.is_contiguous() or weight.device != self.device):
+            raise L.RcvError("validate: the class weights must be a contiguous float32 [%d] tensor on %s" % (C, self.device))
+        counts = state.counts_for(plan.label_shape[0])
+        out = torch.empty(plan.label_shape, dtype=torch.uint8, device=self.device) if labels else None
+        op, fold = plan.fwd.arr[plan.label_op], plan.fwd.arr[plan.label_op + 1]
+        op.p[L.RCV_P_IN2] = targets.data_ptr()
+        op.p[L.RCV_P_X0] = weight.data_ptr() if weight is not None else None
+        op.p[L.RCV_P_X2] = fold.p[L.RCV_P_IN] = counts.data_ptr()
+        op.p[L.RCV_P_OUT] = out.data_ptr() if labels else None
+        fold.p[L.RCV_P_OUT] = state.buf.data_ptr()
+        for k, t in enumerate(inputs):
+            for (is_bwd, idx, slot) in plan.input_slots[k]:
+                plan.fwd.arr[idx].p[slot] = t.data_ptr()
+        try:
+            self._run_inference(plan, torch.cuda.current_stream(self.device).cuda_stream)
+        finally:          # (the records are copied at enqueue: the cached list keeps no pointer into a caller's tensor)
+            op.p[L.RCV_P_IN2] = op.p[L.RCV_P_X0] = op.p[L.RCV_P_X2] = op.p[L.RCV_P_OUT] = None
+            fold.p[L.RCV_P_IN] = fold.p[L.RCV_P_OUT] = None
+        return out
 
     def _fill_dropout(self, plan: Plan):
         """Dropout2d of the pooled head (model.py:408): a fresh keep-scale [N][C] per training forward, drawn as torch's feature dropout

@@ -4,7 +4,10 @@ the reference's valid() builds with O(B*C^2) Python mask loops and `.item()` syn
 
 DetectionMetrics: the object-detection precision / recall of test.py (getPrecRecall, test.py:28-89, printed as its `IoU:` /
 `Dist:` rows).  One op (RCV_OP_OBJECT_MATCH, csrc/objdet.hip) labels the blobs and matches them on the device; the host turns the
-integer counts into the reference's float64 numbers in the reference's order."""
+integer counts into the reference's float64 numbers in the reference's order.
+
+ValidationState: the whole report of valid() -- loss, pixel accuracy over all pixels, mean class accuracy, mean IoU, the score that
+picks the weights -- from a state two records keep on the device (RCV_OP_CLS_VALID, RCV_OP_VALID_FOLD)."""
 from __future__ import annotations
 
 import ctypes
@@ -48,6 +51,97 @@ class SegmentationMetrics:
                 "mean_class_acc": float(class_acc.sum()) / self.C,
                 "mean_iou": float((self.iou_sum / max(self.n_img, 1)).sum()) / self.C * 100.0,
                 "confusion_percent": (self.conf / (lab_cnt / 100.0)).cpu()}
+
+
+def _ratio(a: float, b: float) -> float:
+    """a / b in float64 with IEEE's answers where Python raises: 0 / 0 is NaN (the reference's tensors divide that way)."""
+    if b == 0:
+        return float("nan") if a == 0 or a != a else (float("inf") if a > 0 else float("-inf"))
+    return a / b
+
+
+def validation_report(state, num_class: int) -> dict:
+    """The figures valid() prints (train.py:157-164) from the 76 doubles RCV_OP_VALID_FOLD keeps -- [0] sum of the batch losses,
+    [1] batches, [2] images, [3] pixels, [4:12] iou_sum, [12:76] conf[pred][label] in rows of 8 -- in float64 on the host, in the
+    reference's order.  A class without a label pixel in the whole pass has 0 / 0 in its column of ``confusion_percent``: NaN there, and
+    so in ``mean_class_acc`` and ``score``, exactly as the reference's tensors give it."""
+    s = [float(v) for v in state]
+    C = num_class
+    batches, images, pixels = s[1], s[2], s[3]
+    conf = [[s[12 + 8 * p + l] for l in range(C)] for p in range(C)]
+    lab_cnt = [sum(conf[p][l] for p in range(C)) for l in range(C)]                      # train.py:144 labCnts (integers: exact)
+    percent = [[_ratio(conf[p][l], lab_cnt[l] / 100.0) for l in range(C)] for p in range(C)]      # train.py:157-159
+    mean_class_acc = 0.0
+    for j in range(C):                                                                     # train.py:162-163
+        mean_class_acc += percent[j][j] / C
+    iou = 0.0
+    for c in range(C):                                                                     # train.py:161 torch.sum(IoU / imgCnt)
+        iou += _ratio(s[4 + c], images)
+    mean_iou = iou / C * 100
+    trace = sum(conf[j][j] for j in range(C))
+    return {"loss": _ratio(s[0], batches), "pixel_acc": _ratio(100.0 * trace, pixels), "mean_class_acc": mean_class_acc, "mean_iou": mean_iou,
+            "score": (mean_class_acc + mean_iou) / 2, "confusion": torch.tensor(conf, dtype=torch.float64).to(torch.int64).reshape(C, C),
+            "confusion_percent": torch.tensor(percent, dtype=torch.float64).reshape(C, C), "images": int(images), "batches": int(batches)}
+
+
+class ValidationState:
+    """The running state of one validation pass (valid(), train.py:97-178), kept on the device: 76 doubles that RCV_OP_VALID_FOLD
+    updates once per batch (``model.validate``, ``Trainer.validate``, ``update_from_map``) and the per-image counts buffer
+    RCV_OP_CLS_VALID accumulates into, one per batch size.  ``compute()`` is the one read-back.
+
+    ``pixel_acc`` divides by ALL pixels, as the reference does (``running_acc += ... * outSize``), not by the pixels inside the
+    confusion matrix as ``SegmentationMetrics`` does: the two differ when ``maskLabel`` or -100 leaves labels outside the classes.  A
+    class with no label pixel in the whole pass makes ``mean_class_acc`` and ``score`` NaN, as the reference's 0 / 0 does.  The union
+    of an image's IoU is formed from its counts (row + column - diagonal): a pixel predicted c under a label outside the classes is in
+    no bin and so not in the union, where train.py:149 counts it; with every label a class the terms are the reference's."""
+
+    def __init__(self, num_class: int, device="cuda"):
+        if not isinstance(num_class, int) or not 1 <= num_class <= 8:
+            raise ValueError("ValidationState counts 1..8 classes (got %r)" % (num_class,))
+        self.C = num_class
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise L.RcvError("ValidationState lives on the HIP device (got '%s'); there is no CPU path" % self.device)
+        self.buf = torch.zeros(L.VALID_STATE, dtype=torch.float64, device=self.device)
+        self.device = self.buf.device
+        self._counts = {}
+
+    def reset(self):
+        self.buf.zero_()
+        for c in self._counts.values():
+            c.zero_()
+
+    def counts_for(self, n_images: int) -> torch.Tensor:
+        """int32 [n_images][C][C], zero between batches (the fold clears what it read)."""
+        c = self._counts.get(n_images)
+        if c is None:
+            c = self._counts[n_images] = torch.zeros(n_images, self.C, self.C, dtype=torch.int32, device=self.device)
+        return c
+
+    def update_from_map(self, pred_u8: torch.Tensor, targets: torch.Tensor, loss: torch.Tensor):
+        """A batch whose class map and loss exist already (the Dice route: ``criterion.last_argmax`` and the criterion's value):
+        RCV_OP_CLS_VALID's class-map form counts, RCV_OP_VALID_FOLD books ``loss`` (a device scalar) as the batch loss."""
+        if not torch.is_tensor(pred_u8) or pred_u8.dtype != torch.uint8 or pred_u8.dim() != 3 or pred_u8.device != self.device:
+            raise L.RcvError("ValidationState.update_from_map needs the uint8 [B,H,W] class map on %s" % self.device)
+        if not torch.is_tensor(targets) or tuple(targets.shape) != tuple(pred_u8.shape):
+            raise L.RcvError("ValidationState.update_from_map: targets must be [B,H,W] like the class map %s" % (tuple(pred_u8.shape),))
+        if not torch.is_tensor(loss) or loss.numel() != 1 or loss.device != self.device:
+            raise L.RcvError("ValidationState.update_from_map: loss must be a one-element tensor on %s (no host value: nothing synchronises)"
+                             % self.device)
+        B, H, W = pred_u8.shape
+        pred_u8 = pred_u8.contiguous()
+        targets = targets.to(self.device).to(torch.int64).contiguous()
+        loss = loss.detach().to(torch.float32).reshape(1).contiguous()
+        counts = self.counts_for(B)
+        h = L.handle(self.device.index if self.device.index is not None else torch.cuda.current_device())
+        dims = dict(n=B, h=H, w=W, cout=self.C)
+        ops = [L.make_op(L.OP_CLS_VALID, 0, cin=1, inmode=L.CLS_LABEL_CLASSMAP, p_in=pred_u8.data_ptr(), p_in2=targets.data_ptr(),
+                         p_x2=counts.data_ptr(), **dims),
+               L.make_op(L.OP_VALID_FOLD, 0, npart=0, p_in=counts.data_ptr(), p_x0=loss.data_ptr(), p_out=self.buf.data_ptr(), **dims)]
+        L.OpList(ops).run(h, torch.cuda.current_stream(self.device).cuda_stream)
+
+    def compute(self) -> dict:
+        return validation_report(self.buf.cpu().tolist(), self.C)
 
 
 def patch_scores(conf) -> dict:

@@ -132,6 +132,33 @@ class _EngineOwner:
             pal = device_palette(palette, x.device) if colour else None
             return self._get_engine().predict(inputs, bool(colour), pal)
 
+    def validate(self, x, targets, state, weight=None, labels=False):
+        """One batch of valid() (train.py:114-153) on the device: the forward, ``CrossEntropyLoss2d(weight)(self(x), targets)``,
+        ``torch.max(pred, 1)`` and the per-image (pred, label) counts in one pass whose classifier tail keeps the logits in registers
+        (RCV_OP_CLS_VALID), folded into ``state`` (``metrics.ValidationState``) by RCV_OP_VALID_FOLD.  ``x`` as for ``forward``;
+        ``targets`` int64 [N,H,W]; ``weight`` float32 [C] or None.  Returns None, or with ``labels=True`` the class map as a fresh uint8
+        [N,H,W] tensor -- ``predict``'s, bit for bit, what ``DetectionMetrics.update`` takes.  The batch loss booked in the state is bit
+        for bit ``float(CrossEntropyLoss2d(weight)(self(x), targets))`` for every network but LabelProp (four lanes share a pixel of its
+        16-channel tail: equal to rounding).  Nothing synchronises before ``state.compute()``.  Eval mode only, as ``predict``."""
+        if self.training:
+            raise L.RcvError("validate is an inference call and this module is in training mode: call `.eval()` first")
+        if _graph_mode(self):
+            raise L.RcvError("validate: this model is in classify mode (the pooled patch-classification head gives one class per patch, "
+                             "not a class map); build it with classify off")
+        if not hasattr(self, "_get_engine"):
+            raise L.RcvError("validate: %s has no per-pixel classifier (ROBO_UNet, PB_FCN, PB_FCN_2 and LabelProp have)" % type(self).__name__)
+        if not torch.is_tensor(x) or not torch.is_tensor(targets):
+            raise TypeError("validate: x and targets must be tensors")
+        if x.device.type != "cuda" or targets.device.type != "cuda":
+            raise L.RcvError("validate runs on the HIP device only (input on %s, targets on %s); there is no CPU path" % (x.device, targets.device))
+        if not hasattr(state, "counts_for") or not hasattr(state, "buf"):
+            raise TypeError("validate: state must be a metrics.ValidationState")
+        with torch.no_grad():
+            inputs = self._engine_inputs(x)
+            if weight is not None:
+                weight = torch.as_tensor(weight, dtype=torch.float32, device=x.device).contiguous()
+            return self._get_engine().validate(inputs, targets.to(torch.int64).contiguous(), weight, state, bool(labels))
+
 
 class _BlockMixin(_EngineOwner):
     """Standalone call of a single block (NCHW in, NCHW out like the reference's blocks): the block

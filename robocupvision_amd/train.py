@@ -276,6 +276,56 @@ class Trainer:
         loss = self.criterion(pred, targets)
         return pred, loss, self.criterion.last_argmax
 
+    @torch.no_grad()
+    def validate(self, batches, state=None) -> dict:
+        """valid() (train.py:97-178) over ``batches``, any iterable of ``(imgs, targets)`` on the device (``EpochLoader(train=False)``,
+        ``RGBEpochLoader(train=False)``): with CrossEntropyLoss2d every batch is one ``model.validate`` call; with DiceLoss it is
+        ``model(x)``, the criterion and ``state.update_from_map(criterion.last_argmax, targets, loss)``.  No host synchronisation happens
+        before the one read-back of ``state.compute()``.  Returns that report plus ``reg`` = decay * sum|p| -- taken once: the parameters
+        do not move during a validation pass -- and ``pruned`` = ``count_zero_weights(model)``; ``reg`` is inside ``loss`` only when no
+        prune indices are set (train.py:121-124).  ``state``: a ``metrics.ValidationState`` to fold into (it is NOT reset), default a
+        fresh one."""
+        from .metrics import ValidationState
+        from .model import count_zero_weights
+        model, crit = self.model, self.criterion
+        if model.training:
+            model.eval()
+        if state is not None and not isinstance(state, ValidationState):
+            raise TypeError("Trainer.validate: state must be a metrics.ValidationState (got %s)" % type(state).__name__)
+        if not hasattr(batches, "__iter__"):
+            raise TypeError("Trainer.validate: batches must be an iterable of (imgs, targets)")
+        fused = type(crit) is CrossEntropyLoss2d
+        for imgs, targets in batches:
+            if fused:
+                w = crit.weight
+                if w is not None and w.device != imgs.device:
+                    w = w.to(imgs.device)
+                    crit.weight = w
+                if state is None:
+                    state = ValidationState(int(w.numel()) if w is not None else self._num_class(), imgs.device)
+                model.validate(imgs, targets, state, weight=w)
+            else:
+                pred = model(imgs)
+                loss = crit(pred, targets)
+                if state is None:
+                    state = ValidationState(int(pred.shape[1]), imgs.device)
+                state.update_from_map(crit.last_argmax, targets, loss)
+        if state is None:
+            raise ValueError("Trainer.validate: no batches")
+        opt = self.optimizer
+        reg = opt.l1_term() if hasattr(opt, "l1_term") else None
+        out = state.compute()                  # the pass's one synchronisation; what follows reads parameters only
+        pruned = count_zero_weights(model)
+        out["reg"] = float(reg) if reg is not None else 0.0
+        if self.prune_indices is None:
+            out["loss"] = out["loss"] + out["reg"]
+        out["pruned"] = pruned
+        return out
+
+    def _num_class(self) -> int:
+        nodes = self.model._get_engine().graph["nodes"]
+        return int(nodes[-1]["weight"].shape[0])
+
     def pop_metrics(self) -> dict:
         m = self.metrics.cpu().tolist()
         self.metrics.zero_()
