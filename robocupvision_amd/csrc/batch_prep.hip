@@ -10,28 +10,18 @@
 //   6. label: gather through the NEAREST index tables, mirror, maskLabel as the reference's sequential rule, widen to int64.
 // Nothing random and no trigonometry here: the parameter row {flip, b, c, m00, m01, m10, m11, uv_off} per image comes from the host.
 //
-// Tiling: one workgroup = 8 output rows x 64 output columns of one image; lane = output x (one wave = one row of the tile).  The
-// horizontal pass of the source rows the tile's vertical taps span goes to LDS as bytes ([rows][64][3], <= 74 rows); the vertical pass,
-// the lookup and the jitter read it back, and the three plane stores and the target store are each contiguous over the lanes (reversed
-// when flipped).  STAGE: the source-row segments of the tile are first copied to LDS with 16-byte aligned loads, 8 rows at a time, and
-// the horizontal taps read LDS bytes; otherwise the taps read global bytes through the cache (DESIGN.md 4.5 has the measurement).
-// Every table entry is clamped where it is used: a wrong table gives wrong pixels, never an access outside the operands.
+// Step 1, its tile (one workgroup = 8 output rows x 64 output columns of one image, lane = output x), the staging of source rows in
+// LDS, the label gather, maskLabel and the index test are csrc/pil_resize.h's, shared with csrc/rgb_prep.hip; this file holds what
+// follows the resized bytes (steps 2-6, the byte stores) and the launcher.  The vertical pass, the lookup and the jitter read the
+// horizontal pass back from LDS, and the three plane stores and the target store are each contiguous over the lanes (reversed when
+// flipped).
 //
 // Two more records run the same passes (the kernels are instantiated per form; nothing is copied):
 //   RCV_OP_RESIZE_U8 (rcv_resize_u8) stops after step 1: the three bytes go out as uint8 NHWC [B][H][W][3] and the label is gathered,
 //     not masked, and written as uint8 or int32 -- what a device-resident dataset keeps (everything random comes after the bytes);
 //   RCV_OP_BATCH_PREP_IDX (rcv_batch_prep_indexed) takes image b from store[index[b]]: the index is read from device memory and tested
 //     against [0, N) before it forms an address; an image whose index fails is written as zeros (targets 0) and counted.
-#include "rcv_internal.h"
-
-#define BP_TR 8
-#define BP_TC 64
-#define BP_MAXK 17                       /* taps of a downscale by 8: ceil(8) * 2 + 1 */
-#define BP_ROWS_MAX 74                   /* ceil(7 * 8 + 2 * 8) + 2 source rows under 8 output rows */
-#define BP_RC 8                          /* source rows staged at a time */
-#define BP_SEG 1600                      /* bytes of one staged row segment: ((63 * 8 + 2 * 8 + 2) * 3 + 15) rounded up to 16 */
-#define BP_PREC 22
-#define BP_STAGE_MIN_TAPS 9                  /* taps per output column from which the source rows are staged in LDS */
+#include "pil_resize.h"
 
 enum { BP_PREP = 0, BP_PREP_IDX = 1, BP_BYTES = 2 };          // the form a kernel is instantiated for
 
@@ -43,19 +33,6 @@ struct BpArgs {
   const void* index; int idx_bytes; int* bad;          // BP_PREP_IDX: index [B] of 4 / 8 byte elements, counter of the refused ones
   uint8_t* out8; void* lab_out; int lab_out_bytes;     // BP_BYTES: bytes [B][H][W][3], labels [B][H][W] of 1 / 4 byte elements (or null)
 };
-
-__device__ __forceinline__ int bp_clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-__device__ __forceinline__ int bp_clip8(int acc) { return bp_clampi(acc >> BP_PREC, 0, 255); }
-
-// transform.py:26-49 on one value; m bits: 1 = nb, 2 = nr, 4 = ng, 8 = nl (the branches are uniform over the launch)
-__device__ __forceinline__ int bp_mask(int v, int m) {
-  int rN = 2, gN = 3, lN = 4;
-  if (m & 1) { if (v == 1) v = 0; if (v > 1) v -= 1; rN = 1; gN = 2; lN = 3; }
-  if (m & 2) { if (v == rN) v = 0; if (v > rN) v -= 1; gN = 1; lN = 2; }
-  if (m & 4) { if (v == gN) v = 0; if (v > gN) v -= 1; lN = 1; }
-  if (m & 8) { if (v == lN) v = 0; }
-  return v;
-}
 
 struct BpJitter { bool flip, uv; float b, c, m00, m01, m10, m11; };
 
@@ -69,36 +46,15 @@ __device__ __forceinline__ BpJitter bp_jitter(const BpArgs& a, int b) {
   return j;
 }
 
-// BP_PREP_IDX: the store image of batch row b, or -1 where the index is outside [0, nsrc) (tested before it is used for anything)
-__device__ __forceinline__ int bp_source(const BpArgs& a, int b) {
-  const long long v = a.idx_bytes == 8 ? (long long)((const int64_t*)a.index)[b] : (long long)((const int32_t*)a.index)[b];
-  return v >= 0 && v < (long long)a.nsrc ? (int)v : -1;
-}
-
-// the label under output pixel (x, y) of source image src, through the NEAREST index tables
-__device__ __forceinline__ int bp_label(const BpArgs& a, int src, int y, int x) {
-  const int sy = bp_clampi(a.ly[y], 0, a.Hs - 1), sx = bp_clampi(a.lx[x], 0, a.Ws - 1);
-  const size_t li = ((size_t)src * a.Hs + sy) * a.Ws + sx;
-  return a.lab_bytes == 1 ? (int)((const uint8_t*)a.labels)[li] : ((const int32_t*)a.labels)[li];
-}
-
 // BP_BYTES: the three resized bytes and the gathered label of one output pixel, as they are
 __device__ __forceinline__ void bp_store_bytes(const BpArgs& a, int b, int y, int x, int c0, int c1, int c2) {
   const size_t o = ((size_t)b * a.H + y) * a.W + x;
   uint8_t* q = a.out8 + o * 3;
   q[0] = (uint8_t)c0; q[1] = (uint8_t)c1; q[2] = (uint8_t)c2;
   if (!a.lab_out) return;                  // frames without labels (uniform over the launch)
-  const int lv = bp_label(a, b, y, x);
+  const int lv = pil_label(a, b, y, x);
   if (a.lab_out_bytes == 1) ((uint8_t*)a.lab_out)[o] = (uint8_t)lv;
   else ((int32_t*)a.lab_out)[o] = lv;
-}
-
-// BP_PREP_IDX with a refused index: output pixel (x, y) of batch row b is zeros, its target 0
-__device__ __forceinline__ void bp_zero(const BpArgs& a, int b, int y, int x) {
-  const size_t plane = (size_t)a.H * a.W, o = (size_t)y * a.W + x;
-  float* img = a.imgs + (size_t)b * 3 * plane + o;
-  img[0] = 0.f; img[plane] = 0.f; img[2 * plane] = 0.f;
-  a.tgt[(size_t)b * plane + o] = 0;
 }
 
 // steps 2-6 for one output pixel (x, y: coordinates before the mirror) of batch row b from the three resized bytes of image src
@@ -118,148 +74,65 @@ __device__ __forceinline__ void bp_finish(const BpArgs& a, const BpJitter& j, LU
   float* img = a.imgs + (size_t)b * 3 * plane + o;
   img[0] = v0; img[plane] = v1; img[2 * plane] = v2;
   if (!a.tgt) return;                      // RCV_OP_FRAME_PREP: frames without labels (uniform over the launch)
-  a.tgt[(size_t)b * plane + o] = (int64_t)bp_mask(bp_label(a, src, y, x), a.mask);
+  a.tgt[(size_t)b * plane + o] = (int64_t)pil_mask_label(pil_label(a, src, y, x), a.mask);
 }
 
 template <bool STAGE, int FORM>
 __global__ __launch_bounds__(256) void batch_prep_kernel(BpArgs a) {
   __shared__ float s_lut[FORM == BP_BYTES ? 1 : 768];
-  __shared__ int32_t s_xc[BP_TC * (2 + BP_MAXK)];
-  __shared__ int32_t s_yc[BP_TR * (2 + BP_MAXK)];
-  __shared__ uint8_t s_h[BP_ROWS_MAX * BP_TC * 3];
-  __shared__ __align__(16) uint8_t s_src[STAGE ? BP_RC * BP_SEG : 16];
+  __shared__ int32_t s_xc[PIL_TC * (2 + PIL_MAXK)];
+  __shared__ int32_t s_yc[PIL_TR * (2 + PIL_MAXK)];
+  __shared__ uint8_t s_h[PIL_ROWS_MAX * PIL_TC * 3];
+  __shared__ __align__(16) uint8_t s_src[STAGE ? PIL_RC * PIL_SEG : 16];
   const int tid = threadIdx.x;
   const int bid = blockIdx.x;
   const int tx = bid % a.tiles_x, ty = (bid / a.tiles_x) % a.tiles_y, b = bid / (a.tiles_x * a.tiles_y);
-  const int x0 = tx * BP_TC, y0 = ty * BP_TR;
-  const int tw = min(BP_TC, a.W - x0), th = min(BP_TR, a.H - y0);
+  PilTile t = pil_tile(a, tx, ty);
   int src = b;
   if (FORM == BP_PREP_IDX) {
-    src = bp_source(a, b);
+    src = pil_source(a, (size_t)b);
     if (src < 0) {                          // (the same for the whole workgroup, and in front of every barrier)
-      for (int idx = tid; idx < th * BP_TC; idx += 256)
-        if ((idx & (BP_TC - 1)) < tw) bp_zero(a, b, y0 + (idx >> 6), x0 + (idx & (BP_TC - 1)));
+      pil_zero_tile(a, b, t);
       if (tx == 0 && ty == 0 && tid == 0) atomicAdd(a.bad, 1);
       return;
     }
   }
-  const int sx = 2 + a.kx, sy = 2 + a.ky;
-  if (FORM != BP_BYTES)
+  if (FORM != BP_BYTES)                     // (in front of the barrier that closes pil_horizontal's table loads)
     for (int i = tid; i < 768; i += 256) s_lut[i] = a.norm[i];
-  for (int i = tid; i < tw * sx; i += 256) s_xc[i] = a.xtab[(size_t)x0 * sx + i];
-  for (int i = tid; i < th * sy; i += 256) s_yc[i] = a.ytab[(size_t)y0 * sy + i];
-  __syncthreads();
   BpJitter j = {};
   if (FORM != BP_BYTES) j = bp_jitter(a, b);
-  // source rows under this tile's vertical taps
-  const int ys0 = bp_clampi(s_yc[0], 0, a.Hs - 1);
-  const int ys1 = bp_clampi(s_yc[(th - 1) * sy] + s_yc[(th - 1) * sy + 1], ys0 + 1, a.Hs);
-  const int nrows = min(ys1 - ys0, a.rows_cap);
-  const uint8_t* fb = a.frames + (size_t)src * a.Hs * a.Ws * 3;
-
-  // ---- horizontal pass: s_h[r][x][c] for the rows ys0 .. ys0 + nrows; this thread's column is fixed
-  const int x = tid & (BP_TC - 1);
-  const int32_t* xc = s_xc + (x < tw ? x : 0) * sx;
-  const int xf = bp_clampi(xc[0], 0, a.Ws - 1);
-  const int xn = min(bp_clampi(xc[1], 0, a.kx), a.Ws - xf);
-  if (!STAGE) {
-    if (x < tw) {
-      for (int r = tid >> 6; r < nrows; r += 4) {
-        const uint8_t* p = fb + ((size_t)(ys0 + r) * a.Ws + xf) * 3;
-        int a0 = 1 << (BP_PREC - 1), a1 = a0, a2 = a0;
-        for (int k = 0; k < xn; ++k) {
-          const int c = xc[2 + k];
-          a0 += (int)p[3 * k] * c; a1 += (int)p[3 * k + 1] * c; a2 += (int)p[3 * k + 2] * c;
-        }
-        uint8_t* q = s_h + (r * BP_TC + x) * 3;
-        q[0] = (uint8_t)bp_clip8(a0); q[1] = (uint8_t)bp_clip8(a1); q[2] = (uint8_t)bp_clip8(a2);
-      }
-    }
-  } else {
-    // source pixels under this tile's horizontal taps: [xs0, xs0 + segpix)
-    const int xs0 = bp_clampi(s_xc[0], 0, a.Ws - 1);
-    const int xs1 = bp_clampi(s_xc[(tw - 1) * sx] + s_xc[(tw - 1) * sx + 1], xs0 + 1, a.Ws);
-    const int segpix = min(xs1 - xs0, (BP_SEG - 16) / 3);
-    const int seg = segpix * 3;
-    const int nvmax = (seg + 15 + 15) / 16;
-    const int rel = bp_clampi(xf - xs0, 0, segpix - 1);
-    const int xns = min(xn, segpix - rel);
-    const uintptr_t lo = (uintptr_t)a.frames, hi = lo + (size_t)a.nsrc * a.Hs * a.Ws * 3;
-    for (int r0 = 0; r0 < nrows; r0 += BP_RC) {
-      const int nr = min(BP_RC, nrows - r0);
-      for (int i = tid; i < nr * nvmax; i += 256) {
-        const int rr = i / nvmax, v = i - rr * nvmax;
-        const uintptr_t A = (uintptr_t)(fb + ((size_t)(ys0 + r0 + rr) * a.Ws + xs0) * 3);
-        const uintptr_t va = (A & ~(uintptr_t)15) + 16u * (uintptr_t)v;
-        if (va >= A + seg) continue;
-        uint4 w;
-        if (va >= lo && va + 16 <= hi) {
-          w = *(const uint4*)va;
-        } else {                          // the first / last 16 bytes of the whole frame buffer when it is not 16-byte aligned
-          uint32_t d[4] = {0u, 0u, 0u, 0u};
-          for (int t = 0; t < 16; ++t) {
-            const uintptr_t ad = va + t;
-            if (ad >= lo && ad < hi) d[t >> 2] |= (uint32_t)(*(const uint8_t*)ad) << (8 * (t & 3));
-          }
-          w = make_uint4(d[0], d[1], d[2], d[3]);
-        }
-        *(uint4*)(s_src + rr * BP_SEG + 16 * v) = w;
-      }
-      __syncthreads();
-      if (x < tw) {
-        for (int rr = tid >> 6; rr < nr; rr += 4) {
-          const uintptr_t A = (uintptr_t)(fb + ((size_t)(ys0 + r0 + rr) * a.Ws + xs0) * 3);
-          const uint8_t* p = s_src + rr * BP_SEG + (int)(A & 15) + rel * 3;
-          int a0 = 1 << (BP_PREC - 1), a1 = a0, a2 = a0;
-          for (int k = 0; k < xns; ++k) {
-            const int c = xc[2 + k];
-            a0 += (int)p[3 * k] * c; a1 += (int)p[3 * k + 1] * c; a2 += (int)p[3 * k + 2] * c;
-          }
-          uint8_t* q = s_h + ((r0 + rr) * BP_TC + x) * 3;
-          q[0] = (uint8_t)bp_clip8(a0); q[1] = (uint8_t)bp_clip8(a1); q[2] = (uint8_t)bp_clip8(a2);
-        }
-      }
-      __syncthreads();
-    }
-  }
-  __syncthreads();
+  pil_horizontal<STAGE>(a, src, a.nsrc, t, s_xc, s_yc, s_h, s_src);
 
   // ---- vertical pass + steps 2-6
-  for (int idx = tid; idx < th * BP_TC; idx += 256) {
+  const int x = tid & (PIL_TC - 1);
+  for (int idx = tid; idx < t.th * PIL_TC; idx += 256) {
     const int yl = idx >> 6;
-    if (x >= tw) continue;
-    const int32_t* yc = s_yc + yl * sy;
-    const int yf = yc[0] - ys0, yn = bp_clampi(yc[1], 0, a.ky);
-    int a0 = 1 << (BP_PREC - 1), a1 = a0, a2 = a0;
-    for (int k = 0; k < yn; ++k) {
-      const int c = yc[2 + k];
-      const uint8_t* q = s_h + (bp_clampi(yf + k, 0, nrows - 1) * BP_TC + x) * 3;
-      a0 += (int)q[0] * c; a1 += (int)q[1] * c; a2 += (int)q[2] * c;
-    }
-    if (FORM == BP_BYTES) bp_store_bytes(a, b, y0 + yl, x0 + x, bp_clip8(a0), bp_clip8(a1), bp_clip8(a2));
-    else bp_finish(a, j, s_lut, b, src, y0 + yl, x0 + x, bp_clip8(a0), bp_clip8(a1), bp_clip8(a2));
+    if (x >= t.tw) continue;
+    int c0, c1, c2;
+    pil_vertical(a, t, s_yc, s_h, yl, x, c0, c1, c2);
+    if (FORM == BP_BYTES) bp_store_bytes(a, b, t.y0 + yl, t.x0 + x, c0, c1, c2);
+    else bp_finish(a, j, s_lut, b, src, t.y0 + yl, t.x0 + x, c0, c1, c2);
   }
 }
 
-// H == Hs and W == Ws: no resize (dataset.py:118-121); one thread per pixel, 2048 pixels of one image per workgroup
-#define BP_IDENT_PIX 2048
+// H == Hs and W == Ws: no resize (dataset.py:118-121); one thread per pixel, PIL_IDENT_PIX pixels of one image per workgroup
 template <int FORM>
 __global__ __launch_bounds__(256) void batch_prep_ident_kernel(BpArgs a, int blocks_per_image) {
   const int b = blockIdx.x / blocks_per_image, blk = blockIdx.x % blocks_per_image;
   const int npix = a.H * a.W;
-  const int end = min(npix, (blk + 1) * BP_IDENT_PIX);
+  const int end = min(npix, (blk + 1) * PIL_IDENT_PIX);
   int src = b;
   if (FORM == BP_PREP_IDX) {
-    src = bp_source(a, b);
+    src = pil_source(a, (size_t)b);
     if (src < 0) {
-      for (int p = blk * BP_IDENT_PIX + threadIdx.x; p < end; p += 256) bp_zero(a, b, p / a.W, p % a.W);
+      for (int p = blk * PIL_IDENT_PIX + threadIdx.x; p < end; p += 256) pil_zero(a, b, p / a.W, p % a.W);
       if (blk == 0 && threadIdx.x == 0) atomicAdd(a.bad, 1);
       return;
     }
   }
   const BpJitter j = bp_jitter(a, b);
   const uint8_t* fb = a.frames + (size_t)src * npix * 3;
-  for (int p = blk * BP_IDENT_PIX + threadIdx.x; p < end; p += 256) {
+  for (int p = blk * PIL_IDENT_PIX + threadIdx.x; p < end; p += 256) {
     const int y = p / a.W, x = p - y * a.W;
     const uint8_t* q = fb + (size_t)p * 3;
     bp_finish(a, j, a.norm, b, src, y, x, (int)q[0], (int)q[1], (int)q[2]);
@@ -272,15 +145,6 @@ __global__ __launch_bounds__(256) void resize_u8_label_width_kernel(const void* 
     if (in_bytes == 4) ((uint8_t*)out)[i] = (uint8_t)((const int32_t*)in)[i];
     else ((int32_t*)out)[i] = (int32_t)((const uint8_t*)in)[i];
   }
-}
-
-// Pillow's precompute_coeffs: taps per output index of the BILINEAR filter
-static int bp_ksize(int in, int out) {
-  double scale = (double)in / out;
-  if (scale < 1.0) scale = 1.0;
-  int c = (int)scale;
-  if ((double)c < scale) ++c;
-  return c * 2 + 1;
 }
 
 template <int FORM>
@@ -306,26 +170,16 @@ int rcv_launch_batch_prep(const rcv_handle* h, const rcv_op* op, hipStream_t s, 
     query->n_part = 0; query->n_split = 0; query->part_bytes = 0;
     snprintf(query->label, sizeof(query->label), frames_only ? "frame_prep" : bytes ? "resize_u8" : indexed ? "batch_prep_idx" : "batch_prep");
   }
-  RCV_CHECK_ARG(B >= 1 && H >= 1 && W >= 1 && Hs >= 1 && Ws >= 1, "batch prep: B %d, source %d x %d, output %d x %d: every size must be >= 1", B, Hs, Ws,
-                H, W);
-  RCV_CHECK_ARG(nsrc >= 1, "batch prep: a store of %d images (i[COUNT]): there must be at least 1", nsrc);
-  RCV_CHECK_ARG((long long)Hs <= 8LL * H && (long long)Ws <= 8LL * W,
-                "batch prep: %d x %d -> %d x %d shrinks an axis by more than 8 (the kernel is built for at most %d taps)", Hs, Ws, H, W, BP_MAXK);
+  if (const int e = pil_check_record("batch prep", "COUNT", B, nsrc, Hs, Ws, H, W, kx, ky, indexed, op->i[RCV_I_INMODE], op->p[RCV_P_IN_AUX],
+                                     op->p[RCV_P_EPI_AUX]))
+    return e;
   RCV_CHECK_ARG(lab_bytes == 1 || lab_bytes == 4 || (bytes && lab_bytes == 0), "batch prep: label element size %d unsupported (1 = uint8, 4 = int32)",
                 lab_bytes);
   if (bytes && !no_labels)
     RCV_CHECK_ARG(op->i[RCV_I_INMODE] == 1 || op->i[RCV_I_INMODE] == 4,
                   "resize u8: label element size out %d cannot hold the %d-byte labels (1 = uint8, also the narrowing of int32 planes whose "
                   "values are <= 255; 4 = int32)", op->i[RCV_I_INMODE], lab_bytes);
-  if (indexed)
-    RCV_CHECK_ARG(op->i[RCV_I_INMODE] == 4 || op->i[RCV_I_INMODE] == 8, "batch prep: index element size %d unsupported (4 = int32, 8 = int64)",
-                  op->i[RCV_I_INMODE]);
-  RCV_CHECK_ARG(kx == bp_ksize(Ws, W) && ky == bp_ksize(Hs, H), "batch prep: %d / %d taps per column / row given, %d -> %d and %d -> %d take %d / %d", kx,
-                ky, Ws, W, Hs, H, bp_ksize(Ws, W), bp_ksize(Hs, H));
   RCV_CHECK_ARG((train == 0 || train == 1) && mask >= 0 && mask <= 15, "batch prep: train %d / maskLabel flags %d out of range", train, mask);
-  const int tiles_x = ceil_div(W, BP_TC), tiles_y = ceil_div(H, BP_TR);
-  RCV_CHECK_ARG((double)nsrc * Hs * Ws < 2147483647.0 && (double)B * H * W < 2147483647.0 && (double)B * tiles_x * tiles_y < 2147483647.0,
-                "batch prep: %d images of %d x %d -> %d x %d: more than 2^31 pixels", nsrc > B ? nsrc : B, Hs, Ws, H, W);
   if (no_labels)
     RCV_CHECK_ARG(op->p[RCV_P_X1] && op->p[RCV_P_X2] && (bytes || op->p[RCV_P_X5]),
                   bytes ? "resize u8: null table (frame taps of x / y)" : "frame prep: null table (frame taps of x / y, normalisation)");
@@ -333,8 +187,6 @@ int rcv_launch_batch_prep(const rcv_handle* h, const rcv_op* op, hipStream_t s, 
     RCV_CHECK_ARG(op->p[RCV_P_X1] && op->p[RCV_P_X2] && op->p[RCV_P_X3] && op->p[RCV_P_X4] && (bytes || op->p[RCV_P_X5]),
                   bytes ? "resize u8: null table (frame taps of x / y, label index of x / y)"
                         : "batch prep: null table (frame taps of x / y, label index of x / y, normalisation)");
-  // the index and its counter live for an epoch, as the tables do: a plan without them has nothing to gather by
-  if (indexed) RCV_CHECK_ARG(op->p[RCV_P_IN_AUX] && op->p[RCV_P_EPI_AUX], "batch prep: null index or null bad-index counter");
   if (query) return RCV_OK;
   if (no_labels) RCV_CHECK_ARG(op->p[RCV_P_IN] && op->p[RCV_P_OUT], bytes ? "resize u8: null operand" : "frame prep: null operand");
   else RCV_CHECK_ARG(op->p[RCV_P_IN] && op->p[RCV_P_IN2] && op->p[RCV_P_OUT] && op->p[RCV_P_X0], bytes ? "resize u8: null operand" : "batch prep: null operand");
@@ -353,7 +205,7 @@ int rcv_launch_batch_prep(const rcv_handle* h, const rcv_op* op, hipStream_t s, 
   }
   if (indexed) { a.index = op->p[RCV_P_IN_AUX]; a.idx_bytes = op->i[RCV_I_INMODE]; a.bad = (int*)op->p[RCV_P_EPI_AUX]; }
   a.B = B; a.Hs = Hs; a.Ws = Ws; a.H = H; a.W = W; a.kx = kx; a.ky = ky; a.lab_bytes = no_labels ? 1 : lab_bytes; a.train = train; a.mask = mask;
-  a.tiles_x = tiles_x; a.tiles_y = tiles_y; a.nsrc = nsrc;
+  a.tiles_x = ceil_div(W, PIL_TC); a.tiles_y = ceil_div(H, PIL_TR); a.nsrc = nsrc;
   if (H == Hs && W == Ws && bytes) {          // nothing to resize: copies, and one launch where the label width changes
     const size_t npix = (size_t)B * H * W;
     if (a.out8 != a.frames) RCV_HIP(hipMemcpyAsync(a.out8, a.frames, npix * 3, hipMemcpyDeviceToDevice, s));
@@ -368,19 +220,15 @@ int rcv_launch_batch_prep(const rcv_handle* h, const rcv_op* op, hipStream_t s, 
     return RCV_OK;
   }
   if (H == Hs && W == Ws) {
-    const int bpi = ceil_div(H * W, BP_IDENT_PIX);
+    const int bpi = ceil_div(H * W, PIL_IDENT_PIX);
     RCV_CHECK_ARG((double)B * bpi < 2147483647.0, "batch prep: grid too large");
     if (indexed) hipLaunchKernelGGL(batch_prep_ident_kernel<BP_PREP_IDX>, dim3(B * bpi), dim3(256), 0, s, a, bpi);
     else hipLaunchKernelGGL(batch_prep_ident_kernel<BP_PREP>, dim3(B * bpi), dim3(256), 0, s, a, bpi);
     RCV_HIP(hipGetLastError());
     return RCV_OK;
   }
-  const double scale_y = (double)Hs / H, support_y = scale_y < 1.0 ? 1.0 : scale_y;
-  const double span = (BP_TR - 1) * scale_y + 2.0 * support_y;
-  a.rows_cap = (int)span + ((double)(int)span < span ? 1 : 0) + 2;
-  if (a.rows_cap > BP_ROWS_MAX) a.rows_cap = BP_ROWS_MAX;
-  // staging pays where the row shrinks by more than about 3 (measured); RCV_BP_STAGE=0 / 1 overrides it in diagnostic builds
-  bool stage = kx >= BP_STAGE_MIN_TAPS;
+  a.rows_cap = pil_rows_cap(Hs, H);
+  bool stage = pil_stage(kx);          // RCV_BP_STAGE=0 / 1 overrides it in diagnostic builds
   if (const char* e = RCV_ENV("RCV_BP_STAGE")) stage = e[0] != '0';
   if (bytes) bp_launch_tiles<BP_BYTES>(stage, a, s);
   else if (indexed) bp_launch_tiles<BP_PREP_IDX>(stage, a, s);

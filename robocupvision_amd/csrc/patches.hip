@@ -11,8 +11,10 @@
 //      scale = (in1 - in0) / out, support = max(scale, 1), center = in0 + (xx + 0.5) scale, xmin = max(int(center - support + 0.5), 0),
 //      xmax = min(int(center + support + 0.5), inSize), triangle weights summed left to right, each divided by the sum, then
 //      int(0.5 + w 2^22); the horizontal pass first, the vertical pass second, each from 2^21, int32 sums, >> 22, clipped to a byte;
-//   4. step 4 of csrc/rgb_prep.hip, restated here (that file's code is left alone): c = byte / 255.0 in fp64, a matrix row's three
-//      products summed left to right, ((y - 0.5) / 0.5, u / 0.5, v / 0.5) rounded once to fp32.
+//   4. step 4 of csrc/rgb_prep.hip (pil_yuv_norm of csrc/pil_resize.h, the one both files call): c = byte / 255.0 in fp64, a matrix
+//      row's three products summed left to right, ((y - 0.5) / 0.5, u / 0.5, v / 0.5) rounded once to fp32.
+// The clamps, the 22-bit rounding and the tap count are that header's too; the box coefficient builder, the chunked walk and the text
+// of the guarded 16-byte load (pt_load16: see there) are this file's own.
 //
 // The workgroup (256 threads) reads its box, builds the two coefficient tables in LDS as int32 (threads 0..Sw-1 one row of the x
 // table each, threads 64..64+Sh-1 one row of the y table: a row is a sequential fp64 sum, the rows are independent), then walks the
@@ -33,12 +35,13 @@
 
 #pragma clang fp contract(off)
 
+#include "pil_resize.h"
+
 namespace {
 
 constexpr int PT_THREADS = 256;
 constexpr int PT_CHUNK = 64;             // source rows whose horizontal pass is held in LDS at a time
 constexpr int PT_MAXS = 64;              // largest patch side
-constexpr int PT_PREC = 22;
 
 constexpr int PT_LD = 8;                 // 16-byte words of source rows a thread holds in registers per batch
 constexpr int PT_STAGE_WORDS = PT_THREADS * PT_LD;      // words of a batch: 32 KiB of LDS
@@ -51,8 +54,6 @@ struct PtArgs {
 
 __host__ __device__ inline int pt_round4(int v) { return (v + 3) & ~3; }
 __host__ __device__ inline int pt_round16(int v) { return (v + 15) & ~15; }
-// Pillow's ksize of a whole axis: no box of the frame takes more taps per output index
-static inline long long pt_ksize(int in, int out) { return (in > out ? ((long long)in + out - 1) / out : 1LL) * 2 + 1; }
 // dynamic LDS: x table [Sw][2 + kx] | y table [Sh][2 + ky] | horizontal-pass bytes [PT_CHUNK][Sw][3] | staged source rows
 // [PT_STAGE_WORDS] x 16 bytes; every carve a multiple of 16 bytes
 __host__ __device__ inline size_t pt_table_bytes(int Sh, int Sw, int kx, int ky) {
@@ -62,9 +63,7 @@ __host__ __device__ inline size_t pt_lds_bytes(int Sh, int Sw, int kx, int ky) {
   return pt_table_bytes(Sh, Sw, kx, ky) + (size_t)pt_round16(PT_CHUNK * Sw * 3) + (size_t)PT_STAGE_WORDS * 16;
 }
 
-__device__ __forceinline__ int pt_clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 __device__ __forceinline__ long long pt_clampl(long long v, long long lo, long long hi) { return v < lo ? lo : (v > hi ? hi : v); }
-__device__ __forceinline__ int pt_clip8(int acc) { return pt_clampi(acc >> PT_PREC, 0, 255); }
 
 // one triangle weight of precompute_coeffs
 __device__ __forceinline__ double pt_weight(int x, double center, double ss) {
@@ -81,9 +80,9 @@ __device__ __forceinline__ void pt_coeff_row(int inSize, double in0, double in1,
   const double off = ((double)xx + 0.5) * scale;
   const double center = in0 + off;
   const double lo = center - support, hi = center + support;
-  const int xmin = pt_clampi((int)(lo + 0.5), 0, inSize - 1);
+  const int xmin = pil_clampi((int)(lo + 0.5), 0, inSize - 1);
   const int xmax = min((int)(hi + 0.5), inSize);
-  const int n = pt_clampi(xmax - xmin, 0, K);
+  const int n = pil_clampi(xmax - xmin, 0, K);
   double ww = 0.0;
   for (int x = 0; x < n; ++x) ww += pt_weight(x + xmin, center, ss);
   row[0] = xmin; row[1] = n;
@@ -94,8 +93,8 @@ __device__ __forceinline__ void pt_coeff_row(int inSize, double in0, double in1,
   }
 }
 
-// the 16-byte word at the aligned address va of the frame buffer [lo, hi); bytes outside it (the first / last word of a buffer that is
-// not 16-byte aligned) read as zero and are never looked at
+// pil_load16 (csrc/pil_resize.h) with the four words named: the same values, kept here because with the header's array form the
+// unrolled register batches below are scheduled differently and the full-frame launch measured 0.9 % slower
 __device__ __forceinline__ uint4 pt_load16(uintptr_t va, uintptr_t lo, uintptr_t hi) {
   if (va >= lo && va + 16 <= hi) return *reinterpret_cast<const uint4*>(va);
   uint32_t d0 = 0u, d1 = 0u, d2 = 0u, d3 = 0u;
@@ -163,18 +162,18 @@ __global__ __launch_bounds__(PT_THREADS) void object_patches_kernel(PtArgs a) {
 
   int acc[NPP][3];
 #pragma unroll
-  for (int j = 0; j < NPP; ++j) { acc[j][0] = 1 << (PT_PREC - 1); acc[j][1] = 1 << (PT_PREC - 1); acc[j][2] = 1 << (PT_PREC - 1); }
+  for (int j = 0; j < NPP; ++j) { acc[j][0] = 1 << (PIL_PREC - 1); acc[j][1] = 1 << (PIL_PREC - 1); acc[j][2] = 1 << (PIL_PREC - 1); }
 
   const int n_img = (int)(slot / a.slots_per_image);
   const uint8_t* fb = a.frames + (size_t)n_img * a.Hs * a.Ws * 3;
-  const int ys0 = pt_clampi(s_yc[0], 0, a.Hs - 1);
-  const int ys1 = pt_clampi(s_yc[(a.Sh - 1) * sy] + s_yc[(a.Sh - 1) * sy + 1], ys0 + 1, a.Hs);
+  const int ys0 = pil_clampi(s_yc[0], 0, a.Hs - 1);
+  const int ys1 = pil_clampi(s_yc[(a.Sh - 1) * sy] + s_yc[(a.Sh - 1) * sy + 1], ys0 + 1, a.Hs);
   // source pixels under the box's horizontal taps: [xs0, xs0 + segpix)
-  const int xs0 = pt_clampi(s_xc[0], 0, a.Ws - 1);
-  const int xs1 = pt_clampi(s_xc[(a.Sw - 1) * sx] + s_xc[(a.Sw - 1) * sx + 1], xs0 + 1, a.Ws);
+  const int xs0 = pil_clampi(s_xc[0], 0, a.Ws - 1);
+  const int xs1 = pil_clampi(s_xc[(a.Sw - 1) * sx] + s_xc[(a.Sw - 1) * sx + 1], xs0 + 1, a.Ws);
   const int segpix = xs1 - xs0, segb = segpix * 3;
   const int nv = (segb + 30) / 16;               // 16-byte words that hold a row's segment starting up to 15 bytes into the first
-  const int rb = pt_clampi(PT_STAGE_WORDS / nv, 1, PT_CHUNK);      // source rows per batch (nv <= PT_STAGE_WORDS: refused otherwise)
+  const int rb = pil_clampi(PT_STAGE_WORDS / nv, 1, PT_CHUNK);      // source rows per batch (nv <= PT_STAGE_WORDS: refused otherwise)
   const uintptr_t lo = (uintptr_t)a.frames, hi = lo + a.frames_bytes;
   const uint8_t* seg0 = fb + (size_t)xs0 * 3;
   const size_t pitch = (size_t)a.Ws * 3;
@@ -204,18 +203,18 @@ __global__ __launch_bounds__(PT_THREADS) void object_patches_kernel(PtArgs a) {
     for (int i = tid; i < nb * a.Sw; i += PT_THREADS) {
       const int rr = i / a.Sw, x = i - rr * a.Sw;
       const int32_t* xc = s_xc + x * sx;
-      const int rel = pt_clampi(xc[0] - xs0, 0, segpix - 1);
-      const int xn = min(pt_clampi(xc[1], 0, a.kx), segpix - rel);
+      const int rel = pil_clampi(xc[0] - xs0, 0, segpix - 1);
+      const int xn = min(pil_clampi(xc[1], 0, a.kx), segpix - rel);
       const uintptr_t A = (uintptr_t)(seg0 + (size_t)(row0 + rr) * pitch);
       const uint8_t* p = s_src + 16 * nv * rr + (int)(A & 15) + rel * 3;
-      int a0 = 1 << (PT_PREC - 1), a1 = a0, a2 = a0;
+      int a0 = 1 << (PIL_PREC - 1), a1 = a0, a2 = a0;
 #pragma unroll 4
       for (int t = 0; t < xn; ++t) {
         const int c = xc[2 + t];
         a0 += (int)p[3 * t] * c; a1 += (int)p[3 * t + 1] * c; a2 += (int)p[3 * t + 2] * c;
       }
       uint8_t* q = s_h + ((row0 - c0 + rr) * a.Sw + x) * 3;
-      q[0] = (uint8_t)pt_clip8(a0); q[1] = (uint8_t)pt_clip8(a1); q[2] = (uint8_t)pt_clip8(a2);
+      q[0] = (uint8_t)pil_clip8(a0); q[1] = (uint8_t)pil_clip8(a1); q[2] = (uint8_t)pil_clip8(a2);
     }
     __syncthreads();
     if (row1 == c1) {       // (uniform) the chunk [c0, c1) is complete: its share of the vertical pass
@@ -225,7 +224,7 @@ __global__ __launch_bounds__(PT_THREADS) void object_patches_kernel(PtArgs a) {
         if (p < npix) {
           const int y = p / a.Sw, x = p - y * a.Sw;
           const int32_t* yc = s_yc + y * sy;
-          const int yf = pt_clampi(yc[0], 0, a.Hs - 1), yn = pt_clampi(yc[1], 0, a.ky);
+          const int yf = pil_clampi(yc[0], 0, a.Hs - 1), yn = pil_clampi(yc[1], 0, a.ky);
           const int r0 = max(yf, c0), r1 = min(yf + yn, c1);
           int a0 = acc[j][0], a1 = acc[j][1], a2 = acc[j][2];
           for (int r = r0; r < r1; ++r) {
@@ -245,14 +244,9 @@ __global__ __launch_bounds__(PT_THREADS) void object_patches_kernel(PtArgs a) {
   for (int j = 0; j < NPP; ++j) {
     const int p = tid + PT_THREADS * j;
     if (p < npix) {
-      const int r = pt_clip8(acc[j][0]), g = pt_clip8(acc[j][1]), b = pt_clip8(acc[j][2]);
+      const int r = pil_clip8(acc[j][0]), g = pil_clip8(acc[j][1]), b = pil_clip8(acc[j][2]);
       if (byt) { byt[3 * p] = (uint8_t)r; byt[3 * p + 1] = (uint8_t)g; byt[3 * p + 2] = (uint8_t)b; }
-      const double cr = (double)r / 255.0, cg = (double)g / 255.0, cb = (double)b / 255.0;
-      const double y0_ = cr * 0.299, y1_ = cg * 0.587, y2_ = cb * 0.114;
-      const double u0 = cr * -0.14714119, u1 = cg * -0.28886916, u2 = cb * 0.43601035;
-      const double v0 = cr * 0.61497538, v1 = cg * -0.51496512, v2 = cb * -0.10001026;
-      const double yy = (y0_ + y1_) + y2_, uu = (u0 + u1) + u2, vv = (v0 + v1) + v2;
-      img[p] = (float)((yy - 0.5) / 0.5); img[npix + p] = (float)(uu / 0.5); img[2 * npix + p] = (float)(vv / 0.5);
+      pil_yuv_norm((double)r / 255.0, (double)g / 255.0, (double)b / 255.0, img[p], img[npix + p], img[2 * npix + p]);
     }
   }
 }
@@ -284,7 +278,7 @@ int rcv_launch_object_patches(const rcv_handle* h, const rcv_op* op, hipStream_t
   RCV_CHECK_ARG((long long)W * Ws <= 2147483647LL && (long long)H * Hs <= 2147483647LL,
                 "%s: map %d x %d times frame %d x %d: a box corner times the frame size can pass 32 bits", what, H, W, Hs, Ws);
   RCV_CHECK_ARG((double)N * Cm1 * M < 2147483647.0, "%s: %d x %d x %d slots: more than 2^31", what, N, Cm1, M);
-  const long long kxl = pt_ksize(Ws, Sw), kyl = pt_ksize(Hs, Sh);
+  const long long kxl = pil_ksize(Ws, Sw), kyl = pil_ksize(Hs, Sh);      // of a whole axis: no box of the frame takes more taps per output index
   RCV_CHECK_ARG((3LL * Ws + 30) / 16 <= PT_STAGE_WORDS, "%s: a source row of %d pixels does not fit the %d-byte staging buffer in LDS", what, Ws,
                 PT_STAGE_WORDS * 16);
   const long long ldsl = ((2 + kxl) * Sw + (2 + kyl) * Sh + 8) * 4 + PT_CHUNK * Sw * 3 + 16 + PT_STAGE_WORDS * 16;      // >= pt_lds_bytes, no overflow

@@ -2,7 +2,7 @@
 // labelPropTrain.py / tester.py / makeLPImages.py / classTrainer.py / objDetEval.py) for a whole batch:
 //   uint8 RGB frames [B][Hs][Ws][3] (+ label planes [B][Hs][Ws], uint8 / int32)  ->  fp32 NCHW YUV [B][3][H][W] (+ int64 targets [B][H][W]).
 // Per image, in the reference's order (the contract is restated in tests/rgb_prep_restatement.py and pinned to Pillow there):
-//   1. Scale: Pillow's 8-bit BILINEAR resize as two integer passes from host-made tables, exactly as csrc/batch_prep.hip;
+//   1. Scale: Pillow's 8-bit BILINEAR resize as two integer passes from host-made tables (csrc/pil_resize.h);
 //   2. HorizontalFlip, VerticalFlip: mirrored x / y (frame and label alike);
 //   3. torchvision's PIL ColorJitter: up to four operations on the uint8 pixel, in the order the parameter row gives --
 //        Image.blend(d, x, f) per byte in fp32, multiply and add rounded separately: t = d + f (x - d); 0 if t <= 0, 255 if t >= 255,
@@ -22,17 +22,16 @@
 // Contrast needs the mean of L over the whole image, so the op is two launches on one stream.  The statistics launch has the grid of
 // the main one; a workgroup recomputes its tile's resize and the operations in front of the contrast and writes ONE integer partial sum
 // (nothing to zero, no atomics; integer sums have no order to fix).  The main launch sums its image's partials in its prologue, forms
-// m = floor((2 sum + n) / (2 n)) and does everything.  Both go through rp_horizontal / rp_vertical / rp_ops.  The statistics launch is
-// skipped when the record says that no row holds a contrast (validation mode, rcv.h i[COUNT]).
+// m = floor((2 sum + n) / (2 n)) and does everything.  Both go through pil_horizontal / pil_vertical / rp_ops.  The statistics launch
+// is skipped when the record says that no row holds a contrast (validation mode, rcv.h i[COUNT]).
 //
-// Tiling as csrc/batch_prep.hip: one workgroup = 8 output rows x 64 output columns of one image, lane = output x; the horizontal pass
-// of the source rows under the tile goes to LDS as bytes (from staged source rows where a row shrinks by more than about 3), the
-// vertical pass reads it back; the plane stores are contiguous over the
-// lanes (reversed under a horizontal flip).  Every table entry is clamped where it is used.
+// The resize, its tile (one workgroup = 8 output rows x 64 output columns of one image, lane = output x), the label gather, maskLabel,
+// the index test and step 4's arithmetic are csrc/pil_resize.h's, shared with csrc/batch_prep.hip (step 4: with csrc/patches.hip);
+// this file holds steps 2, 3 and 5 and the launchers.  The plane stores are contiguous over the lanes (reversed under a horizontal flip).
 //
 // RCV_OP_RGB_PREP_IDX (rcv_rgb_prep_indexed) takes image b from store[index[b]]: the index is read from device memory and tested against
 // [0, N) before it forms an address, in both launches (a 0 partial; a zero image with zero targets, counted once).  The kernels are
-// instantiated with the index off for RCV_OP_RGB_PREP, as csrc/batch_prep.hip does.
+// instantiated with the index off for RCV_OP_RGB_PREP.
 // RCV_OP_LP_PAIR_PREP (rcv_lp_pair_prep) is at the end of the file: both frames of a LabelProp pair through steps 2-5 with ONE row, Y only,
 // then the assembly of labelPropTrain.py:162-193, from a store that is already at the network's size.
 //
@@ -42,15 +41,8 @@
 
 #pragma clang fp contract(off)
 
-#define RP_TR 8
-#define RP_TC 64
-#define RP_MAXK 17                       /* taps of a downscale by 8 */
-#define RP_ROWS_MAX 74                   /* source rows under 8 output rows at a downscale by 8 */
-#define RP_RC 8                          /* source rows staged at a time */
-#define RP_SEG 1600                      /* bytes of one staged row segment: ((63 * 8 + 2 * 8 + 2) * 3 + 15) rounded up to 16 */
-#define RP_PREC 22
-#define RP_STAGE_MIN_TAPS 9              /* taps per output column from which the source rows are staged in LDS */
-#define RP_IDENT_PIX 2048                /* pixels of one image per workgroup where nothing is resized */
+#include "pil_resize.h"
+
 #define RP_PAIR_PIX 512                  /* pixels of both frames of a pair per workgroup of lp_pair_prep_kernel */
 #define RP_NPAR 12                       /* floats of a parameter row */
 
@@ -65,19 +57,6 @@ struct RpArgs {
 
 enum { RP_PLAIN = 0, RP_IDX = 1, RP_PAIR = 2 };          // the form a kernel is instantiated for
 
-__device__ __forceinline__ int rp_clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-__device__ __forceinline__ int rp_clip8(int acc) { return rp_clampi(acc >> RP_PREC, 0, 255); }
-
-// transform.py:26-49 on one value; m bits: 1 = nb, 2 = nr, 4 = ng, 8 = nl
-__device__ __forceinline__ int rp_mask(int v, int m) {
-  int rN = 2, gN = 3, lN = 4;
-  if (m & 1) { if (v == 1) v = 0; if (v > 1) v -= 1; rN = 1; gN = 2; lN = 3; }
-  if (m & 2) { if (v == rN) v = 0; if (v > rN) v -= 1; gN = 1; lN = 2; }
-  if (m & 4) { if (v == gN) v = 0; if (v > gN) v -= 1; lN = 1; }
-  if (m & 8) { if (v == lN) v = 0; }
-  return v;
-}
-
 // the parameter row of an image; ops = the four op codes, 4 bits each (15 = none; no indexed array: it would live in scratch memory);
 // cpos = position of the first contrast among its operations, -1 = none (uniform over a workgroup)
 struct RpRow { bool hflip, vflip; int n_ops, cpos, ops, shift; float fb, fc, fs; };
@@ -88,7 +67,7 @@ __device__ __forceinline__ RpRow rp_row(const RpArgs& a, int b) {
   if (a.train) {
     const float* p = a.params + (size_t)b * RP_NPAR;
     j.hflip = p[0] != 0.f; j.vflip = p[1] != 0.f;
-    j.n_ops = rp_clampi((int)p[2], 0, 4);
+    j.n_ops = pil_clampi((int)p[2], 0, 4);
     j.ops = 0;
     for (int k = 0; k < 4; ++k) {
       const int c = (int)p[3 + k];
@@ -98,20 +77,6 @@ __device__ __forceinline__ RpRow rp_row(const RpArgs& a, int b) {
     for (int k = j.n_ops - 1; k >= 0; --k) if (((j.ops >> (4 * k)) & 15) == 1) j.cpos = k;
   }
   return j;
-}
-
-// RP_IDX / RP_PAIR: the store image of element e of the index, or -1 where it is outside [0, nsrc) (tested before it is used for anything)
-__device__ __forceinline__ int rp_source(const RpArgs& a, size_t e) {
-  const long long v = a.idx_bytes == 8 ? (long long)((const int64_t*)a.index)[e] : (long long)((const int32_t*)a.index)[e];
-  return v >= 0 && v < (long long)a.nsrc ? (int)v : -1;
-}
-
-// RP_IDX with a refused index: output pixel (x, y) of batch row b is zeros, its target 0
-__device__ __forceinline__ void rp_zero(const RpArgs& a, int b, int y, int x) {
-  const size_t plane = (size_t)a.H * a.W, o = (size_t)y * a.W + x;
-  float* img = a.imgs + (size_t)b * 3 * plane + o;
-  img[0] = 0.f; img[plane] = 0.f; img[2 * plane] = 0.f;
-  if (a.tgt) a.tgt[(size_t)b * plane + o] = 0;
 }
 
 __device__ __forceinline__ int rp_luma(int r, int g, int b) { return (19595 * r + 38470 * g + 7471 * b + 32768) >> 16; }
@@ -124,7 +89,7 @@ __device__ __forceinline__ int rp_blend(int d, int x, float f) {
 }
 
 // rnd(v) of a value that is never negative, clipped to a byte ((double)v + 0.5 is exact)
-__device__ __forceinline__ int rp_rnd8(float v) { return rp_clampi((int)((double)v + 0.5), 0, 255); }
+__device__ __forceinline__ int rp_rnd8(float v) { return pil_clampi((int)((double)v + 0.5), 0, 255); }
 
 // Pillow's convert("HSV"), H = (H + shift) & 255, convert("RGB") on one pixel
 __device__ __forceinline__ void rp_hue(int shift, int& r, int& g, int& b) {
@@ -149,8 +114,8 @@ __device__ __forceinline__ void rp_hue(int shift, int& r, int& g, int& b) {
     double x = h6 + 1.0;                        // in [5/6, 11/6]
     if (x >= 1.0) x = x - 1.0;                  // fmod(x, 1.0), exact
     const float hf = (float)x;
-    Hh = rp_clampi((int)((double)hf * 255.0), 0, 255);
-    S = rp_clampi((int)((double)s * 255.0), 0, 255);
+    Hh = pil_clampi((int)((double)hf * 255.0), 0, 255);
+    S = pil_clampi((int)((double)s * 255.0), 0, 255);
   }
   Hh = (Hh + shift) & 255;
   if (S == 0) { r = V; g = V; b = V; return; }
@@ -218,159 +183,41 @@ __device__ __forceinline__ int rp_mean(const RpArgs& a, const RpRow& j, int b, u
   return (int)((2ull * sum + n) / (2ull * n));
 }
 
-// the Y of step 4 before Normalize, from c = byte / 255.0 of the three bytes
-__device__ __forceinline__ double rp_y(double cr, double cg, double cb) {
-  const double y0 = cr * 0.299, y1 = cg * 0.587, y2 = cb * 0.114;
-  return (y0 + y1) + y2;
-}
-
-// Normalize([.5], [.5]) of Y, rounded once to fp32
-__device__ __forceinline__ float rp_ynorm(double yy) { return (float)((yy - 0.5) / 0.5); }
-
-// steps 4 and 5 for one output pixel (x, y: coordinates before the mirrors) of batch row b (image src of `labels`) from its bytes after step 3
+// steps 4 and 5 for one output pixel (x, y: coordinates before the mirrors) of batch row b (image src of `labels`) from its bytes after
+// step 3; s_c[v] = v / 255.0
 __device__ __forceinline__ void rp_finish(const RpArgs& a, const RpRow& j, const double* s_c, int b, int src, int y, int x, int r, int g, int bl) {
-  const double cr = s_c[r], cg = s_c[g], cb = s_c[bl];
-  const double yy = rp_y(cr, cg, cb);
-  const double u0 = cr * -0.14714119, u1 = cg * -0.28886916, u2 = cb * 0.43601035;
-  const double v0 = cr * 0.61497538, v1 = cg * -0.51496512, v2 = cb * -0.10001026;
-  const double uu = (u0 + u1) + u2, vv = (v0 + v1) + v2;
+  float yy, uu, vv;
+  pil_yuv_norm(s_c[r], s_c[g], s_c[bl], yy, uu, vv);
   const int xo = j.hflip ? a.W - 1 - x : x, yo = j.vflip ? a.H - 1 - y : y;
   const size_t plane = (size_t)a.H * a.W, o = (size_t)yo * a.W + xo;
   float* img = a.imgs + (size_t)b * 3 * plane + o;
-  img[0] = rp_ynorm(yy); img[plane] = (float)(uu / 0.5); img[2 * plane] = (float)(vv / 0.5);
+  img[0] = yy; img[plane] = uu; img[2 * plane] = vv;
   if (!a.tgt) return;                      // the patch chain: no label plane (uniform over the launch)
-  const int sy = rp_clampi(a.ly[y], 0, a.Hs - 1), sx = rp_clampi(a.lx[x], 0, a.Ws - 1);
-  const size_t li = ((size_t)src * a.Hs + sy) * a.Ws + sx;
-  const int lv = a.lab_bytes == 1 ? (int)((const uint8_t*)a.labels)[li] : ((const int32_t*)a.labels)[li];
-  a.tgt[(size_t)b * plane + o] = (int64_t)rp_mask(lv, a.mask);
+  a.tgt[(size_t)b * plane + o] = (int64_t)pil_mask_label(pil_label(a, src, y, x), a.mask);
 }
 
-struct RpTile { int x0, y0, tw, th, ys0, nrows; };
-
-// the tile's tables to LDS and the horizontal pass of the source rows of image b of `frames` under it: s_h[r][x][c].  STAGE (as csrc/batch_prep.hip, from 9
-// taps per column): the source-row segments of the tile are first copied to LDS with 16-byte aligned loads, RP_RC rows at a time, and
-// the taps read LDS bytes; otherwise the taps read global bytes through the cache.
-template <bool STAGE, int FORM>
-__device__ __forceinline__ RpTile rp_horizontal(const RpArgs& a, int b, int tile, int32_t* s_xc, int32_t* s_yc, uint8_t* s_h, uint8_t* s_src) {
-  const int tid = threadIdx.x;
-  const int tx = tile % a.tiles_x, ty = tile / a.tiles_x;
-  RpTile t;
-  t.x0 = tx * RP_TC; t.y0 = ty * RP_TR;
-  t.tw = min(RP_TC, a.W - t.x0); t.th = min(RP_TR, a.H - t.y0);
-  const int sx = 2 + a.kx, sy = 2 + a.ky;
-  for (int i = tid; i < t.tw * sx; i += 256) s_xc[i] = a.xtab[(size_t)t.x0 * sx + i];
-  for (int i = tid; i < t.th * sy; i += 256) s_yc[i] = a.ytab[(size_t)t.y0 * sy + i];
-  __syncthreads();
-  t.ys0 = rp_clampi(s_yc[0], 0, a.Hs - 1);
-  const int ys1 = rp_clampi(s_yc[(t.th - 1) * sy] + s_yc[(t.th - 1) * sy + 1], t.ys0 + 1, a.Hs);
-  t.nrows = min(ys1 - t.ys0, a.rows_cap);
-  const uint8_t* fb = a.frames + (size_t)b * a.Hs * a.Ws * 3;
-  const int x = tid & (RP_TC - 1);
-  const int32_t* xc = s_xc + (x < t.tw ? x : 0) * sx;
-  const int xf = rp_clampi(xc[0], 0, a.Ws - 1);
-  const int xn = min(rp_clampi(xc[1], 0, a.kx), a.Ws - xf);
-  if (!STAGE) {
-    if (x < t.tw) {
-      for (int r = tid >> 6; r < t.nrows; r += 4) {
-        const uint8_t* p = fb + ((size_t)(t.ys0 + r) * a.Ws + xf) * 3;
-        int a0 = 1 << (RP_PREC - 1), a1 = a0, a2 = a0;
-        for (int k = 0; k < xn; ++k) {
-          const int c = xc[2 + k];
-          a0 += (int)p[3 * k] * c; a1 += (int)p[3 * k + 1] * c; a2 += (int)p[3 * k + 2] * c;
-        }
-        uint8_t* q = s_h + (r * RP_TC + x) * 3;
-        q[0] = (uint8_t)rp_clip8(a0); q[1] = (uint8_t)rp_clip8(a1); q[2] = (uint8_t)rp_clip8(a2);
-      }
-    }
-  } else {
-    // source pixels under this tile's horizontal taps: [xs0, xs0 + segpix)
-    const int xs0 = rp_clampi(s_xc[0], 0, a.Ws - 1);
-    const int xs1 = rp_clampi(s_xc[(t.tw - 1) * sx] + s_xc[(t.tw - 1) * sx + 1], xs0 + 1, a.Ws);
-    const int segpix = min(xs1 - xs0, (RP_SEG - 16) / 3);
-    const int seg = segpix * 3;
-    const int nvmax = (seg + 15 + 15) / 16;
-    const int rel = rp_clampi(xf - xs0, 0, segpix - 1);
-    const int xns = min(xn, segpix - rel);
-    const uintptr_t lo = (uintptr_t)a.frames, hi = lo + (size_t)(FORM == RP_IDX ? a.nsrc : a.B) * a.Hs * a.Ws * 3;
-    for (int r0 = 0; r0 < t.nrows; r0 += RP_RC) {
-      const int nr = min(RP_RC, t.nrows - r0);
-      for (int i = tid; i < nr * nvmax; i += 256) {
-        const int rr = i / nvmax, v = i - rr * nvmax;
-        const uintptr_t A = (uintptr_t)(fb + ((size_t)(t.ys0 + r0 + rr) * a.Ws + xs0) * 3);
-        const uintptr_t va = (A & ~(uintptr_t)15) + 16u * (uintptr_t)v;
-        if (va >= A + seg) continue;
-        uint4 w;
-        if (va >= lo && va + 16 <= hi) {
-          w = *(const uint4*)va;
-        } else {                          // the first / last 16 bytes of the whole frame buffer when it is not 16-byte aligned
-          uint32_t d[4] = {0u, 0u, 0u, 0u};
-          for (int q = 0; q < 16; ++q) {
-            const uintptr_t ad = va + q;
-            if (ad >= lo && ad < hi) d[q >> 2] |= (uint32_t)(*(const uint8_t*)ad) << (8 * (q & 3));
-          }
-          w = make_uint4(d[0], d[1], d[2], d[3]);
-        }
-        *(uint4*)(s_src + rr * RP_SEG + 16 * v) = w;
-      }
-      __syncthreads();
-      if (x < t.tw) {
-        for (int rr = tid >> 6; rr < nr; rr += 4) {
-          const uintptr_t A = (uintptr_t)(fb + ((size_t)(t.ys0 + r0 + rr) * a.Ws + xs0) * 3);
-          const uint8_t* p = s_src + rr * RP_SEG + (int)(A & 15) + rel * 3;
-          int a0 = 1 << (RP_PREC - 1), a1 = a0, a2 = a0;
-          for (int k = 0; k < xns; ++k) {
-            const int c = xc[2 + k];
-            a0 += (int)p[3 * k] * c; a1 += (int)p[3 * k + 1] * c; a2 += (int)p[3 * k + 2] * c;
-          }
-          uint8_t* q = s_h + ((r0 + rr) * RP_TC + x) * 3;
-          q[0] = (uint8_t)rp_clip8(a0); q[1] = (uint8_t)rp_clip8(a1); q[2] = (uint8_t)rp_clip8(a2);
-        }
-      }
-      __syncthreads();
-    }
-  }
-  __syncthreads();
-  return t;
-}
-
-// the vertical pass for the output pixel (x, yl) of the tile (x < tw, yl < th)
-__device__ __forceinline__ void rp_vertical(const RpArgs& a, const RpTile& t, const int32_t* s_yc, const uint8_t* s_h, int yl, int x, int& r, int& g,
-                                            int& b) {
-  const int32_t* yc = s_yc + yl * (2 + a.ky);
-  const int yf = yc[0] - t.ys0, yn = rp_clampi(yc[1], 0, a.ky);
-  int a0 = 1 << (RP_PREC - 1), a1 = a0, a2 = a0;
-  for (int k = 0; k < yn; ++k) {
-    const int c = yc[2 + k];
-    const uint8_t* q = s_h + (rp_clampi(yf + k, 0, t.nrows - 1) * RP_TC + x) * 3;
-    a0 += (int)q[0] * c; a1 += (int)q[1] * c; a2 += (int)q[2] * c;
-  }
-  r = rp_clip8(a0); g = rp_clip8(a1); b = rp_clip8(a2);
-}
-
-// STATS: the statistics launch (one partial sum of L per workgroup); otherwise the main launch.  STAGE: see rp_horizontal.
+// STATS: the statistics launch (one partial sum of L per workgroup); otherwise the main launch.  STAGE: see pil_horizontal.
 // FORM: RP_PLAIN, or RP_IDX (image b is store[index[b]]).  Grid: B * tiles_x * tiles_y.
 template <bool STATS, bool STAGE, int FORM>
 __global__ __launch_bounds__(256) void rgb_prep_kernel(RpArgs a) {
   __shared__ double s_c[256];
   __shared__ unsigned long long s_red[256];
-  __shared__ int32_t s_xc[RP_TC * (2 + RP_MAXK)];
-  __shared__ int32_t s_yc[RP_TR * (2 + RP_MAXK)];
-  __shared__ uint8_t s_h[RP_ROWS_MAX * RP_TC * 3];
-  __shared__ __align__(16) uint8_t s_src[STAGE ? RP_RC * RP_SEG : 16];
+  __shared__ int32_t s_xc[PIL_TC * (2 + PIL_MAXK)];
+  __shared__ int32_t s_yc[PIL_TR * (2 + PIL_MAXK)];
+  __shared__ uint8_t s_h[PIL_ROWS_MAX * PIL_TC * 3];
+  __shared__ __align__(16) uint8_t s_src[STAGE ? PIL_RC * PIL_SEG : 16];
   const int tid = threadIdx.x;
   const int b = blockIdx.x / a.wpi, tile = blockIdx.x % a.wpi;
+  PilTile t = pil_tile(a, tile % a.tiles_x, tile / a.tiles_x);
   int src = b;
   if (FORM == RP_IDX) {
-    src = rp_source(a, (size_t)b);
+    src = pil_source(a, (size_t)b);
     if (src < 0) {                               // (the same for the whole workgroup, and in front of every barrier)
       if (STATS) {
         if (tid == 0) a.part[blockIdx.x] = 0u;
         return;
       }
-      const int x0 = (tile % a.tiles_x) * RP_TC, y0 = (tile / a.tiles_x) * RP_TR;
-      const int tw = min(RP_TC, a.W - x0), th = min(RP_TR, a.H - y0);
-      for (int idx = tid; idx < th * RP_TC; idx += 256)
-        if ((idx & (RP_TC - 1)) < tw) rp_zero(a, b, y0 + (idx >> 6), x0 + (idx & (RP_TC - 1)));
+      pil_zero_tile(a, b, t);
       if (tile == 0 && tid == 0) atomicAdd(a.bad, 1);
       return;
     }
@@ -385,14 +232,14 @@ __global__ __launch_bounds__(256) void rgb_prep_kernel(RpArgs a) {
     s_c[tid] = (double)tid / 255.0;
     m = rp_mean(a, j, b, s_red);
   }
-  const RpTile t = rp_horizontal<STAGE, FORM>(a, src, tile, s_xc, s_yc, s_h, s_src);
-  const int x = tid & (RP_TC - 1);
+  pil_horizontal<STAGE>(a, src, FORM == RP_IDX ? a.nsrc : a.B, t, s_xc, s_yc, s_h, s_src);
+  const int x = tid & (PIL_TC - 1);
   unsigned long long lsum = 0;
-  for (int idx = tid; idx < t.th * RP_TC; idx += 256) {
+  for (int idx = tid; idx < t.th * PIL_TC; idx += 256) {
     const int yl = idx >> 6;
     if (x >= t.tw) continue;
     int r, g, bl;
-    rp_vertical(a, t, s_yc, s_h, yl, x, r, g, bl);
+    pil_vertical(a, t, s_yc, s_h, yl, x, r, g, bl);
     if (STATS) {
       rp_ops(j, j.cpos, 0, r, g, bl);
       lsum += (unsigned long long)rp_luma(r, g, bl);
@@ -407,7 +254,7 @@ __global__ __launch_bounds__(256) void rgb_prep_kernel(RpArgs a) {
   }
 }
 
-// H == Hs and W == Ws: no resize (transform.py:15-16); one thread per pixel, RP_IDENT_PIX pixels of one image per workgroup.
+// H == Hs and W == Ws: no resize (transform.py:15-16); one thread per pixel, PIL_IDENT_PIX pixels of one image per workgroup.
 // FORM: RP_PLAIN, RP_IDX, or (STATS only) RP_PAIR: the statistics launch of RCV_OP_LP_PAIR_PREP -- image b is frame b & 1 of pair b >> 1,
 // its row is the pair's, and a pair with either index outside the store leaves 0 partials for both its frames.
 template <bool STATS, int FORM>
@@ -418,15 +265,15 @@ __global__ __launch_bounds__(256) void rgb_prep_ident_kernel(RpArgs a) {
   const int b = blockIdx.x / a.wpi, blk = blockIdx.x % a.wpi;
   int src = b;
   if (FORM != RP_PLAIN) {
-    src = rp_source(a, (size_t)b);
-    const bool bad = src < 0 || (FORM == RP_PAIR && rp_source(a, (size_t)(b ^ 1)) < 0);
+    src = pil_source(a, (size_t)b);
+    const bool bad = src < 0 || (FORM == RP_PAIR && pil_source(a, (size_t)(b ^ 1)) < 0);
     if (bad) {                                   // (the same for the whole workgroup, and in front of every barrier)
       if (STATS) {
         if (tid == 0) a.part[blockIdx.x] = 0u;
         return;
       }
-      const int start = blk * RP_IDENT_PIX, end = start + min(RP_IDENT_PIX, a.H * a.W - start);
-      for (int p = start + tid; p < end; p += 256) rp_zero(a, b, p / a.W, p % a.W);
+      const int start = blk * PIL_IDENT_PIX, end = start + min(PIL_IDENT_PIX, a.H * a.W - start);
+      for (int p = start + tid; p < end; p += 256) pil_zero(a, b, p / a.W, p % a.W);
       if (blk == 0 && tid == 0) atomicAdd(a.bad, 1);
       return;
     }
@@ -444,7 +291,7 @@ __global__ __launch_bounds__(256) void rgb_prep_ident_kernel(RpArgs a) {
   }
   const int npix = a.H * a.W;
   const uint8_t* fb = a.frames + (size_t)src * npix * 3;
-  const int start = blk * RP_IDENT_PIX, end = start + min(RP_IDENT_PIX, npix - start);
+  const int start = blk * PIL_IDENT_PIX, end = start + min(PIL_IDENT_PIX, npix - start);
   unsigned long long lsum = 0;
   for (int p = start + tid; p < end; p += 256) {
     const uint8_t* q = fb + (size_t)p * 3;
@@ -464,15 +311,6 @@ __global__ __launch_bounds__(256) void rgb_prep_ident_kernel(RpArgs a) {
   }
 }
 
-// Pillow's precompute_coeffs: taps per output index of the BILINEAR filter
-static int rp_ksize(int in, int out) {
-  double scale = (double)in / out;
-  if (scale < 1.0) scale = 1.0;
-  int c = (int)scale;
-  if ((double)c < scale) ++c;
-  return c * 2 + 1;
-}
-
 // Every refusal that depends on the shape of the record, and the tables, sits in front of the `query` return (what rcv_batch_prep
 // refuses is refused here); the batch operands are checked at launch.
 int rcv_launch_rgb_prep(const rcv_handle* h, const rcv_op* op, hipStream_t s, OpQuery* query) {
@@ -487,32 +325,21 @@ int rcv_launch_rgb_prep(const rcv_handle* h, const rcv_op* op, hipStream_t s, Op
     query->n_part = 0; query->n_split = 0; query->part_bytes = 0;
     snprintf(query->label, sizeof(query->label), indexed ? "rgb_prep_idx" : "rgb_prep");
   }
-  RCV_CHECK_ARG(B >= 1 && H >= 1 && W >= 1 && Hs >= 1 && Ws >= 1, "rgb prep: B %d, source %d x %d, output %d x %d: every size must be >= 1", B, Hs, Ws,
-                H, W);
-  RCV_CHECK_ARG(nsrc >= 1, "rgb prep: a store of %d images (i[STRIDE]): there must be at least 1", nsrc);
-  if (indexed)
-    RCV_CHECK_ARG(op->i[RCV_I_INMODE] == 4 || op->i[RCV_I_INMODE] == 8, "rgb prep: index element size %d unsupported (4 = int32, 8 = int64)",
-                  op->i[RCV_I_INMODE]);
-  RCV_CHECK_ARG((long long)Hs <= 8LL * H && (long long)Ws <= 8LL * W,
-                "rgb prep: %d x %d -> %d x %d shrinks an axis by more than 8 (the kernel is built for at most %d taps)", Hs, Ws, H, W, RP_MAXK);
+  if (const int e = pil_check_record("rgb prep", "STRIDE", B, nsrc, Hs, Ws, H, W, kx, ky, indexed, op->i[RCV_I_INMODE], op->p[RCV_P_IN_AUX],
+                                     op->p[RCV_P_EPI_AUX]))
+    return e;
   RCV_CHECK_ARG(lab_bytes == 0 || lab_bytes == 1 || lab_bytes == 4,
                 "rgb prep: label element size %d unsupported (1 = uint8, 4 = int32, 0 = no labels)", lab_bytes);
-  RCV_CHECK_ARG(kx == rp_ksize(Ws, W) && ky == rp_ksize(Hs, H), "rgb prep: %d / %d taps per column / row given, %d -> %d and %d -> %d take %d / %d", kx,
-                ky, Ws, W, Hs, H, rp_ksize(Ws, W), rp_ksize(Hs, H));
   RCV_CHECK_ARG((train == 0 || train == 1) && mask >= 0 && mask <= 15 && (stats == 0 || stats == 1),
                 "rgb prep: train %d / maskLabel flags %d / statistics %d out of range", train, mask, stats);
-  const int tiles_x = ceil_div(W, RP_TC), tiles_y = ceil_div(H, RP_TR);
-  RCV_CHECK_ARG((double)nsrc * Hs * Ws < 2147483647.0 && (double)B * H * W < 2147483647.0 && (double)B * tiles_x * tiles_y < 2147483647.0,
-                "rgb prep: %d images of %d x %d -> %d x %d: more than 2^31 pixels", nsrc > B ? nsrc : B, Hs, Ws, H, W);
   if (with_labels)
     RCV_CHECK_ARG(op->p[RCV_P_X1] && op->p[RCV_P_X2] && op->p[RCV_P_X3] && op->p[RCV_P_X4],
                   "rgb prep: null table (frame taps of x / y, label index of x / y)");
   else
     RCV_CHECK_ARG(op->p[RCV_P_X1] && op->p[RCV_P_X2], "rgb prep: null table (frame taps of x / y)");
-  // the index and its counter live for an epoch, as the tables do: a plan without them has nothing to gather by
-  if (indexed) RCV_CHECK_ARG(op->p[RCV_P_IN_AUX] && op->p[RCV_P_EPI_AUX], "rgb prep: null index or null bad-index counter");
+  const int tiles_x = ceil_div(W, PIL_TC), tiles_y = ceil_div(H, PIL_TR);
   const bool ident = H == Hs && W == Ws;
-  const int wpi = ident ? ceil_div(H * W, RP_IDENT_PIX) : tiles_x * tiles_y;
+  const int wpi = ident ? ceil_div(H * W, PIL_IDENT_PIX) : tiles_x * tiles_y;
   RCV_CHECK_ARG((double)B * wpi < 2147483647.0, "rgb prep: grid too large");
   const bool two = train && stats;
   const int n_part = two ? B * wpi : 0;
@@ -546,11 +373,8 @@ int rcv_launch_rgb_prep(const rcv_handle* h, const rcv_op* op, hipStream_t s, Op
     RCV_HIP(hipGetLastError());
     return RCV_OK;
   }
-  const double scale_y = (double)Hs / H, support_y = scale_y < 1.0 ? 1.0 : scale_y;
-  const double span = (RP_TR - 1) * scale_y + 2.0 * support_y;
-  a.rows_cap = (int)span + ((double)(int)span < span ? 1 : 0) + 2;
-  if (a.rows_cap > RP_ROWS_MAX) a.rows_cap = RP_ROWS_MAX;
-  const bool stage = kx >= RP_STAGE_MIN_TAPS;
+  a.rows_cap = pil_rows_cap(Hs, H);
+  const bool stage = pil_stage(kx);
   void (*stat_kernel)(RpArgs) = stage ? rgb_prep_kernel<true, true, RP_PLAIN> : rgb_prep_kernel<true, false, RP_PLAIN>;
   void (*main_kernel)(RpArgs) = stage ? rgb_prep_kernel<false, true, RP_PLAIN> : rgb_prep_kernel<false, false, RP_PLAIN>;
   if (indexed) {
@@ -580,7 +404,7 @@ __global__ __launch_bounds__(256) void lp_pair_prep_kernel(RpArgs a, int bpp) {
   const int pr = blockIdx.x / bpp, blk = blockIdx.x % bpp;
   const int npix = a.H * a.W;
   const int start = blk * RP_PAIR_PIX, end = start + min(RP_PAIR_PIX, npix - start);
-  const int sa = rp_source(a, (size_t)2 * pr), sb = rp_source(a, (size_t)2 * pr + 1);
+  const int sa = pil_source(a, (size_t)2 * pr), sb = pil_source(a, (size_t)2 * pr + 1);
   float* out0 = a.imgs + (size_t)2 * pr * npix * 8;
   float* out1 = out0 + (size_t)npix * 8;
   int64_t* tgt0 = a.tgt + (size_t)2 * pr * npix;
@@ -609,10 +433,10 @@ __global__ __launch_bounds__(256) void lp_pair_prep_kernel(RpArgs a, int bpp) {
     int ra = qa[0], ga = qa[1], ba = qa[2], rb = qb[0], gb = qb[1], bb = qb[2];
     rp_ops(j, j.n_ops, ma, ra, ga, ba);
     rp_ops(j, j.n_ops, mb, rb, gb, bb);
-    const float ya = rp_ynorm(rp_y(s_c[ra], s_c[ga], s_c[ba])), yb = rp_ynorm(rp_y(s_c[rb], s_c[gb], s_c[bb]));
-    const size_t la_i = (size_t)sa * npix + p, lb_i = (size_t)sb * npix + p;
-    const int la = a.lab_bytes == 1 ? (int)((const uint8_t*)a.labels)[la_i] : ((const int32_t*)a.labels)[la_i];
-    const int lb = a.lab_bytes == 1 ? (int)((const uint8_t*)a.labels)[lb_i] : ((const int32_t*)a.labels)[lb_i];
+    float ya, yb, uv0, uv1;                        // Y only: U and V are dropped
+    pil_yuv_norm(s_c[ra], s_c[ga], s_c[ba], ya, uv0, uv1);
+    pil_yuv_norm(s_c[rb], s_c[gb], s_c[bb], yb, uv0, uv1);
+    const int la = pil_label_at(a.labels, a.lab_bytes, (size_t)sa * npix + p), lb = pil_label_at(a.labels, a.lab_bytes, (size_t)sb * npix + p);
     const int y = p / a.W, x = p - y * a.W;
     const int xo = j.hflip ? a.W - 1 - x : x, yo = j.vflip ? a.H - 1 - y : y;
     const size_t o = (size_t)yo * a.W + xo;
@@ -651,7 +475,7 @@ int rcv_launch_lp_pair_prep(const rcv_handle* h, const rcv_op* op, hipStream_t s
   RCV_CHECK_ARG((double)nsrc * H * W < 2147483647.0 && (double)B * 2.0 * H * W * 8.0 < 2147483647.0,
                 "lp pair prep: a store of %d images, %d pairs of %d x %d: more than 2^31 pixels (or output floats)", nsrc, B, H, W);
   RCV_CHECK_ARG(op->p[RCV_P_IN_AUX] && op->p[RCV_P_EPI_AUX], "lp pair prep: null index or null bad-index counter");
-  const int wpi = ceil_div(H * W, RP_IDENT_PIX), bpp = ceil_div(H * W, RP_PAIR_PIX);
+  const int wpi = ceil_div(H * W, PIL_IDENT_PIX), bpp = ceil_div(H * W, RP_PAIR_PIX);
   RCV_CHECK_ARG((double)B * 2.0 * wpi < 2147483647.0 && (double)B * bpp < 2147483647.0, "lp pair prep: grid too large");
   const bool two = train && stats;
   const int n_part = two ? 2 * B * wpi : 0;

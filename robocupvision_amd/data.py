@@ -159,6 +159,11 @@ def _device_norm(finetune, dev):
 _bad_counters = {}    # device -> int32 [1] on the device: images whose index fell outside the store (prepare_batch(index=) without bad_index=)
 
 
+def _handle(dev):
+    """The library handle of the HIP device ``dev`` (a ``torch.device``; without an index: the current one)."""
+    return L.handle(dev.index if dev.index is not None else torch.cuda.current_device())
+
+
 def prepare_batch(frames, labels, img_size=(120, 160), finetune=False, train=True, params=None, no_ball=False, no_robot=False,
                   no_goal=False, no_line=False, index=None, bad_index=None):
     """``frames`` uint8 [B,Hs,Ws,3] (decoded RGB) and ``labels`` uint8 or int32 [B,Hs,Ws], both on the HIP device -> ``(imgs, targets)``:
@@ -198,17 +203,9 @@ def prepare_batch(frames, labels, img_size=(120, 160), finetune=False, train=Tru
     dev = frames.device
     N = B
     if index is not None:
-        if not torch.is_tensor(index) or index.dtype not in (torch.int32, torch.int64) or index.dim() != 1 or index.shape[0] < 1:
-            raise TypeError("prepare_batch: index must be a non-empty int32 or int64 [B] tensor")
-        if index.device != dev or not index.is_contiguous():
-            raise ValueError("prepare_batch: index must be contiguous and on the device of the store (%s; got %s)" % (dev, index.device))
+        _check_index("prepare_batch", index, 1)
+        bad_index = _index_args("prepare_batch", index, bad_index, dev, 1)
         B = int(index.shape[0])
-        if bad_index is None:
-            bad_index = _bad_counters.get(str(dev))
-            if bad_index is None:
-                bad_index = _bad_counters[str(dev)] = torch.zeros(1, dtype=torch.int32, device=dev)
-        elif not torch.is_tensor(bad_index) or bad_index.dtype != torch.int32 or bad_index.numel() < 1 or bad_index.device != dev:
-            raise TypeError("prepare_batch: bad_index must be an int32 tensor on the device of the store")
     if train:
         if params is None:
             raise ValueError("prepare_batch: train=True needs params (draw_jitter(B))")
@@ -220,7 +217,7 @@ def prepare_batch(frames, labels, img_size=(120, 160), finetune=False, train=Tru
     imgs = torch.empty(B, 3, H, W, dtype=torch.float32, device=dev)
     targets = torch.empty(B, H, W, dtype=torch.int64, device=dev)
     mask = (1 if no_ball else 0) | (2 if no_robot else 0) | (4 if no_goal else 0) | (8 if no_line else 0)
-    h = L.handle(dev.index if dev.index is not None else torch.cuda.current_device())
+    h = _handle(dev)
     if index is not None:
         L.check(L.load().rcv_batch_prep_indexed(h, frames.data_ptr(), labels.data_ptr(), labels.element_size(), N, index.data_ptr(),
                                                 index.element_size(), B, Hs, Ws, H, W, fx.data_ptr(), kx, fy.data_ptr(), ky, lx.data_ptr(),
@@ -261,7 +258,7 @@ def prepare_frames(frames, img_size=(120, 160), finetune=False):
     fx, kx, fy, ky, _, _ = _device_tables(Hs, Ws, H, W, dev)
     norm = _device_norm(finetune, dev)
     imgs = torch.empty(B, 3, H, W, dtype=torch.float32, device=dev)
-    h = L.handle(dev.index if dev.index is not None else torch.cuda.current_device())
+    h = _handle(dev)
     L.check(L.load().rcv_frame_prep(h, frames.data_ptr(), B, Hs, Ws, H, W, fx.data_ptr(), kx, fy.data_ptr(), ky, norm.data_ptr(),
                                     imgs.data_ptr(), torch.cuda.current_stream(dev).cuda_stream), "rcv_frame_prep")
     return imgs
@@ -303,7 +300,7 @@ def resize_u8(frames, labels=None, img_size=(120, 160), label_dtype=torch.uint8)
     fx, kx, fy, ky, lx, ly = _device_tables(Hs, Ws, H, W, dev)
     out = torch.empty(B, H, W, 3, dtype=torch.uint8, device=dev)
     lab_out = None if labels is None else torch.empty(B, H, W, dtype=label_dtype, device=dev)
-    h = L.handle(dev.index if dev.index is not None else torch.cuda.current_device())
+    h = _handle(dev)
     L.check(L.load().rcv_resize_u8(h, frames.data_ptr(), None if labels is None else labels.data_ptr(),
                                    0 if labels is None else labels.element_size(), B, Hs, Ws, H, W, fx.data_ptr(), kx, fy.data_ptr(), ky,
                                    lx.data_ptr(), ly.data_ptr(), out.data_ptr(), None if lab_out is None else lab_out.data_ptr(),
@@ -475,7 +472,7 @@ def prepare_rgb_batch(frames, labels=None, scale=4, train=True, params=None, no_
     imgs = torch.empty(B, 3, H, W, dtype=torch.float32, device=dev)
     targets = None if labels is None else torch.empty(B, H, W, dtype=torch.int64, device=dev)
     mask = (1 if no_ball else 0) | (2 if no_robot else 0) | (4 if no_goal else 0) | (8 if no_line else 0)
-    h = L.handle(dev.index if dev.index is not None else torch.cuda.current_device())
+    h = _handle(dev)
     lab_bytes = 0 if labels is None else labels.element_size()
     if index is not None:
         op = L.make_op(L.OP_RGB_PREP_IDX, n=B, stride=N, inmode=index.element_size(), h=Hs, w=Ws, ho=H, wo=W, cin=kx, cout=ky, inmode2=lab_bytes,
@@ -610,7 +607,7 @@ def prepare_lp_pairs(frames, labels, pairs, train=True, params=None, bad_index=N
         params = params.to(dev).contiguous()
     inputs = torch.empty(2 * B, H, W, 8, dtype=torch.float32, device=dev)
     targets = torch.empty(2 * B, H, W, dtype=torch.int64, device=dev)
-    h = L.handle(dev.index if dev.index is not None else torch.cuda.current_device())
+    h = _handle(dev)
     op = L.make_op(L.OP_LP_PAIR_PREP, n=B, stride=N, h=H, w=W, ho=H, wo=W, cout=num_class, inmode2=labels.element_size(),
                    inmode=pairs.element_size(), aux0=1 if train else 0, count=stats, p_in_aux=pairs.data_ptr(), p_epi_aux=bad_index.data_ptr())
     need = L.op_workspace(h, op)
