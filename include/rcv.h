@@ -311,7 +311,7 @@ enum {
                              * features and for logits the rows are bit for bit those RCV_OP_CE_FWD forms from the logits RCV_OP_CLS_FWD /
                              * RCV_OP_NHWC_TO_NCHW write (same grid, pixel -> thread mapping and summation order); with 16 channels four
                              * lanes share a pixel and the rows are sums over other pixel sets (the loss agrees to rounding)          */
-  RCV_OP_VALID_FOLD = 61     /* folds one batch into the running validation state and clears the counts it read (rcv_valid_fold; one
+  RCV_OP_VALID_FOLD = 61,    /* folds one batch into the running validation state and clears the counts it read (rcv_valid_fold; one
                              * workgroup).  p[IN] = counts int32[N][C][C] of RCV_OP_CLS_VALID (zero afterwards); the batch loss: p[IN2] =
                              * partial rows with i[NPART] > 0, summed in RCV_OP_CE_FWD's finalising order to the fp32 loss, OR p[X0] = a
                              * device float with i[NPART] = 0 (exactly one of the two, checked when planned); i[N], i[H], i[W], i[COUT] = C;
@@ -319,6 +319,30 @@ enum {
                              * [2] += N (images), [3] += N*H*W (pixels), [4 + c] = iou_sum[c]: one thread per class adds, image by image in
                              * index order, inter / union with inter = n[c][c], union = sum_l n[c][l] + sum_p n[p][c] - inter, 1.0 where
                              * union is 0 (train.py:148-153); [12 + 8 * pred + label] += sum over the images of n[pred][label]        */
+  RCV_OP_PW = 62,            /* pointwise (1x1) convolution between feature maps (rcv_conv_pw; csrc/conv_pw.hip; model.py:345 ConvSep.conv_1x1,
+                             * model.py:366 trConvSep.conv): out[n][p][co] = sum_ci load(in)[n][p][ci] * W[co][ci], NHWC, over the N*H*W pixels
+                             * (any count: the tail is guarded).  i[CIN] / i[COUT] = channels of p[IN] / p[OUT], multiples of 8 in 8..128;
+                             * p[W] = the PARAMETER itself, [COUT][CIN] -- or, with RCV_F_TRANSPOSED_SRC, [CIN][COUT]: the data gradient of the
+                             * layer whose parameter it is (the same product with the filter transposed); nothing is packed.  p[X0] = a
+                             * per-output-channel factor of the filter or NULL (the inference BatchNorm fold).  i[INMODE] PLAIN / AFFINE /
+                             * AFFINE_RELU / GRAD_ENC / GRAD_DEC with p[IN_C], p[IN_AUX]; RCV_F_BIAS / _RELU / _RESID and the statistics rows
+                             * (i[STATS], p[EPI_AUX], p[EPI_C], p[PART]) exactly as RCV_OP_CONV; one partial row per pixel tile, every row
+                             * written.  i[STRIDE], i[DIL], i[HO], i[WO] are not looked at                                                */
+  RCV_OP_PW_WGRAD = 63,      /* its filter gradient (rcv_wgrad_pw), split over pixels: dW[co][ci] = sum_p load(dy)[p][co] * load(x)[p][ci].
+                             * p[IN] = x (i[CIN] channels, i[INMODE] PLAIN / AFFINE / AFFINE_RELU, p[IN_C]), p[IN2] = dy (i[COUT] channels,
+                             * i[INMODE2] PLAIN / GRAD_ENC / GRAD_DEC, p[IN2_AUX], p[IN2_C]); p[PART] = float[i[NSPLIT]][COUT][CIN]
+                             * (i[NSPLIT] filled by rcv_op_workspace): every row is written whole, each element once; no atomics.  i[AUX0] =
+                             * 16x16 filter blocks per wave at most (4 or 8; 0 = the library's default, 4): speed only                    */
+  RCV_OP_PW_WGRAD_REDUCE = 64, /* fixed-order sum (row 0, 1, ...; float64, rounded once) of those rows -> p[OUT] = dW [COUT][CIN]; i[CIN],
+                             * i[COUT], i[NSPLIT], p[PART]                                                                              */
+  RCV_OP_CROSS_PACK = 65,    /* two 1-D filters -> one dense 3x3 filter in parameter layout with a cross of non-zero taps, which the 3x3
+                             * records then read like any parameter (csrc/conv_pw.hip).  p[OUT] = dense float[D0][D1][3][3], D0 = i[COUT],
+                             * D1 = i[CIN]; i[AUX0] = 0: cat(conv_nx1(x), conv_1xn(x)) (model.py:342-349), p[IN] = [D0/2][D1][3][1] in the
+                             * centre column of rows < D0/2, p[IN2] = [D0/2][D1][1][3] in the centre row of the others; i[AUX0] = 1:
+                             * trconv1x3(x) + trconv3x1(x) (model.py:367-376), p[IN] = [D0][D1][1][3] in the centre row, p[IN2] =
+                             * [D0][D1][3][1] in the centre column, the centre tap their sum.  Every element of the dense filter is written */
+  RCV_OP_CROSS_GRAD = 66     /* the gather that undoes it on a gradient: p[IN] = dense gradient float[D0][D1][3][3], p[OUT] / p[X0] = the
+                             * gradients of the first / second 1-D filter; with i[AUX0] = 1 the centre tap's gradient goes to both        */
 };
 
 /* i[RCV_I_AUX0] of RCV_OP_PRUNE: how the threshold of a tensor is chosen */
@@ -545,6 +569,11 @@ int rcv_wgrad3x3(rcv_handle* h, const rcv_op* op, void* stream);
 int rcv_conv5x5(rcv_handle* h, const rcv_op* op, void* stream);
 /* its filter and bias gradient (RCV_OP_WGRAD5; aten::convolution_backward of model.py:256-267, model.py:403-414).           */
 int rcv_wgrad5x5(rcv_handle* h, const rcv_op* op, void* stream);
+/* nn.Conv2d(k=1, bias=False) between feature maps (model.py:345 ConvSep.conv_1x1, model.py:366 trConvSep.conv): forward, and with
+ * RCV_F_TRANSPOSED_SRC the data gradient (RCV_OP_PW).                                                                       */
+int rcv_conv_pw(rcv_handle* h, const rcv_op* op, void* stream);
+/* its filter gradient's partial rows (RCV_OP_PW_WGRAD; RCV_OP_PW_WGRAD_REDUCE sums them).                                    */
+int rcv_wgrad_pw(rcv_handle* h, const rcv_op* op, void* stream);
 
 /* nn.BatchNorm2d train-mode statistics -> normalisation constants (model.py:113,116,189,192).   *
  *   part [n_part][2][C] -> scale,shift (float[5][C] slot layout c0,c1), mean, istd, running.    */

@@ -16,6 +16,10 @@ def __getattr__(name):
     if name == "labelprop_next":
         from .model import labelprop_next
         return labelprop_next
+    # the FCN of the reference's shipped segmentation checkpoints, its blocks and the separable blocks (model.py:84-90, 144-164, 235-254, 311-377)
+    if name in ("FCN", "DownSamplerThick", "ConvPoolDouble", "View", "ConvSep", "trConvSep"):
+        from . import model
+        return getattr(model, name)
     # robocupvision_amd.data / prepare_batch / draw_jitter / SSYUVDataset: batches prepared on the device (data.py)
     if name == "data":
         import importlib

@@ -40,6 +40,8 @@ OP_LP_PAIR_PREP = 54        # both frames of a LabelProp pair from the store -> 
 OP_CONV5, OP_WGRAD5, OP_WGRAD5_REDUCE, OP_PACK5 = 55, 56, 57, 58      # the 5x5 classifier convolution family (rcv.h RCV_OP_CONV5 ..., csrc/conv5.hip)
 OP_LP_INPUT = 59            # LabelProp's input from a prediction of the previous frame: class map or logits as the prior (rcv.h RCV_OP_LP_INPUT, csrc/lp_input.hip)
 OP_CLS_VALID, OP_VALID_FOLD = 60, 61      # the validation tail: loss rows, class map and per-image confusion counts from the logits in registers; its fold into the running state (rcv.h, csrc/cls_valid.hip)
+OP_PW, OP_PW_WGRAD, OP_PW_WGRAD_REDUCE = 62, 63, 64      # pointwise (1x1) convolution between feature maps: forward / data gradient, filter gradient, its reduction (rcv.h, csrc/conv_pw.hip)
+OP_CROSS_PACK, OP_CROSS_GRAD = 65, 66     # two 1-D filters <-> one dense 3x3 filter with a cross of taps (ConvSep / trConvSep; rcv.h, csrc/conv_pw.hip)
 VALID_STATE = 76            # doubles of the state OP_VALID_FOLD keeps: loss sum, batches, images, pixels, iou_sum[8], conf[8][8]
 LP_PRIOR_U8, LP_PRIOR_LOGITS, LP_PRIOR_I64 = 1, 4, 8      # i[INMODE] of OP_LP_INPUT: the prior's form
 PRUNE_MAX_RATIO, PRUNE_STD_SEARCH, PRUNE_SMALLEST_K = range(3)      # i[AUX0] of OP_PRUNE: pruneModelNew / pruneModel / pruneModel2
@@ -89,7 +91,7 @@ EXPORTS = [
     "rcv_sgd_step_pruned", "rcv_prune_check", "rcv_prune", "rcv_find_objects", "rcv_rgb_prep",
     "rcv_farneback_flow", "rcv_update_labels", "rcv_object_patches", "rcv_resize_u8", "rcv_batch_prep_indexed",
     "rcv_rgb_prep_indexed", "rcv_lp_pair_prep", "rcv_conv5x5", "rcv_wgrad5x5", "rcv_op_stream_hints", "rcv_set_stream_min_mb",
-    "rcv_lp_input", "rcv_cls_valid", "rcv_valid_fold",
+    "rcv_lp_input", "rcv_cls_valid", "rcv_valid_fold", "rcv_conv_pw", "rcv_wgrad_pw",
 ]
 
 
@@ -166,7 +168,7 @@ def load():
         for name in ("rcv_conv3x3", "rcv_convT3x3s2", "rcv_wgrad3x3", "rcv_bnn_stage_fwd", "rcv_bnn_stage_bwd", "rcv_bnn_head_fwd",
                      "rcv_bnn_head_bwd"):
             getattr(lib, name).argtypes = [C.c_void_p, C.POINTER(RcvOp), C.c_void_p]
-        for name in ("rcv_conv5x5", "rcv_wgrad5x5"):
+        for name in ("rcv_conv5x5", "rcv_wgrad5x5", "rcv_conv_pw", "rcv_wgrad_pw"):
             if hasattr(lib, name):      # (RCV_LIBRARY may name the build of an older revision: scripts/plan_diff.sh, scripts/ab.sh)
                 getattr(lib, name).argtypes = [C.c_void_p, C.POINTER(RcvOp), C.c_void_p]
         if hasattr(lib, "rcv_set_stream_min_mb"):      # (RCV_LIBRARY may name an older build)

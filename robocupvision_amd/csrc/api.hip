@@ -110,6 +110,12 @@ static int dispatch(const rcv_handle* h, const rcv_op* op, hipStream_t s, OpQuer
     case RCV_OP_WGRAD5_REDUCE:
     case RCV_OP_PACK5:
       return rcv_launch_conv5(h, op, s, q);
+    case RCV_OP_PW:
+    case RCV_OP_PW_WGRAD:
+    case RCV_OP_PW_WGRAD_REDUCE:
+    case RCV_OP_CROSS_PACK:
+    case RCV_OP_CROSS_GRAD:
+      return rcv_launch_pw(h, op, s, q);
     case RCV_OP_POOL_CLS_FWD:
     case RCV_OP_POOL_CLS_BWD:
       return rcv_launch_pool_cls(h, op, s, q);
@@ -167,7 +173,7 @@ int rcv_op_workspace(const rcv_handle* h, rcv_op* op, size_t* part_bytes) {
   const int rc = dispatch(h, op, nullptr, &q);
   if (rc) return rc;
   op->i[RCV_I_NPART] = q.n_part;
-  if (op->kind == RCV_OP_WGRAD || op->kind == RCV_OP_WGRAD5) op->i[RCV_I_NSPLIT] = q.n_split;
+  if (op->kind == RCV_OP_WGRAD || op->kind == RCV_OP_WGRAD5 || op->kind == RCV_OP_PW_WGRAD) op->i[RCV_I_NSPLIT] = q.n_split;
   *part_bytes = q.part_bytes;
   return RCV_OK;
 }
@@ -313,6 +319,14 @@ int rcv_conv5x5(rcv_handle* h, const rcv_op* op, void* stream) {
 }
 int rcv_wgrad5x5(rcv_handle* h, const rcv_op* op, void* stream) {
   RCV_CHECK_ARG(op && op->kind == RCV_OP_WGRAD5, "rcv_wgrad5x5: record kind must be RCV_OP_WGRAD5");
+  return rcv_run(h, op, 1, stream);
+}
+int rcv_conv_pw(rcv_handle* h, const rcv_op* op, void* stream) {
+  RCV_CHECK_ARG(op && op->kind == RCV_OP_PW, "rcv_conv_pw: record kind must be RCV_OP_PW");
+  return rcv_run(h, op, 1, stream);
+}
+int rcv_wgrad_pw(rcv_handle* h, const rcv_op* op, void* stream) {
+  RCV_CHECK_ARG(op && op->kind == RCV_OP_PW_WGRAD, "rcv_wgrad_pw: record kind must be RCV_OP_PW_WGRAD");
   return rcv_run(h, op, 1, stream);
 }
 

@@ -196,6 +196,7 @@ int rcv_launch_conv(const rcv_handle* h, const rcv_op* op, hipStream_t s, OpQuer
 int rcv_launch_wgrad(const rcv_handle* h, const rcv_op* op, hipStream_t s, OpQuery* query);
 int rcv_filter_layout(const rcv_handle* h, const rcv_op* op, int force);     // rcv_op_filter_layout (conv_dispatch.hip)
 int rcv_launch_conv5(const rcv_handle* h, const rcv_op* op, hipStream_t s, OpQuery* query);     // the 5x5 classifier family (conv5.hip)
+int rcv_launch_pw(const rcv_handle* h, const rcv_op* op, hipStream_t s, OpQuery* query);        // the pointwise family and the cross filters (conv_pw.hip)
 int rcv_launch_small(const rcv_handle* h, const rcv_op* op, hipStream_t s, OpQuery* query);
 int rcv_launch_pool_cls(const rcv_handle* h, const rcv_op* op, hipStream_t s, OpQuery* query);
 int rcv_launch_objdet(const rcv_handle* h, const rcv_op* op, hipStream_t s, OpQuery* query);

@@ -256,11 +256,12 @@ class _Lowering:
                 raise L.RcvError("all graph inputs must share the batch size")
             v.input_index = k
             self.in_vals.append(v)
-        self.nodes = [_Node(d, i) for i, d in enumerate(g["nodes"])]
+        self.nodes = [_Node(dict(d) if d.get("cross") is not None else d, i) for i, d in enumerate(g["nodes"])]
+        self.tail: List[L.RcvOp] = []               # backward ops behind every node's: the gathers of the cross filters' gradients
 
         self.jobs: List[L.RcvPackJob] = []          # weight packing table (all layers, one launch per forward)
         self.pre: List[L.RcvOp] = []                # eval mode: running statistics -> constants, ahead of everything else
-        self.pack5: List[L.RcvOp] = []              # RCV_OP_PACK5 records of a 5x5 classifier (head of the forward list, behind `pre`)
+        self.head_ops: List[L.RcvOp] = []           # parameter-only records of the forward list's head, behind `pre` and ahead of the pack launch: RCV_OP_PACK5 of a 5x5 classifier, RCV_OP_CROSS_PACK of a cross filter (which the pack launch reads)
         self.bn_finalize_flags = L.F_TRAINING if training else 0
         self.batch_at: Dict[int, int] = {}          # index of a folded reduction -> index of the launch that now carries it
         self._late: List[tuple] = []                # side-stream ops of the node being lowered, emitted behind its data-gradient op
@@ -279,7 +280,8 @@ class _Lowering:
         return v.buf.data_ptr()
 
     def add_pack(self, param, D0, D1, rows_from_d1, flip, merged=False, wino=0, scale: Optional[torch.Tensor] = None, min_rows: int = 0):
-        """wino: the layout rcv_op_filter_layout asked for (0 plain, 2 Winograd, 3 split-bf16: three bf16 per value, rows padded to 32).
+        """(scripts/bench_fcn.py::pack3 restates the sizes below for the centre-tap records it times: change them together.)
+        wino: the layout rcv_op_filter_layout asked for (0 plain, 2 Winograd, 3 split-bf16: three bf16 per value, rows padded to 32).
         min_rows: the contraction channels of the record that reads the filter where they exceed the parameter's (zero rows between)."""
         wino = int(wino)
         merged = bool(merged) or wino == 4
@@ -366,6 +368,8 @@ class _Lowering:
 
     def fwd_conv(self, node: _Node):
         d = node.d
+        if d.get("cross") is not None:
+            self.cross_weight(node)
         src = self.ref(d["src"])
         w, b, bn = d["weight"], d.get("bias"), d.get("bn")
         Cout, Cin = w.shape[0], w.shape[1]
@@ -404,6 +408,92 @@ class _Lowering:
             self.fwd.append(op)
             node.out = Value("plain", r, Cout, Ho, Wo, None, node)
 
+    def cross_weight(self, node: _Node):
+        """A node whose 3x3 filter is the cross of two 1-D filters (d["cross"] = (first, second, form); rcv.h RCV_OP_CROSS_PACK): the
+        dense filter is a plan-owned tensor in parameter layout, written at the head of every forward list ahead of the pack
+        launch; the conv / up lowering then reads it as it reads a parameter."""
+        a, b, form = node.d["cross"]
+        if form == 0:      # cat(conv_nx1(x), conv_1xn(x)): [planes/2][in][3][1] and [planes/2][in][1][3]
+            if tuple(a.shape[2:]) != (3, 1) or tuple(b.shape[2:]) != (1, 3) or a.shape[:2] != b.shape[:2]:
+                raise L.RcvError("cross node %d: a concatenated pair is [C/2][Cin][3][1] and [C/2][Cin][1][3] (got %s, %s)"
+                                 % (node.idx, tuple(a.shape), tuple(b.shape)))
+            D0, D1 = 2 * a.shape[0], a.shape[1]
+        else:              # trconv1x3(x) + trconv3x1(x): [in][out][1][3] and [in][out][3][1]
+            if tuple(a.shape[2:]) != (1, 3) or tuple(b.shape[2:]) != (3, 1) or a.shape[:2] != b.shape[:2]:
+                raise L.RcvError("cross node %d: a summed transposed pair is [Cin][C][1][3] and [Cin][C][3][1] (got %s, %s)"
+                                 % (node.idx, tuple(a.shape), tuple(b.shape)))
+            D0, D1 = a.shape[0], a.shape[1]
+        dense = self.eng._zeros(self.plan, D0, D1, 3, 3)
+        self.head_ops.append(L.make_op(L.OP_CROSS_PACK, 0, cout=D0, cin=D1, aux0=form, p_in=a.data_ptr(), p_in2=b.data_ptr(),
+                                    p_out=dense.data_ptr()))
+        node.d["weight"] = dense
+        node.t["cross"] = (a, b, form, D0, D1)
+
+    def wgrad_ptr(self, node: _Node, w) -> int:
+        """Where the filter-gradient reduction of `node` writes: the parameter's slice of the flat gradient, or for a cross filter a
+        dense scratch gradient that an RCV_OP_CROSS_GRAD record at the end of the backward list gathers into the two parameters'."""
+        if "cross" not in node.t:
+            return self.fl.grad_ptr(w)
+        a, b, form, D0, D1 = node.t["cross"]
+        dense = self.eng._zeros(self.plan, D0, D1, 3, 3)
+        self.tail.append(L.make_op(L.OP_CROSS_GRAD, 0, cout=D0, cin=D1, aux0=form, p_in=dense.data_ptr(), p_out=self.fl.grad_ptr(a),
+                                   p_x0=self.fl.grad_ptr(b)))
+        return dense.data_ptr()
+
+    def fwd_pw(self, node: _Node):
+        """relu(bn(conv1x1(x))), no bias (model.py:345-350, 366-375): RCV_OP_PW reads the parameter itself; in a folded inference plan
+        the BatchNorm scale multiplies the filter while it is staged and the shift is the bias."""
+        d = node.d
+        src = self.ref(d["src"])
+        w, bn = d["weight"], d["bn"]
+        Cout, Cin = w.shape[0], w.shape[1]
+        if tuple(w.shape[2:]) != (1, 1) or bn is None or _conv_order(d) != "bn_relu" or d.get("bias") is not None:
+            raise L.RcvError("pw node %d: built for a bias-free 1x1 conv followed by BatchNorm and ReLU" % node.idx)
+        if Cin != src.C:
+            raise L.RcvError("pw node %d: input has %d channels, weight expects %d" % (node.idx, src.C, Cin))
+        if src.kind not in ("plain", "affine", "affine_relu"):
+            raise L.RcvError("pw node %d: input kind '%s' unsupported (an NHWC tensor)" % (node.idx, src.kind))
+        r = self.eng._alloc(self.plan, self.N, src.H, src.W, Cout)
+        self.bn_tensors(node, Cout)
+        cst = node.t["consts"]
+        op = L.make_op(L.OP_PW, 0, n=self.N, h=src.H, w=src.W, cin=Cin, cout=Cout, ho=src.H, wo=src.W, stride=1, dil=1,
+                       inmode=src.load_mode, p_in_c=_ptr(src.consts), p_w=w.data_ptr(), p_out=r.data_ptr())
+        op.p[L.RCV_P_IN] = self.bind_in(self.fwd, src, L.RCV_P_IN) or None
+        if self.fold:
+            op.flags |= L.F_BIAS | L.F_RELU
+            op.p[L.RCV_P_X0] = cst.data_ptr()                      # row 0 = scale
+            op.p[L.RCV_P_BIAS] = cst.data_ptr() + 4 * 3 * Cout     # row 3 = shift (no conv bias)
+            self.emit_bn_forward(node, bn, op, Cout, src.H, src.W)
+            node.out = Value("plain", r, Cout, src.H, src.W, None, node)
+            return
+        self.emit_bn_forward(node, bn, op, Cout, src.H, src.W)
+        node.out = Value("affine_relu", r, Cout, src.H, src.W, cst, node)
+
+    def bwd_pw(self, node: _Node):
+        d = node.d
+        out, src = node.out, self.ref(d["src"])
+        w, bn = d["weight"], d["bn"]
+        Cout, Cin = w.shape[0], w.shape[1]
+        if out.grad is None:
+            raise L.RcvError("pw node %d has no gradient producer" % node.idx)
+        self.emit_bn_backward(node, bn, Cout, out.H, out.W)
+        wop = L.make_op(L.OP_PW_WGRAD, 0, n=self.N, h=src.H, w=src.W, cin=Cin, cout=Cout, inmode=src.load_mode, inmode2=L.LOAD_GRAD_DEC,
+                        p_in_c=_ptr(src.consts), p_in2=out.grad.data_ptr(), p_in2_aux=out.buf.data_ptr(),
+                        p_in2_c=node.t["bconsts"].data_ptr())
+        wop.p[L.RCV_P_IN] = (src.buf.data_ptr() if src.buf is not None else None)
+        self.eng._workspace(self.plan, wop)
+        self.side(wop, (src.input_index, L.RCV_P_IN) if src.input_index is not None else None)
+        self.side(L.make_op(L.OP_PW_WGRAD_REDUCE, 0, cin=Cin, cout=Cout, nsplit=wop.i[L.RCV_I_NSPLIT], p_part=wop.p[L.RCV_P_PART],
+                            p_out=self.fl.grad_ptr(w)))
+        if src.needs_grad:
+            # the same product with the filter transposed: the record reads the forward's parameter as [CIN][COUT]
+            dop = L.make_op(L.OP_PW, L.F_TRANSPOSED_SRC, n=self.N, h=src.H, w=src.W, cin=Cout, cout=Cin, ho=src.H, wo=src.W, stride=1, dil=1,
+                            inmode=L.LOAD_GRAD_DEC, p_in=out.grad.data_ptr(), p_in_aux=out.buf.data_ptr(),
+                            p_in_c=node.t["bconsts"].data_ptr(), p_w=w.data_ptr())
+            self.grad_target(src, dop, src.H, src.W)
+            self.bwd.append(dop)
+        self.flush_side()
+
     def fwd_pool(self, node: _Node):
         d = node.d
         src = self.ref(d["src"])
@@ -421,6 +511,8 @@ class _Lowering:
 
     def fwd_up(self, node: _Node):
         d = node.d
+        if d.get("cross") is not None:
+            self.cross_weight(node)
         src = self.ref(d["src"])
         w, b, bn = d["weight"], d.get("bias"), d["bn"]
         Cin, Cout = w.shape[0], w.shape[1]
@@ -530,7 +622,7 @@ class _Lowering:
         The records join the head of the forward list, next to the pack launch of the 3x3 filters."""
         Cout, Cin = w.shape[0], w.shape[1]
         dst = self.eng._zeros(self.plan, 25 * (CLS3_PAD if flip else Cin) * 16)
-        self.pack5.append(L.make_op(L.OP_PACK5, L.F_FLIP if flip else 0, cin=Cin, cout=Cout, p_in=w.data_ptr(), p_out=dst.data_ptr()))
+        self.head_ops.append(L.make_op(L.OP_PACK5, L.F_FLIP if flip else 0, cin=Cin, cout=Cout, p_in=w.data_ptr(), p_out=dst.data_ptr()))
         return dst
 
     def cls5_conv(self, node: _Node, src: Value, w) -> L.RcvOp:
@@ -699,7 +791,7 @@ class _Lowering:
         if prod is None:
             self.plan.input_grads[v.input_index] = v.grad
             writer_op.i[L.RCV_I_STATS] = L.STATS_NONE
-        elif prod.op == "conv" and prod.d.get("bn") is not None:
+        elif prod.op in ("conv", "pw") and prod.d.get("bn") is not None:
             writer_op.i[L.RCV_I_STATS] = L.STATS_BWD_ENC if _conv_order(prod.d) == "relu_bn" else L.STATS_BWD_DEC
             writer_op.p[L.RCV_P_EPI_AUX] = v.buf.data_ptr()
             writer_op.p[L.RCV_P_EPI_C] = prod.t["consts"].data_ptr()     # row 2 = batch mean
@@ -722,7 +814,8 @@ class _Lowering:
                              p_x4=node.t["mean"].data_ptr(), p_x5=node.t["istd"].data_ptr()))
 
     def node_params(self, nd):
-        ps = [nd.d.get("weight"), nd.d.get("bias")]
+        ps = list(nd.d["cross"][:2]) if nd.d.get("cross") is not None else [nd.d.get("weight")]
+        ps.append(nd.d.get("bias"))
         bn_ = nd.d.get("bn")
         if bn_ is not None:
             ps += [bn_.weight, bn_.bias]
@@ -860,7 +953,7 @@ class _Lowering:
         self.eng._workspace(self.plan, wop)
         self.side(wop, (src.input_index, L.RCV_P_IN2) if src.input_index is not None else None)
         self.side(L.make_op(L.OP_WGRAD_REDUCE, 0, cin=Cout, cout=Cin, nsplit=wop.i[L.RCV_I_NSPLIT],
-                            p_part=wop.p[L.RCV_P_PART], p_out=self.fl.grad_ptr(w)))
+                            p_part=wop.p[L.RCV_P_PART], p_out=self.wgrad_ptr(node, w)))
         if b is not None:   # bias ahead of a BatchNorm: gradient is identically zero
             self.side(L.make_op(L.OP_MEMSET, 0, count=b.numel(), p_out=self.fl.grad_ptr(b)))
         if src.needs_grad:
@@ -921,7 +1014,7 @@ class _Lowering:
         self.eng._workspace(self.plan, wop)
         self.side(wop, (src.input_index, L.RCV_P_IN) if src.input_index is not None else None)
         self.side(L.make_op(L.OP_WGRAD_REDUCE, 0, cin=Cin, cout=Cout, nsplit=wop.i[L.RCV_I_NSPLIT],
-                            p_part=wop.p[L.RCV_P_PART], p_out=self.fl.grad_ptr(w),
+                            p_part=wop.p[L.RCV_P_PART], p_out=self.wgrad_ptr(node, w),
                             p_bias=(self.fl.grad_ptr(b) if bias_grad else 0)))
         if b is not None and not bias_grad:   # bias ahead of a BatchNorm: gradient is identically zero
             self.side(L.make_op(L.OP_MEMSET, 0, count=b.numel(), p_out=self.fl.grad_ptr(b)))
@@ -965,6 +1058,9 @@ class _Lowering:
 
     def finish(self) -> Plan:
         plan, fwd, bwd, fl, training = self.plan, self.fwd, self.bwd, self.fl, self.training
+        # the gathers of the cross filters' gradients read dense gradients that a (possibly batched, hence later) reduction launch
+        # writes: they close the list, on the stream the reductions run on
+        bwd += self.tail
         # ---- batched filter-gradient reductions: the records keep their positions (every index into the list stays valid); all but
         # the last reduction of a group become RCV_OP_NOP, the last one becomes the table-driven launch of the whole group ----
         plan.reduce_outputs = {}               # index of a batched launch -> [(gradient pointer it writes, zero-fill?)] (schedule tests)
@@ -1022,10 +1118,15 @@ class _Lowering:
                 marks.append((end, lo))
             elif marks:
                 marks[-1] = (end, min(marks[-1][1], lo))
+        # a cross filter's parameters are final only behind the last record.  One mark at the end of the list is the simple, safe
+        # answer for the standalone blocks; a NETWORK that embedded a ConvSep / trConvSep would lose the gradient-ready overlap of its
+        # data-parallel exchange with it (every bucket final at the end): such a network wants a gather per bucket instead
+        if self.tail and marks:
+            marks = [(len(bwd), 0)]
         plan.bwd_marks = marks if training else []
 
         # ---- head of the forward list: running statistics -> constants (eval), then the pack launch (whose jobs may scale by them) ----
-        head = list(self.pre) + self.pack5
+        head = list(self.pre) + self.head_ops
         if self.jobs:        # (a graph without 3x3 filters -- a lone 1x1 classifier -- packs nothing)
             table = (L.RcvPackJob * len(self.jobs))(*self.jobs)
             host = torch.frombuffer(bytearray(bytes(table)), dtype=torch.uint8)
@@ -1047,7 +1148,8 @@ class _Lowering:
         # second HIP stream inside rcv_run (measured -4 % step time: their latency-bound phases fill the other kernels' gaps)
         if SIDE_STREAM_WGRAD:
             for op in bwd:
-                if op.kind in (L.OP_WGRAD, L.OP_WGRAD_REDUCE, L.OP_WGRAD_REDUCE_BATCH, L.OP_MEMSET, L.OP_WGRAD5, L.OP_WGRAD5_REDUCE):
+                if op.kind in (L.OP_WGRAD, L.OP_WGRAD_REDUCE, L.OP_WGRAD_REDUCE_BATCH, L.OP_MEMSET, L.OP_WGRAD5, L.OP_WGRAD5_REDUCE,
+                               L.OP_PW_WGRAD, L.OP_PW_WGRAD_REDUCE, L.OP_CROSS_GRAD):
                     op.flags |= L.F_SIDE_STREAM
         plan.fwd = L.OpList(fwd)
         plan.bwd = L.OpList(bwd)
@@ -1068,7 +1170,7 @@ class Engine:
         self.bn_modules = list(bn_modules)
         used = set()
         for d in graph["nodes"]:
-            for q in (d.get("weight"), d.get("bias")):
+            for q in (d.get("weight"), d.get("bias")) + tuple((d.get("cross") or ())[:2]):
                 if q is not None:
                     used.add(id(q))
             if d.get("bn") is not None:
@@ -1335,6 +1437,14 @@ class Engine:
         elif k == L.OP_WGRAD5:
             flops = 2.0 * 25 * cin * cout * px
             nbytes = 4.0 * px * (cin + cout)
+        elif k == L.OP_PW:
+            flops = 2.0 * cin * cout * px
+            nbytes = 4.0 * px * (cin * two(i[L.RCV_I_INMODE]) + cout * (1 + resid + bstats))
+        elif k == L.OP_PW_WGRAD:
+            flops = 2.0 * cin * cout * px
+            nbytes = 4.0 * px * (cin + cout * two(i[L.RCV_I_INMODE2]))
+        elif k == L.OP_PW_WGRAD_REDUCE:
+            nbytes = 4.0 * (i[L.RCV_I_NSPLIT] + 1) * cin * cout
         elif k == L.OP_WGRAD5_REDUCE:
             nbytes = 4.0 * i[L.RCV_I_NSPLIT] * (25 * 8 * 16 + 8) + 4.0 * 25 * cin * cout
         elif k == L.OP_WGRAD_REDUCE:
@@ -1453,8 +1563,9 @@ class Engine:
         mode = {True: "all", False: "off"}.get(mode, mode)
         for k in range(ops.n):
             op = ops.arr[k]
-            if op.kind in (L.OP_WGRAD, L.OP_WGRAD_REDUCE, L.OP_WGRAD_REDUCE_BATCH, L.OP_MEMSET):
-                on = mode == "all" or (mode == "reduce" and op.kind != L.OP_WGRAD)
+            # (the pointwise family's records and the cross filters' gather, which follows the reduction it reads wherever that runs)
+            if op.kind in (L.OP_WGRAD, L.OP_WGRAD_REDUCE, L.OP_WGRAD_REDUCE_BATCH, L.OP_MEMSET, L.OP_PW_WGRAD, L.OP_PW_WGRAD_REDUCE, L.OP_CROSS_GRAD):
+                on = mode == "all" or (mode == "reduce" and op.kind not in (L.OP_WGRAD, L.OP_PW_WGRAD))
                 op.flags = (op.flags | L.F_SIDE_STREAM) if on else (op.flags & ~L.F_SIDE_STREAM)
 
     def _decide_side_stream(self, plan: Plan, ops: L.OpList):

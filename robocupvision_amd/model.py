@@ -25,7 +25,8 @@ from .bnn import BNNL, BNNMC      # the reference's model.py:569-619 (kernels: c
 
 __all__ = ["ROBO_UNet", "CrossEntropyLoss2d", "DiceLoss", "PB_FCN", "PB_FCN_2", "LabelProp", "Conv", "Pool", "LevelDown",
            "labelprop_batch", "labelprop_next", "upSampleTransposeConv", "UltClassifier", "ConvPoolSimple", "ConvPool", "DownSampler", "Classifier", "pruneModelNew",
-           "count_zero_weights", "getParamSize", "BNNL", "BNNMC", "pruneModel", "pruneModel2"]
+           "count_zero_weights", "getParamSize", "BNNL", "BNNMC", "pruneModel", "pruneModel2",
+           "View", "ConvPoolDouble", "DownSamplerThick", "FCN", "ConvSep", "trConvSep"]
 
 
 # ------------------------------------------------------------------------------------------
@@ -1119,6 +1120,201 @@ class PB_FCN(_EngineOwner, nn.Module):
 
     def forward(self, x):
         return _run_engine(self._get_engine(), self.training, self._engine_inputs(x))
+
+
+class View(nn.Module):
+    """x.view(-1, numFeat) (model.py:84-90): a reshape, no kernel; works on any device like the reference's."""
+
+    def __init__(self, numFeat):
+        super().__init__()
+        self.numFeat = numFeat
+
+    def forward(self, x):
+        return x.view(-1, self.numFeat)
+
+
+class ConvPoolDouble(_BlockMixin, nn.Module):
+    """relu(bn(pool(relu(conv2(relu(conv1(x))))))): two dilated 3x3 convs, then a stride-2 3x3 conv as the 'pool' (model.py:144-164)."""
+
+    def __init__(self, inplanes, planes):
+        super().__init__()
+        self.relu = nn.ReLU()
+        self.conv1 = nn.Conv2d(inplanes, planes, kernel_size=3, dilation=2, padding=2, bias=False)
+        self.conv2 = nn.Conv2d(planes, planes, kernel_size=3, dilation=2, padding=2, bias=False)
+        self.pool = nn.Conv2d(planes, planes, kernel_size=3, padding=1, stride=2, bias=False)
+        self.bn = nn.BatchNorm2d(planes)
+
+    def _nodes(self, nodes: list, src):
+        for conv in (self.conv1, self.conv2):
+            nodes.append({"op": "conv", "src": src, "weight": conv.weight, "bias": None, "bn": None, "stride": 1, "dil": 2,
+                          "order": "relu"})
+            src = ("node", len(nodes) - 1)
+        nodes.append({"op": "conv", "src": src, "weight": self.pool.weight, "bias": None, "bn": self.bn,
+                      "stride": 2, "dil": 1, "order": "bn_relu"})
+        return ("node", len(nodes) - 1)
+
+    def _block_graph(self):
+        nodes: list = []
+        out = self._nodes(nodes, ("in", 0))
+        nodes.append({"op": "mat", "src": out})
+        return {"inputs": [{"layout": "nhwc", "requires_grad": True}], "nodes": nodes}
+
+    def forward(self, x):
+        return self._block_forward(x)
+
+
+class DownSamplerThick(nn.Module):
+    """FCN's encoder (model.py:235-254): children and construction order as the reference (state_dict / init parity)."""
+
+    def __init__(self, planes):
+        super().__init__()
+        outPlanes = planes // 2
+        self.conv0 = ConvPoolSimple(3, outPlanes, 3, 1, 2, 2, False)
+        self.conv0_1 = ConvPoolSimple(outPlanes, outPlanes, 3, 1, 2, 2, False)
+        self.conv1 = ConvPoolSimple(outPlanes, outPlanes, 3, 2, 1, 1, False)
+        self.conv2 = ConvPoolDouble(outPlanes, planes)
+        self.conv3 = ConvPoolDouble(planes, planes * 2)
+        self.conv4 = ConvPoolSimple(planes * 2, planes * 4, 3, 1, 2, 2, False)
+        self.conv5 = ConvPoolSimple(planes * 4, planes * 2, 3, 1, 2, 2, False)
+
+    def _nodes(self, nodes: list, src):
+        """model.py:248-254; returns the references of (x3, x2, x1, x0)."""
+        def add(node):
+            nodes.append(node)
+            return ("node", len(nodes) - 1)
+
+        x0 = add(self.conv0_1._node(add(self.conv0._node(src))))
+        x1 = add(self.conv1._node(x0))
+        x2 = self.conv2._nodes(nodes, x1)
+        x3 = self.conv3._nodes(nodes, x2)
+        x3 = add(self.conv5._node(add(self.conv4._node(x3))))
+        return x3, x2, x1, x0
+
+    def forward(self, x):
+        raise L.RcvError("DownSamplerThick is executed as part of FCN's graph; standalone use is not built")
+
+
+class FCN(_EngineOwner, nn.Module):
+    """The oldest segmentation net (model.py:311-330), the one the trained checkpoints shipped with the reference
+    (pth/bestModelSeg1*.pth) load into: DownSamplerThick(32), three transposed-conv decoder blocks with skip adds and a 1x1
+    classifier on 16 channels, five classes.  Training, eval, ``predict`` and ``validate`` as PB_FCN."""
+
+    def __init__(self):
+        super().__init__()
+        planes = 32
+        self.FCN = DownSamplerThick(32)
+        self.up1 = upSampleTransposeConv(planes * 2, planes)
+        self.up2 = upSampleTransposeConv(planes, planes // 2)
+        self.up3 = upSampleTransposeConv(planes // 2, planes // 2)
+        self.classifier = Classifier(planes // 2, 5, 1)
+
+    # graph of model.py:325-330
+    def _graph(self):
+        nodes: list = []
+        f3, f2, f1, f0 = self.FCN._nodes(nodes, ("in", 0))
+        x = f3
+        for layer, skip in ((self.up1, f2), (self.up2, f1), (self.up3, f0)):
+            nodes.append(layer._node(x, skip))
+            x = ("node", len(nodes) - 1)
+        nodes.append(self.classifier._node(x))
+        return {"inputs": [{"layout": "nchw"}], "nodes": nodes}
+
+    def _get_engine(self) -> Engine:
+        eng = self.__dict__.get("_engine")
+        if eng is None:
+            eng = Engine(self._graph(), list(self.parameters()), _bn_modules(self))
+            self.__dict__["_engine"] = eng
+        return eng
+
+    def _engine_inputs(self, x):
+        if x.dim() != 4 or x.shape[1] != 3:
+            raise ValueError("FCN expects float32 [B,3,H,W], got %s" % (tuple(x.shape),))
+        if x.shape[2] % 8 or x.shape[3] % 8:
+            raise ValueError("H and W must be multiples of 8 (got %dx%d)" % (x.shape[2], x.shape[3]))
+        return [x.to(torch.float32).contiguous()]
+
+    def forward(self, x):
+        return _run_engine(self._get_engine(), self.training, self._engine_inputs(x))
+
+
+class ConvSep(_BlockMixin, nn.Module):
+    """relu(bn2(conv_1x1(relu(bn1(cat(conv_nx1(x), conv_1xn(x))))))) (model.py:333-361): the separable stand-in for Conv.  The 1-D
+    pair runs as ONE 3x3 record whose filter is the cross of the two (first half of the channels: centre column, second half: centre
+    row; same stride, dilation and padding); the 1x1 conv is the pointwise family (csrc/conv_pw.hip)."""
+
+    def __init__(self, inplanes, planes, size, stride=1):
+        super().__init__()
+        if size != 3:
+            raise NotImplementedError("only ConvSep(size=3) is built: the 1-D pair is lowered to the 3x3 records (got size=%r)" % (size,))
+        if planes % 2:
+            raise NotImplementedError("ConvSep is built for an even number of planes: each 1-D conv gives planes // 2 of the channels "
+                                      "the 1x1 conv and its BatchNorm expect (got planes=%r)" % (planes,))
+        self.stride = stride
+        self.size = size
+        self.inch = inplanes
+        self.ch = planes
+        dilation = 1 if stride > 1 else 2
+        padding = size // 2 + dilation - 1
+        self.conv_nx1 = nn.Conv2d(inplanes, planes // 2, dilation=dilation, kernel_size=(size, 1), padding=(padding, 0), stride=stride,
+                                  bias=False)
+        self.conv_1xn = nn.Conv2d(inplanes, planes // 2, dilation=dilation, kernel_size=(1, size), padding=(0, padding), stride=stride,
+                                  bias=False)
+        self.bn1 = nn.BatchNorm2d(planes)
+        self.conv_1x1 = nn.Conv2d(planes, planes, kernel_size=1, bias=False)
+        self.bn2 = nn.BatchNorm2d(planes)
+
+    def _nodes(self, nodes: list, src):
+        nodes.append({"op": "conv", "src": src, "cross": (self.conv_nx1.weight, self.conv_1xn.weight, 0), "bias": None, "bn": self.bn1,
+                      "stride": self.stride, "dil": 1 if self.stride > 1 else 2, "order": "bn_relu"})
+        nodes.append({"op": "pw", "src": ("node", len(nodes) - 1), "weight": self.conv_1x1.weight, "bn": self.bn2, "order": "bn_relu"})
+        return ("node", len(nodes) - 1)
+
+    def _block_graph(self):
+        nodes: list = []
+        out = self._nodes(nodes, ("in", 0))
+        nodes.append({"op": "mat", "src": out})
+        return {"inputs": [{"layout": "nhwc", "requires_grad": True}], "nodes": nodes}
+
+    def forward(self, x):
+        return self._block_forward(x)
+
+    def getComp(self, W, H, pruned):
+        W = W // self.stride
+        H = H // self.stride
+        ratio_nx1 = float(self.conv_nx1.weight.nonzero().size(0)) / float(self.conv_nx1.weight.numel()) if pruned else 1
+        ratio_1xn = float(self.conv_1xn.weight.nonzero().size(0)) / float(self.conv_1xn.weight.numel()) if pruned else 1
+        ratio_1x1 = float(self.conv_1x1.weight.nonzero().size(0)) / float(self.conv_1x1.weight.numel()) if pruned else 1
+        return self.size * W * H * self.inch * self.ch * 2 * (ratio_1xn + ratio_nx1) + W * H * self.ch * self.ch * 2 * ratio_1x1 \
+            + W * H * self.ch * 8, W, H
+
+
+class trConvSep(_BlockMixin, nn.Module):
+    """relu(bn2(trconv1x3(y) + trconv3x1(y))), y = relu(bn1(conv(x))) (model.py:363-377): the separable stand-in for
+    upSampleTransposeConv.  The 1x1 conv is the pointwise family; the pair of 1-D transposed convs runs as ONE 3x3 stride-2 transposed
+    record whose filter is the cross of the two, the centre tap their sum."""
+
+    def __init__(self, inplanes, planes):
+        super().__init__()
+        self.conv = nn.Conv2d(inplanes, planes, kernel_size=1, bias=False)
+        self.trconv1x3 = nn.ConvTranspose2d(planes, planes, kernel_size=(1, 3), padding=(0, 1), stride=2, output_padding=1, bias=False)
+        self.trconv3x1 = nn.ConvTranspose2d(planes, planes, kernel_size=(3, 1), padding=(1, 0), stride=2, output_padding=1, bias=False)
+        self.bn1 = nn.BatchNorm2d(planes)
+        self.bn2 = nn.BatchNorm2d(planes)
+
+    def _nodes(self, nodes: list, src):
+        nodes.append({"op": "pw", "src": src, "weight": self.conv.weight, "bn": self.bn1, "order": "bn_relu"})
+        nodes.append({"op": "up", "src": ("node", len(nodes) - 1), "skip": None, "concat": False,
+                      "cross": (self.trconv1x3.weight, self.trconv3x1.weight, 1), "bias": None, "bn": self.bn2})
+        return ("node", len(nodes) - 1)
+
+    def _block_graph(self):
+        nodes: list = []
+        out = self._nodes(nodes, ("in", 0))
+        nodes.append({"op": "mat", "src": out})
+        return {"inputs": [{"layout": "nhwc", "requires_grad": True}], "nodes": nodes}
+
+    def forward(self, x):
+        return self._block_forward(x)
 
 
 class PB_FCN_2(ROBO_UNet):
