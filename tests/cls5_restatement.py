@@ -1,7 +1,7 @@
 """Float64 restatement of the 5x5 classifier records (include/rcv.h RCV_OP_PACK5 / _CONV5 / _WGRAD5 / _WGRAD5_REDUCE; csrc/conv5.hip),
 written from the record descriptions: explicit taps over a zero-padded plane, no convolution routine.  tests/test_cls5_plan.py pins
-every function here to torch.nn.functional.conv2d and its autograd in float64 on the CPU; tests/test_gpu_cls5.py compares the kernels
-with it."""
+every function here to torch.nn.functional.conv2d and its autograd in float64 on the CPU (wgrad5_reduce, the reduction's summation
+order: tests/test_rest.py); tests/test_gpu_cls5.py compares the kernels with it."""
 import torch
 
 TAPS, COLS, CB = 25, 16, 8      # taps, columns of a packed filter, padded class channels (engine.CLS3_PAD)
@@ -67,6 +67,18 @@ def wgrad5(v, g):
         dy, dx = divmod(t, 5)
         dw[:, :, dy, dx] = torch.einsum("nyxo,nyxi->oi", G, p[:, dy:dy + H, dx:dx + W])
     return dw, G.sum((0, 1, 2))
+
+
+def wgrad5_reduce(part, cin, classes):
+    """RCV_OP_WGRAD5_REDUCE in its documented order: part [nsplit][25 * 8 * 16 + 8] fp32, a row = the filter part [tap][class][16
+    columns, the first CIN used] then the bias part [8]; rows 0, 1, ... are added in float64 in that order and the sum is rounded to
+    fp32 once -> dW [classes][CIN][5][5], db [classes]."""
+    u = torch.zeros(part.shape[1], dtype=torch.float64)
+    for s in range(part.shape[0]):
+        u = u + part[s].double()
+    u = u.float()
+    dw = u[:TAPS * CB * COLS].reshape(TAPS, CB, COLS)[:, :classes, :cin].permute(1, 2, 0).reshape(classes, cin, 5, 5).contiguous()
+    return dw, u[TAPS * CB * COLS:TAPS * CB * COLS + classes].clone()
 
 
 def stats_rows(kind, out, e, epi_c):

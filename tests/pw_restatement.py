@@ -1,7 +1,8 @@
 """Float64 restatement of the pointwise (1x1) records and of the cross filters (rcv.h RCV_OP_PW, RCV_OP_PW_WGRAD, RCV_OP_CROSS_PACK,
 RCV_OP_CROSS_GRAD; csrc/conv_pw.hip), written from the record documentation alone: plain tensor arithmetic, no conv call.  The CPU
 tests (tests/test_rest.py) pin it to torch's float64 ``conv2d`` / ``conv_transpose2d``; the GPU tests (tests/test_gpu_pw.py) compare
-the kernels with it.  Activations are NHWC [N,H,W,C]; constants are [5,C] rows c0..c4."""
+the kernels with it.  Activations are NHWC [N,H,W,C]; constants are [5,C] rows c0..c4.  pw_reduce restates the summation ORDER of
+RCV_OP_PW_WGRAD_REDUCE, for a bitwise comparison."""
 import torch
 
 LOAD_PLAIN, LOAD_AFFINE, LOAD_GRAD_ENC, LOAD_GRAD_DEC, LOAD_NCHW, LOAD_AFFINE_RELU = range(6)      # rcv.h RCV_LOAD_*
@@ -26,15 +27,20 @@ def load(mode, x, c=None, aux=None):
     raise ValueError("load mode %r" % (mode,))
 
 
-def pw_conv(v, w, transposed=False, scale=None, bias=None, relu=False, resid=None):
+def pw_conv(v, w, transposed=False, scale=None, bias=None, relu=False, resid=None, matmul=False):
     """out[n][p][co] = sum_ci v[n][p][ci] * W[co][ci]; ``w`` is the parameter, [Cout][Cin] or with ``transposed`` [Cin][Cout];
-    ``scale`` multiplies the filter per output channel; then bias, ReLU, residual, in the epilogue's order."""
+    ``scale`` multiplies the filter per output channel; then bias, ReLU, residual, in the epilogue's order.
+    ``matmul``: the same sum as one float64 matrix product, for tensors of 10^5 pixels and more, where the [.., Cout, Cin] product of
+    the plain form takes gigabytes (tests/test_rest.py: bitwise the plain form on integers, within 1e-12 on randn)."""
     Wm = w.double().reshape(w.shape[0], w.shape[1])
     if transposed:
         Wm = Wm.t()
     if scale is not None:
         Wm = Wm * scale.double()[:, None]
-    out = (v.double().unsqueeze(-2) * Wm).sum(-1)          # [N,H,W,1,Cin] * [Cout,Cin] -> [N,H,W,Cout]
+    if matmul:
+        out = (v.double().reshape(-1, v.shape[-1]) @ Wm.t()).reshape(*v.shape[:-1], Wm.shape[0])
+    else:
+        out = (v.double().unsqueeze(-2) * Wm).sum(-1)          # [N,H,W,1,Cin] * [Cout,Cin] -> [N,H,W,Cout]
     if bias is not None:
         out = out + bias.double()
     if relu:
@@ -56,11 +62,52 @@ def stats_rows(kind, v, e=None, epi_c=None):
     return torch.stack([V.sum((0, 1, 2)), (V * (E - Cc[2])).sum((0, 1, 2))])
 
 
-def pw_wgrad(x_loaded, dy_loaded):
-    """dW[co][ci] = sum_p dy[p][co] * x[p][ci]."""
+def pw_wgrad(x_loaded, dy_loaded, matmul=False):
+    """dW[co][ci] = sum_p dy[p][co] * x[p][ci].  ``matmul``: as one float64 matrix product (see pw_conv)."""
     X = x_loaded.double().reshape(-1, x_loaded.shape[-1])
     G = dy_loaded.double().reshape(-1, dy_loaded.shape[-1])
+    if matmul:
+        return G.t() @ X
     return (G.unsqueeze(2) * X.unsqueeze(1)).sum(0)
+
+
+def order_sensitive_rows(gen, nsplit, *shape):
+    """fp32 partial rows [nsplit][*shape] on which the ORDER of a float64 summation shows in the fp32 result.  (On plain randn rows it
+    does not: float64 rounds at 2^-53 of the running sum and the final rounding to fp32 hides that.)  Rows are randn; in about a third
+    of the places the rows 2m and 2m + 1 hold +B and -B instead, B = randn * 2^40.  The big terms cancel in the end, but while a
+    running sum holds one, what is added to it is rounded to about 2^-12: the result, of magnitude sqrt(nsplit), carries the
+    summation order in its bits from 2^-12 down, well inside the 24 bits of an fp32 number."""
+    part = torch.randn(nsplit, *shape, generator=gen)
+    m = nsplit // 2
+    if m:
+        big = torch.randn(m, *shape, generator=gen) * 2.0 ** 40
+        where = torch.rand(m, *shape, generator=gen) < 0.35
+        part[0:2 * m:2] = torch.where(where, big, part[0:2 * m:2])
+        part[1:2 * m:2] = torch.where(where, -big, part[1:2 * m:2])
+    return part
+
+
+def pw_reduce(part, swap=False):
+    """RCV_OP_PW_WGRAD_REDUCE in its documented order: part [nsplit][...] fp32 -> lane l of 16 sums the rows l, l + 16, ... in float64,
+    in that order; the 16 lane sums are added in lane order; the total is rounded to fp32 once.  ``swap`` adds rows l + 16 and l of
+    every full group of four (l, l + 16, l + 32, l + 48) in the other order: a WRONG order, for the tests to show that their rows
+    tell the two apart."""
+    ns = part.shape[0]
+    P = part.double()
+    lanes = []
+    for lane in range(16):
+        u = torch.zeros(part.shape[1:], dtype=torch.float64)
+        order = list(range(lane, ns, 16))
+        if swap:
+            for k in range(0, len(order) - 3, 4):
+                order[k], order[k + 1] = order[k + 1], order[k]
+        for s in order:
+            u = u + P[s]
+        lanes.append(u)
+    t = lanes[0]
+    for lane in range(1, 16):
+        t = t + lanes[lane]
+    return t.float()
 
 
 def cross_pack(a, b, form):

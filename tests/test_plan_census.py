@@ -7,13 +7,15 @@ two-tensor template branch), under a gradient load as well.  No exceptions.
 
 Round coverage: the persistent kernels loop over tiles inside a workgroup; every family has float64 cases and an exact-statistics case
 on which, on 256 CUs, a workgroup runs three rounds or more with a ragged last one.  Their (label, workgroups, tiles) are pinned: a
-planner change shows here, not as lost coverage."""
+planner change shows here, not as lost coverage.  The 5x5 classifier family and the pointwise family (RCV_OP_CONV5 / _WGRAD5 / _PW /
+_PW_WGRAD, outside the census above) have their multi-round tables in tests/persistent_cases.py, checked further down."""
 import ast
 import os
 
 import pytest
 
 import conv_record_cases as RC
+import persistent_cases as PCS
 import plan_census as PC
 import small_ops_cases as K
 from conftest import ROOT
@@ -212,6 +214,93 @@ def test_filter_gradient_rounds():
         L.op_workspace(h, a), L.op_workspace(big, b)
         if other != shape and PC.label_of(h, a).startswith("wgrad_first"):
             assert PC.label_of(big, b) == PC.label_of(h, a) and a.i[L.RCV_I_NSPLIT] == b.i[L.RCV_I_NSPLIT], other
+
+
+# ------------------------------------------------------------------ the 5x5 and the pointwise families (tests/persistent_cases.py)
+# The tables entry for entry, as above: (label, workgroups, work items on 256 CUs).
+C5_PLANE_PINS = [((11, 121, 161), "8x32", 1056), ((345, 33, 16), "16x16", 1035)]
+CONV5_PINS = [
+    ("forward", (11, 121, 161), 8, 8, ("conv5_mfma<8,8x32>", 512, 1056)), ("dgrad", (11, 121, 161), 8, 8, ("conv5_mfma<8,8x32>", 512, 1056)),
+    ("forward", (11, 121, 161), 16, 8, ("conv5_mfma<16,8x32>", 512, 1056)), ("dgrad", (11, 121, 161), 8, 16, ("conv5_mfma<8,8x32>", 512, 1056)),
+    ("forward", (345, 33, 16), 8, 8, ("conv5_mfma<8,16x16>", 512, 1035)), ("dgrad", (345, 33, 16), 8, 8, ("conv5_mfma<8,16x16>", 512, 1035)),
+    ("forward", (345, 33, 16), 16, 8, ("conv5_mfma<16,16x16>", 512, 1035)), ("dgrad", (345, 33, 16), 8, 16, ("conv5_mfma<8,16x16>", 512, 1035)),
+]
+WGRAD5_PINS = [
+    ((11, 121, 161), 8, ("wgrad5_mfma<8,8x32>", 256, 1056)), ((11, 121, 161), 16, ("wgrad5_mfma<16,8x32>", 256, 1056)),
+    ((345, 33, 16), 8, ("wgrad5_mfma<8,16x16>", 256, 1035)), ((345, 33, 16), 16, ("wgrad5_mfma<16,16x16>", 256, 1035)),
+]
+PW_PINS = [
+    (16, 8, (3, 300, 293), ("pw_mfma<1,4>", 512, 1031)), (16, 32, (3, 300, 293), ("pw_mfma<2,4>", 512, 1031)),
+    (24, 40, (3, 300, 293), ("pw_mfma<4,4>", 512, 1031)), (32, 64, (3, 300, 293), ("pw_mfma<4,4>", 512, 1031)),
+    (64, 128, (3, 150, 293), ("pw_mfma<8,2>", 512, 1031)),
+]
+PW_WGRAD_PINS = [
+    (8, 8, (3, 300, 293), ("pw_wgrad_mfma<1,64,1>", 1024, 4121)), (64, 32, (3, 300, 293), ("pw_wgrad_mfma<2,64,1>", 1024, 4121)),
+    (64, 64, (3, 300, 293), ("pw_wgrad_mfma<4,64,1>", 512, 4121)), (128, 128, (3, 150, 293), ("pw_wgrad_mfma<4,64,4>", 256, 2061)),
+]
+
+
+def test_the_5x5_and_pointwise_tables_are_what_is_pinned_here():
+    assert PCS.C5_PLANES == C5_PLANE_PINS and PCS.CONV5_CASES == CONV5_PINS and PCS.WGRAD5_CASES == WGRAD5_PINS
+    assert PCS.PW_CASES == PW_PINS and PCS.PW_WGRAD_CASES == PW_WGRAD_PINS
+    assert PCS.PW_RANDOM_CASE in PW_PINS and PCS.PW_WGRAD_RANDOM_CASE in PW_WGRAD_PINS and PCS.WGRAD5_RANDOM_CASE in WGRAD5_PINS
+    assert set(PCS.CONV5_RANDOM_CASES) <= set(CONV5_PINS) and {c[0] for c in PCS.CONV5_RANDOM_CASES} == {"forward", "dgrad"}
+    assert PCS.PW_REDUCE_NSPLIT == (1, 15, 16, 17, 48, 49, 63, 64, 65, 113, 1024) and PCS.PW_REDUCE_PAIRS == ((8, 8), (24, 40))
+    assert PCS.WGRAD5_REDUCE_NSPLIT == (1, 2, 255, 256) and PCS.WGRAD5_REDUCE_CLASSES == (1, 5, 8)
+    assert PCS.PW_CAP8_PAIRS == ((64, 64), (128, 64), (128, 128))
+
+
+def test_5x5_and_pointwise_multi_round_cases_loop_on_256_cus():
+    """Every row of the four tables, on the 256-CU planning handle: the label and the (workgroups, work items) it pins, three rounds or
+    more with a ragged last one, and the restated rules against the plan query where both exist (i[NPART] = the restated tile
+    count, i[NSPLIT] = pw_restatement.wgrad_rows / min(tiles, CUs): asserted inside the *_rounds functions).  Every template instance of
+    the four kernels has a case: conv5_kernel<8 / 16>, wgrad5_kernel<8 / 16> on both tiles, pw_kernel<1,4> <2,4> <4,4> <8,2>,
+    pw_wgrad_kernel<1> <2> <4> (the default cap reaches no other)."""
+    h = L.planner_handle(256)
+    assert L.load().rcv_num_cus(h) == 256
+    seen = set()
+    for case in PCS.CONV5_CASES:
+        for extra in (dict(), dict(flags=L.F_BIAS), dict(flags=L.F_RESID), dict(stats=L.STATS_FWD), dict(inmode=L.LOAD_AFFINE_RELU)):
+            assert PCS.assert_multi_round(PCS.conv5_record(case, **extra), h, case[4]) == case[4][1:]
+        seen.add(case[4][0])
+    for case in PCS.WGRAD5_CASES:
+        for extra in (dict(), dict(inmode=L.LOAD_AFFINE_RELU)):
+            assert PCS.assert_multi_round(PCS.wgrad5_record(case, **extra), h, case[2]) == case[2][1:]
+        seen.add(case[2][0])
+    for case in PCS.PW_CASES:
+        for form in PCS.PW_FORMS:
+            assert PCS.assert_multi_round(PCS.pw_record(case, form), h, PCS.pw_pin(case, form)) == case[3][1:]
+        seen.add(case[3][0])
+    for case in PCS.PW_WGRAD_CASES:
+        for modes in ((L.LOAD_PLAIN, L.LOAD_PLAIN), (L.LOAD_AFFINE_RELU, L.LOAD_GRAD_DEC)):
+            assert PCS.assert_multi_round(PCS.pw_wgrad_record(case, *modes), h, case[3]) == case[3][1:]
+        assert case[3][0] == PCS.pw_cap_label(case[0], case[1], 4)
+        seen.add(case[3][0])
+    assert {"conv5_mfma<%d,%s>" % (c, t) for c in (8, 16) for t in ("8x32", "16x16")} <= seen
+    assert {"wgrad5_mfma<%d,%s>" % (c, t) for c in (8, 16) for t in ("8x32", "16x16")} <= seen
+    assert {"pw_mfma<1,4>", "pw_mfma<2,4>", "pw_mfma<4,4>", "pw_mfma<8,2>"} <= seen
+    assert {"pw_wgrad_mfma<%d,64,1>" % nb for nb in (1, 2, 4)} <= seen
+    # the default cap reaches NB = 1, 2, 4 and no other, over every channel pair the kernels take
+    assert {PCS.pw_cap_label(a, b, 4).split(",")[0] for a in range(8, 129, 8) for b in range(8, 129, 8)} == \
+        {"pw_wgrad_mfma<%d" % nb for nb in (1, 2, 4)}
+    # what the issue of these cases counted: 75 rounds of the 5x5 classifier at 32 x 480 x 640
+    grid, tiles = PCS.conv5_rounds(L.make_op(L.OP_CONV5, 0, n=32, h=480, w=640, cin=16, cout=8, ho=480, wo=640, stride=1, dil=1), h)
+    assert (grid, tiles) == (512, 38400)
+
+
+def test_the_cap_of_eight_filter_blocks_per_wave_plans_as_restated():
+    """i[AUX0] = 8 on RCV_OP_PW_WGRAD: the label of the plan query is the restated rule's, pw_wgrad_kernel<8> at 128 input channels;
+    the rows do not depend on the cap."""
+    h = L.planner_handle(256)
+    for cin, cout in PCS.PW_CAP8_PAIRS + ((8, 8), (24, 40), (128, 8), (8, 128)):
+        for cap in (0, 4, 8):
+            op = L.make_op(L.OP_PW_WGRAD, 0, n=3, h=16, w=20, cin=cin, cout=cout, aux0=cap)
+            L.op_workspace(h, op)
+            assert PC.label_of(h, op) == PCS.pw_cap_label(cin, cout, cap or 4), (cin, cout, cap)
+            assert op.i[L.RCV_I_NSPLIT] == 15
+    assert [PCS.pw_cap_label(a, b, 8) for a, b in PCS.PW_CAP8_PAIRS] == ["pw_wgrad_mfma<4,64,1>", "pw_wgrad_mfma<8,64,1>", "pw_wgrad_mfma<8,64,2>"]
+    with pytest.raises(L.RcvError, match="filter blocks per wave"):
+        PC.label_of(h, L.make_op(L.OP_PW_WGRAD, 0, n=3, h=16, w=20, cin=64, cout=64, aux0=3))
 
 
 # sources of kernel_case_records() that are the multi-round cases themselves

@@ -235,6 +235,55 @@ def test_restated_pointwise_conv_is_conv2d(cin, cout):
     assert float((R.pw_wgrad(v, gy) - wd.grad[:, :, 0, 0]).abs().max()) <= 1e-12
 
 
+@pytest.mark.parametrize("cin,cout", [(8, 8), (24, 40), (128, 64)])
+def test_matmul_form_of_the_restatement_is_the_plain_form(cin, cout):
+    """pw_conv / pw_wgrad with matmul=True (what the multi-round GPU cases use at 10^5 pixels): bit for bit the plain form on integer
+    operands, where every float64 sum is exact, and within 1e-12 of it on randn (sums of at most 128 / 960 terms of magnitude ~1)."""
+    g = torch.Generator().manual_seed(5 * cin + cout)
+    ints = lambda *s: torch.randint(-4, 5, s, generator=g).float()
+    rnd = lambda *s: torch.randn(*s, generator=g)
+    for make, bar in ((ints, 0.0), (rnd, 1e-12)):
+        x, gy, resid = make(3, 16, 20, cin), make(3, 16, 20, cout), make(3, 16, 20, cout)
+        w, wt, bias = make(cout, cin, 1, 1), make(cin, cout, 1, 1), make(cout)
+        scale = torch.randint(1, 4, (cout,), generator=g).float() if bar == 0.0 else torch.rand(cout, generator=g) + 0.5
+        pairs = [(R.pw_conv(x, w), R.pw_conv(x, w, matmul=True)),
+                 (R.pw_conv(x, w, scale=scale, bias=bias, relu=True), R.pw_conv(x, w, scale=scale, bias=bias, relu=True, matmul=True)),
+                 (R.pw_conv(x, wt, transposed=True, resid=resid), R.pw_conv(x, wt, transposed=True, resid=resid, matmul=True)),
+                 (R.pw_wgrad(x, gy), R.pw_wgrad(x, gy, matmul=True))]
+        for plain, mm in pairs:
+            assert plain.shape == mm.shape and plain.dtype == mm.dtype == torch.float64
+            if bar == 0.0:
+                assert torch.equal(plain, mm)
+            else:
+                assert float((plain - mm).abs().max()) <= bar
+
+
+def test_restated_reductions_follow_their_documented_order():
+    """pw_reduce: 16 lanes over the rows l, l + 16, ..., lane sums in lane order, rounded once; wgrad5_reduce: rows in order, the filter
+    part transposed to [class][CIN][5][5].  On integer rows every order gives the plain sum; on order_sensitive_rows the order shows
+    in the fp32 result (rows l and l + 16 exchanged: at least a quarter of the elements change), which is what lets the GPU test see
+    a reordered loop."""
+    import cls5_restatement as R5
+    g = torch.Generator().manual_seed(11)
+    for ns in (1, 17, 64, 113):
+        part = torch.randint(-9, 10, (ns, 40, 24), generator=g).float()
+        assert torch.equal(R.pw_reduce(part).double(), part.double().sum(0)) and torch.equal(R.pw_reduce(part, swap=True), R.pw_reduce(part))
+    for ns in (113, 128, 1024):      # (two groups of four per lane or more: the first starts from zero, its order cannot show)
+        for shape in ((8, 8), (40, 24)):
+            rows = R.order_sensitive_rows(g, ns, *shape)
+            changed = float((R.pw_reduce(rows, swap=True) != R.pw_reduce(rows)).float().mean())
+            assert changed >= (0.25 if ns >= 128 else 0.02), (ns, shape, changed)      # (113 rows: lane 0 alone has a second group)
+    rows = R.order_sensitive_rows(g, 113, 40, 24)
+    assert float((R.pw_reduce(rows).double() - rows.double().sum(0)).abs().max()) <= 113 * 2.0 ** -10      # (the big terms cancel)
+    part = torch.randint(-9, 10, (7, 25 * 8 * 16 + 8), generator=g).float()
+    dw, db = R5.wgrad5_reduce(part, 16, 5)
+    total = part.double().sum(0)
+    assert dw.shape == (5, 16, 5, 5) and db.shape == (5,)
+    for co, ci, t in ((0, 0, 0), (4, 15, 24), (2, 7, 13)):
+        assert float(dw[co, ci, t // 5, t % 5]) == float(total[(t * 8 + co) * 16 + ci])
+    assert torch.equal(db.double(), total[25 * 8 * 16:25 * 8 * 16 + 5])
+
+
 @pytest.mark.parametrize("stride", [1, 2])
 def test_cross_filter_is_the_concatenated_pair(stride):
     """cat(conv_nx1(x), conv_1xn(x)) == one 3x3 conv with the cross filter: same stride, dilation, padding = dilation (ConvSep's
