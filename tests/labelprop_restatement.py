@@ -80,7 +80,7 @@ def tail_forward_np(t, tc, top, w, b):
     v = np.maximum(t * np.asarray(tc[0], np.float64) + np.asarray(tc[1], np.float64), 0.0)
     rch = top.shape[-1]
     v[..., :rch] += np.asarray(top, np.float64)
-    logits = np.einsum("nhwk,ck->nchw", v, np.asarray(w, np.float64)) + np.asarray(b, np.float64)[None, :, None, None]
+    logits = np.einsum("nhwk,ck->nchw", v, np.asarray(w, np.float64), optimize=True) + np.asarray(b, np.float64)[None, :, None, None]
     return v, logits
 
 
@@ -106,9 +106,9 @@ def tail_backward_np(t, tc, v, w, dlogits, rch):
     [2,16]: sum g*m and sum g*m*(t - mean) with m = (t*scale + shift > 0), the ReLU mask of upConv3 ALONE."""
     t, dl = np.asarray(t, np.float64), np.asarray(dlogits, np.float64)
     w = np.asarray(w, np.float64)
-    dW = np.einsum("nchw,nhwk->ck", dl, v)
+    dW = np.einsum("nchw,nhwk->ck", dl, v, optimize=True)
     db = dl.sum((0, 2, 3))
-    g = np.einsum("nchw,ck->nhwk", dl, w)
+    g = np.einsum("nchw,ck->nhwk", dl, w, optimize=True)
     m = (t * np.asarray(tc[0], np.float64) + np.asarray(tc[1], np.float64)) > 0
     gm = np.where(m, g, 0.0)
     stats = np.stack([gm.sum((0, 1, 2)), (gm * (t - np.asarray(tc[2], np.float64))).sum((0, 1, 2))])
@@ -179,3 +179,95 @@ def loop_assembly(images, labels, num_class=5):
         outputs[cnt], outputs[cnt + 1] = lab[0], lab[1]
         cnt += 2
     return inputs, outputs
+
+
+# ------------------------------------------------------------------------------------------ exact cases of the tail kernels
+# Operands on the integer grid of small_ops_restatement (every product and partial sum an integer below 2^24: exact in fp32 in any
+# order), so that tests/test_gpu_labelprop_train.py compares lp_tail_fwd<0> / lp_tail_bwd<nC,0> with this file bit for bit.
+TAIL_SMALL_PLANES = [(2, 9, 11), (1, 1, 1)]
+
+
+def tail_big_planes(num_cus):
+    """Two planes beyond one grid pass of the tail kernels (4 workgroups per CU, 256 pixels a chunk): a multiple of 256 pixels, and an
+    odd count (256 CUs: 1x1025x256, 3x299x293)."""
+    cap = 4 * num_cus * 256
+    hodd = cap // (3 * 293) + 1
+    hodd += 1 - hodd % 2
+    out = [(1, cap // 256 + 1, 256), (3, hodd, 293)]
+    assert all(n * h * w > cap for n, h, w in out) and (out[0][1] * 256) % 256 == 0 and (3 * hodd * 293) % 2 == 1
+    return out
+
+
+TAIL_MODES, TAIL_RCH, TAIL_CLASSES = (0, 1, 5), (4, 8, 12, 16), (1, 5, 8)
+
+
+def tail_exact_cases(num_cus):
+    """(plane, classes, skip width, skip load mode, first pixel of the second grid pass): the full product on the two small planes;
+    beyond one grid pass every skip width on both planes, the class count and the load mode rotating (each big case costs about a
+    second of float64 host arithmetic)."""
+    cap = 4 * num_cus * 256
+    out = [(pl, nC, rch, mode, 0) for pl in TAIL_SMALL_PLANES for nC in TAIL_CLASSES for rch in TAIL_RCH for mode in TAIL_MODES]
+    for ri, rch in enumerate(TAIL_RCH):
+        for pi, pl in enumerate(tail_big_planes(num_cus)):
+            out.append((pl, TAIL_CLASSES[(2 * ri + pi) % 3], rch, TAIL_MODES[(ri + 2 * pi) % 3], cap))
+    return out
+
+
+def build_tail(plane, nC, rch, mode, second=0, seed=0, density=1.0):
+    """t [N,H,W,16], r [N,H,W,rch], w [nC,16], b [nC], dl [N,nC,H,W] on the grid ({-1..1} on the large planes; `density` thins t, r
+    and dl further), tc [5][16] / rc [5][rch] from grid_consts.  The two pixels of drop_masks (the last one; the first of the second
+    grid pass, `second`) have dl = 1 for every class, v > 0 in every channel, the ReLU mask on and t != mean; the filter's column sums
+    are non-zero: removing either pixel changes every entry of dW, db and both statistics rows."""
+    import small_ops_restatement as S
+    N, H, W = plane
+    npix = N * H * W
+    rng = np.random.default_rng(52000 + 7 * seed + npix + 3 * nC + 5 * rch + mode)
+    a = 1 if npix > 50000 else 2
+    c = dict(plane=plane, nC=nC, rch=rch, mode=mode, npix=npix, second=second)
+    c["t"] = S.grid(rng, (N, H, W, 16), a, density)
+    c["r"] = S.grid(rng, (N, H, W, rch), a, density)
+    c["tc"], c["rc"] = S.grid_consts(rng, 16), S.grid_consts(rng, rch)
+    c["w"], c["b"] = S.grid(rng, (nC, 16), 2), S.grid(rng, (nC,), 2)
+    dl = S.grid(rng, (npix, nC), a, density)
+    col = c["w"].sum(0)
+    c["w"][0, col == 0] += np.where(c["w"][0, col == 0] < 2, 1, -1)
+    idx, _ = S.drop_masks(npix, second)
+    c["t"].reshape(npix, 16)[idx] = 2 * np.sign(c["tc"][0])
+    c["r"].reshape(npix, rch)[idx] = 1.0 if mode == 0 else 2 * np.sign(c["rc"][0])
+    dl[idx] = 1.0
+    c["dl"] = np.ascontiguousarray(dl.reshape(N, H, W, nC).transpose(0, 3, 1, 2))
+    return c
+
+
+def tail_reference(c, keep=None):
+    """-> logits, dW, db, g, gskip, statistics rows; keep: a boolean vector over the pixels, a dropped pixel adds nothing to the
+    reductions (its logits gradient reads zero)."""
+    v, logits = tail_forward_np(c["t"], c["tc"], load_np(c["r"], c["rc"], c["mode"]), c["w"], c["b"])
+    dl = c["dl"] if keep is None else c["dl"] * np.asarray(keep, np.float32).reshape(c["plane"])[:, None]
+    return (logits,) + tail_backward_np(c["t"], c["tc"], v, c["w"], dl, c["rch"])
+
+
+def check_tail(c):
+    """The preconditions of an exact tail case: sums of |terms| of the logits, dW, db, g and the statistics rows are integers below
+    2^24; the ReLU mask meets values at and below zero; each of the two pixels of drop_masks adds a non-zero term to every entry of dW,
+    db and both statistics rows (a kernel that loses one of them gets every reduced entry wrong).  -> tail_reference(c)."""
+    import small_ops_restatement as S
+    A = lambda x: np.abs(np.asarray(x, np.float64))
+    npix, nC = c["npix"], c["nC"]
+    v, _ = tail_forward_np(c["t"], c["tc"], load_np(c["r"], c["rc"], c["mode"]), c["w"], c["b"])
+    full = tail_reference(c)
+    g = full[3]
+    dlp = np.ascontiguousarray(np.asarray(c["dl"], np.float64).transpose(0, 2, 3, 1)).reshape(npix, nC)
+    S.assert_exact(A(c["w"]).sum(1) * A(v).max() + A(c["b"]), 1.0, "tail logits")
+    S.assert_exact(A(dlp).T @ A(v).reshape(npix, 16), 1.0, "tail dW")
+    S.assert_exact(A(dlp).sum(0), 1.0, "tail db")
+    S.assert_exact(S.stats_abs(S.STATS_BWD_DEC, g, c["t"], c["tc"]), 1.0, "tail statistics")
+    assert float(A(dlp).sum(1).max() * A(c["w"]).max()) < 2.0 ** 24
+    z = np.asarray(c["t"], np.float64).reshape(npix, 16) * c["tc"][0] + c["tc"][1]
+    if npix > 1:
+        assert (z == 0).any() and (z < 0).any(), "the mask must meet pixels at and below zero"
+    for i in S.drop_masks(npix, c["second"])[0]:
+        gi = g.reshape(npix, 16)[i]
+        assert np.all(dlp[i] != 0) and np.all(v.reshape(npix, 16)[i] != 0) and np.all(z[i] > 0) and np.all(gi != 0), i
+        assert np.all(np.asarray(c["t"], np.float64).reshape(npix, 16)[i] != c["tc"][2]), i
+    return full

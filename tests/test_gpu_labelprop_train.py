@@ -17,6 +17,7 @@ from robocupvision_amd.train import Trainer
 from test_gpu_blocks import close, _t
 from test_gpu_net import check_mask
 from test_gpu_pbfcn import _check_after
+from test_gpu_small_ops import _exact
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -58,13 +59,20 @@ TAIL_CASES = [(2, 9, 11, 5, L.LOAD_AFFINE_RELU), (1, 7, 5, 1, L.LOAD_AFFINE_RELU
 @pytest.mark.parametrize("ci", range(len(TAIL_CASES)))
 def test_tail_kernels_vs_float64(ci):
     N, H, W, nC, mode = TAIL_CASES[ci]
+    _tail_randn_case(ci, N, H, W, nC, mode, 8)
+
+
+def _tail_randn_case(ci, N, H, W, nC, mode, rch):
+    """Random operands through all forms of the tail: the fused-loss, the plain and the eval-mode forward give the same logits bit for
+    bit, the loss row equals RCV_OP_CE_FWD's on the same logits, the fused-loss backward equals the logits-gradient one, two runs are
+    equal; all of it against float64 at the project's bars."""
     rng = np.random.default_rng(300 + ci)
     t = rng.standard_normal((N, H, W, 16)).astype(np.float32)
-    r = rng.standard_normal((N, H, W, 8)).astype(np.float32)
+    r = rng.standard_normal((N, H, W, rch)).astype(np.float32)
     tc = np.zeros((5, 16), np.float32)
     tc[0], tc[1], tc[2] = rng.uniform(0.5, 1.5, 16), rng.standard_normal(16) * 0.3, rng.standard_normal(16) * 0.2
-    rc = np.zeros((5, 8), np.float32)
-    rc[0], rc[1] = rng.uniform(0.5, 1.5, 8), rng.standard_normal(8) * 0.3
+    rc = np.zeros((5, rch), np.float32)
+    rc[0], rc[1] = rng.uniform(0.5, 1.5, rch), rng.standard_normal(rch) * 0.3
     w = (rng.standard_normal((nC, 16)) * 0.3).astype(np.float32)
     b = (rng.standard_normal(nC) * 0.1).astype(np.float32)
     tgt = rng.integers(0, nC, (N, H, W)).astype(np.int64)
@@ -72,7 +80,7 @@ def test_tail_kernels_vs_float64(ci):
     cw = rng.uniform(0.5, 6.0, nC).astype(np.float32)
     t_d, r_d, tc_d, rc_d, w_d, b_d, cw_d = (_dev(a) for a in (t, r, tc, rc, w, b, cw))
     tgt_d = _dev(tgt, torch.int64)
-    common = dict(n=N, h=H, w=W, cin=16, cout=nC, aux0=mode, aux1=8, p_w=w_d.data_ptr(), p_x3=r_d.data_ptr(), p_x4=rc_d.data_ptr())
+    common = dict(n=N, h=H, w=W, cin=16, cout=nC, aux0=mode, aux1=rch, p_w=w_d.data_ptr(), p_x3=r_d.data_ptr(), p_x4=rc_d.data_ptr())
 
     # forward: the fused-loss launch, the plain launch and the eval-mode classifier record give the same logits, bit for bit
     logits_d, logits2_d, loss_d = _nan(N, nC, H, W), _nan(N, nC, H, W), _nan(4)
@@ -116,7 +124,7 @@ def test_tail_kernels_vs_float64(ci):
                    p_x0=loss_d.data_ptr(), p_x1=one_d.data_ptr(), p_out=dl_d.data_ptr()))
     outs = []
     for with_ce in (False, True, True):
-        dup_d, dskip_d, dw_d, db_d = _nan(N, H, W, 16), _nan(N, H, W, 8), _nan(nC, 16), _nan(nC)
+        dup_d, dskip_d, dw_d, db_d = _nan(N, H, W, 16), _nan(N, H, W, rch), _nan(nC, 16), _nan(nC)
         bop = L.make_op(L.OP_LP_TAIL_BWD, L.F_FUSED_UP | (L.F_FUSED_CE if with_ce else 0), stats=L.STATS_BWD_DEC, p_out=dup_d.data_ptr(),
                         p_in_aux=dskip_d.data_ptr(), p_epi_aux=t_d.data_ptr(), p_epi_c=tc_d.data_ptr(), p_x1=dw_d.data_ptr(),
                         p_x2=db_d.data_ptr(), p_in2=(tgt_d if with_ce else dl_d).data_ptr(), **common)
@@ -133,15 +141,95 @@ def test_tail_kernels_vs_float64(ci):
         assert torch.equal(a, c), "fused-loss and logits-gradient forms differ"
         assert torch.equal(c, e), "two runs differ"
     gup, gskip, gw, gb, gpart = outs[0]
-    dW, db, g, gs, stats = R.tail_backward_np(t, tc, v, w, dl, 8)
+    dW, db, g, gs, stats = R.tail_backward_np(t, tc, v, w, dl, rch)
     close(dl_d, torch.from_numpy(dl), "dlogits", rtol=1e-4)
     close(gw, torch.from_numpy(dW), "dW", rtol=1e-4, floor=1.0)
     close(gb, torch.from_numpy(db), "db", rtol=1e-4, floor=1.0)
     close(gup, torch.from_numpy(g), "d upConv3", rtol=1e-4)
-    assert torch.equal(gskip, gup[..., :8].contiguous()), "the skip gradient is the first 8 channels of the data gradient"
+    assert torch.equal(gskip, gup[..., :rch].contiguous()), "the skip gradient is the first rch channels of the data gradient"
     rows = gpart.reshape(n_part, 2, 16).double().sum(0)
     close(rows, torch.from_numpy(stats), "statistics rows", rtol=1e-4, floor=1.0)
     del ws_f, ws_c
+
+
+def _cus():
+    return int(L.load().rcv_num_cus(L.handle(0)))
+
+
+GUARD = 64      # floats behind a buffer that no lane may touch
+
+
+def _guarded(a):
+    """The array on the device with GUARD zeros behind it (the skip tensor: nothing behind its N*H*W*rch floats belongs to it)."""
+    return _dev(np.concatenate([np.asarray(a, np.float32).reshape(-1), np.zeros(GUARD, np.float32)]))
+
+
+def _tail_exact_case(plane, nC, rch, mode, second):
+    """lp_tail_fwd<0> and lp_tail_bwd<nC,0> on integer-grid operands: logits, d upConv3, the skip gradient, dW, db and the float64 fold
+    of the partial statistics rows equal the restatement bit for bit; the skip gradient is the first rch channels of the data
+    gradient and nothing is stored behind its N*H*W*rch floats."""
+    N, H, W = plane
+    npix = N * H * W
+    c = R.build_tail(plane, nC, rch, mode, second)
+    logits, dW, db, g, gskip, stats = R.check_tail(c)
+    t_d, tc_d, rc_d, w_d, b_d, dl_d = (_dev(c[k]) for k in ("t", "tc", "rc", "w", "b", "dl"))
+    r_d = _guarded(c["r"])
+    common = dict(n=N, h=H, w=W, cin=16, cout=nC, aux0=mode, aux1=rch, p_w=w_d.data_ptr(), p_x3=r_d.data_ptr(), p_x4=rc_d.data_ptr())
+    logits_d, dup_d, dskip_d, dw_d, db_d = _nan(N, nC, H, W), _nan(N, H, W, 16), _nan(npix * rch + GUARD), _nan(nC, 16), _nan(nC)
+    fop = L.make_op(L.OP_LP_TAIL_FWD, L.F_FUSED_UP, p_in=t_d.data_ptr(), p_in_c=tc_d.data_ptr(), p_bias=b_d.data_ptr(),
+                    p_out=logits_d.data_ptr(), **common)
+    bop = L.make_op(L.OP_LP_TAIL_BWD, L.F_FUSED_UP, stats=L.STATS_BWD_DEC, p_out=dup_d.data_ptr(), p_in_aux=dskip_d.data_ptr(),
+                    p_epi_aux=t_d.data_ptr(), p_epi_c=tc_d.data_ptr(), p_x1=dw_d.data_ptr(), p_x2=db_d.data_ptr(), p_in2=dl_d.data_ptr(), **common)
+    ws = _with_workspace(bop)
+    n_part = bop.i[L.RCV_I_NPART]
+    labels = L.OpList([fop, bop]).labels(L.handle(0))
+    assert labels == ["lp_tail_fwd<0>", "lp_tail_bwd<%d,0>" % nC], labels
+    assert n_part == min(-(-npix // 256), 4 * _cus())
+    _run(fop)
+    _run(bop)
+    torch.cuda.synchronize()
+    what = "lp tail %s %d classes rch %d mode %d: " % (plane, nC, rch, mode)
+    _exact(logits_d, logits, what + "logits")
+    _exact(dup_d, g, what + "d upConv3")
+    _exact(dskip_d[:npix * rch].reshape(N, H, W, rch), gskip, what + "skip gradient")
+    assert torch.equal(dskip_d[:npix * rch].reshape(N, H, W, rch), dup_d[..., :rch].contiguous())
+    assert bool(torch.isnan(dskip_d[npix * rch:]).all()), what + "a lane without a skip stored behind the skip gradient"
+    _exact(dw_d, dW, what + "dW")
+    _exact(db_d, db, what + "db")
+    _exact(ws[:n_part * 32].reshape(n_part, 2, 16).double().sum(0), stats, what + "statistics rows")
+    return n_part
+
+
+@pytest.mark.parametrize("rch", R.TAIL_RCH)
+def test_tail_kernels_exact(rch):
+    """Every class count in {1, 5, 8} and skip load mode on 2x9x11 and 1x1x1; both planes beyond one grid pass (a multiple of 256
+    pixels and an odd count, sized from the device's CU count): the backward's COUT*16 + COUT + 8 register sums per lane carried into
+    a second chunk.  The first pixel of the second pass and the last pixel add a non-zero term to every reduced entry
+    (R.check_tail), so a lost pixel, chunk or accumulator cannot go unseen."""
+    cus = _cus()
+    cap = 4 * cus * 256
+    big = 0
+    for plane, nC, rch_, mode, second in R.tail_exact_cases(cus):
+        if rch_ != rch:
+            continue
+        npix = plane[0] * plane[1] * plane[2]
+        n_part = _tail_exact_case(plane, nC, rch, mode, second)
+        if second:
+            print("lp tail %s: %d pixels, one grid pass covers %d (%d CUs x 4 workgroups x 256)" % (plane, npix, cap, cus))
+            assert npix > cap and n_part == 4 * cus and n_part * 256 < npix
+            big += 1
+    assert big == 2
+
+
+@pytest.mark.parametrize("rch", [4, 16])
+def test_tail_fused_loss_forms_beyond_one_grid_pass(rch):
+    """The fused cross-entropy forms (lp_tail_fwd<1>, lp_tail_bwd<5,1>) past one grid pass at the narrowest and the widest skip, random
+    operands: the assertions and bars of test_tail_kernels_vs_float64."""
+    cus = _cus()
+    N, H, W = R.tail_big_planes(cus)[1]
+    print("lp tail fused forms %s: %d pixels, one grid pass covers %d" % ((N, H, W), N * H * W, 4 * cus * 256))
+    assert N * H * W > 4 * cus * 256
+    _tail_randn_case(40 + rch, N, H, W, 5, L.LOAD_AFFINE_RELU if rch == 4 else L.LOAD_AFFINE, rch)
 
 
 # ------------------------------------------------------------------------------------------ batch assembly
@@ -165,6 +253,33 @@ def test_batch_assembly_equals_the_fixture_exactly(tag):
     im5 = torch.cat([im, torch.full_like(im[:, :, :2], 9.0)], 2)
     x5, _ = M.labelprop_batch(im5, lab)
     assert torch.equal(x5, x)
+
+
+def test_batch_assembly_beyond_the_grid_cap():
+    """RCV_OP_LP_BATCH is capped at 8 workgroups per CU: an odd pixel count beyond 8 * CUs * 256 (3x419x421 on 256 CUs), three
+    channels per frame, bitwise against the restatement; labels 5, -1, -100 and 1 << 40 sit in the second pass."""
+    cus = _cus()
+    cap = 8 * cus * 256
+    B, W = 3, 421
+    H = cap // (B * W) + 1
+    H += 1 - H % 2
+    while B * H * W - cap < 16:
+        H += 2
+    print("lp batch %dx%dx%d: %d pixels, one grid pass covers %d" % (B, H, W, B * H * W, cap))
+    assert B * H * W > cap and (B * H * W) % 2 == 1
+    rng = np.random.default_rng(77)
+    im = rng.standard_normal((B, 2, 3, H, W)).astype(np.float32)
+    lab = rng.integers(0, 5, (B, 2, H, W)).astype(np.int64)
+    b2, hw = cap // (H * W), cap % (H * W)                       # element `cap` = (pair b2, pixel hw): the first of the second pass
+    assert b2 == B - 1 and hw + 8 < H * W
+    flat = lab.reshape(B, 2, H * W)
+    flat[b2, 0, hw:hw + 4] = [5, -1, -100, 1 << 40]
+    flat[b2, 1, hw + 2:hw + 6] = [1 << 40, 5, -1, -100]
+    flat[b2, :, -1] = [-100, 1 << 40]
+    x, t = M.labelprop_batch(_t(im).to(DEV), _t(lab).to(DEV))
+    xr, tr_ = R.assemble_np(im, lab)
+    assert torch.equal(x.cpu(), torch.from_numpy(xr)) and torch.equal(t.cpu(), torch.from_numpy(tr_))
+    assert float(x[2 * b2 + 1, 3:].reshape(5, -1)[:, hw:hw + 4].max()) == -1.0 and int(t[2 * b2].reshape(-1)[hw + 3]) == 1 << 40
 
 
 # ------------------------------------------------------------------------------------------ whole step

@@ -10,6 +10,7 @@ import torch
 
 from conftest import GOLDEN, sd_hash
 import labelprop_restatement as R
+import small_ops_restatement as S
 import robocupvision_amd
 import robocupvision_amd.model as M
 from robocupvision_amd import _lib as L
@@ -174,6 +175,66 @@ def test_restatement_of_the_tail_agrees_with_the_reference():
     dbeta, dgamma = k[tag + "/grad/upConv3.bn.bias"], k[tag + "/grad/upConv3.bn.weight"]
     assert np.abs(stats[0] - dbeta).max() <= 1e-4 * np.abs(dbeta).max()
     assert np.abs(stats[1] / np.sqrt(var + 1e-5) - dgamma).max() <= 1e-4 * np.abs(dgamma).max()
+
+
+@pytest.mark.parametrize("rch", [4, 8, 12, 16])
+@pytest.mark.parametrize("mode", [0, 1, 5])
+def test_restatement_of_the_tail_equals_float64_autograd(rch, mode):
+    """tail_forward_np / load_np / tail_backward_np at every skip width the launcher accepts, on a 2x5x7 plane, against torch float64
+    autograd of  logits = W (cat(relu(t c0 + c1)[:rch] + f(r), relu(t c0 + c1)[rch:])) + b:  logits, dW, db, the gradient of the
+    decoder output, the skip gradient, and the statistics rows as the gradients of the shift (row 0) and of the scale (row 1 + mean
+    times row 0)."""
+    rng = np.random.default_rng(100 * rch + mode)
+    N, H, W, nC = 2, 5, 7, 5
+    t, r = rng.standard_normal((N, H, W, 16)), rng.standard_normal((N, H, W, rch))
+    tc, rc = rng.standard_normal((5, 16)), rng.standard_normal((5, rch))
+    w, b, dl = rng.standard_normal((nC, 16)), rng.standard_normal(nC), rng.standard_normal((N, nC, H, W))
+    top = R.load_np(r, rc, mode)
+    v, logits = R.tail_forward_np(t, tc, top, w, b)
+    dW, db, g, gskip, stats = R.tail_backward_np(t, tc, v, w, dl, rch)
+    T = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float64))
+    c0, c1 = T(tc[0]).requires_grad_(True), T(tc[1]).requires_grad_(True)
+    wt, bt, rt = T(w).requires_grad_(True), T(b).requires_grad_(True), T(r)
+    ft = rt if mode == 0 else rt * T(rc[0]) + T(rc[1])
+    ft = (torch.relu(ft) if mode == 5 else ft).detach().requires_grad_(True)
+    u = torch.relu(T(t) * c0 + c1)
+    u.retain_grad()
+    vt = torch.cat([u[..., :rch] + ft, u[..., rch:]], -1)
+    lt = torch.einsum("nhwk,ck->nchw", vt, wt) + bt[None, :, None, None]
+    (lt * T(dl)).sum().backward()
+    near = lambda a, x: float(np.abs(a - x.detach().numpy()).max()) <= 1e-12 * max(1.0, float(x.detach().abs().max()))
+    assert near(top, ft) and near(v, vt) and near(logits, lt)
+    assert near(dW, wt.grad) and near(db, bt.grad) and near(g, u.grad) and near(gskip, ft.grad)
+    assert gskip.shape == (N, H, W, rch) and np.array_equal(gskip, g[..., :rch])
+    assert near(stats[0], c1.grad) and near(stats[1] + tc[2] * stats[0], c0.grad)
+
+
+def test_exact_tail_cases_hold_their_preconditions():
+    """The integer-grid cases of tests/test_gpu_labelprop_train.py, sized for 256 CUs here (on the device by rcv_num_cus): every class
+    count, skip width and load mode on the small planes, every skip width on both planes beyond one grid pass; R.check_tail."""
+    cases = R.tail_exact_cases(256)
+    small = [k for k in cases if not k[4]]
+    big = [k for k in cases if k[4]]
+    assert {k[1:4] for k in small if k[0] == (2, 9, 11)} == {(nC, rch, m) for nC in (1, 5, 8) for rch in (4, 8, 12, 16) for m in (0, 1, 5)}
+    assert {k[0] for k in small} == {(2, 9, 11), (1, 1, 1)} and len(big) == 8
+    assert {(k[0], k[2]) for k in big} == {(pl, rch) for pl in [(1, 1025, 256), (3, 299, 293)] for rch in (4, 8, 12, 16)}
+    assert {k[1] for k in big} == {1, 5, 8} and {k[3] for k in big} == {0, 1, 5}
+    h = L.planner_handle(256)
+    for plane, nC, rch, mode, second in cases:
+        npix = plane[0] * plane[1] * plane[2]
+        assert (second == 4 * 256 * 256 and npix > second) if second else npix <= 256
+        op = _rec(L.OP_LP_TAIL_BWD, n=plane[0], h=plane[1], w=plane[2], cout=nC, aux0=mode, aux1=rch)
+        L.op_workspace(h, op)
+        assert op.i[L.RCV_I_NPART] == (1024 if second else 1)          # the capped grid: one pass is short of a big plane
+        c = R.build_tail(plane, nC, rch, mode, second)
+        full = R.check_tail(c)
+        if plane == (2, 9, 11) or (rch, second) == (16, 4 * 256 * 256):
+            # what check_tail's per-pixel terms stand for: the restatement without either pixel differs in EVERY reduced entry
+            idx, masks = S.drop_masks(npix, second)
+            assert idx == [npix - 1, second or npix // 2]
+            for keep in masks:
+                part = R.tail_reference(c, keep)
+                assert all(np.all(full[j] != part[j]) for j in (1, 2, 5)) and np.array_equal(full[0], part[0])
 
 
 def test_twin_equals_the_reference_at_init():
