@@ -341,8 +341,22 @@ enum {
                              * centre column of rows < D0/2, p[IN2] = [D0/2][D1][1][3] in the centre row of the others; i[AUX0] = 1:
                              * trconv1x3(x) + trconv3x1(x) (model.py:367-376), p[IN] = [D0][D1][1][3] in the centre row, p[IN2] =
                              * [D0][D1][3][1] in the centre column, the centre tap their sum.  Every element of the dense filter is written */
-  RCV_OP_CROSS_GRAD = 66     /* the gather that undoes it on a gradient: p[IN] = dense gradient float[D0][D1][3][3], p[OUT] / p[X0] = the
+  RCV_OP_CROSS_GRAD = 66,    /* the gather that undoes it on a gradient: p[IN] = dense gradient float[D0][D1][3][3], p[OUT] / p[X0] = the
                              * gradients of the first / second 1-D filter; with i[AUX0] = 1 the centre tap's gradient goes to both        */
+  RCV_OP_CLS_PROBA = 67      /* the softmax form of the classifier tails (rcv_cls_proba; csrc/cls_proba.hip): the [softmax] section that
+                             * closes every exported net.cfg, and the confidence gate of a pseudo-label.  Source forms 0 and 1 of
+                             * RCV_OP_CLS_LABEL, slot for slot: i[N], i[H], i[W], i[CIN], i[COUT] = 1..8 classes, i[INMODE] 0 = features
+                             * (p[IN], p[W], p[BIAS] or NULL, CIN 8 / 16; with RCV_F_FUSED_UP p[IN_C], p[X3], p[X4], i[AUX0], i[AUX1]),
+                             * 1 = NHWC logits of i[CIN] floats per pixel plus p[BIAS]; form 2 is refused.  No logits are stored.  Per
+                             * pixel: m = the first maximum of the logits z in class order (a NaN never wins), cls = its index, e_c =
+                             * expf(z_c - m), S = ((e_0 + e_1) + e_2) + ... in class order, p_c = e_c / S (IEEE division, no fast
+                             * intrinsics; RCV_OP_LP_INPUT's softmax).  Outputs, each optional, at least one (checked at launch), a NULL
+                             * slot is not written: p[X0] = probabilities float[N][COUT][H][W]; p[OUT] = class map uint8[N][H][W], bit
+                             * for bit RCV_OP_CLS_LABEL's; p[X1] = confidence float[N][H][W] = p[cls], the float stored in p[X0]; p[X2]
+                             * = pseudo-label int64[N][H][W] = cls where that stored confidence >= f[0], else -100 (the ignore value
+                             * of the losses: any target outside [0, COUT)).  A NaN logit gives whatever the expressions give (NaN
+                             * probabilities for the pixel, the class from the other logits, pseudo-label -100); a NaN f[0] gives
+                             * -100 everywhere.  No atomics; every element is written once by a fixed lane                            */
 };
 
 /* i[RCV_I_AUX0] of RCV_OP_PRUNE: how the threshold of a tensor is chosen */
@@ -820,6 +834,11 @@ int rcv_cls_valid(rcv_handle* h, const float* x, const float* w, const float* bi
  * float `loss` (n_rows = 0, rows NULL); counts are zero afterwards.                                                                   */
 int rcv_valid_fold(rcv_handle* h, int32_t* counts, const float* rows, int n_rows, const float* loss, int N, int H, int W, int num_class,
                    double* state, void* stream);
+/* RCV_OP_CLS_PROBA, source form 0 without the fused decoder input: softmax over c of (bias[c] + sum_k x[p][k] w[c][k]) with the fixed
+ * arithmetic stated at the kind; proba float[N][COUT][H][W], labels uint8[N][H][W], confidence float[N][H][W], pseudo int64[N][H][W]
+ * (class where confidence >= threshold, else -100): each may be NULL, not all four.                                                  */
+int rcv_cls_proba(rcv_handle* h, const float* x, const float* w, const float* bias /*may be NULL*/, int N, int H, int W, int CIN, int COUT,
+                  float* proba, uint8_t* labels, float* confidence, int64_t* pseudo, float threshold, void* stream);
 
 /* The BNN-L / BNN-M-C patch classifiers (model.py:569-619; objDetEval.py:89-119, classVal.py).  Each call runs ONE record of the kind
  * named (RCV_OP_BNN_STAGE_FWD / _BWD: conv -> Dropout2d -> MaxPool2d(k, 2) -> ReLU of model.py:590-592,615-618 and its

@@ -58,4 +58,8 @@ def __getattr__(name):
     if name in ("farneback_flow", "update_labels", "propagate_labels", "rgb_to_gray", "optFlow", "updateLabels"):
         from . import flow
         return getattr(flow, name)
+    # the robot-side export (net.cfg + weights.dat), written and read back: export.py
+    if name in ("net_cfg", "save_export", "load_export", "ExportedNet", "saveParams", "loadParams"):
+        from . import export
+        return getattr(export, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

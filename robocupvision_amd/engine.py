@@ -196,6 +196,7 @@ class Plan:
         self.logits_slots: List[tuple] = []   # (fwd op index, slot) of the records that write the logits (inference: a fresh tensor per call)
         self.label_op: Optional[int] = None   # eval-labels plan: fwd index of the RCV_OP_CLS_LABEL record (its outputs are fresh tensors per call)
         self.label_shape: Optional[tuple] = None   # ... and the (N, H, W) of its class map
+        self.label_classes: Optional[int] = None   # ... and its classes (eval-proba plan: the probabilities are [N, classes, H, W])
         self.valid_classes: Optional[int] = None   # eval-valid plan: classes of the RCV_OP_CLS_VALID record at label_op (RCV_OP_VALID_FOLD follows it)
         self.input_grads: List[Optional[torch.Tensor]] = []
         self.n_head = 0                      # leading ops of fwd that depend on the parameters only (filter repack, eval-mode BN constants)
@@ -226,7 +227,8 @@ class _Lowering:
         self.training = training
         # eval-labels plan (Engine.predict): the eval plan up to the classifier node, whose tail is RCV_OP_CLS_LABEL -- a uint8 class map
         # (+ colour image) instead of logits; no logits buffer exists.  labels == "valid": the eval-valid plan (Engine.validate), the same
-        # plan with RCV_OP_CLS_VALID + RCV_OP_VALID_FOLD as its tail
+        # plan with RCV_OP_CLS_VALID + RCV_OP_VALID_FOLD as its tail.  labels == "proba": the eval-proba plan (Engine.proba), the same plan
+        # with RCV_OP_CLS_PROBA as its tail (probabilities, class map, confidence, pseudo-label)
         self.labels = labels
         if labels and training:
             raise L.RcvError("an eval-labels plan is an inference plan")
@@ -638,9 +640,10 @@ class _Lowering:
         """The classifier node of an eval-labels plan: RCV_OP_CLS_LABEL in place of RCV_OP_CLS_FWD (1x1) resp. of RCV_OP_NHWC_TO_NCHW
         behind the padded conv (3x3).  Its outputs (p[OUT] class map, p[X0] colour, p[X1] palette) are set per call by Engine.predict.
         In an eval-valid plan the record is RCV_OP_CLS_VALID (same slots and source forms) with its partial rows, followed by
-        RCV_OP_VALID_FOLD; targets, class weights, counts, class map and state are set per call by Engine.validate."""
+        RCV_OP_VALID_FOLD; targets, class weights, counts, class map and state are set per call by Engine.validate.  In an eval-proba
+        plan the record is RCV_OP_CLS_PROBA (same slots and source forms); its outputs and threshold are set per call by Engine.proba."""
         Cout, Cin = w.shape[0], w.shape[1]
-        tail_kind = L.OP_CLS_VALID if self.labels == "valid" else L.OP_CLS_LABEL
+        tail_kind = {"valid": L.OP_CLS_VALID, "proba": L.OP_CLS_PROBA}.get(self.labels, L.OP_CLS_LABEL)
         dims = dict(n=self.N, h=src.H, w=src.W, cout=Cout)
         if tuple(w.shape[2:]) == (1, 1) and src.kind == "fused_up":
             tt, skip = src.fused
@@ -670,6 +673,7 @@ class _Lowering:
         node.out = Value("plain", None, Cout, src.H, src.W, None, node)
         self.plan.label_op = len(self.fwd) - 1
         self.plan.label_shape = (self.N, src.H, src.W)
+        self.plan.label_classes = Cout
         if self.labels == "valid":
             tail = self.fwd[-1]
             rows = self.eng._workspace(self.plan, tail)
@@ -1243,11 +1247,11 @@ class Engine:
 
     def _plan_for(self, inputs: Sequence[torch.Tensor], training: bool, labels: bool = False) -> Plan:
         self._ensure_device(inputs[0].device)
-        # four plan variants per input shape: training, eval (logits), eval-labels (class map, Engine.predict) and eval-valid (loss rows,
-        # class map and counts, Engine.validate); one cache, one budget
+        # five plan variants per input shape: training, eval (logits), eval-labels (class map, Engine.predict), eval-valid (loss rows,
+        # class map and counts, Engine.validate) and eval-proba (probabilities, Engine.proba); one cache, one budget
         # (the key's second item stays a truth value -- True: training -- for every reader of `plans`; the labels variant is None, the
-        # valid variant "")
-        key = (tuple(tuple(t.shape) for t in inputs), ("" if labels == "valid" else None) if labels else training)
+        # valid variant "", the proba variant ())
+        key = (tuple(tuple(t.shape) for t in inputs), {"valid": "", "proba": ()}.get(labels) if labels else training)
         plan = self.plans.get(key)
         if plan is None:
             plan = self._build([tuple(t.shape) for t in inputs], training, labels)
@@ -1347,6 +1351,42 @@ class Engine:
         finally:          # (the records are copied at enqueue: the cached list keeps no pointer into a caller's tensor)
             op.p[L.RCV_P_OUT] = op.p[L.RCV_P_X0] = op.p[L.RCV_P_X1] = None
         return (labels, col) if colour else labels
+
+    def proba(self, inputs: Sequence[torch.Tensor], labels: bool = False, confidence: bool = False, min_confidence: Optional[float] = None,
+              probabilities: bool = True):
+        """Runs the eval-proba plan: the network up to the classifier, whose tail (RCV_OP_CLS_PROBA) writes softmax(logits) over the
+        classes as a fresh float32 [N,C,H,W] tensor -- the [softmax] section of the robot-side export -- and, on request, the class map
+        (uint8 [N,H,W], ``predict``'s bit for bit), the confidence (float32 [N,H,W], the stored probability of that class) and, with
+        ``min_confidence`` = tau, the pseudo-label (int64 [N,H,W]: the class where confidence >= tau, else -100, which the losses
+        ignore).  No logits are stored.  Returns the probabilities alone, or a tuple (probabilities, [labels], [confidence],
+        [pseudo-label]) of what was asked for, in that order; ``probabilities=False`` leaves the probabilities out of both the stores
+        and the result (``infer.Segmenter`` wants the maps only).  Nothing synchronises; leaves no forward in flight."""
+        if not (probabilities or labels or confidence or min_confidence is not None):
+            raise L.RcvError("proba: nothing asked for (probabilities, labels, confidence, min_confidence: at least one)")
+        for t in inputs:
+            if t.dtype != torch.float32 or not t.is_contiguous():
+                raise L.RcvError("engine inputs must be contiguous float32 tensors")
+        plan = self._plan_for(inputs, False, labels="proba")
+        N, H, W = plan.label_shape
+        prob = torch.empty((N, plan.label_classes, H, W), dtype=torch.float32, device=self.device) if probabilities else None
+        lab = torch.empty(plan.label_shape, dtype=torch.uint8, device=self.device) if labels else None
+        conf = torch.empty(plan.label_shape, dtype=torch.float32, device=self.device) if confidence else None
+        pseudo = torch.empty(plan.label_shape, dtype=torch.int64, device=self.device) if min_confidence is not None else None
+        op = plan.fwd.arr[plan.label_op]
+        op.p[L.RCV_P_X0] = prob.data_ptr() if probabilities else None
+        op.p[L.RCV_P_OUT] = lab.data_ptr() if labels else None
+        op.p[L.RCV_P_X1] = conf.data_ptr() if confidence else None
+        op.p[L.RCV_P_X2] = pseudo.data_ptr() if pseudo is not None else None
+        op.f[0] = float(min_confidence) if min_confidence is not None else 0.0
+        for k, t in enumerate(inputs):
+            for (is_bwd, idx, slot) in plan.input_slots[k]:
+                plan.fwd.arr[idx].p[slot] = t.data_ptr()
+        try:
+            self._run_inference(plan, torch.cuda.current_stream(self.device).cuda_stream)
+        finally:          # (the records are copied at enqueue: the cached list keeps no pointer into a caller's tensor)
+            op.p[L.RCV_P_X0] = op.p[L.RCV_P_OUT] = op.p[L.RCV_P_X1] = op.p[L.RCV_P_X2] = None
+        out = [t for t in (prob, lab, conf, pseudo) if t is not None]
+        return out[0] if len(out) == 1 else tuple(out)
 
     def validate(self, inputs: Sequence[torch.Tensor], targets: torch.Tensor, weight: Optional[torch.Tensor], state, labels: bool = False):
         """Runs the eval-valid plan: the network up to the classifier, whose tail (RCV_OP_CLS_VALID) forms the weighted cross entropy

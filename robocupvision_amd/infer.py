@@ -32,7 +32,7 @@ import torch
 
 from . import _lib as L
 from .data import prepare_frames
-from .palette import device_palette
+from .palette import colorize, device_palette
 from .patches import check_keywords, classify_patches, object_patches
 
 __all__ = ["Segmenter", "LabelPropagator", "find_objects", "Objects", "ObjectsRecord", "DBCONVERT"]
@@ -196,14 +196,25 @@ class Segmenter:
     the ``object_patches`` keywords size / margin / return_bytes (needs ``objects``; the map size is ``img_size``); the call then
     returns ``(labels, colour, objects, patches)`` with the ``Patches`` cut out of the full-resolution frames.  ``classifier``: a
     patch classifier for ``classify_objects`` (needs ``patches``; put in eval mode here); the call then returns ``(labels, colour,
-    objects, patches, classes)`` with the uint8 [N,C-1,M] class of every found object, 255 where a slot holds none."""
+    objects, patches, classes)`` with the uint8 [N,C-1,M] class of every found object, 255 where a slot holds none.
+    ``pseudo_labels``: a confidence threshold tau; the call then returns the pseudo-label map next to the class map, ``(labels,
+    pseudo, colour, ...)``: int64 [B,H,W], the class where the softmax confidence is >= tau, else -100 -- ``Trainer.step`` targets
+    as they are (the losses ignore labels outside [0, C)).  One forward (``model.proba``'s plan) and one colour launch."""
 
-    def __init__(self, model, img_size=(120, 160), finetune=False, palette=None, objects=None, patches=None, classifier=None):
+    def __init__(self, model, img_size=(120, 160), finetune=False, palette=None, objects=None, patches=None, classifier=None,
+                 pseudo_labels=None):
         if not hasattr(model, "predict"):
             raise TypeError("Segmenter: model must be one of this package's networks (it has no predict)")
         if getattr(model, "classify", False):
             raise L.RcvError("Segmenter: this model is in classify mode (one class per patch, not a class map)")
         self.model = model.eval()
+        self._tau = None
+        if pseudo_labels is not None:
+            if not hasattr(model, "proba"):
+                raise TypeError("Segmenter: pseudo_labels needs a model with proba")
+            self._tau = float(pseudo_labels)
+            if not 0.0 <= self._tau <= 1.0:
+                raise ValueError("Segmenter: pseudo_labels is a confidence threshold in [0, 1] (got %r)" % (pseudo_labels,))
         self.img_size = (int(img_size[0]), int(img_size[1]))
         self.finetune = bool(finetune)
         self._palette = palette
@@ -236,16 +247,21 @@ class Segmenter:
             pal = self._device_palettes.get(imgs.device)
             if pal is None:
                 pal = self._device_palettes[imgs.device] = device_palette(self._palette, imgs.device)
-        labels, colour = self.model.predict(imgs, colour=True, palette=pal)
+        if self._tau is None:
+            head = self.model.predict(imgs, colour=True, palette=pal)
+        else:
+            labels, pseudo = self.model._proba_maps(imgs, self._tau)
+            head = (labels, pseudo, colorize(labels, pal))
+        labels = head[0]
         if self._objects is None:
-            return labels, colour
+            return head
         objs = find_objects(labels, **self._objects)
         if self._patches is None:
-            return labels, colour, objs
+            return head + (objs,)
         cut = object_patches(frames, objs, map_size=self.img_size, **self._patches)
         if self._classifier is None:
-            return labels, colour, objs, cut
-        return labels, colour, objs, cut, classify_patches(cut, self._classifier)
+            return head + (objs, cut)
+        return head + (objs, cut, classify_patches(cut, self._classifier))
 
 
 class LabelPropagator:

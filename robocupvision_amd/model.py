@@ -160,6 +160,35 @@ class _EngineOwner:
                 weight = torch.as_tensor(weight, dtype=torch.float32, device=x.device).contiguous()
             return self._get_engine().validate(inputs, targets.to(torch.int64).contiguous(), weight, state, bool(labels))
 
+    def proba(self, x, labels=False, confidence=False, min_confidence=None):
+        """The class probabilities of every pixel, on the device, without the logits: what the robot's engine outputs (every exported
+        ``net.cfg`` ends in ``[softmax]``).  ``x`` as for ``forward``.  Returns a fresh float32 [N,C,H,W] tensor, softmax over the
+        classes of the logits ``self(x)`` writes in eval mode with the arithmetic fixed (RCV_OP_CLS_PROBA: first maximum m,
+        ``expf(z - m)``, sum in class order, IEEE division) -- or a tuple of it and, in this order, what is asked for: ``labels=True``
+        the class map uint8 [N,H,W] (``predict``'s, bit for bit), ``confidence=True`` float32 [N,H,W], the probability of that class,
+        ``min_confidence=tau`` the pseudo-label int64 [N,H,W]: the class where confidence >= tau, else -100, usable as the targets
+        of ``Trainer.step`` (the losses ignore labels outside [0, C)).  Nothing synchronises.  Eval mode only, refusals as ``predict``."""
+        return self._proba_call(x, bool(labels), bool(confidence), None if min_confidence is None else float(min_confidence), True)
+
+    def _proba_maps(self, x, min_confidence):
+        """(class map, pseudo-label) of ``proba`` without the probabilities (``infer.Segmenter(pseudo_labels=tau)``)."""
+        return self._proba_call(x, True, False, float(min_confidence), False)
+
+    def _proba_call(self, x, labels, confidence, min_confidence, probabilities):
+        if self.training:
+            raise L.RcvError("proba is an inference call and this module is in training mode: call `.eval()` first")
+        if _graph_mode(self):
+            raise L.RcvError("proba: this model is in classify mode (the pooled patch-classification head gives one class per patch, "
+                             "not a class map); build it with classify off")
+        if not hasattr(self, "_get_engine"):
+            raise L.RcvError("proba: %s has no per-pixel classifier (ROBO_UNet, PB_FCN, PB_FCN_2 and LabelProp have)" % type(self).__name__)
+        if not torch.is_tensor(x):
+            raise TypeError("proba: x must be a tensor")
+        if x.device.type != "cuda":
+            raise L.RcvError("proba runs on the HIP device only (input on %s); there is no CPU path" % x.device)
+        with torch.no_grad():
+            return self._get_engine().proba(self._engine_inputs(x), labels, confidence, min_confidence, probabilities)
+
 
 class _BlockMixin(_EngineOwner):
     """Standalone call of a single block (NCHW in, NCHW out like the reference's blocks): the block
