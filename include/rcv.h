@@ -343,7 +343,7 @@ enum {
                              * [D0][D1][3][1] in the centre column, the centre tap their sum.  Every element of the dense filter is written */
   RCV_OP_CROSS_GRAD = 66,    /* the gather that undoes it on a gradient: p[IN] = dense gradient float[D0][D1][3][3], p[OUT] / p[X0] = the
                              * gradients of the first / second 1-D filter; with i[AUX0] = 1 the centre tap's gradient goes to both        */
-  RCV_OP_CLS_PROBA = 67      /* the softmax form of the classifier tails (rcv_cls_proba; csrc/cls_proba.hip): the [softmax] section that
+  RCV_OP_CLS_PROBA = 67,     /* the softmax form of the classifier tails (rcv_cls_proba; csrc/cls_proba.hip): the [softmax] section that
                              * closes every exported net.cfg, and the confidence gate of a pseudo-label.  Source forms 0 and 1 of
                              * RCV_OP_CLS_LABEL, slot for slot: i[N], i[H], i[W], i[CIN], i[COUT] = 1..8 classes, i[INMODE] 0 = features
                              * (p[IN], p[W], p[BIAS] or NULL, CIN 8 / 16; with RCV_F_FUSED_UP p[IN_C], p[X3], p[X4], i[AUX0], i[AUX1]),
@@ -357,6 +357,24 @@ enum {
                              * of the losses: any target outside [0, COUT)).  A NaN logit gives whatever the expressions give (NaN
                              * probabilities for the pixel, the class from the other logits, pseudo-label -100); a NaN f[0] gives
                              * -100 everywhere.  No atomics; every element is written once by a fixed lane                            */
+  RCV_OP_CLS_CALIB = 68      /* the calibration form of the classifier tails (rcv_cls_calib; csrc/cls_calib.hip): counts per predicted
+                             * class, label and confidence bin, from which the host reads what every threshold of a sweep keeps; nothing
+                             * per pixel is stored.  Source forms 0 and 1 slot for slot as RCV_OP_CLS_PROBA (i[N], i[H], i[W], i[CIN],
+                             * i[COUT] = C = 1..8, i[INMODE], p[IN], p[W], p[BIAS]; with RCV_F_FUSED_UP p[IN_C], p[X3], p[X4], i[AUX0],
+                             * i[AUX1]): class cls and confidence cf are formed by RCV_OP_CLS_PROBA's expressions, so cf is bit for bit
+                             * the float that record stores in p[X1].  Form 2: p[IN] = a stored class map uint8[N][H][W] and p[X1] = a
+                             * stored confidence map float[N][H][W] (i[CIN] is not looked at).  RCV_F_FUSED_UP belongs to form 0.
+                             * p[IN2] = targets int64[N][H][W] or NULL; p[X0] = edges float[K] in device memory, K = i[COUNT] in 1..32,
+                             * ascending (not checked: see the bin rule); p[X2] = state int64[K + 1][C][C + 3], ACCUMULATED into.
+                             * Per pixel: bin = #{ j : cf >= edges[j] } -- a count of K comparisons on the fp32 confidence, the very
+                             * comparison of RCV_OP_CLS_PROBA's pseudo-label gate, in [0, K] whatever the edges hold; the labelled pixels
+                             * with bin > j are those f[0] = edges[j] keeps there.  q = (uint32)(cf * 2^26): the product is exact in
+                             * fp32, the conversion truncates (cf <= 0 gives 0, cf >= 64 gives 2^32 - 1; a softmax confidence lies in
+                             * (0, 1]).  With target t, 0 <= t < C decided on the int64 value: state[bin][cls][t] += 1 and
+                             * state[bin][cls][C + 1] += q; otherwise, and with p[IN2] NULL: state[bin][cls][C] += 1 and
+                             * state[bin][cls][C + 2] += q.  A pixel whose confidence is NaN counts nowhere; in form 2 neither does a
+                             * pixel whose class byte is >= C.  Each workgroup counts in LDS and adds its non-zero entries with 64-bit
+                             * integer atomics: every sum is an integer sum, so the state is bitwise reproducible in any order      */
 };
 
 /* i[RCV_I_AUX0] of RCV_OP_PRUNE: how the threshold of a tensor is chosen */
@@ -839,6 +857,11 @@ int rcv_valid_fold(rcv_handle* h, int32_t* counts, const float* rows, int n_rows
  * (class where confidence >= threshold, else -100): each may be NULL, not all four.                                                  */
 int rcv_cls_proba(rcv_handle* h, const float* x, const float* w, const float* bias /*may be NULL*/, int N, int H, int W, int CIN, int COUT,
                   float* proba, uint8_t* labels, float* confidence, int64_t* pseudo, float threshold, void* stream);
+/* RCV_OP_CLS_CALIB, source form 0 without the fused decoder input: class and confidence as rcv_cls_proba forms them, counted into
+ * state int64[K + 1][COUT][COUT + 3] (accumulated; layout, bin rule and fixed-point sums at the kind) against targets int64[N][H][W] or
+ * NULL and the K ascending edges float[K] in device memory, 1 <= K <= 32.                                                          */
+int rcv_cls_calib(rcv_handle* h, const float* x, const float* w, const float* bias /*may be NULL*/, int N, int H, int W, int CIN, int COUT,
+                  const int64_t* targets /*may be NULL*/, const float* edges, int K, int64_t* state, void* stream);
 
 /* The BNN-L / BNN-M-C patch classifiers (model.py:569-619; objDetEval.py:89-119, classVal.py).  Each call runs ONE record of the kind
  * named (RCV_OP_BNN_STAGE_FWD / _BWD: conv -> Dropout2d -> MaxPool2d(k, 2) -> ReLU of model.py:590-592,615-618 and its

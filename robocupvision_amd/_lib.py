@@ -43,7 +43,10 @@ OP_CLS_VALID, OP_VALID_FOLD = 60, 61      # the validation tail: loss rows, clas
 OP_PW, OP_PW_WGRAD, OP_PW_WGRAD_REDUCE = 62, 63, 64      # pointwise (1x1) convolution between feature maps: forward / data gradient, filter gradient, its reduction (rcv.h, csrc/conv_pw.hip)
 OP_CROSS_PACK, OP_CROSS_GRAD = 65, 66     # two 1-D filters <-> one dense 3x3 filter with a cross of taps (ConvSep / trConvSep; rcv.h, csrc/conv_pw.hip)
 OP_CLS_PROBA = 67           # the softmax tail: probabilities, class map, confidence and confidence-gated pseudo-label, no logits (rcv.h RCV_OP_CLS_PROBA, csrc/cls_proba.hip)
-VALID_STATE = 76           # doubles of the state OP_VALID_FOLD keeps: loss sum, batches, images, pixels, iou_sum[8], conf[8][8]
+OP_CLS_CALIB = 68           # the calibration tail: counts per predicted class x label x confidence bin and fixed-point confidence sums, nothing per pixel stored (rcv.h RCV_OP_CLS_CALIB, csrc/cls_calib.hip)
+CALIB_MAX_EDGES = 32        # i[COUNT] of OP_CLS_CALIB: 1..32 confidence edges; the state is int64 [K + 1][C][C + 3]
+CALIB_Q_SCALE = 1 << 26     # its confidence sums are sums of (uint32)(confidence * 2^26)
+VALID_STATE = 76          # doubles of the state OP_VALID_FOLD keeps: loss sum, batches, images, pixels, iou_sum[8], conf[8][8]
 LP_PRIOR_U8, LP_PRIOR_LOGITS, LP_PRIOR_I64 = 1, 4, 8      # i[INMODE] of OP_LP_INPUT: the prior's form
 PRUNE_MAX_RATIO, PRUNE_STD_SEARCH, PRUNE_SMALLEST_K = range(3)      # i[AUX0] of OP_PRUNE: pruneModelNew / pruneModel / pruneModel2
 PRUNE_MAX_ITER = 4096
@@ -93,6 +96,7 @@ EXPORTS = [
     "rcv_farneback_flow", "rcv_update_labels", "rcv_object_patches", "rcv_resize_u8", "rcv_batch_prep_indexed",
     "rcv_rgb_prep_indexed", "rcv_lp_pair_prep", "rcv_conv5x5", "rcv_wgrad5x5", "rcv_op_stream_hints", "rcv_set_stream_min_mb",
     "rcv_lp_input", "rcv_cls_valid", "rcv_valid_fold", "rcv_conv_pw", "rcv_wgrad_pw", "rcv_cls_proba",
+    "rcv_cls_calib",
 ]
 
 
@@ -163,6 +167,8 @@ def load():
             lib.rcv_valid_fold.argtypes = [C.c_void_p] * 3 + [C.c_int, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 2
         if hasattr(lib, "rcv_cls_proba"):      # (RCV_LIBRARY may name an older build)
             lib.rcv_cls_proba.argtypes = [C.c_void_p] * 4 + [C.c_int] * 5 + [C.c_void_p] * 4 + [C.c_float, C.c_void_p]
+        if hasattr(lib, "rcv_cls_calib"):      # (RCV_LIBRARY may name an older build)
+            lib.rcv_cls_calib.argtypes = [C.c_void_p] * 4 + [C.c_int] * 5 + [C.c_void_p] * 2 + [C.c_int, C.c_void_p, C.c_void_p]
         lib.rcv_colorize.argtypes =[C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 3
         lib.rcv_sgd_step.argtypes = [C.c_void_p] * 5 + [C.c_int64, C.c_float, C.c_float, C.c_float, C.c_int, C.c_float, C.c_void_p]
         lib.rcv_sgd_step_pruned.argtypes = [C.c_void_p] * 6 + [C.c_int64, C.c_float, C.c_float, C.c_float, C.c_int, C.c_float, C.c_void_p]

@@ -144,6 +144,8 @@ static int dispatch(const rcv_handle* h, const rcv_op* op, hipStream_t s, OpQuer
       return rcv_launch_cls_valid(h, op, s, q);
     case RCV_OP_CLS_PROBA:
       return rcv_launch_cls_proba(h, op, s, q);
+    case RCV_OP_CLS_CALIB:
+      return rcv_launch_cls_calib(h, op, s, q);
     case RCV_OP_VALID_FOLD:
       return rcv_launch_valid_fold(h, op, s, q);
     case RCV_OP_BNN_STAGE_FWD:
@@ -686,6 +688,18 @@ int rcv_cls_proba(rcv_handle* h, const float* x, const float* w, const float* bi
   op.f[0] = threshold;
   op.p[RCV_P_IN] = (void*)x; op.p[RCV_P_W] = (void*)w; op.p[RCV_P_BIAS] = (void*)bias; op.p[RCV_P_X0] = proba; op.p[RCV_P_OUT] = labels;
   op.p[RCV_P_X1] = confidence; op.p[RCV_P_X2] = pseudo;
+  return rcv_run(h, &op, 1, stream);
+}
+
+int rcv_cls_calib(rcv_handle* h, const float* x, const float* w, const float* bias, int N, int H, int W, int CIN, int COUT, const int64_t* targets,
+                  const float* edges, int K, int64_t* state, void* stream) {
+  rcv_op op;
+  memset(&op, 0, sizeof(op));
+  op.kind = RCV_OP_CLS_CALIB;
+  op.i[RCV_I_N] = N; op.i[RCV_I_H] = H; op.i[RCV_I_W] = W; op.i[RCV_I_CIN] = CIN; op.i[RCV_I_COUT] = COUT; op.i[RCV_I_INMODE] = 0;
+  op.i[RCV_I_COUNT] = K;
+  op.p[RCV_P_IN] = (void*)x; op.p[RCV_P_W] = (void*)w; op.p[RCV_P_BIAS] = (void*)bias; op.p[RCV_P_IN2] = (void*)targets;
+  op.p[RCV_P_X0] = (void*)edges; op.p[RCV_P_X2] = state;
   return rcv_run(h, &op, 1, stream);
 }
 

@@ -6,7 +6,8 @@
 // expressions of cls_common.h and of cls_label.hip's kernels, so they are bit for bit the logits RCV_OP_CLS_FWD / RCV_OP_NHWC_TO_NCHW
 // store.  No logits are stored here.
 //
-// Arithmetic, fixed as the contract (the one lp_input.hip states for its soft prior):
+// Arithmetic, fixed as the contract (the one lp_input.hip states for its soft prior; its lines stand in cls_softmax.h, shared with
+// cls_calib.hip):
 //   m = the first maximum of z in class order (`z_c > m` from -inf; a NaN never wins), cls = its index,
 //   e_c = expf(z_c - m),  S = ((e_0 + e_1) + e_2) + ... in class order,  p_c = e_c / S with an IEEE division; no fast intrinsics.
 // Outputs, each optional (a NULL slot is not written), at least one required:
@@ -24,7 +25,7 @@
 // q + 4, so one instruction covers 16 neighbouring pixels (64 contiguous bytes) of four planes, and 5 classes leave in two
 // instructions.  Class bytes, confidences and pseudo-labels leave from the lane that owns the pixel, coalesced along pixels.  No LDS
 // beyond the classifier's filter, no atomics; every output element is written once by a fixed lane: deterministic.
-#include "cls_common.h"
+#include "cls_softmax.h"
 
 struct CpOut {
   float* prob;          // [N][C][H][W] or NULL
@@ -39,25 +40,7 @@ struct CpOut {
 // them, p = its pixel (< 2^31), valid = p < total.
 template <int LPP>
 __device__ __forceinline__ void cp_tail(const CpOut& o, const float (&lg)[CLS_MAX_OUT], int COUT, uint32_t p, bool valid, int q) {
-  float mx = -INFINITY;
-  int am = 0;
-#pragma unroll
-  for (int c = 0; c < CLS_MAX_OUT; ++c) if (c < COUT && lg[c] > mx) { mx = lg[c]; am = c; }
-  float e[CLS_MAX_OUT];
-  float S = 0.f;
-#pragma unroll
-  for (int c = 0; c < CLS_MAX_OUT; ++c) {
-    e[c] = c < COUT ? expf(lg[c] - mx) : 0.f;
-    if (c == 0) S = e[0];
-    else if (c < COUT) S += e[c];
-  }
-  float pr[CLS_MAX_OUT];
-  float cf = 0.f;
-#pragma unroll
-  for (int c = 0; c < CLS_MAX_OUT; ++c) {
-    pr[c] = c < COUT ? __fdiv_rn(e[c], S) : 0.f;
-    if (c == am) cf = pr[c];
-  }
+  CLS_SOFTMAX(lg, COUT, pr, am, cf)          // float pr[], int am, float cf (cls_softmax.h)
   if (!valid) return;
   if (o.prob) {
     const uint32_t n = p / o.HW, hw = p - n * o.HW;

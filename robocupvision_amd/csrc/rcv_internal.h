@@ -209,6 +209,7 @@ int rcv_launch_lp_pair_prep(const rcv_handle* h, const rcv_op* op, hipStream_t s
 int rcv_launch_cls_label(const rcv_handle* h, const rcv_op* op, hipStream_t s, OpQuery* query);
 int rcv_launch_cls_valid(const rcv_handle* h, const rcv_op* op, hipStream_t s, OpQuery* query);      // cls_valid.hip
 int rcv_launch_cls_proba(const rcv_handle* h, const rcv_op* op, hipStream_t s, OpQuery* query);      // cls_proba.hip
+int rcv_launch_cls_calib(const rcv_handle* h, const rcv_op* op, hipStream_t s, OpQuery* query);      // cls_calib.hip
 int rcv_launch_valid_fold(const rcv_handle* h, const rcv_op* op, hipStream_t s, OpQuery* query);
 int rcv_launch_bnn(const rcv_handle* h, const rcv_op* op, hipStream_t s, OpQuery* query);
 int rcv_launch_prune(const rcv_handle* h, const rcv_op* op, hipStream_t s, OpQuery* query);

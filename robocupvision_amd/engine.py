@@ -228,7 +228,8 @@ class _Lowering:
         # eval-labels plan (Engine.predict): the eval plan up to the classifier node, whose tail is RCV_OP_CLS_LABEL -- a uint8 class map
         # (+ colour image) instead of logits; no logits buffer exists.  labels == "valid": the eval-valid plan (Engine.validate), the same
         # plan with RCV_OP_CLS_VALID + RCV_OP_VALID_FOLD as its tail.  labels == "proba": the eval-proba plan (Engine.proba), the same plan
-        # with RCV_OP_CLS_PROBA as its tail (probabilities, class map, confidence, pseudo-label)
+        # with RCV_OP_CLS_PROBA as its tail (probabilities, class map, confidence, pseudo-label).  labels == "calib": the eval-calib plan
+        # (Engine.calibrate), the same plan with RCV_OP_CLS_CALIB as its tail (counts per class, label and confidence bin)
         self.labels = labels
         if labels and training:
             raise L.RcvError("an eval-labels plan is an inference plan")
@@ -641,10 +642,13 @@ class _Lowering:
         behind the padded conv (3x3).  Its outputs (p[OUT] class map, p[X0] colour, p[X1] palette) are set per call by Engine.predict.
         In an eval-valid plan the record is RCV_OP_CLS_VALID (same slots and source forms) with its partial rows, followed by
         RCV_OP_VALID_FOLD; targets, class weights, counts, class map and state are set per call by Engine.validate.  In an eval-proba
-        plan the record is RCV_OP_CLS_PROBA (same slots and source forms); its outputs and threshold are set per call by Engine.proba."""
+        plan the record is RCV_OP_CLS_PROBA (same slots and source forms); its outputs and threshold are set per call by Engine.proba.  In
+        an eval-calib plan it is RCV_OP_CLS_CALIB (same source forms); targets, edges and state are set per call by Engine.calibrate."""
         Cout, Cin = w.shape[0], w.shape[1]
-        tail_kind = {"valid": L.OP_CLS_VALID, "proba": L.OP_CLS_PROBA}.get(self.labels, L.OP_CLS_LABEL)
+        tail_kind = {"valid": L.OP_CLS_VALID, "proba": L.OP_CLS_PROBA, "calib": L.OP_CLS_CALIB}.get(self.labels, L.OP_CLS_LABEL)
         dims = dict(n=self.N, h=src.H, w=src.W, cout=Cout)
+        if self.labels == "calib":
+            dims["count"] = 1          # (the number of edges: a placeholder the plan can be queried with; Engine.calibrate sets the state's)
         if tuple(w.shape[2:]) == (1, 1) and src.kind == "fused_up":
             tt, skip = src.fused
             self.fwd.append(L.make_op(tail_kind, L.F_FUSED_UP, cin=Cin, inmode=L.CLS_LABEL_FEATURES, aux0=skip.load_mode,
@@ -1247,11 +1251,12 @@ class Engine:
 
     def _plan_for(self, inputs: Sequence[torch.Tensor], training: bool, labels: bool = False) -> Plan:
         self._ensure_device(inputs[0].device)
-        # five plan variants per input shape: training, eval (logits), eval-labels (class map, Engine.predict), eval-valid (loss rows,
-        # class map and counts, Engine.validate) and eval-proba (probabilities, Engine.proba); one cache, one budget
+        # six plan variants per input shape: training, eval (logits), eval-labels (class map, Engine.predict), eval-valid (loss rows,
+        # class map and counts, Engine.validate), eval-proba (probabilities, Engine.proba) and eval-calib (calibration counts,
+        # Engine.calibrate); one cache, one budget
         # (the key's second item stays a truth value -- True: training -- for every reader of `plans`; the labels variant is None, the
-        # valid variant "", the proba variant ())
-        key = (tuple(tuple(t.shape) for t in inputs), {"valid": "", "proba": ()}.get(labels) if labels else training)
+        # valid variant "", the proba variant (), the calib variant frozenset())
+        key = (tuple(tuple(t.shape) for t in inputs), {"valid": "", "proba": (), "calib": frozenset()}.get(labels) if labels else training)
         plan = self.plans.get(key)
         if plan is None:
             plan = self._build([tuple(t.shape) for t in inputs], training, labels)
@@ -1387,6 +1392,37 @@ class Engine:
             op.p[L.RCV_P_X0] = op.p[L.RCV_P_OUT] = op.p[L.RCV_P_X1] = op.p[L.RCV_P_X2] = None
         out = [t for t in (prob, lab, conf, pseudo) if t is not None]
         return out[0] if len(out) == 1 else tuple(out)
+
+    def calibrate(self, inputs: Sequence[torch.Tensor], state, targets: Optional[torch.Tensor] = None):
+        """Runs the eval-calib plan: the network up to the classifier, whose tail (RCV_OP_CLS_CALIB) forms the class and the softmax
+        confidence of every pixel as ``proba`` does and counts it into ``state`` (a ``metrics.CalibrationState``: its edges and its
+        int64 [K+1][C][C+3] table) by predicted class, label (``targets``: int64 [N,H,W], or None: every pixel unlabelled) and confidence
+        bin.  Nothing per pixel is stored, nothing synchronises; leaves no forward in flight."""
+        for t in inputs:
+            if t.dtype != torch.float32 or not t.is_contiguous():
+                raise L.RcvError("engine inputs must be contiguous float32 tensors")
+        plan = self._plan_for(inputs, False, labels="calib")
+        C = plan.label_classes
+        if getattr(state, "C", None) != C or state.buf.device != self.device:
+            raise L.RcvError("calibrate: the state counts %s classes on %s; this network has %d on %s"
+                             % (getattr(state, "C", None), state.buf.device, C, self.device))
+        if targets is not None and (targets.dtype != torch.int64 or not targets.is_contiguous() or tuple(targets.shape) != plan.label_shape
+                                    or targets.device != self.device):
+            raise L.RcvError("calibrate: targets must be a contiguous int64 %s tensor on %s (got %s %s on %s)"
+                             % (list(plan.label_shape), self.device, targets.dtype, list(targets.shape), targets.device))
+        op = plan.fwd.arr[plan.label_op]
+        op.i[L.RCV_I_COUNT] = state.K
+        op.p[L.RCV_P_IN2] = targets.data_ptr() if targets is not None else None
+        op.p[L.RCV_P_X0] = state.edges_dev.data_ptr()
+        op.p[L.RCV_P_X2] = state.buf.data_ptr()
+        for k, t in enumerate(inputs):
+            for (is_bwd, idx, slot) in plan.input_slots[k]:
+                plan.fwd.arr[idx].p[slot] = t.data_ptr()
+        try:
+            self._run_inference(plan, torch.cuda.current_stream(self.device).cuda_stream)
+        finally:          # (the records are copied at enqueue: the cached list keeps no pointer into a caller's tensor)
+            op.p[L.RCV_P_IN2] = op.p[L.RCV_P_X0] = op.p[L.RCV_P_X2] = None
+            op.i[L.RCV_I_COUNT] = 1
 
     def validate(self, inputs: Sequence[torch.Tensor], targets: torch.Tensor, weight: Optional[torch.Tensor], state, labels: bool = False):
         """Runs the eval-valid plan: the network up to the classifier, whose tail (RCV_OP_CLS_VALID) forms the weighted cross entropy

@@ -7,7 +7,10 @@ DetectionMetrics: the object-detection precision / recall of test.py (getPrecRec
 integer counts into the reference's float64 numbers in the reference's order.
 
 ValidationState: the whole report of valid() -- loss, pixel accuracy over all pixels, mean class accuracy, mean IoU, the score that
-picks the weights -- from a state two records keep on the device (RCV_OP_CLS_VALID, RCV_OP_VALID_FOLD)."""
+picks the weights -- from a state two records keep on the device (RCV_OP_CLS_VALID, RCV_OP_VALID_FOLD).
+
+CalibrationState: what a confidence threshold keeps -- per class and edge the kept and the correct pixels, the confusion of what
+survives, accuracy against mean confidence per bin, ECE -- from one integer table RCV_OP_CLS_CALIB keeps on the device."""
 from __future__ import annotations
 
 import ctypes
@@ -142,6 +145,142 @@ class ValidationState:
 
     def compute(self) -> dict:
         return validation_report(self.buf.cpu().tolist(), self.C)
+
+
+# the edges of a calibration pass that names none: coarse where a threshold is never chosen, fine towards 1
+DEFAULT_CALIB_EDGES = (0.3, 0.4, 0.5, 0.6, 0.7, 0.75, 0.8, 0.85, 0.9, 0.925, 0.95, 0.97, 0.98, 0.99, 0.995, 0.999)
+
+
+class CalibrationReport(dict):
+    """The report of ``calibration_report``: a dict with one method."""
+
+    def threshold(self, precision: float, cls=None):
+        """The smallest edge at which the precision of the kept labelled pixels -- of class ``cls``, or of all classes -- reaches
+        ``precision``; None when no edge does (a NaN precision, nothing kept, reaches nothing)."""
+        row = self["all"]["precision"] if cls is None else [p[cls] for p in self["precision"]]
+        for e, p in zip(self["edges"], row):
+            if p >= precision:
+                return e
+        return None
+
+
+def calibration_report(table, edges, num_class: int) -> CalibrationReport:
+    """What a confidence threshold keeps, from the integers RCV_OP_CLS_CALIB counts: ``table`` int [K+1][C][C+3] (bin b holds the
+    pixels whose confidence passes exactly b of the K ascending ``edges``; per predicted class: C label columns, column C = pixels
+    without a label inside the classes, column C+1 / C+2 = the sum of (uint32)(confidence * 2^26) over the labelled / unlabelled ones).
+    Everything is float64 arithmetic on the host; 0 / 0 is NaN (``_ratio``).
+      per edge j and class c (lists [K][C]; the pixels predicted c with confidence >= edges[j] are those of the bins above j):
+        ``kept`` labelled pixels, ``correct`` of them with label c, ``precision`` = correct / kept, ``coverage`` = kept / all labelled
+        pixels predicted c, ``kept_unlabelled``; ``all``: the same five over all classes (lists [K])
+      ``kept_confusion`` int64 [K][C][C]: [pred][label] counts of what survives edge j, as ``validation_report``'s ``confusion``
+      ``bins``: per bin (lists [K+1]) ``count``, ``accuracy`` and ``mean_confidence`` (fixed-point sum / 2^26 / count) over the labelled
+        pixels, ``lo`` / ``hi`` its confidence range [lo, hi), and ``per_class`` the same three as lists [K+1][C]
+      ``ece`` = sum over the non-empty bins of (n_b / n) * |accuracy_b - mean_confidence_b| over the labelled pixels
+      ``labelled`` / ``unlabelled``: pixels counted; ``threshold(precision, cls=None)``: see ``CalibrationReport``."""
+    C = num_class
+    edges = [float(e) for e in edges]
+    K = len(edges)
+    t = [[[int(v) for v in row] for row in plane] for plane in table]
+    if len(t) != K + 1 or any(len(pl) != C or any(len(r) != C + 3 for r in pl) for pl in t):
+        raise ValueError("calibration_report: the table must be [%d][%d][%d] for %d edges and %d classes" % (K + 1, C, C + 3, K, C))
+    scale = float(L.CALIB_Q_SCALE)
+    n_bc = [[sum(t[b][c][:C]) for c in range(C)] for b in range(K + 1)]              # labelled pixels per bin and predicted class
+    ok_bc = [[t[b][c][c] for c in range(C)] for b in range(K + 1)]
+    pred_c = [sum(n_bc[b][c] for b in range(K + 1)) for c in range(C)]
+    n = sum(pred_c)
+    out = CalibrationReport(edges=edges, num_class=C, labelled=n, unlabelled=sum(t[b][c][C] for b in range(K + 1) for c in range(C)))
+    kept, correct, unl, conf = [], [], [], []
+    for j in range(K):
+        above = range(j + 1, K + 1)
+        kept.append([sum(n_bc[b][c] for b in above) for c in range(C)])
+        correct.append([sum(ok_bc[b][c] for b in above) for c in range(C)])
+        unl.append([sum(t[b][c][C] for b in above) for c in range(C)])
+        conf.append([[sum(t[b][p][l] for b in above) for l in range(C)] for p in range(C)])
+    out["kept"], out["correct"], out["kept_unlabelled"] = kept, correct, unl
+    out["precision"] = [[_ratio(float(correct[j][c]), float(kept[j][c])) for c in range(C)] for j in range(K)]
+    out["coverage"] = [[_ratio(float(kept[j][c]), float(pred_c[c])) for c in range(C)] for j in range(K)]
+    a_kept, a_ok = [sum(r) for r in kept], [sum(r) for r in correct]
+    out["all"] = {"kept": a_kept, "correct": a_ok, "kept_unlabelled": [sum(r) for r in unl],
+                  "precision": [_ratio(float(a_ok[j]), float(a_kept[j])) for j in range(K)],
+                  "coverage": [_ratio(float(a_kept[j]), float(n)) for j in range(K)]}
+    out["kept_confusion"] = torch.tensor(conf, dtype=torch.int64).reshape(K, C, C)
+    count = [sum(r) for r in n_bc]
+    acc = [_ratio(float(sum(ok_bc[b])), float(count[b])) for b in range(K + 1)]
+    mean = [_ratio(sum(t[b][c][C + 1] for c in range(C)) / scale, float(count[b])) for b in range(K + 1)]
+    out["bins"] = {"lo": [float("-inf")] + edges, "hi": edges + [float("inf")], "count": count, "accuracy": acc, "mean_confidence": mean,
+                   "per_class": {"count": n_bc,
+                                 "accuracy": [[_ratio(float(ok_bc[b][c]), float(n_bc[b][c])) for c in range(C)] for b in range(K + 1)],
+                                 "mean_confidence": [[_ratio(t[b][c][C + 1] / scale, float(n_bc[b][c])) for c in range(C)]
+                                                     for b in range(K + 1)]}}
+    ece = float("nan") if n == 0 else 0.0
+    for b in range(K + 1):
+        if count[b]:
+            ece += count[b] / n * abs(acc[b] - mean[b])
+    out["ece"] = ece
+    return out
+
+
+def calibration_edges(edges):
+    """The edges of a ``CalibrationState`` as a float32 tensor on the host: 1..32 finite values in [0, 1], strictly ascending once
+    rounded to fp32 (the device compares in fp32).  ValueError otherwise."""
+    try:
+        vals = [float(e) for e in edges]
+    except (TypeError, ValueError):
+        raise ValueError("calibration edges must be a sequence of numbers (got %r)" % (edges,))
+    if not 1 <= len(vals) <= L.CALIB_MAX_EDGES:
+        raise ValueError("calibration edges: %d values (1..%d)" % (len(vals), L.CALIB_MAX_EDGES))
+    if any(v != v or v in (float("inf"), float("-inf")) or not 0.0 <= v <= 1.0 for v in vals):
+        raise ValueError("calibration edges must be finite and in [0, 1] (got %r)" % (vals,))
+    e32 = torch.tensor(vals, dtype=torch.float32)
+    if len(vals) > 1 and not bool((e32[1:] > e32[:-1]).all()):
+        raise ValueError("calibration edges must be strictly ascending once rounded to float32 (got %r)" % (vals,))
+    return e32
+
+
+class CalibrationState:
+    """The running state of one calibration pass, kept on the device: the K confidence edges (fp32) and the int64 [K+1][C][C+3] table
+    RCV_OP_CLS_CALIB accumulates into (``model.calibrate``, ``Trainer.calibrate``, ``update_from_maps``).  ``compute()`` is the one
+    read-back; every figure of its report (``calibration_report``) comes from integers, so a pass is reproducible bit for bit."""
+
+    def __init__(self, num_class: int, edges, device="cuda"):
+        if not isinstance(num_class, int) or not 1 <= num_class <= 8:
+            raise ValueError("CalibrationState counts 1..8 classes (got %r)" % (num_class,))
+        e32 = calibration_edges(edges)
+        self.C = num_class
+        self.K = int(e32.numel())
+        self.edges = [float(v) for v in e32.tolist()]
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise L.RcvError("CalibrationState lives on the HIP device (got '%s'); there is no CPU path" % self.device)
+        self.edges_dev = e32.to(self.device)
+        self.buf = torch.zeros(self.K + 1, self.C, self.C + 3, dtype=torch.int64, device=self.device)
+        self.device = self.buf.device
+
+    def reset(self):
+        self.buf.zero_()
+
+    def update_from_maps(self, class_map_u8: torch.Tensor, confidence: torch.Tensor, targets=None):
+        """A batch whose class map (uint8 [B,H,W]) and confidence map (float32 [B,H,W]) exist already -- ``LabelPropagator`` output, an
+        average of several networks: RCV_OP_CLS_CALIB's map form.  A class byte >= C and a NaN confidence count nowhere."""
+        if not torch.is_tensor(class_map_u8) or class_map_u8.dtype != torch.uint8 or class_map_u8.dim() != 3 or class_map_u8.device != self.device:
+            raise L.RcvError("CalibrationState.update_from_maps needs the uint8 [B,H,W] class map on %s" % self.device)
+        if (not torch.is_tensor(confidence) or confidence.dtype != torch.float32 or tuple(confidence.shape) != tuple(class_map_u8.shape)
+                or confidence.device != self.device):
+            raise L.RcvError("CalibrationState.update_from_maps: confidence must be float32 %s on %s" % (list(class_map_u8.shape), self.device))
+        if targets is not None and (not torch.is_tensor(targets) or tuple(targets.shape) != tuple(class_map_u8.shape)):
+            raise L.RcvError("CalibrationState.update_from_maps: targets must be [B,H,W] like the class map %s" % (tuple(class_map_u8.shape),))
+        B, H, W = class_map_u8.shape
+        class_map_u8, confidence = class_map_u8.contiguous(), confidence.contiguous()
+        if targets is not None:
+            targets = targets.to(self.device).to(torch.int64).contiguous()
+        h = L.handle(self.device.index if self.device.index is not None else torch.cuda.current_device())
+        op = L.make_op(L.OP_CLS_CALIB, 0, n=B, h=H, w=W, cin=1, cout=self.C, inmode=L.CLS_LABEL_CLASSMAP, count=self.K,
+                       p_in=class_map_u8.data_ptr(), p_x1=confidence.data_ptr(), p_in2=targets.data_ptr() if targets is not None else 0,
+                       p_x0=self.edges_dev.data_ptr(), p_x2=self.buf.data_ptr())
+        L.OpList([op]).run(h, torch.cuda.current_stream(self.device).cuda_stream)
+
+    def compute(self) -> CalibrationReport:
+        return calibration_report(self.buf.cpu().tolist(), self.edges, self.C)
 
 
 def patch_scores(conf) -> dict:

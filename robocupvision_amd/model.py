@@ -189,6 +189,32 @@ class _EngineOwner:
         with torch.no_grad():
             return self._get_engine().proba(self._engine_inputs(x), labels, confidence, min_confidence, probabilities)
 
+    def calibrate(self, x, state, targets=None):
+        """One batch of a confidence calibration pass on the device: the forward, then the class and the softmax confidence of every
+        pixel -- ``proba``'s, bit for bit -- counted into ``state`` (``metrics.CalibrationState``) by predicted class, label and
+        confidence bin (RCV_OP_CLS_CALIB as the classifier's tail).  ``x`` as for ``forward``; ``targets`` int64 [N,H,W], or None for
+        frames without labels (every pixel counts as unlabelled, as a target outside [0, C) does).  For every edge tau of the state the
+        labelled pixels counted above it are exactly those ``proba(min_confidence=tau)`` keeps.  Nothing per pixel is stored and nothing
+        synchronises before ``state.compute()``.  Returns None.  Eval mode only, refusals as ``predict``."""
+        if self.training:
+            raise L.RcvError("calibrate is an inference call and this module is in training mode: call `.eval()` first")
+        if _graph_mode(self):
+            raise L.RcvError("calibrate: this model is in classify mode (the pooled patch-classification head gives one class per patch, "
+                             "not a class map); build it with classify off")
+        if not hasattr(self, "_get_engine"):
+            raise L.RcvError("calibrate: %s has no per-pixel classifier (ROBO_UNet, PB_FCN, PB_FCN_2 and LabelProp have)" % type(self).__name__)
+        if not torch.is_tensor(x) or not (targets is None or torch.is_tensor(targets)):
+            raise TypeError("calibrate: x and targets must be tensors (targets may be None)")
+        if x.device.type != "cuda" or (targets is not None and targets.device.type != "cuda"):
+            raise L.RcvError("calibrate runs on the HIP device only (input on %s%s); there is no CPU path"
+                             % (x.device, "" if targets is None else ", targets on %s" % targets.device))
+        if not hasattr(state, "edges_dev") or not hasattr(state, "buf"):
+            raise TypeError("calibrate: state must be a metrics.CalibrationState")
+        with torch.no_grad():
+            if targets is not None:
+                targets = targets.to(torch.int64).contiguous()
+            self._get_engine().calibrate(self._engine_inputs(x), state, targets)
+
 
 class _BlockMixin(_EngineOwner):
     """Standalone call of a single block (NCHW in, NCHW out like the reference's blocks): the block

@@ -322,6 +322,32 @@ class Trainer:
         out["pruned"] = pruned
         return out
 
+    @torch.no_grad()
+    def calibrate(self, batches, state=None, edges=None):
+        """A confidence calibration pass over ``batches``, any iterable of ``(imgs, targets)`` or of bare ``imgs`` (frames without
+        labels) on the device: every batch is one ``model.calibrate`` call, which counts class, label and confidence bin of every pixel
+        without storing anything per pixel.  No host synchronisation happens before the one read-back of ``state.compute()``, whose
+        report (``metrics.calibration_report``: what every threshold keeps per class, how much of it is right, the confusion of what
+        survives, accuracy against mean confidence per bin, ECE, ``threshold(precision)``) is returned.  ``state``: a
+        ``metrics.CalibrationState`` to count into (it is NOT reset), default a fresh one over ``edges`` (default
+        ``metrics.DEFAULT_CALIB_EDGES``)."""
+        from .metrics import DEFAULT_CALIB_EDGES, CalibrationState
+        model = self.model
+        if model.training:
+            model.eval()
+        if state is not None and not isinstance(state, CalibrationState):
+            raise TypeError("Trainer.calibrate: state must be a metrics.CalibrationState (got %s)" % type(state).__name__)
+        if not hasattr(batches, "__iter__"):
+            raise TypeError("Trainer.calibrate: batches must be an iterable of (imgs, targets) or of imgs")
+        for batch in batches:
+            imgs, targets = (batch, None) if torch.is_tensor(batch) else (batch[0], batch[1] if len(batch) > 1 else None)
+            if state is None:
+                state = CalibrationState(self._num_class(), DEFAULT_CALIB_EDGES if edges is None else edges, imgs.device)
+            model.calibrate(imgs, state, targets)
+        if state is None:
+            raise ValueError("Trainer.calibrate: no batches")
+        return state.compute()
+
     def _num_class(self) -> int:
         nodes = self.model._get_engine().graph["nodes"]
         return int(nodes[-1]["weight"].shape[0])
