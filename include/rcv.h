@@ -357,7 +357,7 @@ enum {
                              * of the losses: any target outside [0, COUT)).  A NaN logit gives whatever the expressions give (NaN
                              * probabilities for the pixel, the class from the other logits, pseudo-label -100); a NaN f[0] gives
                              * -100 everywhere.  No atomics; every element is written once by a fixed lane                            */
-  RCV_OP_CLS_CALIB = 68      /* the calibration form of the classifier tails (rcv_cls_calib; csrc/cls_calib.hip): counts per predicted
+  RCV_OP_CLS_CALIB = 68,     /* the calibration form of the classifier tails (rcv_cls_calib; csrc/cls_calib.hip): counts per predicted
                              * class, label and confidence bin, from which the host reads what every threshold of a sweep keeps; nothing
                              * per pixel is stored.  Source forms 0 and 1 slot for slot as RCV_OP_CLS_PROBA (i[N], i[H], i[W], i[CIN],
                              * i[COUT] = C = 1..8, i[INMODE], p[IN], p[W], p[BIAS]; with RCV_F_FUSED_UP p[IN_C], p[X3], p[X4], i[AUX0],
@@ -375,7 +375,43 @@ enum {
                              * state[bin][cls][C + 2] += q.  A pixel whose confidence is NaN counts nowhere; in form 2 neither does a
                              * pixel whose class byte is >= C.  Each workgroup counts in LDS and adds its non-zero entries with 64-bit
                              * integer atomics: every sum is an integer sum, so the state is bitwise reproducible in any order      */
+  RCV_OP_MAP_FILTER = 69     /* a class map cleaned by a windowed class count and one decision rule (rcv_map_filter; csrc/map_filter.hip):
+                             * the majority vote of labelExtraction.py:70-89 __filterMask (switched off there at :46) and the morphology
+                             * test.py:41 leaves commented in front of connectedComponents (cv2.MORPH_CLOSE, 3x3).  i[N], i[H], i[W],
+                             * i[COUT] = C = 1..8, i[COUNT] = window k = 1..15, i[INMODE] = element bytes of the map (1 = uint8, 8 =
+                             * int64), i[AUX0] = rule (RCV_MF_*), i[AUX1] / i[STRIDE] / i[DIL] = the rule's parameters (at the rules),
+                             * i[INMODE2] = 1 when p[IN] is a bit map (the *_FINISH rules), else 0; p[IN] = the windowed input [N][H][W],
+                             * p[IN2] = the original map of the *_FINISH rules, p[OUT] = the result [N][H][W], never p[IN] (halo pixels
+                             * are read after their neighbours are written), p[X0] = int32[N] or NULL: the number of pixels of each
+                             * image whose value changed is ADDED to it (not by the *_BITS rules).  A pixel value v is a class when
+                             * 0 <= v < C (decided on the int64 value), else void: 255, -100, anything else.  Per pixel: h[c] = the
+                             * number of in-image pixels of class c in the window, whose offsets on each axis are -(k / 2) ... k - 1 -
+                             * (k / 2) (k = 4: -2 ... +1, the reference's range(-2, 2, 1)); n = the number of in-image pixels of the
+                             * window; a void pixel counts in no h[c] but in n.  A pixel the rule leaves alone keeps every bit of its
+                             * value.  Integer arithmetic only, no workspace; the morphological rules (RCV_MF_ERODE_BITS and above) take
+                             * odd k only: with a symmetric window opening is anti-extensive and closing extensive                    */
 };
+
+/* i[RCV_I_AUX0] of RCV_OP_MAP_FILTER: the decision rule.  S = i[AUX1], a bit set of classes < C; v = the pixel's own value */
+enum {
+  RCV_MF_MAJORITY = 0,       /* i[STRIDE] = min_major >= 1, i[DIL] = min_own >= 0, i[AUX1] = fill_void (0 / 1).  m = max h, a = the lowest
+                              * class attaining it, own = h[v] for a class, 0 for void.  A void pixel keeps its value unless fill_void;
+                              * otherwise out = a if m >= min_major or (v is a class and own < min_own), else v.  The reference's
+                              * filter is k = 4, min_major = 15, min_own = 7                                                        */
+  RCV_MF_ERODE = 1,          /* i[STRIDE] = fill (0..255 for uint8 maps, any int32 for int64 maps): a class pixel with v in S and h[v] < n
+                              * becomes fill; everything else is unchanged                                                          */
+  RCV_MF_ERODE_BITS = 2,     /* map -> bit map uint8[N][H][W]: bit c set iff c in S, v == c and h[c] == n                               */
+  RCV_MF_DILATE_BITS = 3,    /* map -> bit map uint8[N][H][W]: bit c set iff c in S and h[c] > 0                                        */
+  RCV_MF_OPEN_FINISH = 4,    /* p[IN] = bit map (RCV_MF_ERODE_BITS'), p[IN2] = original map -> map; the counts are taken per bit of the bit
+                              * map (bits outside S are not counted).  i[STRIDE] = fill: a class pixel with v in S whose count for v is 0
+                              * becomes fill; everything else is unchanged                                                          */
+  RCV_MF_CLOSE_FINISH = 5    /* p[IN] = bit map (RCV_MF_DILATE_BITS'), p[IN2] = original map -> map.  i[DIL] = O, a bit set of classes < C
+                              * plus bit 8 for void: the lowest c in S whose count equals n and for which v == c or v in O gives out =
+                              * c; without one out = v                                                                              */
+};
+/* the tile of one workgroup of RCV_OP_MAP_FILTER (tests build planes past it) */
+#define RCV_MAP_FILTER_TILE_H 32
+#define RCV_MAP_FILTER_TILE_W 64
 
 /* i[RCV_I_AUX0] of RCV_OP_PRUNE: how the threshold of a tensor is chosen */
 enum {
@@ -714,6 +750,17 @@ int rcv_farneback_flow(rcv_handle* h, const uint8_t* prev, const uint8_t* next, 
  * (rint(row + flow[1]), rint(col + flow[0])), sums in fp32, halves to even; 0 where it lies outside the plane (or is NaN).  out must
  * not be labels.                                                                                                                 */
 int rcv_update_labels(rcv_handle* h, const void* labels, int elem_bytes, const float* flow, int N, int H, int W, void* out, void* stream);
+
+/* RCV_OP_MAP_FILTER, one launch: N class maps (elem_bytes 1 = uint8, 8 = int64) of num_class = 1..8 classes through a window x window
+ * class count (1..15, offsets -(window / 2) ... window - 1 - (window / 2), in-image pixels only) and one rule (RCV_MF_*, defined at the
+ * enum): majority vote (labelExtraction.py:70-89: window 4, min_major 15, min_own 7), erosion, and the two halves each of opening and
+ * closing (test.py:41's cv2.MORPH_CLOSE is RCV_MF_DILATE_BITS, then RCV_MF_CLOSE_FINISH on its bit map).  set / arg0 / arg1 are i[AUX1] /
+ * i[STRIDE] / i[DIL] of the record: (fill_void, min_major, min_own), (S, fill, -), (S, -, -), (S, -, -), (S, fill, -), (S, -, O).
+ * in: the class map, for the *_FINISH rules the uint8 bit map; original: the class map of the *_FINISH rules, NULL otherwise; out: the
+ * result, never in (uint8 bit map for the *_BITS rules); changed: int32[N] added to, or NULL.  Exact; no workspace, no host
+ * synchronisation.                                                                                                              */
+int rcv_map_filter(rcv_handle* h, const void* in, const void* original /*may be NULL*/, int elem_bytes, int N, int H, int W, int num_class,
+                   int window, int rule, int set, int arg0, int arg1, void* out, int32_t* changed /*may be NULL*/, void* stream);
 
 /* The batch assembly of labelPropTrain.py:162-193 in one launch: for every frame pair b, inputs[2b] = [Ya, Yb, Ya - Yb,
  * labelToPred(label_b)], targets[2b] = label_a, and the swapped sample at 2b + 1; Y = channel 0 of a frame, labelToPred

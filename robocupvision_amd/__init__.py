@@ -44,6 +44,10 @@ def __getattr__(name):
     if name in ("Segmenter", "find_objects", "Objects", "DBCONVERT", "LabelPropagator"):
         from . import infer
         return getattr(infer, name)
+    # ... and the cleaning between the two (labelExtraction.py:70-89 __filterMask; test.py:41's commented MORPH_CLOSE): RCV_OP_MAP_FILTER
+    if name in ("majority_filter", "erode_map", "open_map", "close_map", "trim_pseudo_labels"):
+        from . import infer
+        return getattr(infer, name)
     # ... and the patches of those objects, cut out of the full-resolution frames for the patch classifiers: patches.py
     if name == "patches":
         import importlib

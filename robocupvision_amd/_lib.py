@@ -46,7 +46,12 @@ OP_CLS_PROBA = 67           # the softmax tail: probabilities, class map, confid
 OP_CLS_CALIB = 68           # the calibration tail: counts per predicted class x label x confidence bin and fixed-point confidence sums, nothing per pixel stored (rcv.h RCV_OP_CLS_CALIB, csrc/cls_calib.hip)
 CALIB_MAX_EDGES = 32        # i[COUNT] of OP_CLS_CALIB: 1..32 confidence edges; the state is int64 [K + 1][C][C + 3]
 CALIB_Q_SCALE = 1 << 26     # its confidence sums are sums of (uint32)(confidence * 2^26)
-VALID_STATE = 76          # doubles of the state OP_VALID_FOLD keeps: loss sum, batches, images, pixels, iou_sum[8], conf[8][8]
+OP_MAP_FILTER = 69          # a class map through a windowed class count and one decision rule: majority vote, erosion, opening, closing (rcv.h RCV_OP_MAP_FILTER, csrc/map_filter.hip)
+MF_MAJORITY, MF_ERODE, MF_ERODE_BITS, MF_DILATE_BITS, MF_OPEN_FINISH, MF_CLOSE_FINISH = range(6)      # i[AUX0] of OP_MAP_FILTER: the rule (rcv.h RCV_MF_*)
+MAP_FILTER_TILE_H, MAP_FILTER_TILE_W = 32, 64      # the tile of one of its workgroups (rcv.h RCV_MAP_FILTER_TILE_H / _W)
+MAP_FILTER_MAX_WINDOW = 15  # its largest window: 15 * 15 = 225 is what a byte lane of the packed counts holds
+MF_OVER_VOID = 1 << 8       # the void bit of MF_CLOSE_FINISH's over set (i[DIL])
+VALID_STATE = 76         # doubles of the state OP_VALID_FOLD keeps: loss sum, batches, images, pixels, iou_sum[8], conf[8][8]
 LP_PRIOR_U8, LP_PRIOR_LOGITS, LP_PRIOR_I64 = 1, 4, 8      # i[INMODE] of OP_LP_INPUT: the prior's form
 PRUNE_MAX_RATIO, PRUNE_STD_SEARCH, PRUNE_SMALLEST_K = range(3)      # i[AUX0] of OP_PRUNE: pruneModelNew / pruneModel / pruneModel2
 PRUNE_MAX_ITER = 4096
@@ -96,7 +101,7 @@ EXPORTS = [
     "rcv_farneback_flow", "rcv_update_labels", "rcv_object_patches", "rcv_resize_u8", "rcv_batch_prep_indexed",
     "rcv_rgb_prep_indexed", "rcv_lp_pair_prep", "rcv_conv5x5", "rcv_wgrad5x5", "rcv_op_stream_hints", "rcv_set_stream_min_mb",
     "rcv_lp_input", "rcv_cls_valid", "rcv_valid_fold", "rcv_conv_pw", "rcv_wgrad_pw", "rcv_cls_proba",
-    "rcv_cls_calib",
+    "rcv_cls_calib", "rcv_map_filter",
 ]
 
 
@@ -169,6 +174,8 @@ def load():
             lib.rcv_cls_proba.argtypes = [C.c_void_p] * 4 + [C.c_int] * 5 + [C.c_void_p] * 4 + [C.c_float, C.c_void_p]
         if hasattr(lib, "rcv_cls_calib"):      # (RCV_LIBRARY may name an older build)
             lib.rcv_cls_calib.argtypes = [C.c_void_p] * 4 + [C.c_int] * 5 + [C.c_void_p] * 2 + [C.c_int, C.c_void_p, C.c_void_p]
+        if hasattr(lib, "rcv_map_filter"):      # (RCV_LIBRARY may name an older build)
+            lib.rcv_map_filter.argtypes = [C.c_void_p] * 3 + [C.c_int] * 10 + [C.c_void_p] * 3
         lib.rcv_colorize.argtypes =[C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p] * 3
         lib.rcv_sgd_step.argtypes = [C.c_void_p] * 5 + [C.c_int64, C.c_float, C.c_float, C.c_float, C.c_int, C.c_float, C.c_void_p]
         lib.rcv_sgd_step_pruned.argtypes = [C.c_void_p] * 6 + [C.c_int64, C.c_float, C.c_float, C.c_float, C.c_int, C.c_float, C.c_void_p]

@@ -162,6 +162,8 @@ static int dispatch(const rcv_handle* h, const rcv_op* op, hipStream_t s, OpQuer
       return rcv_launch_flow(h, op, s, q);
     case RCV_OP_OBJECT_PATCHES:
       return rcv_launch_object_patches(h, op, s, q);
+    case RCV_OP_MAP_FILTER:
+      return rcv_launch_map_filter(h, op, s, q);
     case RCV_OP_NOP:
       if (q) { snprintf(q->label, sizeof(q->label), "nop"); q->n_part = 0; q->n_split = 0; q->part_bytes = 0; }
       return RCV_OK;
@@ -505,6 +507,18 @@ int rcv_update_labels(rcv_handle* h, const void* labels, int elem_bytes, const f
   op.kind = RCV_OP_REMAP_LABELS;
   op.i[RCV_I_N] = N; op.i[RCV_I_H] = H; op.i[RCV_I_W] = W; op.i[RCV_I_INMODE] = elem_bytes;
   op.p[RCV_P_IN] = (void*)labels; op.p[RCV_P_IN2] = (void*)flow; op.p[RCV_P_OUT] = out;
+  return rcv_run(h, &op, 1, stream);
+}
+
+int rcv_map_filter(rcv_handle* h, const void* in, const void* original, int elem_bytes, int N, int H, int W, int num_class, int window,
+                   int rule, int set, int arg0, int arg1, void* out, int32_t* changed, void* stream) {
+  rcv_op op;
+  memset(&op, 0, sizeof(op));
+  op.kind = RCV_OP_MAP_FILTER;
+  op.i[RCV_I_N] = N; op.i[RCV_I_H] = H; op.i[RCV_I_W] = W; op.i[RCV_I_COUT] = num_class; op.i[RCV_I_COUNT] = window;
+  op.i[RCV_I_INMODE] = elem_bytes; op.i[RCV_I_INMODE2] = (rule == RCV_MF_OPEN_FINISH || rule == RCV_MF_CLOSE_FINISH) ? 1 : 0;
+  op.i[RCV_I_AUX0] = rule; op.i[RCV_I_AUX1] = set; op.i[RCV_I_STRIDE] = arg0; op.i[RCV_I_DIL] = arg1;
+  op.p[RCV_P_IN] = (void*)in; op.p[RCV_P_IN2] = (void*)original; op.p[RCV_P_OUT] = out; op.p[RCV_P_X0] = changed;
   return rcv_run(h, &op, 1, stream);
 }
 

@@ -216,6 +216,7 @@ int rcv_launch_prune(const rcv_handle* h, const rcv_op* op, hipStream_t s, OpQue
 int rcv_launch_objects(const rcv_handle* h, const rcv_op* op, hipStream_t s, OpQuery* query);
 int rcv_launch_flow(const rcv_handle* h, const rcv_op* op, hipStream_t s, OpQuery* query);
 int rcv_launch_object_patches(const rcv_handle* h, const rcv_op* op, hipStream_t s, OpQuery* query);
+int rcv_launch_map_filter(const rcv_handle* h, const rcv_op* op, hipStream_t s, OpQuery* query);      // map_filter.hip
 // small_kernels.hip: ce_finalize_kernel / rows_reduce_kernel for the translation units that share them
 int rcv_enqueue_ce_finalize(const float* part, int n_part, float* loss_out, hipStream_t s);
 int rcv_enqueue_rows_reduce(const float* part, int n_rows, int width, float* out0, int n0, float* out1, hipStream_t s);

@@ -35,7 +35,8 @@ from .data import prepare_frames
 from .palette import colorize, device_palette
 from .patches import check_keywords, classify_patches, object_patches
 
-__all__ = ["Segmenter", "LabelPropagator", "find_objects", "Objects", "ObjectsRecord", "DBCONVERT"]
+__all__ = ["Segmenter", "LabelPropagator", "find_objects", "Objects", "ObjectsRecord", "DBCONVERT", "majority_filter", "erode_map",
+           "open_map", "close_map", "trim_pseudo_labels"]
 
 
 class _Rules(dict):
@@ -188,6 +189,168 @@ def find_objects(class_map: torch.Tensor, num_class: int = 5, min_area=0, min_ra
     return Objects(rows, counts)
 
 
+_MF_PLAN_SLOT = (ctypes.c_int64 * 2)()      # two distinct non-NULL addresses for records that are only planned (never read or written)
+
+
+def _mf_int(name, what, x):
+    try:
+        return _as_int(x)
+    except (TypeError, ValueError) as e:
+        raise L.RcvError("%s: %s: %s" % (name, what, e)) from None
+
+
+def _mf_set(name, what, classes, default):
+    """A sequence of class numbers as a bit set (None: ``default``); whether a class exists is the library's refusal."""
+    if classes is None:
+        classes = default
+    if isinstance(classes, int) and not isinstance(classes, bool):
+        classes = (classes,)
+    bits = 0
+    try:
+        for c in classes:
+            c = _as_int(c)
+            if not 0 <= c < 30:
+                raise ValueError("class %d out of range" % c)
+            bits |= 1 << c
+    except (TypeError, ValueError) as e:
+        raise L.RcvError("%s: %s: %s" % (name, what, e)) from None
+    return bits
+
+
+def _map_filter(name, class_map, num_class, window, passes, return_changed=False, plan_only=False):
+    """``passes``: one (rule, set, arg0, arg1) for the single-launch rules, two for opening / closing (the first writes the uint8 bit
+    map the second counts).  Plans every record first (bad arguments are refused with the library's message, on any device), then
+    enqueues them in one run on the current stream."""
+    if not isinstance(class_map, torch.Tensor) or class_map.dim() != 3:
+        raise L.RcvError("%s: class_map must be a [N,H,W] tensor" % name)
+    eb = {torch.uint8: 1, torch.int64: 8}.get(class_map.dtype)
+    if eb is None:
+        raise L.RcvError("%s: dtype %s unsupported (torch.uint8 or torch.int64)" % (name, class_map.dtype))
+    N, H, W = class_map.shape
+    C, k = _mf_int(name, "num_class", num_class), _mf_int(name, "window", window)
+    ops = [L.make_op(L.OP_MAP_FILTER, 0, n=N, h=H, w=W, cout=C, count=k, inmode=eb, inmode2=1 if rule >= L.MF_OPEN_FINISH else 0,
+                     aux0=rule, aux1=s, stride=a0, dil=a1) for rule, s, a0, a1 in passes]
+    on_device = class_map.device.type == "cuda" and not plan_only
+    h = L.planner_handle()
+    if on_device:
+        dev = class_map.device
+        h = L.handle(dev.index if dev.index is not None else torch.cuda.current_device())
+        class_map = class_map.contiguous()
+        out = torch.empty_like(class_map)
+        changed = torch.zeros(N, dtype=torch.int32, device=dev) if return_changed else None
+        src, dst, cnt = class_map.data_ptr(), out.data_ptr(), changed.data_ptr() if return_changed else None
+        mid = _workspace(dev, ("map_filter bits", N, H, W), N * H * W).data_ptr() if len(ops) == 2 else None
+    else:
+        src, dst, mid, cnt = ctypes.addressof(_MF_PLAN_SLOT), ctypes.addressof(_MF_PLAN_SLOT) + 8, ctypes.addressof(_MF_PLAN_SLOT), None
+    if len(ops) == 2:
+        ops[0].p[L.RCV_P_IN], ops[0].p[L.RCV_P_OUT] = src, (mid if on_device else dst)
+        ops[1].p[L.RCV_P_IN], ops[1].p[L.RCV_P_IN2], ops[1].p[L.RCV_P_OUT], ops[1].p[L.RCV_P_X0] = mid, src, dst, cnt
+    else:
+        ops[0].p[L.RCV_P_IN], ops[0].p[L.RCV_P_OUT], ops[0].p[L.RCV_P_X0] = src, dst, cnt
+    for op in ops:
+        L.op_workspace(h, op)
+    if plan_only:
+        return None
+    if not on_device:
+        raise L.RcvError("%s needs the class map on the HIP device (there is no CPU path)" % name)
+    L.OpList(ops).run(h, torch.cuda.current_stream(dev).cuda_stream)
+    return (out, changed) if return_changed else out
+
+
+def majority_filter(class_map: torch.Tensor, num_class: int = 5, window: int = 4, min_major: int = 15, min_own: int = 7,
+                    fill_void: bool = False, return_changed: bool = False, _plan_only: bool = False):
+    """The windowed majority vote of labelExtraction.py:70-89 ``__filterMask`` (switched off there at :46: 480 * 640 * 16 Python
+    iterations per mask) for a batch of class maps on the device (RCV_OP_MAP_FILTER, rule RCV_MF_MAJORITY; the defaults are the
+    reference's).  class_map uint8 or int64 [N,H,W]; a value v is a class when 0 <= v < num_class, else void (255, -100, ...).  Per
+    pixel the classes of the window x window neighbourhood (offsets -(window // 2) ... window - 1 - window // 2 on both axes, in-image
+    pixels only) are counted; m = the largest count, a = the lowest class that has it.  A void pixel keeps its value unless
+    ``fill_void``; otherwise the pixel becomes a when m >= min_major, or when it is a class with fewer than min_own pixels of its own
+    class in the window; else it keeps its value.  Returns a new map of the same dtype; ``return_changed`` adds int32 [N], the pixels
+    of each image whose value changed.  Enqueued on the current stream, nothing synchronises."""
+    name = "majority_filter"
+    return _map_filter(name, class_map, num_class, window,
+                       [(L.MF_MAJORITY, 1 if fill_void else 0, _mf_int(name, "min_major", min_major), _mf_int(name, "min_own", min_own))],
+                       return_changed, _plan_only)
+
+
+def _all_classes(name, num_class):
+    return range(min(max(_mf_int(name, "num_class", num_class), 0), 30))
+
+
+def erode_map(class_map: torch.Tensor, num_class: int, classes=None, window: int = 3, fill: int = 0, return_changed: bool = False,
+              _plan_only: bool = False, _name: str = "erode_map"):
+    """Erosion of the regions of ``classes`` (None: every class): a pixel of such a class survives only where every in-image pixel
+    of its window has its class (scipy's ``binary_erosion(class_map == c, ones((k, k)), border_value=1)``); the others become
+    ``fill`` (0..255 for uint8 maps, any int32 for int64 maps).  Void pixels and other classes are unchanged.  One launch
+    (RCV_MF_ERODE); arguments and result as ``majority_filter``."""
+    return _map_filter(_name, class_map, num_class, window,
+                       [(L.MF_ERODE, _mf_set(_name, "classes", classes, _all_classes(_name, num_class)), _mf_int(_name, "fill", fill), 0)],
+                       return_changed, _plan_only)
+
+
+def open_map(class_map: torch.Tensor, num_class: int, classes=None, window: int = 3, fill: int = 0, return_changed: bool = False,
+             _plan_only: bool = False):
+    """Morphological opening (erosion, then dilation; odd windows) of the regions of ``classes`` (None: every class): what of a
+    region is no window wide -- speckles, thin bridges -- becomes ``fill``; everything else is unchanged.  Two launches
+    (RCV_MF_ERODE_BITS into a cached uint8 bit map, RCV_MF_OPEN_FINISH)."""
+    name = "open_map"
+    s = _mf_set(name, "classes", classes, _all_classes(name, num_class))
+    return _map_filter(name, class_map, num_class, window, [(L.MF_ERODE_BITS, s, 0, 0), (L.MF_OPEN_FINISH, s, _mf_int(name, "fill", fill), 0)],
+                       return_changed, _plan_only)
+
+
+def close_map(class_map: torch.Tensor, num_class: int, classes=None, window: int = 3, over=(0,), over_void: bool = True,
+              return_changed: bool = False, _plan_only: bool = False):
+    """Morphological closing (dilation, then erosion; odd windows) of the regions of ``classes`` (None: 1 ... num_class - 1, the
+    objects) -- test.py:41's commented ``cv2.morphologyEx(imgPred, cv2.MORPH_CLOSE, np.ones((3,3)))`` per class: holes and gaps
+    narrower than the window are filled.  A closing claims only pixels of the classes in ``over`` (default: background) and, with
+    ``over_void``, void pixels: one object never eats another; where two closings claim a pixel the lowest class wins.  Two
+    launches (RCV_MF_DILATE_BITS into a cached uint8 bit map, RCV_MF_CLOSE_FINISH)."""
+    name = "close_map"
+    s = _mf_set(name, "classes", classes, _all_classes(name, num_class)[1:])
+    o = _mf_set(name, "over", over, ()) | (L.MF_OVER_VOID if over_void else 0)
+    return _map_filter(name, class_map, num_class, window, [(L.MF_DILATE_BITS, s, 0, 0), (L.MF_CLOSE_FINISH, s, 0, o)], return_changed,
+                       _plan_only)
+
+
+def trim_pseudo_labels(pseudo: torch.Tensor, num_class: int, window: int = 3, return_changed: bool = False, _plan_only: bool = False):
+    """``erode_map(pseudo, num_class, None, window, fill=-100)`` for the int64 pseudo-label maps of ``Segmenter(pseudo_labels=tau)``: a
+    pseudo-label survives only where its whole window agrees with it, so the band along every class boundary and the rim of every
+    -100 hole become -100 (ignored by the losses)."""
+    if isinstance(pseudo, torch.Tensor) and pseudo.dtype != torch.int64:
+        raise L.RcvError("trim_pseudo_labels: int64 pseudo-labels expected (uint8 holds no -100), got %s" % pseudo.dtype)
+    return erode_map(pseudo, num_class, None, window, -100, return_changed, _plan_only, "trim_pseudo_labels")
+
+
+_CLEAN_STEPS = {"majority": (majority_filter, {"num_class", "window", "min_major", "min_own", "fill_void"}),
+                "erode": (erode_map, {"num_class", "classes", "window", "fill"}),
+                "open": (open_map, {"num_class", "classes", "window", "fill"}),
+                "close": (close_map, {"num_class", "classes", "window", "over", "over_void"}),
+                "trim": (trim_pseudo_labels, {"num_class", "window"})}
+
+
+def _clean_steps(clean, num_class, pseudo):
+    """``Segmenter(clean=...)`` checked and planned: [(function, keywords)] for the class map and for the pseudo-label map."""
+    if not isinstance(clean, (list, tuple)):
+        raise L.RcvError("Segmenter: clean must be a list of (step, keywords) pairs, e.g. [('majority', {}), ('close', {'window': 3})]")
+    on_labels, on_pseudo = [], []
+    for step in clean:
+        if not isinstance(step, (list, tuple)) or len(step) != 2 or not isinstance(step[1], dict):
+            raise L.RcvError("Segmenter: clean step %r is not a (step, keywords) pair" % (step,))
+        fn, allowed = _CLEAN_STEPS.get(step[0], (None, None)) if isinstance(step[0], str) else (None, None)
+        if fn is None or (step[0] == "trim" and not pseudo):
+            raise L.RcvError("Segmenter: clean step %r unknown (majority, erode, open, close%s)"
+                             % (step[0], "; trim with pseudo_labels" if not pseudo else ", trim"))
+        if not set(step[1]) <= allowed:
+            raise L.RcvError("Segmenter: clean step %r takes the keywords %s (got %s)" % (step[0], sorted(allowed), sorted(step[1])))
+        kw = dict(step[1])
+        kw.setdefault("num_class", num_class)
+        probe = torch.zeros(1, 1, 1, dtype=torch.int64 if step[0] == "trim" else torch.uint8)
+        fn(probe, _plan_only=True, **kw)          # a wrong step is refused at construction, with the library's message
+        (on_pseudo if step[0] == "trim" else on_labels).append((fn, kw))
+    return on_labels, on_pseudo
+
+
 class Segmenter:
     """``Segmenter(model)(frames)`` = ``model.predict(prepare_frames(frames, img_size, finetune), colour=True, palette=palette)``.
     ``model``: a ROBO_UNet, PB_FCN, PB_FCN_2 (segmentation mode) on the HIP device; it is put in eval mode here, once -- a caller
@@ -199,10 +362,15 @@ class Segmenter:
     objects, patches, classes)`` with the uint8 [N,C-1,M] class of every found object, 255 where a slot holds none.
     ``pseudo_labels``: a confidence threshold tau; the call then returns the pseudo-label map next to the class map, ``(labels,
     pseudo, colour, ...)``: int64 [B,H,W], the class where the softmax confidence is >= tau, else -100 -- ``Trainer.step`` targets
-    as they are (the losses ignore labels outside [0, C)).  One forward (``model.proba``'s plan) and one colour launch."""
+    as they are (the losses ignore labels outside [0, C)).  One forward (``model.proba``'s plan) and one colour launch.
+    ``clean``: a list of ``(step, keywords)`` pairs applied in order to the class map before colour, objects and patches see it --
+    ``"majority"``, ``"erode"``, ``"open"``, ``"close"`` with the keywords of ``majority_filter`` / ``erode_map`` / ``open_map`` /
+    ``close_map`` (num_class defaults to the model's); the colour mask is then ``colorize`` of the cleaned map.  With
+    ``pseudo_labels`` a ``("trim", {...})`` step (``trim_pseudo_labels``) applies to the pseudo-label map instead.  Without ``clean``
+    nothing changes."""
 
     def __init__(self, model, img_size=(120, 160), finetune=False, palette=None, objects=None, patches=None, classifier=None,
-                 pseudo_labels=None):
+                 pseudo_labels=None, clean=None):
         if not hasattr(model, "predict"):
             raise TypeError("Segmenter: model must be one of this package's networks (it has no predict)")
         if getattr(model, "classify", False):
@@ -239,6 +407,9 @@ class Segmenter:
             if not isinstance(classifier, torch.nn.Module):
                 raise TypeError("Segmenter: classifier must be a module (BNNL, BNNMC, PB_FCN(classify=1), PB_FCN_2(True))")
             self._classifier = classifier.eval()
+        self._clean = None
+        if clean is not None:
+            self._clean = _clean_steps(clean, getattr(model, "numClass", 5), self._tau is not None)
 
     def __call__(self, frames):
         imgs = prepare_frames(frames, self.img_size, self.finetune)
@@ -247,7 +418,17 @@ class Segmenter:
             pal = self._device_palettes.get(imgs.device)
             if pal is None:
                 pal = self._device_palettes[imgs.device] = device_palette(self._palette, imgs.device)
-        if self._tau is None:
+        if self._clean is not None:
+            if self._tau is None:
+                labels, pseudo = self.model.predict(imgs), None
+            else:
+                labels, pseudo = self.model._proba_maps(imgs, self._tau)
+                for fn, kw in self._clean[1]:
+                    pseudo = fn(pseudo, **kw)
+            for fn, kw in self._clean[0]:
+                labels = fn(labels, **kw)
+            head = (labels, colorize(labels, pal)) if pseudo is None else (labels, pseudo, colorize(labels, pal))
+        elif self._tau is None:
             head = self.model.predict(imgs, colour=True, palette=pal)
         else:
             labels, pseudo = self.model._proba_maps(imgs, self._tau)
